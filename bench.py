@@ -149,6 +149,35 @@ def cpu_baseline(limit_s: int = 300):
 
 
 # --------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_PER_PARAM = 16384
+
+
+def dump_outputs(out_dir: str, model, loss) -> None:
+    """What a caller of the timed path receives from its last step, as .npy files for output-by-output comparison of two builds:
+    ``loss.npy`` (float64 [1]), ``grad_norms.npy`` (float64, the L2 norm of every parameter gradient in ``named_parameters`` order)
+    and ``grad.<parameter>.npy`` (float32): the whole gradient when it has at most DUMP_SAMPLE_PER_PARAM elements, otherwise
+    that many elements at flat indices drawn from a generator seeded by the parameter name (the same indices in every run)."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.named_parameters())
+    per = min(DUMP_SAMPLE_PER_PARAM, (DUMP_BUDGET_BYTES - 8 * (len(params) + 1)) // (4 * max(len(params), 1)))
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    norms = []
+    for name, p in params:
+        g = p.grad if p.grad is not None else torch.zeros_like(p)
+        flat = g.detach().reshape(-1)
+        norms.append(float(torch.linalg.vector_norm(flat, dtype=torch.float64)))
+        if flat.numel() > per:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (per,), generator=gen).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, f"grad.{name}.npy"), flat.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "grad_norms.npy"), np.array(norms, dtype=np.float64))
+
+
+# --------------------------------------------------------------------------------------------------------------
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` without a launcher around it: start the N ranks as CHILD processes of
     `python -m torch.distributed.run` (the same command line the driver uses), BEFORE this process has made any GPU call -
@@ -178,6 +207,8 @@ def main():
     ap.add_argument("--engine-mode", default="auto", choices=["auto", "packed", "stack"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling leg at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, gradient norms, a fixed sample of every gradient) to DIR/*.npy")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_worker:
@@ -187,6 +218,8 @@ def main():
     wide = args.workload == "wide"
     steps = args.steps if args.steps is not None else (2 if wide else 6)
     warmup = args.warmup if args.warmup is not None else (1 if wide else 2)
+    if steps < 1 or warmup < 0:
+        ap.error(f"--steps must be >= 1 and --warmup >= 0 (got {steps}, {warmup})")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -278,7 +311,7 @@ def main():
         t0 = time.time()
         marks = []
         for b in batches:
-            step(b, acc)                 # ends with the engine's loss.item(): the step's own work is done when it returns
+            acc["last_loss"], _ = step(b, acc)   # ends with the engine's loss.item(): the step's own work is done when it returns
             marks.append(time.time())
             if world > 1 and os.environ.get("DTA_BENCH_WATCHDOG"):
                 print(f"[bench +{time.time() - T_START:6.1f}s] rank {rank}: step done in {marks[-1] - (marks[-2] if len(marks) > 1 else t0):.2f}s, mode {engine.last_mode}, "
@@ -340,6 +373,9 @@ def main():
     note(rank, f"timed leg done: {steps} steps in {wall:.2f}s")
     engine_mode = engine.last_mode
     peak_hbm = torch.cuda.max_memory_allocated(dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, acc["last_loss"])
+        note(rank, f"outputs of the last timed step written to {args.dump_outputs}")
 
     # ---- ROOFLINE leg: the same steps with HIP events on the launch stream around every C-ABI launch
     timer = ops.KernelTimer()

@@ -4,7 +4,7 @@ prefix-of-each-other pairs and head geometries that the fixed cases of test_gpu_
 import numpy as np
 import pytest
 import torch
-from hypothesis import HealthCheck, given, settings, strategies as st
+from hypothesis import HealthCheck, example, given, settings, strategies as st
 
 import test_gpu_attention as ga
 from dynamictreeattn_amd.token_trie import TokenTrie
@@ -40,6 +40,7 @@ def test_hip_tree_attention_equals_the_oracle_on_random_tries(seqs, heads, order
 
 @settings(max_examples=12, **COMMON)
 @given(rollouts, st.sampled_from([(2, 1), (4, 2), (6, 2)]), st.sampled_from(["forward", "backward"]), st.integers(0, 3))
+@example(seqs=[[0]], heads=(6, 2), order="forward", seed=1)      # one token: dQ and dK are exactly zero
 def test_fp32_tree_attention_equals_the_oracle_on_random_tries(seqs, heads, order, seed):
     """The plain-FMA fp32 kernels (tree_attn_f32.hip) on random tries: out, lse and all three gradients at 2e-5 against the fp32 oracle."""
     import math
@@ -60,7 +61,19 @@ def test_fp32_tree_attention_equals_the_oracle_on_random_tries(seqs, heads, orde
     o = ops.tree_attention(qd, kd, vd, meta)
     o.backward(do.to(DEV))
     rel = lambda a, b: float((a.detach().cpu() - b.detach()).norm() / max(float(b.detach().norm()), 1e-3 * b.numel() ** 0.5))
-    assert rel(o, o_ref) <= 2e-5 and rel(qd.grad, qr.grad) <= 2e-5 and rel(kd.grad, kr.grad) <= 2e-5 and rel(vd.grad, vr.grad) <= 2e-5
+    assert rel(o, o_ref) <= 2e-5 and rel(vd.grad, vr.grad) <= 2e-5
+    # dQ / dK: a row that sees only itself (a trie root; for dK one without descendants) has an exactly zero gradient, which
+    # the kernel reaches through dP - D, two fp32 dot products of the same 128 terms.  Such rows are held to the worst-case
+    # fp32 error of that cancellation (2 * 128 * eps * sum |dO * V|, scaled like the gradient); every other row to 2e-5.
+    grp = heads[0] // heads[1]
+    dpd = 2 * 128 * 2.0 ** -23 * (do * v.repeat_interleave(grp, 1)).abs().sum(-1) * 128 ** -0.5        # [T, Hq]
+    bound = {"dq": dpd * k.repeat_interleave(grp, 1).abs().amax(-1), "dk": (dpd * q.abs().amax(-1)).view(-1, heads[1], grp).sum(-1)}
+    for key, a, b in (("dq", qd.grad, qr.grad), ("dk", kd.grad, kr.grad)):
+        zero = (b == 0).flatten(1).all(1)
+        a = a.detach().cpu()
+        assert (a[zero].abs().amax(-1) <= bound[key][zero]).all(), key
+        if not zero.all():
+            assert rel(a[~zero], b[~zero]) <= 2e-5, key
     assert (lse.cpu().t() * math.log(2.0) - lse_ref.detach()).abs().max() <= 2e-5
 
 
