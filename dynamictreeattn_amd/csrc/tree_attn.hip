@@ -151,7 +151,8 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 struct TileIter {
   const int32_t* runs; int ri, re;      // run cursor
   int k0, kend, flag;                   // current tile
-  int diag_first_q;                     // NULL-run mode: packed index of the tile's first query
+  int diag_first_q;                     // NULL-run mode: packed index of the tile's first query (-64 with a subtree bound:
+                                        // then every tile needs the mask, below the diagonal too)
   __device__ __forceinline__ bool load_run() {
     while (ri < re) {
       k0 = __builtin_amdgcn_readfirstlane(runs[4 * ri]); kend = __builtin_amdgcn_readfirstlane(runs[4 * ri + 1]);
@@ -389,7 +390,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
   const int qrow_c = qrow < p.Tq ? qrow : p.Tq - 1;
   const int qidx = p.q_offset + qrow;
 
-  TileIter it; it.runs = p.runs; it.diag_first_q = p.q_offset + q0;
+  TileIter it; it.runs = p.runs; it.diag_first_q = p.subtree_end ? -64 : p.q_offset + q0;
   if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; if (!it.load_run()) return; }
   else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; if (it.kend <= 0) return; }
 
@@ -530,7 +531,7 @@ __global__ __launch_bounds__(512, 2) void tree_attn_fwd4_kernel(AttnParams p) {
   const int qrow_c = qrow < p.Tq ? qrow : p.Tq - 1;
   const int qidx = p.q_offset + qrow;
 
-  TileIter it; it.runs = p.runs; it.diag_first_q = p.q_offset + q0;
+  TileIter it; it.runs = p.runs; it.diag_first_q = p.subtree_end ? -64 : p.q_offset + q0;
   if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; if (!it.load_run()) return; }
   else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; if (it.kend <= 0) return; }
 
@@ -706,7 +707,7 @@ __global__ __launch_bounds__(256, 1) void tree_attn_fwd3_kernel(AttnParams p) {
   const int qrow_c = qrow < p.Tq ? qrow : p.Tq - 1;
   const int qidx = p.q_offset + qrow;
 
-  TileIter it; it.runs = p.runs; it.diag_first_q = p.q_offset + q0;
+  TileIter it; it.runs = p.runs; it.diag_first_q = p.subtree_end ? -64 : p.q_offset + q0;
   if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; if (!it.load_run()) return; }
   else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; if (it.kend <= 0) return; }
 
@@ -891,7 +892,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
   const float lse2 = p.lse_r[(int64_t)hq * p.Tq + qrow_c];
   if (h == 0 && qrow < p.Tq) p.delta[(int64_t)hq * p.Tq + qrow] = -delta;    // workspace holds -delta: the dK/dV kernel loads it as the INITIAL dP accumulator
 
-  TileIter it; it.runs = p.runs; it.diag_first_q = p.q_offset + q0;
+  TileIter it; it.runs = p.runs; it.diag_first_q = p.subtree_end ? -64 : p.q_offset + q0;
   bool any = true;
   if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; any = it.load_run(); }
   else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; any = it.kend > 0; }

@@ -1,6 +1,7 @@
 """GPU parity of the HIP tree-attention kernels through the C ABI against the fp32 oracle.
 Tolerances: inputs are rounded to bf16/f16 first, so the comparison isolates the kernel's own
-error: relative Frobenius error <= 6e-3 (bf16) / 1e-3 (f16) on out, dq, dk, dv; lse abs <= 2e-3."""
+error: relative Frobenius error <= 6e-3 (bf16) / 1e-3 (f16) on out, dq, dk, dv; lse abs <= 2e-3.  `_run` also checks every
+(row, head) against the float64 reference with the per-row bound of attn_ref64.py."""
 import math
 import os
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_ref64
 import cases
 
 import hostmirror
@@ -50,6 +52,8 @@ def _run(plan, se, Hq, Hkv, dtype, seed=0):
     assert torch.equal(out, o.detach())                       # same launch, same bits
     assert _rel(o, o_ref) <= tol and _rel(qd.grad, qr.grad) <= tol and _rel(kd.grad, kr.grad) <= tol and _rel(vd.grad, vr.grad) <= tol
     assert (lse.cpu().t() * math.log(2.0) - lse_ref.detach()).abs().max() <= 2e-3
+    ref = attn_ref64.reference(qd, kd, vd, do.to(dtype), o, torch.from_numpy(se).long())
+    attn_ref64.check_all(ref, dtype, f"T={T} Hq={Hq}/{Hkv}", out=o, lse=lse, dq=qd.grad, dk=kd.grad, dv=vd.grad)
     return o, qd.grad, kd.grad, vd.grad
 
 
