@@ -1,6 +1,6 @@
 // Fused row kernels of the decoder layer for gfx950 — HBM-bound, 16-byte accesses, fp32 math.
 //   dta_rmsnorm_fwd/bwd        y = w · cast(x · rsqrt(mean(x²)+eps))                 (Qwen3RMSNorm arithmetic)
-//   dta_qk_norm_rope_fwd/bwd   per (token, head) of 128: optional RMSNorm, then RoPE at position = trie depth
+//   dta_qk_norm_rope_fwd/bwd   per (token, head) of 128 or 64: optional RMSNorm, then RoPE at position = trie depth
 //   dta_swiglu_fwd/bwd         y = cast(silu(g)) · u
 // These replace ~40 torch elementwise launches per layer (fp32 up-casts included); together they are ~18 ms of a
 // 250 ms step (profiles/r1_bench_kernel_stats.csv).  Reference call sites: the model call of
@@ -205,32 +205,33 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-// q/k head-norm + RoPE.  x: [T, NH, 128]; 16 lanes own one head (8 elements each); a wave = 4 heads.
-// cs: [T, 128] float = {cos[0..63], sin[0..63]} of the token's depth.  w == NULL: RoPE only.
+// q/k head-norm + RoPE.  x: [T, NH, D], D = 128 or 64; LPH = D/8 lanes own one head (8 elements each); a wave = 64/LPH heads (4 or 8).
+// cs: [T, D] float = {cos[0..D/2-1], sin[0..D/2-1]} of the token's depth.  w == NULL: RoPE only.
 // ---------------------------------------------------------------------------------------------
-// HPL = heads of ONE token per 16-lane group (4 when NH % 4 == 0): the token's cos/sin values - 64 bytes per lane, four times the 16 bytes
+// HPL = heads of ONE token per LPH-lane group (4 when NH % 4 == 0): the token's cos/sin values - 64 bytes per lane, four times the 16 bytes
 // of x - are fetched once and reused, and HPL independent 16-byte loads are in flight per lane.
-template <int DT, int HPL>
+template <int DT, int HPL, int D>
 __global__ __launch_bounds__(256) void qk_norm_rope_fwd_kernel(const void* __restrict__ x_, const void* __restrict__ w_, const float* __restrict__ cs,
                                                                void* __restrict__ y_, float* __restrict__ rstd, int64_t n_units, int NH,
                                                                int64_t x_st, float eps) {
   using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
-  const int lane = threadIdx.x & 63, sub = lane & 15;
-  const int64_t unit = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);     // global (token, head group) index
+  constexpr int LPH = D / 8, LSH = D == 128 ? 4 : 3;              // lanes per head, log2
+  const int lane = threadIdx.x & 63, sub = lane & (LPH - 1);
+  const int64_t unit = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / LPH) + (lane >> LSH);     // global (token, head group) index
   if (unit >= n_units) return;
   const int groups = NH / HPL;
   const int64_t tok = unit / groups; const int head0 = (int)(unit - tok * groups) * HPL;
-  const e* x = reinterpret_cast<const e*>(x_) + tok * x_st + (int64_t)head0 * 128 + 8 * sub;
+  const e* x = reinterpret_cast<const e*>(x_) + tok * x_st + (int64_t)head0 * D + 8 * sub;
   const int64_t hid0 = tok * NH + head0;
-  e* y = reinterpret_cast<e*>(y_) + hid0 * 128 + 8 * sub;
+  e* y = reinterpret_cast<e*>(y_) + hid0 * D + 8 * sub;
   v8 v[HPL];
 #pragma unroll
-  for (int h = 0; h < HPL; ++h) v[h] = *reinterpret_cast<const v8*>(x + h * 128);
-  // rotate_half partner: element i <-> i +- 64  == lane sub ^ 8 of the same head
-  const float* c = cs + tok * 128 + 8 * (sub & 7);
+  for (int h = 0; h < HPL; ++h) v[h] = *reinterpret_cast<const v8*>(x + h * D);
+  // rotate_half partner: element i <-> i +- D/2  == lane sub ^ (LPH/2) of the same head
+  const float* c = cs + tok * D + 8 * (sub & (LPH / 2 - 1));
   float cj[8], sj[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { cj[j] = c[j]; sj[j] = sub < 8 ? -c[64 + j] : c[64 + j]; }
+  for (int j = 0; j < 8; ++j) { cj[j] = c[j]; sj[j] = sub < LPH / 2 ? -c[D / 2 + j] : c[D / 2 + j]; }
   v8 wv;
   if (w_) wv = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(w_) + 8 * sub);
 #pragma unroll
@@ -241,8 +242,8 @@ __global__ __launch_bounds__(256) void qk_norm_rope_fwd_kernel(const void* __res
 #pragma unroll
       for (int j = 0; j < 8; ++j) { const float f = (float)v[h][j]; ss = __builtin_fmaf(f, f, ss); }
 #pragma unroll
-      for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-      const float r = __builtin_amdgcn_rsqf(ss * (1.f / 128.f) + eps);
+      for (int o = LPH / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+      const float r = __builtin_amdgcn_rsqf(ss * (1.f / D) + eps);
       if (sub == 0) rstd[hid0 + h] = r;
 #pragma unroll
       for (int j = 0; j < 8; ++j) { const e t = (e)((float)v[h][j] * r); a[j] = (float)(e)((float)wv[j] * (float)t); }
@@ -253,30 +254,31 @@ __global__ __launch_bounds__(256) void qk_norm_rope_fwd_kernel(const void* __res
     v8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float other = __shfl_xor(a[j], 8);
+      const float other = __shfl_xor(a[j], LPH / 2);
       o[j] = (e)(a[j] * cj[j] + other * sj[j]);
     }
-    *reinterpret_cast<v8*>(y + h * 128) = o;
+    *reinterpret_cast<v8*>(y + h * D) = o;
   }
 }
 
 // dx_ may be dy_ (in place): a lane writes exactly the 16-byte groups it read; its partner's values arrive through registers.
-template <int DT, int HPL>
+template <int DT, int HPL, int D>
 __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __restrict__ x_, const void* __restrict__ w_, const float* __restrict__ cs,
                                                                const void* dy_, const float* __restrict__ rstd,
                                                                void* dx_, float* __restrict__ dw_part, int64_t n_units, int NH,
                                                                int64_t x_st, int64_t dy_st_t, int64_t dy_st_h, int64_t dx_st) {
   using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  constexpr int LPH = D / 8, LSH = D == 128 ? 4 : 3, UPB = 4 * (64 / LPH);    // lanes per head (log2), (token, head group) units per workgroup pass
   __shared__ float red[256 * 8];
-  const int lane = threadIdx.x & 63, sub = lane & 15;
+  const int lane = threadIdx.x & 63, sub = lane & (LPH - 1);
   const int groups = NH / HPL;
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
   v8 wv;
   if (w_) wv = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(w_) + 8 * sub);
-  for (int64_t base = (int64_t)blockIdx.x * 16; base < n_units; base += (int64_t)gridDim.x * 16) {
-    const int64_t unit = base + (threadIdx.x >> 6) * 4 + (lane >> 4);
+  for (int64_t base = (int64_t)blockIdx.x * UPB; base < n_units; base += (int64_t)gridDim.x * UPB) {
+    const int64_t unit = base + (threadIdx.x >> 6) * (64 / LPH) + (lane >> LSH);
     const bool live = unit < n_units;
     const int64_t uc = live ? unit : n_units - 1;
     const int64_t tok = uc / groups; const int head0 = (int)(uc - tok * groups) * HPL;
@@ -285,22 +287,22 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __res
 #pragma unroll
     for (int h = 0; h < HPL; ++h) g[h] = *reinterpret_cast<const v8*>(dy + h * dy_st_h);
     if (w_) {
-      const e* x = reinterpret_cast<const e*>(x_) + tok * x_st + (int64_t)head0 * 128 + 8 * sub;
+      const e* x = reinterpret_cast<const e*>(x_) + tok * x_st + (int64_t)head0 * D + 8 * sub;
 #pragma unroll
-      for (int h = 0; h < HPL; ++h) v[h] = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(x + h * 128));
+      for (int h = 0; h < HPL; ++h) v[h] = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(x + h * D));
     }
-    const float* c = cs + tok * 128 + 8 * (sub & 7);
+    const float* c = cs + tok * D + 8 * (sub & (LPH / 2 - 1));
     float cj[8], sj[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { cj[j] = c[j]; sj[j] = sub < 8 ? c[64 + j] : -c[64 + j]; }
-    e* dx = reinterpret_cast<e*>(dx_) + tok * dx_st + (int64_t)head0 * 128 + 8 * sub;
+    for (int j = 0; j < 8; ++j) { cj[j] = c[j]; sj[j] = sub < LPH / 2 ? c[D / 2 + j] : -c[D / 2 + j]; }
+    e* dx = reinterpret_cast<e*>(dx_) + tok * dx_st + (int64_t)head0 * D + 8 * sub;
 #pragma unroll
     for (int h = 0; h < HPL; ++h) {
       float da[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float gj = (float)g[h][j];
-        const float other = __shfl_xor(gj, 8);
+        const float other = __shfl_xor(gj, LPH / 2);
         da[j] = gj * cj[j] + other * sj[j];
       }
       v8 o;
@@ -310,26 +312,26 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __res
 #pragma unroll
         for (int j = 0; j < 8; ++j) { t[j] = (float)v[h][j] * r; dot = __builtin_fmaf(da[j] * (float)wv[j], t[j], dot); if (live) acc[j] = __builtin_fmaf(da[j], t[j], acc[j]); }
 #pragma unroll
-        for (int o2 = 8; o2 > 0; o2 >>= 1) dot += __shfl_xor(dot, o2);
-        dot *= (1.f / 128.f);
+        for (int o2 = LPH / 2; o2 > 0; o2 >>= 1) dot += __shfl_xor(dot, o2);
+        dot *= (1.f / D);
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (e)(r * (da[j] * (float)wv[j] - t[j] * dot));
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (e)da[j];
       }
-      if (live) *reinterpret_cast<v8*>(dx + h * 128) = o;
+      if (live) *reinterpret_cast<v8*>(dx + h * D) = o;
     }
   }
-  if (w_) {                                              // dw partial [gridDim.x, 128]
+  if (w_) {                                              // dw partial [gridDim.x, D]
 #pragma unroll
     for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = acc[j];
     __syncthreads();
-    if (threadIdx.x < 128) {
-      const int s = threadIdx.x >> 3, j = threadIdx.x & 7;                   // element 8*s + j
+    if (threadIdx.x < D) {
+      const int s = threadIdx.x >> 3, j = threadIdx.x & 7;                   // element 8*s + j: the lanes sub == s of all 256/LPH heads
       float t = 0.f;
-      for (int g2 = 0; g2 < 16; ++g2) t += red[(g2 * 16 + s) * 8 + j];
-      dw_part[(int64_t)blockIdx.x * 128 + threadIdx.x] = t;
+      for (int g2 = 0; g2 < 256 / LPH; ++g2) t += red[(g2 * LPH + s) * 8 + j];
+      dw_part[(int64_t)blockIdx.x * D + threadIdx.x] = t;
     }
   }
 }
@@ -531,39 +533,43 @@ extern "C" int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, con
 extern "C" int dta_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,
                                     int32_t T, int32_t NH, int32_t head_dim, int64_t x_stride_t, float eps, int32_t dtype, void* stream) {
   if (!x || !cos_sin || !y || T <= 0 || NH <= 0 || (w && !rstd)) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || head_dim != 128) return DTA_EUNSUPPORTED;
+  if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64)) return DTA_EUNSUPPORTED;
   if (!al16(x) || !al16(y) || (w && !al16(w)) || x_stride_t % 8) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
-#define DTA_QK_FWD(HPL_)                                                                                                       \
-  do { const int64_t n = (int64_t)T * (NH / HPL_); const dim3 grid((unsigned)((n + 15) / 16)), block(256);                   \
-       if (dtype == DTA_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_BF16, HPL_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_F16, HPL_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); \
-       else hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_F32, HPL_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); } while (0)
-  if (NH % 4 == 0) DTA_QK_FWD(4); else DTA_QK_FWD(1);
+#define DTA_QK_FWD(HPL_, D_)                                                                                                   \
+  do { const int64_t n = (int64_t)T * (NH / HPL_); const int upb = 4 * (64 / (D_ / 8));                                        \
+       const dim3 grid((unsigned)((n + upb - 1) / upb)), block(256);                                                          \
+       if (dtype == DTA_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_BF16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); \
+       else if (dtype == DTA_F16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_F16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); \
+       else hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_F32, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); } while (0)
+  if (head_dim == 64) { if (NH % 4 == 0) DTA_QK_FWD(4, 64); else DTA_QK_FWD(1, 64); }
+  else if (NH % 4 == 0) DTA_QK_FWD(4, 128); else DTA_QK_FWD(1, 128);
 #undef DTA_QK_FWD
   return DTA_LAUNCH_STATUS();
 }
 
-/* dw_partial: float [dta_qk_norm_rope_bwd_blocks(T*NH), 128] (ignored when w == NULL). */
+/* dw_partial: float [dta_qk_norm_rope_bwd_blocks(T*NH), head_dim] (ignored when w == NULL); the row count does not depend on head_dim. */
 extern "C" int dta_qk_norm_rope_bwd_blocks(int64_t n_heads_total) { return row_blocks(n_heads_total, 16, 1024); }
 extern "C" int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, const void* dy, const float* rstd,
                                     void* dx, float* dw_partial, int32_t T, int32_t NH, int32_t head_dim,
                                     int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t, int32_t dtype, void* stream) {
   if (!cos_sin || !dy || !dx || T <= 0 || NH <= 0 || (w && (!x || !rstd || !dw_partial))) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || head_dim != 128) return DTA_EUNSUPPORTED;
+  if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64)) return DTA_EUNSUPPORTED;
   if (!al16(dy) || !al16(dx) || (w && (!al16(w) || !al16(x))) || x_stride_t % 8 || dy_stride_t % 8 || dy_stride_h % 8 || dx_stride_t % 8) return DTA_EALIGN;
-  if (dx_stride_t < (int64_t)NH * 128) return DTA_EINVAL;
+  if (dx_stride_t < (int64_t)NH * head_dim) return DTA_EINVAL;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
-  // the grid - and with it the number of dw_partial rows the caller sized from dta_qk_norm_rope_bwd_blocks(T*NH) - does not depend on HPL
+  // the grid - and with it the number of dw_partial rows the caller sized from dta_qk_norm_rope_bwd_blocks(T*NH) - depends on neither HPL nor
+  // head_dim (the grid-stride loop covers any unit count; a D = 64 workgroup takes 32 units per pass instead of 16)
   const dim3 grid(row_blocks((int64_t)T * NH, 16, 1024)), block(256);
-#define DTA_QK_BWD(HPL_)                                                                                                       \
+#define DTA_QK_BWD(HPL_, D_)                                                                                                   \
   do { const int64_t n = (int64_t)T * (NH / HPL_);                                                                            \
-       if (dtype == DTA_BF16) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_BF16, HPL_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_F16, HPL_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); \
-       else hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_F32, HPL_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); } while (0)
-  if (NH % 4 == 0) DTA_QK_BWD(4); else DTA_QK_BWD(1);
+       if (dtype == DTA_BF16) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_BF16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); \
+       else if (dtype == DTA_F16) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_F16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); \
+       else hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_F32, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); } while (0)
+  if (head_dim == 64) { if (NH % 4 == 0) DTA_QK_BWD(4, 64); else DTA_QK_BWD(1, 64); }
+  else if (NH % 4 == 0) DTA_QK_BWD(4, 128); else DTA_QK_BWD(1, 128);
 #undef DTA_QK_BWD
   return DTA_LAUNCH_STATUS();
 }

@@ -1,4 +1,4 @@
-// Tree attention forward / backward for gfx950 (MI355X, CDNA4).  head_dim = 128, bf16 or f16.
+// Tree attention forward / backward for gfx950 (MI355X, CDNA4).  head_dim 128 or 64 (templated; see img_off_d), bf16 or f16.
 //
 // One kernel family serves both forms of the reference's "node attends to its ancestor path":
 //   * packed trie (DFS pre-order): key s visible to query t  <=>  s <= t < subtree_end[s]
@@ -15,7 +15,7 @@
 //              order.  Heavy key tiles are cut into split-Q work units whose fp32 slabs a finalize launch sums in order:
 //              no atomics, bitwise reproducible.
 //   Tiles (K/V for fwd, Q/dO for dK/dV) go global -> LDS by LDS-DMA issued from INLINE ASM (dma_* below) into one
-//   XOR-swizzled 256-B-row image that serves BOTH row reads (ds_read_b128) and transposed reads (ds_read_b64_tr_b16);
+//   XOR-swizzled 256-B-row (D = 64: 128-B-row) image that serves BOTH row reads (ds_read_b128) and transposed reads (ds_read_b64_tr_b16);
 //   the dQ kernel stages through registers (issue early, write late).
 //
 // Why inline asm for the DMA: with the builtin, hipcc (ROCm 7.2) waits `vmcnt(0)` for the in-flight prefetch of the
@@ -116,8 +116,25 @@ __device__ __forceinline__ int img_off(int row, int ch) {
   return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
 }
 
-template <class V8> __device__ __forceinline__ V8 row_frag(const char* img, int row, int ch) {
-  return *reinterpret_cast<const V8*>(img + img_off(row, ch));
+// ---- head_dim 64: the same image with 128-B rows (8 chunks) --------------------------------------------------------
+// 16-B slot of chunk `pc` of row `row` in the 64 banks (256 B): 8 * (row & 1) + pc.  With pc = ch ^ f(row), f a 3-bit function of the row:
+//   ds_read_b128 row reads (lane = row r of a 32-row block, all lanes of a group read the same logical chunk): the four lane groups are the
+//     rows {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (x2 for the lane halves); in each, the 8 rows of one parity have 8 distinct
+//     r >> 1 (mod 8), so f must be a bijection of bits 1..3 of the row -> 16 distinct slots.
+//   ds_read_b64_tr_b16 transposed reads (2 groups x 32 lanes): a group reads rows 4j..4j+3 x the four chunks 4mb..4mb+3; rows 4j and 4j+2
+//     (and 4j+1, 4j+3) have the same parity and XOR the same aligned chunk quad onto itself unless bit 2 of f differs between them, i.e. bit 2
+//     of f must follow row bit 1 -> 16 distinct slots.
+//   f(row) = {row bit 1, row bit 3, row bit 2} (bits 2, 1, 0) meets both; it depends on row bits 1..3 only, so row offsets of 16 rows keep
+//   every lane's swizzle (the FragOffs property below).  The swizzle of the D = 128 image (16 chunks, 4-bit f of row bits 0..3) is unchanged.
+__device__ __forceinline__ int swz64(int row) { return ((row & 2) << 1) | ((row >> 2) & 3); }
+template <int D> __device__ __forceinline__ int img_off_d(int row, int ch) {
+  if constexpr (D == 128) return img_off(row, ch);
+  else { static_assert(D == 64, "head_dim 64 or 128"); return row * 128 + ((ch ^ swz64(row)) << 4); }
+}
+template <int D> constexpr int tile_bytes() { return 64 * 2 * D; }   // 64 rows x D x 2 B
+
+template <class V8, int D = 128> __device__ __forceinline__ V8 row_frag(const char* img, int row, int ch) {
+  return *reinterpret_cast<const V8*>(img + img_off_d<D>(row, ch));
 }
 
 __device__ __forceinline__ s16x4 tr_read(const char* p) {
@@ -127,12 +144,12 @@ __device__ __forceinline__ s16x4 tr_read(const char* p) {
 // A-operand fragment read TRANSPOSED from the image: A[m = 32*mb + (lane&31)][kk], where the 16-deep
 // k-step covers image rows R0..R0+15 in the accumulator-as-operand order
 // (element j of lane half h <-> image row R0 + 8*(j>>2) + 4*h + (j&3)) and m indexes image columns.
-template <class V8> __device__ __forceinline__ V8 tr_frag(const char* img, int R0, int mb, int lane) {
+template <class V8, int D = 128> __device__ __forceinline__ V8 tr_frag(const char* img, int R0, int mb, int lane) {
   const int G = lane >> 4, hh = lane >> 5, i = lane & 15, qd = i >> 2, p = i & 3;
   const int ch = 4 * mb + 2 * (G & 1) + (p >> 1);
   const int ra = R0 + 4 * hh + qd;
-  s16x4 lo = tr_read(img + img_off(ra, ch) + 8 * (p & 1));
-  s16x4 hi = tr_read(img + img_off(ra + 8, ch) + 8 * (p & 1));
+  s16x4 lo = tr_read(img + img_off_d<D>(ra, ch) + 8 * (p & 1));
+  s16x4 hi = tr_read(img + img_off_d<D>(ra + 8, ch) + 8 * (p & 1));
   s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(V8, both);
 }
@@ -213,19 +230,21 @@ __device__ __forceinline__ float half_max(float x) {      // max(x, value of the
 
 // Per-lane byte offsets of every fragment read inside one image, computed once: the XOR swizzle depends on the
 // lane only (row blocks of 32 and k-steps of 16 rows leave row&3 and (row>>2)&3 unchanged), so inside the tile
-// loop every ds_read is <lane offset register> + <compile-time immediate>.
-struct FragOffs { int row[8]; int tr[8]; };
-__device__ __forceinline__ FragOffs frag_offsets(int lane) {
-  FragOffs o;
+// loop every ds_read is <lane offset register> + <compile-time immediate>.  row[s]: k-step s (D/16 of them) of a row read;
+// tr[mb], tr[D/32 + mb]: low / high half of the transposed read of 32-column block mb.
+template <int D> struct FragOffsT { int row[D / 16]; int tr[D / 16]; };
+using FragOffs = FragOffsT<128>;
+template <int D = 128> __device__ __forceinline__ FragOffsT<D> frag_offsets(int lane) {
+  FragOffsT<D> o;
   const int r = lane & 31, h = lane >> 5;
 #pragma unroll
-  for (int s = 0; s < 8; ++s) o.row[s] = img_off(r, 2 * s + h);
+  for (int s = 0; s < D / 16; ++s) o.row[s] = img_off_d<D>(r, 2 * s + h);
   const int G = lane >> 4, i = lane & 15, qd = i >> 2, pp = i & 3;
 #pragma unroll
-  for (int mb = 0; mb < 4; ++mb) {
+  for (int mb = 0; mb < D / 32; ++mb) {
     const int ch = 4 * mb + 2 * (G & 1) + (pp >> 1);
-    o.tr[mb] = img_off(4 * h + qd, ch) + 8 * (pp & 1);
-    o.tr[4 + mb] = img_off(4 * h + qd + 8, ch) + 8 * (pp & 1);
+    o.tr[mb] = img_off_d<D>(4 * h + qd, ch) + 8 * (pp & 1);
+    o.tr[D / 32 + mb] = img_off_d<D>(4 * h + qd + 8, ch) + 8 * (pp & 1);
   }
   return o;
 }
@@ -235,9 +254,9 @@ template <class V8> __device__ __forceinline__ V8 tr_pair(const char* lo_p, cons
   s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(V8, both);
 }
-template <class V8> __device__ __forceinline__ V8 tr_frag_o(const char* img_r0, const FragOffs& o, int mb) {
+template <class V8, int D> __device__ __forceinline__ V8 tr_frag_o(const char* img_r0, const FragOffsT<D>& o, int mb) {
   s16x4 lo = tr_read(img_r0 + o.tr[mb]);
-  s16x4 hi = tr_read(img_r0 + o.tr[4 + mb]);
+  s16x4 hi = tr_read(img_r0 + o.tr[D / 32 + mb]);
   s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(V8, both);
 }
@@ -280,33 +299,58 @@ __device__ __forceinline__ uint32_t dma_src_off(int row, int img_row, int lane, 
   const int ch = (lane & 15) ^ (((img_row & 3) << 2) | ((img_row >> 2) & 3));
   return (uint32_t)((row * stride + ch * 8) * (int64_t)esz);
 }
+// head_dim D: a 1-KiB piece is 1024 / (2 D) image rows of D / 8 chunks (D = 64: 8 rows, lane -> row lane >> 3, chunk lane & 7)
+template <int D> __device__ __forceinline__ uint32_t dma_src_off_d(int row, int img_row, int lane, int64_t stride, int esz) {
+  if constexpr (D == 128) return dma_src_off(row, img_row, lane, stride, esz);
+  else return (uint32_t)((row * stride + ((lane & 7) ^ swz64(img_row)) * 8) * (int64_t)esz);
+}
+template <int D> constexpr int dma_lane_row_shift() { return D == 128 ? 4 : 3; }
+// one piece of image A (at lds) and one of image B (at lds + TB): the D = 64 tiles, whose waves own one piece per image (or an odd count)
+template <int TB> __device__ __forceinline__ void dma_one2(uint32_t oa, const void* ba, uint32_t ob, const void* bb, uint32_t lds) {
+  asm volatile(
+      "s_nop 4\n\t"
+      "s_mov_b32 m0, %4\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %0, %2\n\t"
+      "s_add_u32 m0, %4, %5\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %3"
+      :: "v"(oa), "v"(ob), "s"(ba), "s"(bb), "s"(lds), "n"(TB) : "memory", "scc");
+}
 
-// K/V tile pair of the forward: NW waves move the 16 + 16 pieces; wave w owns pieces (16/NW)*w .. of both images.
+// K/V tile pair of the forward: NW waves move the DH/8 + DH/8 pieces (DH = the kernel's head_dim: 16 + 16 at 128, 8 + 8 at 64); wave w owns
+// pieces (DH/8/NW)*w .. of both images.
 // subtree_end of the 64 keys goes by 4-byte DMA from wave 0; keys at or beyond the run end are excluded by the
 // caller's `k <= min(q, kend-1)` test, not by a sentinel.
+#define DTA_KV_PPW(NW) (DH / 8 / (NW))
+#define DTA_KV_ROW(NW, I) ((512 / DH) * (wave * DTA_KV_PPW(NW) + (I)) + (lane >> dma_lane_row_shift<DH>()))
 #define DTA_KV_OFFSETS(NW)                                                                                 \
-  uint32_t voff_k[16 / (NW)], voff_v[16 / (NW)];                                                           \
-  _Pragma("unroll") for (int i_ = 0; i_ < 16 / (NW); ++i_) {                                               \
-    const int row_ = 4 * (wave * (16 / (NW)) + i_) + (lane >> 4);                                          \
-    voff_k[i_] = dma_src_off(row_, row_, lane, p.kv_st, sizeof(e));                                        \
-    voff_v[i_] = dma_src_off(row_, row_, lane, p.v_st, sizeof(e)); }
+  uint32_t voff_k[DTA_KV_PPW(NW)], voff_v[DTA_KV_PPW(NW)];                                                 \
+  _Pragma("unroll") for (int i_ = 0; i_ < DTA_KV_PPW(NW); ++i_) {                                          \
+    const int row_ = DTA_KV_ROW(NW, i_);                                                                   \
+    voff_k[i_] = dma_src_off_d<DH>(row_, row_, lane, p.kv_st, sizeof(e));                                  \
+    voff_v[i_] = dma_src_off_d<DH>(row_, row_, lane, p.v_st, sizeof(e)); }
 #define DTA_KV_DMA(BASE, K0, NW)                                                                           \
   DTA_DMA_GUARD(NW) { char* base_ = (BASE); const int k0_ = (K0);                                          \
     if (wave == 0) {                                                                                       \
       if (p.subtree_end) { int ki_ = k0_ + lane; ki_ = ki_ < p.Tk ? ki_ : p.Tk - 1;                        \
-        dma_dword((uint32_t)ki_ * 4u, p.subtree_end, lds_addr(base_ + 2 * TILE_BYTES)); }                  \
-      else reinterpret_cast<int*>(base_ + 2 * TILE_BYTES)[lane] = 0x7fffffff; }                            \
+        dma_dword((uint32_t)ki_ * 4u, p.subtree_end, lds_addr(base_ + 2 * tile_bytes<DH>())); }           \
+      else reinterpret_cast<int*>(base_ + 2 * tile_bytes<DH>())[lane] = 0x7fffffff; }                     \
     const char* kb_ = reinterpret_cast<const char*>(kbase) + (int64_t)k0_ * p.kv_st * (int64_t)sizeof(e);  \
     const char* vb_ = reinterpret_cast<const char*>(vbase) + (int64_t)k0_ * p.v_st * (int64_t)sizeof(e);   \
-    uint32_t ok_[16 / (NW)], ov_[16 / (NW)];                                                               \
-    _Pragma("unroll") for (int i_ = 0; i_ < 16 / (NW); ++i_) { ok_[i_] = voff_k[i_]; ov_[i_] = voff_v[i_]; } \
+    uint32_t ok_[DTA_KV_PPW(NW)], ov_[DTA_KV_PPW(NW)];                                                     \
+    _Pragma("unroll") for (int i_ = 0; i_ < DTA_KV_PPW(NW); ++i_) { ok_[i_] = voff_k[i_]; ov_[i_] = voff_v[i_]; } \
     if (k0_ + 64 > p.Tk) {                         /* ragged last tile of the tensor: clamp the row per lane */ \
-      _Pragma("unroll") for (int i_ = 0; i_ < 16 / (NW); ++i_) {                                           \
-        const int row_ = 4 * (wave * (16 / (NW)) + i_) + (lane >> 4);                                      \
+      _Pragma("unroll") for (int i_ = 0; i_ < DTA_KV_PPW(NW); ++i_) {                                      \
+        const int row_ = DTA_KV_ROW(NW, i_);                                                               \
         const int rr_ = k0_ + row_ < p.Tk ? row_ : p.Tk - 1 - k0_;                                         \
-        ok_[i_] = dma_src_off(rr_, row_, lane, p.kv_st, sizeof(e)); ov_[i_] = dma_src_off(rr_, row_, lane, p.v_st, sizeof(e)); } } \
-    _Pragma("unroll") for (int i_ = 0; i_ < 16 / (NW); i_ += 2)                                            \
-      dma_pair2(ok_[i_], ok_[i_ + 1], kb_, ov_[i_], ov_[i_ + 1], vb_, lds_addr(base_ + (wave * (16 / (NW)) + i_) * 1024)); }
+        ok_[i_] = dma_src_off_d<DH>(rr_, row_, lane, p.kv_st, sizeof(e)); ov_[i_] = dma_src_off_d<DH>(rr_, row_, lane, p.v_st, sizeof(e)); } } \
+    if constexpr (DH == 128) {                                                                             \
+      _Pragma("unroll") for (int i_ = 0; i_ < DTA_KV_PPW(NW); i_ += 2)                                     \
+        dma_pair2(ok_[i_], ok_[i_ + 1], kb_, ov_[i_], ov_[i_ + 1], vb_, lds_addr(base_ + (wave * DTA_KV_PPW(NW) + i_) * 1024)); \
+    } else {                                                                                               \
+      _Pragma("unroll") for (int i_ = 0; i_ < DTA_KV_PPW(NW); ++i_)                                        \
+        dma_one2<tile_bytes<DH>()>(ok_[i_], kb_, ov_[i_], vb_, lds_addr(base_ + (wave * DTA_KV_PPW(NW) + i_) * 1024)); } }
 
 // The same tile DMA in two steps, so that a one-wave-per-SIMD kernel can issue the pieces BETWEEN its MFMAs instead of in one exposed burst
 // (8 pieces cost a wave ~900 cycles of issue): DTA_KV_DMA_PREP declares the bases / offsets (and sends the subtree_end row), DTA_KV_DMA_PAIR(i)
@@ -335,11 +379,11 @@ __device__ __forceinline__ uint32_t dma_src_off(int row, int img_row, int lane, 
 #define DTA_V_PRELOAD_N 4
 #endif
 #if DTA_V_PRELOAD_N
-#define DTA_V_PRELOAD v8 vpre_[DTA_V_PRELOAD_N]; _Pragma("unroll") for (int i_ = 0; i_ < DTA_V_PRELOAD_N; ++i_) { vpre_[i_] = tr_frag_o<v8>(Vs + 4096 * (i_ >> 2), offs, i_ & 3); asm volatile("" : "+v"(vpre_[i_])); }
-#define DTA_V_FRAG(S4, DB) ((4 * (S4) + (DB) < DTA_V_PRELOAD_N) ? vpre_[4 * (S4) + (DB) < DTA_V_PRELOAD_N ? 4 * (S4) + (DB) : 0] : tr_frag_o<v8>(Vs + 4096 * (S4), offs, (DB)))
+#define DTA_V_PRELOAD v8 vpre_[DTA_V_PRELOAD_N]; _Pragma("unroll") for (int i_ = 0; i_ < DTA_V_PRELOAD_N; ++i_) { vpre_[i_] = tr_frag_o<v8>(Vs + 32 * DH * (i_ / (DH / 32)), offs, i_ % (DH / 32)); asm volatile("" : "+v"(vpre_[i_])); }
+#define DTA_V_FRAG(S4, DB) (((DH / 32) * (S4) + (DB) < DTA_V_PRELOAD_N) ? vpre_[(DH / 32) * (S4) + (DB) < DTA_V_PRELOAD_N ? (DH / 32) * (S4) + (DB) : 0] : tr_frag_o<v8>(Vs + 32 * DH * (S4), offs, (DB)))
 #else
 #define DTA_V_PRELOAD
-#define DTA_V_FRAG(S4, DB) tr_frag_o<v8>(Vs + 4096 * (S4), offs, (DB))
+#define DTA_V_FRAG(S4, DB) tr_frag_o<v8>(Vs + 32 * DH * (S4), offs, (DB))
 #endif
 
 // The 16 score MFMAs of a tile.  Default: the two key blocks' chains INTERLEAVED with the fragment reads one k-step ahead (every MFMA's
@@ -350,18 +394,18 @@ __device__ __forceinline__ uint32_t dma_src_off(int row, int img_row, int lane, 
 #endif
 #if DTA_SCORE_ORDER
 #define DTA_SCORE_MFMAS                                                                                    \
-    { v8 ka_ = *reinterpret_cast<const v8*>(Ks + offs.row[0]), kb2_ = *reinterpret_cast<const v8*>(Ks + 8192 + offs.row[0]); \
-      _Pragma("unroll") for (int s = 0; s < 8; ++s) {                                                      \
+    { v8 ka_ = *reinterpret_cast<const v8*>(Ks + offs.row[0]), kb2_ = *reinterpret_cast<const v8*>(Ks + 64 * DH + offs.row[0]); \
+      _Pragma("unroll") for (int s = 0; s < DH / 16; ++s) {                                                \
         v8 na_ = ka_, nb_ = kb2_;                                                                          \
-        if (s < 7) { na_ = *reinterpret_cast<const v8*>(Ks + offs.row[s + 1]); nb_ = *reinterpret_cast<const v8*>(Ks + 8192 + offs.row[s + 1]); } \
+        if (s < DH / 16 - 1) { na_ = *reinterpret_cast<const v8*>(Ks + offs.row[s + 1]); nb_ = *reinterpret_cast<const v8*>(Ks + 64 * DH + offs.row[s + 1]); } \
         X[0] = T::mma(ka_, qf[s], X[0]); X[1] = T::mma(kb2_, qf[s], X[1]);                                 \
         ka_ = na_; kb2_ = nb_;                                                                             \
       } }
 #else
 #define DTA_SCORE_MFMAS                                                                                    \
     _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                       \
-      _Pragma("unroll") for (int s = 0; s < 8; ++s)                                                        \
-        X[kb] = T::mma(*reinterpret_cast<const v8*>(Ks + 8192 * kb + offs.row[s]), qf[s], X[kb]);
+      _Pragma("unroll") for (int s = 0; s < DH / 16; ++s)                                                  \
+        X[kb] = T::mma(*reinterpret_cast<const v8*>(Ks + 64 * DH * kb + offs.row[s]), qf[s], X[kb]);
 #endif
 
 // =================================================================================================
@@ -369,11 +413,12 @@ __device__ __forceinline__ uint32_t dma_src_off(int row, int img_row, int lane, 
 // they share the staged K/V tiles.  One barrier per 64-key tile, LDS double buffered, tile loop unrolled
 // over the two buffers so that every LDS address is lane-offset + immediate.
 // =================================================================================================
-template <int DT, int HPB>
+template <int DT, int HPB, int DH>
 __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
-  constexpr int NW = DTA_DMA_WAVES(HPB), BUF = 2 * TILE_BYTES + SE_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[QK_LDS];
+  constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32;      // image bytes, k-steps over D, 32-wide accumulator blocks over D
+  constexpr int NW = DTA_DMA_WAVES(HPB), BUF = 2 * TB + SE_BYTES;
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // wave-uniform values live in SGPRs
@@ -395,18 +440,18 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
   else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; if (it.kend <= 0) return; }
 
   const e* qp = reinterpret_cast<const e*>(p.q) + (int64_t)qrow_c * p.q_st + (int64_t)hq * p.q_sh;
-  v8 qf[8];
+  v8 qf[NKS];
 #pragma unroll
-  for (int s = 0; s < 8; ++s) qf[s] = *reinterpret_cast<const v8*>(qp + 16 * s + 8 * h);
+  for (int s = 0; s < NKS; ++s) qf[s] = *reinterpret_cast<const v8*>(qp + 16 * s + 8 * h);
 
   const e* kbase = reinterpret_cast<const e*>(p.k) + (int64_t)kvh * p.kv_sh;
   const e* vbase = reinterpret_cast<const e*>(p.v) + (int64_t)kvh * p.v_sh;
-  const FragOffs offs = frag_offsets(lane);
+  const FragOffsT<DH> offs = frag_offsets<DH>(lane);
   DTA_KV_OFFSETS(NW)
 
-  f32x16 O[4];
+  f32x16 O[NDB];
 #pragma unroll
-  for (int db = 0; db < 4; ++db)
+  for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int g = 0; g < 16; ++g) O[db][g] = 0.f;
   float m = -1e30f, lsum = 0.f;
@@ -419,7 +464,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
   // global loads of Q, and with them still "pending" at the loop header it put `s_waitcnt vmcnt(7) .. vmcnt(0)` in front of the first eight
   // score MFMAs of the loop body - where vmcnt(0) also waits for the NEXT tile's DMA issued a few hundred cycles earlier.
 #pragma unroll
-  for (int s = 0; s < 8; ++s) asm volatile("" : "+v"(qf[s]));
+  for (int s = 0; s < NKS; ++s) asm volatile("" : "+v"(qf[s]));
   DMA_WAIT(); __syncthreads();
 
   // one tile out of buffer BUFI (compile-time): prefetch the next tile into the other buffer, S^T, softmax, PV
@@ -429,8 +474,8 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
     DTA_STAMP_AT(5) DTA_STAMP_TILE                                                                         \
     if (has_next) { nk0_ = it.k0; nkend_ = it.kend; nmask_ = it.masked(); DTA_KV_DMA(smem + (1 - (BUFI)) * BUF, it.k0, NW) } \
     DTA_STAMP_AT(0)                                                                                        \
-    const char* Ks = smem + (BUFI) * BUF; const char* Vs = Ks + TILE_BYTES;                                \
-    const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TILE_BYTES);                                   \
+    const char* Ks = smem + (BUFI) * BUF; const char* Vs = Ks + TB;                                \
+    const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TB);                                   \
     f32x16 X[2];                                                                                           \
     _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                       \
       _Pragma("unroll") for (int g = 0; g < 16; ++g) X[kb][g] = 0.f;                                       \
@@ -459,7 +504,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
       const float mnew = fmaxf(m, mc);                                                                     \
       const float alpha = fast_exp2(m - mnew);                                                             \
       m = mnew; lsum *= alpha;                                                                             \
-      _Pragma("unroll") for (int db = 0; db < 4; ++db)                                                     \
+      _Pragma("unroll") for (int db = 0; db < NDB; ++db)                                                   \
         _Pragma("unroll") for (int g = 0; g < 16; ++g) O[db][g] *= alpha;                                  \
     }                                                                                                      \
     DTA_STAMP_AT(2)                                                                                        \
@@ -467,7 +512,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
       _Pragma("unroll") for (int g = 0; g < 16; ++g) { const float pv = fast_exp2(__builtin_fmaf(X[kb][g], c, -m)); lsum += pv; X[kb][g] = pv; } \
     _Pragma("unroll") for (int s4 = 0; s4 < 4; ++s4) {                                                     \
       const v8 pb = pack_half<DT>(X[s4 >> 1], s4 & 1);                                                     \
-      _Pragma("unroll") for (int db = 0; db < 4; ++db) O[db] = T::mma(DTA_V_FRAG(s4, db), pb, O[db]);      \
+      _Pragma("unroll") for (int db = 0; db < NDB; ++db) O[db] = T::mma(DTA_V_FRAG(s4, db), pb, O[db]);      \
     }                                                                                                      \
     DTA_STAMP_AT(3)                                                                                        \
     DMA_WAIT(); __syncthreads();               /* the next tile has landed in every wave's view */          \
@@ -489,7 +534,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
   if (qrow < p.Tq) {
     e* op = reinterpret_cast<e*>(p.out) + (int64_t)qrow * p.o_st + (int64_t)hq * p.o_sh;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+    for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         v4 w;
@@ -514,6 +559,7 @@ constexpr int FWD4_LDS = 3 * (2 * TILE_BYTES + SE_BYTES);
 template <int DT>
 __global__ __launch_bounds__(512, 2) void tree_attn_fwd4_kernel(AttnParams p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
+  constexpr int DH = 128;                                            // the A/B forms exist for head_dim 128 only
   constexpr int NW = 8, BUF = 2 * TILE_BYTES + SE_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[FWD4_LDS];
 
@@ -691,6 +737,7 @@ constexpr float FWD3_THR = FWD_THR;          // the reference maximum follows a 
 template <int DT>
 __global__ __launch_bounds__(256, 1) void tree_attn_fwd3_kernel(AttnParams p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
+  constexpr int DH = 128;                                            // the A/B forms exist for head_dim 128 only
   constexpr int NW = 4, BUF = 2 * TILE_BYTES + SE_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[QK_LDS];
 
@@ -854,10 +901,11 @@ __global__ __launch_bounds__(256, 1) void tree_attn_fwd3_kernel(AttnParams p) {
 // =================================================================================================
 // backward part 1: delta + dQ   (query tile owns the workgroup; same sweep as the forward)
 // =================================================================================================
-template <int DT, int HPB>
+template <int DT, int HPB, int DH>
 __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnParams p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
-  __shared__ __attribute__((aligned(16))) char smem[QK_LDS];
+  constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32;
+  __shared__ __attribute__((aligned(16))) char smem[2 * (2 * TB + SE_BYTES)];
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // wave-uniform values live in SGPRs
@@ -877,10 +925,10 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
   const e* qp = reinterpret_cast<const e*>(p.q) + (int64_t)qrow_c * p.q_st + (int64_t)hq * p.q_sh;
   const e* dop = reinterpret_cast<const e*>(p.dout) + (int64_t)qrow_c * p.o_st + (int64_t)hq * p.o_sh;
   const e* op = reinterpret_cast<const e*>(p.o) + (int64_t)qrow_c * p.o_st + (int64_t)hq * p.o_sh;
-  v8 qf[8], dof[8];
+  v8 qf[NKS], dof[NKS];
   float dsum = 0.f;
 #pragma unroll
-  for (int s = 0; s < 8; ++s) {
+  for (int s = 0; s < NKS; ++s) {
     qf[s] = *reinterpret_cast<const v8*>(qp + 16 * s + 8 * h);
     dof[s] = *reinterpret_cast<const v8*>(dop + 16 * s + 8 * h);
     const v8 of = *reinterpret_cast<const v8*>(op + 16 * s + 8 * h);
@@ -899,12 +947,12 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 
   const e* kbase = reinterpret_cast<const e*>(p.k) + (int64_t)kvh * p.kv_sh;
   const e* vbase = reinterpret_cast<const e*>(p.v) + (int64_t)kvh * p.v_sh;
-  constexpr int NW = DTA_DMA_WAVES(HPB), BUF = 2 * TILE_BYTES + SE_BYTES;
+  constexpr int NW = DTA_DMA_WAVES(HPB), BUF = 2 * TB + SE_BYTES;
   DTA_KV_OFFSETS(NW)                      // K/V tiles by LDS-DMA as in the forward (no staging registers, no ds_write)
 
-  f32x16 DQ[4];
+  f32x16 DQ[NDB];
 #pragma unroll
-  for (int db = 0; db < 4; ++db)
+  for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int g = 0; g < 16; ++g) DQ[db][g] = 0.f;
   const float c = p.scale * LOG2E;
@@ -923,8 +971,8 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
     while (true) {
       int nk0 = 0, nkend = 0; bool nmask = false;
       if (has_next) { nk0 = it.k0; nkend = it.kend; nmask = it.masked(); DTA_KV_DMA(smem + (cur ^ 1) * BUF, it.k0, NW) }
-      const char* Ks = smem + cur * BUF; const char* Vs = Ks + TILE_BYTES;
-      const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TILE_BYTES);
+      const char* Ks = smem + cur * BUF; const char* Vs = Ks + TB;
+      const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TB);
       // one 32-key block at a time keeps S^T/dP^T at 32 live accumulators (2 waves per SIMD need <= 256 registers)
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -932,20 +980,20 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 #pragma unroll
         for (int g = 0; g < 16; ++g) X[g] = 0.f;
         {                                                  // fragment reads one k-step ahead of the MFMAs that use them
-          v8 kf_ = row_frag<v8>(Ks, 32 * kb + r, h), vf_ = row_frag<v8>(Vs, 32 * kb + r, h);
+          v8 kf_ = row_frag<v8, DH>(Ks, 32 * kb + r, h), vf_ = row_frag<v8, DH>(Vs, 32 * kb + r, h);
 #pragma unroll
-          for (int s = 0; s < 8; ++s) {
+          for (int s = 0; s < NKS; ++s) {
             v8 nk_ = kf_, nv_ = vf_;
-            if (s < 7) { nk_ = row_frag<v8>(Ks, 32 * kb + r, 2 * s + 2 + h); nv_ = row_frag<v8>(Vs, 32 * kb + r, 2 * s + 2 + h); }
+            if (s < NKS - 1) { nk_ = row_frag<v8, DH>(Ks, 32 * kb + r, 2 * s + 2 + h); nv_ = row_frag<v8, DH>(Vs, 32 * kb + r, 2 * s + 2 + h); }
             X = T::mma(kf_, qf[s], X);
             DP = T::mma(vf_, dof[s], s == 0 ? DI : DP);
             kf_ = nk_; vf_ = nv_;
           }
           // hipcc's scheduler otherwise sinks every read pair directly in front of its two MFMAs (one register pair re-used: each MFMA
-          // pair then waits a full LDS latency): pin the order {4 reads} {2 MFMA, 2 reads} x 6 {4 MFMA}
+          // pair then waits a full LDS latency): pin the order {4 reads} {2 MFMA, 2 reads} x (NKS - 2) {4 MFMA}
           __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
-          for (int i_ = 0; i_ < 6; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
+          for (int i_ = 0; i_ < NKS - 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
           __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         }
         // dS^T / scale = P ∘ (dP − delta); the interval mask only on tiles of runs flagged partial
@@ -973,7 +1021,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
         for (int s2 = 0; s2 < 2; ++s2) {
           const v8 db_ = pack_half<DT>(X, s2);
 #pragma unroll
-          for (int db = 0; db < 4; ++db) DQ[db] = T::mma(tr_frag<v8>(Ks, 32 * kb + 16 * s2, db, lane), db_, DQ[db]);
+          for (int db = 0; db < NDB; ++db) DQ[db] = T::mma(tr_frag<v8, DH>(Ks, 32 * kb + 16 * s2, db, lane), db_, DQ[db]);
         }
       }
       DMA_WAIT(); __syncthreads();
@@ -985,7 +1033,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
   if (qrow < p.Tq) {
     e* dqp = reinterpret_cast<e*>(p.dq) + (int64_t)qrow * p.dq_st + (int64_t)hq * p.dq_sh;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+    for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         v4 w;
@@ -1014,30 +1062,32 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 #if DTA_KV2_PIN == 2      /* just-in-time reads, but the two chains alternating: {delta row} {2 reads, 1 MFMA} x 16 */
 #define DTA_KV2_PIN_ORDER                                                                                  \
     __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                                     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) { __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
+    _Pragma("unroll") for (int i_ = 0; i_ < 2 * NKS; ++i_) { __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
 #elif DTA_KV2_PIN
 #define DTA_KV2_PIN_ORDER                                                                                  \
     __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);                                                    \
-    _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 4, 0); } \
+    _Pragma("unroll") for (int i_ = 0; i_ < NKS - 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 4, 0); } \
     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
 #else
 #define DTA_KV2_PIN_ORDER
 #endif
 
-constexpr int KV2_FRAGS = 4 * 16384;                                // 4 key slots x {K: 8 fragments x 1 KiB, V: 8 x 1 KiB}
-constexpr int KV2_BUF = 2 * TILE_BYTES + 512;
-constexpr int KV2_LDS = KV2_FRAGS + 2 * KV2_BUF + 16;                   // + se_min[4]: ONE __shared__ object (a second one makes hipcc drain vmcnt in front of every LDS read)
+template <int D> constexpr int kv2_slot() { return 2 * (D / 16) * 1024; }    // one key slot: {K: D/16 fragments x 1 KiB, V: D/16 x 1 KiB}
+template <int D> constexpr int kv2_frags() { return 4 * kv2_slot<D>(); }    // 4 key slots
+template <int D> constexpr int kv2_buf() { return 2 * tile_bytes<D>() + 512; }
+template <int D> constexpr int kv2_lds() { return kv2_frags<D>() + 2 * kv2_buf<D>() + 16; }   // + se_min[4]: ONE __shared__ object (a second one makes hipcc drain vmcnt in front of every LDS read)
 
-template <int DT>
+template <int DT, int DH>
 __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int KT = 128;
-  __shared__ __attribute__((aligned(16))) char smem_all[KV2_LDS];
+  constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32, KV2_FRAGS = kv2_frags<DH>(), KV2_BUF = kv2_buf<DH>(), KSLOT = kv2_slot<DH>();
+  __shared__ __attribute__((aligned(16))) char smem_all[kv2_lds<DH>()];
   const int tid8 = threadIdx.x, tid = tid8 & 255, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid8 >> 6);       // 0..7
   DTA_PRIO_YOUNGER_HALF(wave8)
   const int grp = wave8 >> 2, wave = wave8 & 3;
-  char* kvs = smem_all + wave * 16384;                               // this key slot's K fragments (+8192: V)
+  char* kvs = smem_all + wave * KSLOT;                               // this key slot's K fragments (+KSLOT/2: V)
   char* smem = smem_all + KV2_FRAGS;                                 // the Q/dO buffers
   const int bid = blockIdx.x;
   const int kvh = bid % p.Hkv; const int unit = bid / p.Hkv;
@@ -1054,9 +1104,9 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
       const e* kp = reinterpret_cast<const e*>(p.k) + (int64_t)kc * p.kv_st + (int64_t)kvh * p.kv_sh;
       const e* vp = reinterpret_cast<const e*>(p.v) + (int64_t)kc * p.v_st + (int64_t)kvh * p.v_sh;
 #pragma unroll
-      for (int s = 0; s < 8; ++s) {
+      for (int s = 0; s < NKS; ++s) {
         *reinterpret_cast<v8*>(kvs + s * 1024 + lane * 16) = *reinterpret_cast<const v8*>(kp + 16 * s + 8 * h);
-        *reinterpret_cast<v8*>(kvs + 8192 + s * 1024 + lane * 16) = *reinterpret_cast<const v8*>(vp + 16 * s + 8 * h);
+        *reinterpret_cast<v8*>(kvs + KSLOT / 2 + s * 1024 + lane * 16) = *reinterpret_cast<const v8*>(vp + 16 * s + 8 * h);
       }
     } }
   int* se_min_s = reinterpret_cast<int*>(smem_all + KV2_FRAGS + 2 * KV2_BUF);
@@ -1067,10 +1117,10 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
   __syncthreads();
   const int se_min = __builtin_amdgcn_readfirstlane(min(min(se_min_s[0], se_min_s[1]), min(se_min_s[2], se_min_s[3])));
 
-  const FragOffs offs = frag_offsets(lane);
-  f32x16 DK[4], DV[4];
+  const FragOffsT<DH> offs = frag_offsets<DH>(lane);
+  f32x16 DK[NDB], DV[NDB];
 #pragma unroll
-  for (int db = 0; db < 4; ++db)
+  for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int g = 0; g < 16; ++g) { DK[db][g] = 0.f; DV[db][g] = 0.f; }
 
@@ -1084,14 +1134,15 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
   const int total = ntile * p.group;
   const float c = p.scale * LOG2E;
 
-  // tile DMA: 16 one-KiB pieces per image over 8 waves = 2 per wave per image (piece = 2*wave8 + i: rows 8*wave8 + 4*i ..);
-  // lse / delta rows (64 floats each) by 4-byte DMA from waves 0 / 1.
-  uint32_t voff_q[2], voff_d[2];
+  // tile DMA: DH/8 one-KiB pieces per image over 8 waves = NP = DH/64 per wave per image (D = 128: piece = 2*wave8 + i, rows 8*wave8 + 4*i ..;
+  // D = 64: piece = wave8, rows 8*wave8 ..); lse / delta rows (64 floats each) by 4-byte DMA from waves 0 / 1.
+  constexpr int NP = DH / 64;
+  uint32_t voff_q[NP], voff_d[NP];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row_ = 8 * wave8 + 4 * i + (lane >> 4);
-    voff_q[i] = dma_src_off(row_, row_, lane, p.q_st, sizeof(e));
-    voff_d[i] = dma_src_off(row_, row_, lane, p.o_st, sizeof(e));
+  for (int i = 0; i < NP; ++i) {
+    const int row_ = 8 * wave8 + (512 / DH) * i + (lane >> dma_lane_row_shift<DH>());
+    voff_q[i] = dma_src_off_d<DH>(row_, row_, lane, p.q_st, sizeof(e));
+    voff_d[i] = dma_src_off_d<DH>(row_, row_, lane, p.o_st, sizeof(e));
   }
   const uint32_t lds_tiles = lds_addr(smem);
   // scalar cursor of the NEXT tile to stage: byte offsets of its first row in q / dout and float offset of its row
@@ -1105,22 +1156,24 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
 #define KV2_DMA(B)                                                                                         \
   { const uint32_t lb_ = lds_tiles + (uint32_t)(B) * KV2_BUF;                                              \
     if (wave8 < 2) { int qr_ = row_n + lane; qr_ = qr_ < p.Tq ? qr_ : p.Tq - 1;   /* wave 0: lse[64], wave 1: delta[64] */ \
-      dma_dword((uint32_t)qr_ * 4u, (wave8 == 0 ? p.lse_r : p.delta) + c_cur, lb_ + 2 * TILE_BYTES + wave8 * 256); } \
-    uint32_t oq0_ = voff_q[0], oq1_ = voff_q[1], od0_ = voff_d[0], od1_ = voff_d[1];                       \
+      dma_dword((uint32_t)qr_ * 4u, (wave8 == 0 ? p.lse_r : p.delta) + c_cur, lb_ + 2 * TB + wave8 * 256); } \
+    uint32_t oq_[NP], od_[NP];                                                                             \
+    _Pragma("unroll") for (int i_ = 0; i_ < NP; ++i_) { oq_[i_] = voff_q[i_]; od_[i_] = voff_d[i_]; }      \
     if (row_n + 64 > p.Tq) {                       /* ragged last tile of the tensor: clamp the row per lane */ \
-      const int ra_ = 8 * wave8 + (lane >> 4), rb_ = ra_ + 4;                                              \
-      const int ca_ = row_n + ra_ < p.Tq ? ra_ : p.Tq - 1 - row_n, cb_ = row_n + rb_ < p.Tq ? rb_ : p.Tq - 1 - row_n; \
-      oq0_ = dma_src_off(ca_, ra_, lane, p.q_st, sizeof(e)); oq1_ = dma_src_off(cb_, rb_, lane, p.q_st, sizeof(e)); \
-      od0_ = dma_src_off(ca_, ra_, lane, p.o_st, sizeof(e)); od1_ = dma_src_off(cb_, rb_, lane, p.o_st, sizeof(e)); } \
-    dma_pair2(oq0_, oq1_, reinterpret_cast<const char*>(p.q) + q_cur, od0_, od1_, reinterpret_cast<const char*>(p.dout) + d_cur, lb_ + wave8 * 2048); \
+      _Pragma("unroll") for (int i_ = 0; i_ < NP; ++i_) {                                                  \
+        const int ra_ = 8 * wave8 + (512 / DH) * i_ + (lane >> dma_lane_row_shift<DH>());                  \
+        const int ca_ = row_n + ra_ < p.Tq ? ra_ : p.Tq - 1 - row_n;                                       \
+        oq_[i_] = dma_src_off_d<DH>(ca_, ra_, lane, p.q_st, sizeof(e)); od_[i_] = dma_src_off_d<DH>(ca_, ra_, lane, p.o_st, sizeof(e)); } } \
+    if constexpr (NP == 2) dma_pair2(oq_[0], oq_[1], reinterpret_cast<const char*>(p.q) + q_cur, od_[0], od_[1], reinterpret_cast<const char*>(p.dout) + d_cur, lb_ + wave8 * 2048); \
+    else dma_one2<TB>(oq_[0], reinterpret_cast<const char*>(p.q) + q_cur, od_[0], reinterpret_cast<const char*>(p.dout) + d_cur, lb_ + wave8 * 1024); \
     ++ti_n; row_n += 64; q_cur += q_step; d_cur += d_step;                                                 \
     if (ti_n >= ntile) { ti_n = 0; row_n = qbeg - p.q_offset; q_cur += q_wrap; d_cur += d_wrap; c_cur += p.Tq; } }
 
   // Per-lane LDS byte offsets of every fragment read of this wave group inside a tile buffer, computed once; the tile loop is
   // unrolled over the two buffers so that the buffer offset is an instruction immediate (no per-tile address VALU).
-  int ar[8], at[8];
+  int ar[NKS], at[NKS];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { ar[j] = offs.row[j] + grp * (32 * 256); at[j] = offs.tr[j] + grp * (32 * 256); }
+  for (int j = 0; j < NKS; ++j) { ar[j] = offs.row[j] + grp * (64 * DH); at[j] = offs.tr[j] + grp * (64 * DH); }
   const int rc_off = (32 * grp + 4 * h) * 4;                            // this lane's first row constant (lse / -delta) inside a buffer
 
   // one 64-row query tile out of buffer BUFI (compile-time)
@@ -1131,7 +1184,7 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
     if (ti_c >= ntile) ti_c = 0;                                                                           \
     if (idx + 1 < total) KV2_DMA(1 - (BUFI))      /* lands while this tile computes; waited for at the tile end */ \
     const char* tb = smem + (BUFI) * KV2_BUF;                                                              \
-    const char* rc = tb + 2 * TILE_BYTES + rc_off;                                                         \
+    const char* rc = tb + 2 * TB + rc_off;                                                         \
     const int qi0 = qbeg + 64 * ti + 32 * grp;                       /* packed index of this group's first row */ \
     const bool full = (qbeg + 64 * ti >= k0 + KT - 1) && (qbeg + 64 * ti + 63 < se_min);   /* workgroup-uniform: no mask needed */ \
     /* S starts at 0 (inline constant); dP starts at -delta, read from LDS straight into the accumulator registers:    \
@@ -1142,11 +1195,11 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
       DP[4 * gq] = d4.x; DP[4 * gq + 1] = d4.y; DP[4 * gq + 2] = d4.z; DP[4 * gq + 3] = d4.w;              \
     }                                                                                                      \
     _Pragma("unroll") for (int g = 0; g < 16; ++g) S[g] = 0.f;                                             \
-    _Pragma("unroll") for (int s = 0; s < 8; ++s) {                                                        \
+    _Pragma("unroll") for (int s = 0; s < NKS; ++s) {                                                      \
       const v8 aq = *reinterpret_cast<const v8*>(tb + ar[s]);                                              \
-      const v8 ad = *reinterpret_cast<const v8*>(tb + ar[s] + TILE_BYTES);                                 \
+      const v8 ad = *reinterpret_cast<const v8*>(tb + ar[s] + TB);                                         \
       const v8 kfs = *reinterpret_cast<const v8*>(kvs + s * 1024 + lane * 16);                             \
-      const v8 vfs = *reinterpret_cast<const v8*>(kvs + 8192 + s * 1024 + lane * 16);                      \
+      const v8 vfs = *reinterpret_cast<const v8*>(kvs + KSLOT / 2 + s * 1024 + lane * 16);                 \
       S = T::mma(aq, kfs, S); DP = T::mma(ad, vfs, DP);                                                    \
     }                                                                                                      \
     DTA_KV2_PIN_ORDER                                                                                      \
@@ -1172,9 +1225,9 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
     }                                                                                                      \
     _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                                     \
       const v8 pb = pack_half<DT>(S, s2), sbf = pack_half<DT>(DP, s2);                                     \
-      _Pragma("unroll") for (int db = 0; db < 4; ++db) {                                                   \
-        const v8 adt = tr_pair<v8>(tb + at[db] + TILE_BYTES + 4096 * s2, tb + at[4 + db] + TILE_BYTES + 4096 * s2); \
-        const v8 aqt = tr_pair<v8>(tb + at[db] + 4096 * s2, tb + at[4 + db] + 4096 * s2);                  \
+      _Pragma("unroll") for (int db = 0; db < NDB; ++db) {                                                 \
+        const v8 adt = tr_pair<v8>(tb + at[db] + TB + 32 * DH * s2, tb + at[NDB + db] + TB + 32 * DH * s2); \
+        const v8 aqt = tr_pair<v8>(tb + at[db] + 32 * DH * s2, tb + at[NDB + db] + 32 * DH * s2);          \
         DV[db] = T::mma(adt, pb, DV[db]); DK[db] = T::mma(aqt, sbf, DK[db]);                               \
       }                                                                                                    \
     }                                                                                                      \
@@ -1199,7 +1252,7 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
     // group 1 hands its partial sums to group 0 through LDS, 32 accumulators (one d-block of dK and dV) at a time
     float* red = reinterpret_cast<float*>(smem_all);
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
+    for (int db = 0; db < NDB; ++db) {
       if (grp == 1) {
 #pragma unroll
         for (int g = 0; g < 16; ++g) { red[g * 256 + tid] = DK[db][g]; red[(16 + g) * 256 + tid] = DV[db][g]; }
@@ -1214,26 +1267,26 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
     if (grp == 1) return;
   }
 #pragma unroll
-  for (int db = 0; db < 4; ++db)
+  for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int g = 0; g < 16; ++g) DK[db][g] *= p.scale;
   const int kloc = wave * 32 + r;
   if (slab >= 0) {
-    float* ws = p.dkv_ws + ((int64_t)slab * p.Hkv + kvh) * (2 * KT * 128) + (int64_t)kloc * 128;
+    float* ws = p.dkv_ws + ((int64_t)slab * p.Hkv + kvh) * (2 * KT * DH) + (int64_t)kloc * DH;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+    for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const int d = 32 * db + 8 * gq + 4 * h;
         *reinterpret_cast<float4*>(ws + d) = make_float4(DK[db][4 * gq], DK[db][4 * gq + 1], DK[db][4 * gq + 2], DK[db][4 * gq + 3]);
-        *reinterpret_cast<float4*>(ws + KT * 128 + d) = make_float4(DV[db][4 * gq], DV[db][4 * gq + 1], DV[db][4 * gq + 2], DV[db][4 * gq + 3]);
+        *reinterpret_cast<float4*>(ws + KT * DH + d) = make_float4(DV[db][4 * gq], DV[db][4 * gq + 1], DV[db][4 * gq + 2], DV[db][4 * gq + 3]);
       }
   } else if (kidx < p.Tk && p.accumulate == 2) {
     // fp32 accumulation buffers (the grad-KV stack of the block-wise engine: hundreds of adds per row stay exact to fp32)
     float* dkp = reinterpret_cast<float*>(p.dk) + (int64_t)kidx * p.dkv_st + (int64_t)kvh * p.dkv_sh;
     float* dvp = reinterpret_cast<float*>(p.dv) + (int64_t)kidx * p.dkv_st + (int64_t)kvh * p.dkv_sh;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+    for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const int d = 32 * db + 8 * gq + 4 * h;
@@ -1247,7 +1300,7 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
     e* dkp = reinterpret_cast<e*>(p.dk) + (int64_t)kidx * p.dkv_st + (int64_t)kvh * p.dkv_sh;
     e* dvp = reinterpret_cast<e*>(p.dv) + (int64_t)kidx * p.dkv_st + (int64_t)kvh * p.dkv_sh;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+    for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const int d = 32 * db + 8 * gq + 4 * h;
@@ -1269,18 +1322,19 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
 // Sums the fp32 slabs of every split key tile in a fixed order and writes dK/dV (bitwise reproducible).
 // dkv_splits[s] = {key tile, first slab, number of slabs, 0}.
 constexpr int FIN_SPLIT = 8;          // blockIdx.y: each (split key tile, kv head) is summed by 8 workgroups — the sums are load-latency bound
-template <int DT>
+template <int DT, int DH>
 __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_finalize_kernel(AttnParams p) {
   using e = typename Ty<DT>::e; using v4 = typename Ty<DT>::v4;
   const int KT = p.ktile;
   const int kvh = blockIdx.x % p.Hkv, sp = blockIdx.x / p.Hkv;
   const int kt = p.dkv_splits[4 * sp], first = p.dkv_splits[4 * sp + 1], n = p.dkv_splits[4 * sp + 2];
-  const int per = 2 * KT * 32 / FIN_SPLIT;                                // float4 indices per workgroup
-  const float* ws0 = p.dkv_ws + ((int64_t)first * p.Hkv + kvh) * (2 * KT * 128);
-  const int64_t slab_st = (int64_t)p.Hkv * (2 * KT * 128);
+  constexpr int Q4 = DH / 4, Q4_SHIFT = DH == 128 ? 5 : 4;             // float4 per D-wide row
+  const int per = 2 * KT * Q4 / FIN_SPLIT;                                // float4 indices per workgroup
+  const float* ws0 = p.dkv_ws + ((int64_t)first * p.Hkv + kvh) * (2 * KT * DH);
+  const int64_t slab_st = (int64_t)p.Hkv * (2 * KT * DH);
   for (int i = blockIdx.y * per + threadIdx.x; i < (blockIdx.y + 1) * per; i += 256) {   // float4 index inside a slab
-    const int which = i / (KT * 32), rem = i - which * KT * 32;
-    const int key = rem >> 5, d = (rem & 31) << 2;
+    const int which = i / (KT * Q4), rem = i - which * KT * Q4;
+    const int key = rem >> Q4_SHIFT, d = (rem & (Q4 - 1)) << 2;
     const int kidx = kt * KT + key;
     if (kidx >= p.Tk) continue;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1313,6 +1367,18 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_finalize_kernel(AttnPar
   }
 }
 
+// the backward launches of one (dtype, head_dim): dQ (head pairs, then the odd head alone), dK/dV, and the slab finalize
+template <int DT, int DH>
+void launch_bwd(const AttnParams& p, const AttnParams& pp, const AttnParams& ps, int npair, dim3 gqp, dim3 gqs, int ndkv, bool fin, int n_splits,
+                int which, hipStream_t st) {
+  if (which & 1) {
+    if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 2, DH>), gqp, dim3(512), 0, st, pp);
+    if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 1, DH>), gqs, dim3(256), 0, st, ps);
+  }
+  if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DT, DH>), dim3(ndkv * p.Hkv), dim3(512), 0, st, p);
+  if (fin && p.dkv_units && n_splits > 0) hipLaunchKernelGGL((tree_attn_bwd_dkv_finalize_kernel<DT, DH>), dim3(n_splits * p.Hkv, FIN_SPLIT), dim3(256), 0, st, p);
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -1324,11 +1390,11 @@ extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v,
                                     float scale, int32_t dtype, void* stream) {
   if (!q || !k || !v || !out || !lse || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
   if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
-  if (head_dim != 128 || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32)) return DTA_EUNSUPPORTED;
+  if ((head_dim != 128 && head_dim != 64) || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32)) return DTA_EUNSUPPORTED;
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (q_st | q_sh | kv_st | kv_sh | v_st | v_sh | o_st | o_sh) % 8 != 0) return DTA_EALIGN;
   if (dtype == DTA_F32) {                                    // fp32 models: the plain-FMA correctness path (tree_attn_f32.hip)
     DTA_REFUSE_IF_PRIOR_ERROR();
-    return dta_attn_fwd_f32(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
+    return dta_attn_fwd_f32(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
                             scale, static_cast<hipStream_t>(stream));
   }
   // the tile DMA addresses a 64-row tile as scalar base + 32-bit lane offset: token strides must keep 64 rows inside 4 GiB
@@ -1347,22 +1413,30 @@ extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v,
     p.hgroups = npair; p.head0 = 0;
     dim3 grid(nqt * Hkv * npair), block(512);
     static const int form = [] { const char* e_ = getenv("DTA_FWD_FORM"); return e_ ? atoi(e_) : DTA_FWD_FORM_DEFAULT; }();   // 1: 8 waves, one head each; 3: 4 waves, two heads each, one wave per SIMD; 4: 8 waves, head groups half a tile apart (A/B switch)
-    if (form == 3) {
+    if (head_dim == 64) {                                      // the A/B forms exist for head_dim 128 only
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 64>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 64>), grid, block, 0, st, p);
+    } else if (form == 3) {
       if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd3_kernel<DTA_BF16>), grid, dim3(256), 0, st, p);
       else hipLaunchKernelGGL((tree_attn_fwd3_kernel<DTA_F16>), grid, dim3(256), 0, st, p);
     } else if (form == 4) {
       if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd4_kernel<DTA_BF16>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((tree_attn_fwd4_kernel<DTA_F16>), grid, block, 0, st, p);
     } else {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 128>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 128>), grid, block, 0, st, p);
     }
   }
   if (p.group % 2) {
     p.hgroups = 1; p.head0 = p.group - 1;
     dim3 grid(nqt * Hkv), block(256);
-    if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1>), grid, block, 0, st, p);
+    if (head_dim == 64) {
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 64>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 64>), grid, block, 0, st, p);
+    } else {
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 128>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 128>), grid, block, 0, st, p);
+    }
   }
   return DTA_LAUNCH_STATUS();
 }
@@ -1380,13 +1454,13 @@ extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v,
   if (!q || !k || !v || !out || !dout || !lse || !delta || !dq || !dk || !dv || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
   if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
   if (dkv_units && (n_units <= 0 || n_splits < 0 || (n_splits > 0 && (!dkv_splits || !dkv_ws)))) return DTA_EINVAL;
-  if (head_dim != 128 || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) || accumulate < 0 || accumulate > 2) return DTA_EUNSUPPORTED;
+  if ((head_dim != 128 && head_dim != 64) || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) || accumulate < 0 || accumulate > 2) return DTA_EUNSUPPORTED;
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) || !aligned16(dv) ||
       (q_st | q_sh | kv_st | kv_sh | v_st | v_sh | o_st | o_sh | dq_st | dq_sh | dkv_st | dkv_sh) % 8 != 0) return DTA_EALIGN;
   if (dtype == DTA_F32) {
     if ((which & 7) == 0) return DTA_EINVAL;
     DTA_REFUSE_IF_PRIOR_ERROR();
-    return dta_attn_bwd_f32(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv,
+    return dta_attn_bwd_f32(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
                             q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which,
                             static_cast<hipStream_t>(stream));
   }
@@ -1410,31 +1484,24 @@ extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v,
   AttnParams pp = p, ps = p;
   pp.hgroups = npair; pp.head0 = 0; ps.hgroups = 1; ps.head0 = p.group - 1;
   const dim3 gqp(nqt * Hkv * (npair > 0 ? npair : 1)), gqs(nqt * Hkv);
-  if (dtype == DTA_BF16) {
-    if (which & 1) {
-      if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DTA_BF16, 2>), gqp, dim3(512), 0, st, pp);
-      if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DTA_BF16, 1>), gqs, dim3(256), 0, st, ps);
-    }
-    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DTA_BF16>), dim3(ndkv * Hkv), dim3(512), 0, st, p);
-    if (fin && dkv_units && n_splits > 0) hipLaunchKernelGGL(tree_attn_bwd_dkv_finalize_kernel<DTA_BF16>, dim3(n_splits * Hkv, FIN_SPLIT), dim3(256), 0, st, p);
+  if (head_dim == 64) {
+    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 64>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    else launch_bwd<DTA_F16, 64>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
   } else {
-    if (which & 1) {
-      if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DTA_F16, 2>), gqp, dim3(512), 0, st, pp);
-      if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DTA_F16, 1>), gqs, dim3(256), 0, st, ps);
-    }
-    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DTA_F16>), dim3(ndkv * Hkv), dim3(512), 0, st, p);
-    if (fin && dkv_units && n_splits > 0) hipLaunchKernelGGL(tree_attn_bwd_dkv_finalize_kernel<DTA_F16>, dim3(n_splits * Hkv, FIN_SPLIT), dim3(256), 0, st, p);
+    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 128>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    else launch_bwd<DTA_F16, 128>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
   }
   return DTA_LAUNCH_STATUS();
 }
 
-// Token-major convenience forms declared in dta.h: head stride = 128 elements.
+// Token-major convenience forms declared in dta.h: head stride = 128 elements, so head_dim 128 only (other head dims: the _ex forms).
 extern "C" int dta_tree_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
                                  const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                                  int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
                                  int64_t q_stride_t, int64_t kv_stride_t, int64_t o_stride_t,
                                  float scale, int32_t dtype, void* stream) {
-  return dta_tree_attn_fwd_ex(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim,
+  // any other head_dim goes on as 0: the _ex form's argument checks come first, then DTA_EUNSUPPORTED, as before head_dim 64 existed
+  return dta_tree_attn_fwd_ex(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim == 128 ? 128 : 0,
                               q_stride_t, 128, kv_stride_t, 128, kv_stride_t, 128, o_stride_t, 128, scale, dtype, stream);
 }
 
@@ -1447,6 +1514,6 @@ extern "C" int dta_tree_attn_bwd(const void* q, const void* k, const void* v, co
                                  int64_t dq_stride_t, int64_t dkv_stride_t,
                                  float scale, int32_t dtype, int32_t accumulate, void* stream) {
   return dta_tree_attn_bwd_ex(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend,
-                              Tq, Tk, q_offset, Hq, Hkv, head_dim, q_stride_t, 128, kv_stride_t, 128, kv_stride_t, 128, o_stride_t, 128,
+                              Tq, Tk, q_offset, Hq, Hkv, head_dim == 128 ? 128 : 0, q_stride_t, 128, kv_stride_t, 128, kv_stride_t, 128, o_stride_t, 128,
                               dq_stride_t, 128, dkv_stride_t, 128, scale, dtype, accumulate, 3, nullptr, 0, nullptr, 0, nullptr, stream);
 }

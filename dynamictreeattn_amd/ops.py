@@ -237,7 +237,7 @@ class _TreeAttention(torch.autograd.Function):
         q, k, v, out, lse = ctx.saved_tensors
         Hq, Hkv = q.shape[1], k.shape[1]
         if ATTN_FUSED_GRAD and q.shape[0] == k.shape[0]:
-            # the three gradients side by side in ONE [T, Hq+2Hkv, 128] buffer, the layout of the fused projection's gradient: _QKVPrep's
+            # the three gradients side by side in ONE [T, Hq+2Hkv, D] buffer, the layout of the fused projection's gradient: _QKVPrep's
             # backward then transforms dq and dk in place and hands the buffer on - no gather of dv (0.65 ms per step at tau2 size)
             fused = torch.empty((q.shape[0], Hq + 2 * Hkv, q.shape[2]), dtype=q.dtype, device=q.device)
             dq, dk, dv = fused[:, :Hq], fused[:, Hq:Hq + Hkv], fused[:, Hq + Hkv:]
@@ -276,8 +276,8 @@ class _StackAttention(torch.autograd.Function):
 
 
 def stack_attention(q, k_new, v_new, kst, vst, gk, gv, start: int, scale: Optional[float] = None):
-    """q [B,Hq,128], k_new/v_new [B,Hkv,128] at stack positions start..start+B-1; kst/vst [cap,Hkv,128] (model dtype),
-    gk/gv [cap,Hkv,128] fp32 grad stacks (may be None under no_grad) -> out [B,Hq,128]."""
+    """q [B,Hq,D], k_new/v_new [B,Hkv,D] at stack positions start..start+B-1; kst/vst [cap,Hkv,D] (model dtype),
+    gk/gv [cap,Hkv,D] fp32 grad stacks (may be None under no_grad) -> out [B,Hq,D] (D = head_dim, 64 or 128)."""
     if q.dtype not in _DT:
         raise TypeError("stack_attention supports bf16 / f16 / f32 (got %s)" % q.dtype)
     scale = q.shape[-1] ** -0.5 if scale is None else scale
@@ -285,7 +285,7 @@ def stack_attention(q, k_new, v_new, kst, vst, gk, gv, start: int, scale: Option
 
 
 def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, meta: TreeAttnMeta, scale: Optional[float] = None) -> torch.Tensor:
-    """q [T,Hq,128], k/v [T,Hkv,128] packed in DFS pre-order -> out [T,Hq,128].  Differentiable."""
+    """q [T,Hq,D], k/v [T,Hkv,D] packed in DFS pre-order -> out [T,Hq,D] (D = head_dim, 64 or 128).  Differentiable."""
     if q.dtype not in _DT:
         raise TypeError("tree_attention supports bf16 / f16 / f32 (got %s)" % q.dtype)
     scale = q.shape[-1] ** -0.5 if scale is None else scale
@@ -692,12 +692,12 @@ class _QKVPrep(torch.autograd.Function):
 
 def qkv_prep(qkv: torch.Tensor, wq: Optional[torch.Tensor], wk: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float,
              Hq: int, Hkv: int):
-    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, 128]."""
+    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D]."""
     return _QKVPrep.apply(qkv, wq, wk, cos_sin, eps, Hq, Hkv)
 
 
 def qk_norm_rope(x: torch.Tensor, w: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float) -> torch.Tensor:
-    """x [T, NH, 128] -> RoPE(RMSNorm_128(x) * w) at the positions encoded in cos_sin [T,128] (fp32)."""
+    """x [T, NH, D] (D = 64 or 128) -> RoPE(RMSNorm_D(x) * w) at the positions encoded in cos_sin [T,D] (fp32)."""
     return _QKNormRope.apply(x, w, cos_sin, eps)
 
 

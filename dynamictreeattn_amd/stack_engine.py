@@ -6,7 +6,7 @@ per token and layer) alive; on deep-and-wide tries with the larger models that e
 `block_size` keeps fitting: its state is the KV stack of the CURRENT root-to-leaf path (tte:108-131) plus the activations
 of one block.  This module restores that bound:
 
-* state: K/V stacks `[max_len, Hkv, 128]` per layer (model dtype) and fp32 grad-KV stacks, the path's token ids, its
+* state: K/V stacks `[max_len, Hkv, head_dim]` per layer (model dtype) and fp32 grad-KV stacks, the path's token ids, its
   log-prob / entropy values and the gradient side channels `g_lp`, `g_ent` (tte:77-131);
 * the walk is the reference's: for each leaf in DFS order pop the diverged tail of the previous leaf back to their LCP, then
   push the new leaf's tail — no-grad, and only the part that outlives the next pop (`cut_f1_tail`, tte:596-609);

@@ -27,6 +27,11 @@ QWEN3_14B = dict(vocab_size=151936, hidden_size=5120, intermediate_size=17408, n
                  num_attention_heads=40, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-6,
                  rope_theta=1000000.0)
 
+# Qwen2.5-0.5B(-Instruct) / Qwen2-0.5B geometry: head_dim 64, GQA group of 7, q/k/v biases, no q/k head norm, tied head
+QWEN25_0P5B = dict(vocab_size=151936, hidden_size=896, intermediate_size=4864, num_hidden_layers=24,
+                   num_attention_heads=14, num_key_value_heads=2, head_dim=64, rms_norm_eps=1e-6,
+                   rope_theta=1000000.0, qkv_bias=True, qk_norm=False, tie_word_embeddings=True)
+
 
 def as_tensors(seqs: List[List[int]]) -> List[torch.Tensor]:
     return [torch.tensor(s, dtype=torch.long) for s in seqs]

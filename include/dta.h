@@ -25,7 +25,7 @@ extern "C" {
 
 #define DTA_OK 0
 #define DTA_EINVAL (-1)      /* null pointer / negative size / inconsistent sizes */
-#define DTA_EUNSUPPORTED (-2)/* head_dim != 128, dtype not bf16/f16, Hq % Hkv != 0 ...  */
+#define DTA_EUNSUPPORTED (-2)/* head_dim not 64 / 128 (token-major attention forms: not 128), dtype not bf16/f16, Hq % Hkv != 0 ... */
 #define DTA_EALIGN (-3)      /* pointer or stride not 16-byte aligned */
 #define DTA_ELAUNCH (-4)     /* hipGetLastError() after the launch was not hipSuccess */
 #define DTA_EPRIOR (-5)      /* a HIP error was ALREADY pending on this thread when the entry point was called (an earlier
@@ -85,11 +85,15 @@ int dta_preorder_meta(const int64_t* tokens, const int64_t* leaf_tok_off,
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Tree attention (MFMA-bound).  head_dim must be 128; dtype DTA_BF16 or DTA_F16 (MFMA kernels), or DTA_F32 (every buffer fp32;
- * plain fp32 FMAs, one workgroup per 64 rows, split-Q work units ignored - the correctness path of fp32 models).
+ * Tree attention (MFMA-bound).  head_dim 128 or 64 (the _ex forms; the token-major forms dta_tree_attn_fwd / _bwd below take
+ * 128 only and return DTA_EUNSUPPORTED for any other head_dim); dtype DTA_BF16 or DTA_F16 (MFMA kernels), or DTA_F32 (every
+ * buffer fp32; plain fp32 FMAs, one workgroup per 64 rows, split-Q work units ignored - the correctness path of fp32 models).
+ * Alignment: every base pointer 16 bytes, every stride a multiple of 8 elements - a head row is 256 B (D = 128) or 128 B (D = 64),
+ * i.e. whole 16-byte chunks either way.
  *
- * q/out/dout/dq: [Tq, Hq, 128] with element strides (q_stride_t, 128); k/v/dk/dv: [Tk, Hkv, 128]
- * with (kv_stride_t, 128).  Query row i has packed index q_offset + i.  It attends key s iff
+ * Token-major forms: q/out/dout/dq: [Tq, Hq, 128] with element strides (q_stride_t, 128); k/v/dk/dv: [Tk, Hkv, 128]
+ * with (kv_stride_t, 128).  The _ex forms take every head stride explicitly ([.., H, D] rows of head_dim elements).
+ * Query row i has packed index q_offset + i.  It attends key s iff
  * s <= q_offset+i  &&  q_offset+i < subtree_end[s]   (subtree_end == NULL: no upper bound, i.e. the
  * rectangular-causal stack form of tree_training_engine.py:171-186 with q_offset = start).
  *
@@ -148,7 +152,7 @@ int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v, const void
                                           unless bit3; bit2: slab finalize alone (lets a profiler bracket each launch) */,
                          /* optional split of the dK/dV sweep into balanced work units (NULL: one per key tile):
                           * dkv_units[u] = {key tile, q_begin, q_end (packed), slab or -1}; units of a split key tile
-                          * write fp32 slabs [2][DTA_KTILE][128] into dkv_ws (slab-major, then kv head) which a finalize
+                          * write fp32 slabs [2][DTA_KTILE][head_dim] into dkv_ws (slab-major, then kv head) which a finalize
                           * launch sums in order: dkv_splits[s] = {key tile, first slab, n slabs, 0}. */
                          const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
                          void* stream);
@@ -193,15 +197,15 @@ int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, void* x_out
 int dta_rmsnorm_bwd_blocks(int32_t R);   /* rows of the dw_partial workspace [blocks, H] (float); caller sums dim 0.  H % 8 == 0; bwd: H <= 8192 */
 int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
                     int32_t R, int32_t H, int32_t dtype, void* stream);
-/* x: [T, NH, 128] with token stride x_stride_t; cos_sin: float [T, 128] = {cos[64], sin[64]} of the token's
- * depth; y: [T, NH, 128] contiguous; w (head-norm weight [128]) may be NULL = RoPE only. */
+/* head_dim D = 128 or 64.  x: [T, NH, D] with token stride x_stride_t; cos_sin: float [T, D] = {cos[D/2], sin[D/2]} of the token's
+ * depth (rotate-half pairs element i with i + D/2); y: [T, NH, D] contiguous; w (head-norm weight [D]) may be NULL = RoPE only. */
 int dta_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,
                          int32_t T, int32_t NH, int32_t head_dim, int64_t x_stride_t, float eps, int32_t dtype, void* stream);
-int dta_qk_norm_rope_bwd_blocks(int64_t n_heads_total);   /* rows of dw_partial [blocks, 128] */
+int dta_qk_norm_rope_bwd_blocks(int64_t n_heads_total);   /* rows of dw_partial [blocks, head_dim] (the same count for D = 64 and 128) */
 int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, const void* dy, const float* rstd,
                          void* dx, float* dw_partial, int32_t T, int32_t NH, int32_t head_dim,
                          int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t,
-                         int32_t dtype, void* stream);   /* dx: [T, NH, 128] with dx_stride_t elements between tokens (>= NH*128); dx == dy (same strides) is allowed: in place */
+                         int32_t dtype, void* stream);   /* dx: [T, NH, D] with dx_stride_t elements between tokens (>= NH*D); dx == dy (same strides) is allowed: in place */
 /* gate/up: [rows, cols] with `ld` elements between rows (they may be the two halves of one fused [rows, 2*cols]
  * projection output); y/dy: [rows, cols] contiguous; dgate/dup: `ld_grad` between rows. */
 int dta_swiglu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream);
@@ -216,7 +220,7 @@ int dta_transpose(const void* in, void* out, int64_t rows, int64_t cols, int64_t
 
 /* out[i] = round_to(out_dtype)( sum_{s < slabs} part[s * slab_stride + i]  + (extra ? extra[i] : 0) ),  i < n; all sums in fp32.
  * The reduction of weight-gradient partials fused with the rounding to the parameter dtype: the per-workgroup dw partials of
- * dta_rmsnorm_bwd / dta_qk_norm_rope_bwd (slabs = workgroups, n = H or 128) and the slices of the split-K weight-gradient GEMM
+ * dta_rmsnorm_bwd / dta_qk_norm_rope_bwd (slabs = workgroups, n = H or head_dim) and the slices of the split-K weight-gradient GEMM
  * (slabs = the split, n = out*in, extra = the product of the rows the equal slices leave over).  Stands where the reference's
  * autograd sums a weight's gradient over all rows of a model call in one GEMM (tree_training_engine.py:440).  `out` may not alias
  * `part` or `extra`.  Any n; the vector form is taken when slabs <= 16 and n, slab_stride are multiples of 4 with 16-byte aligned pointers. */

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the three tree-attention kernels on one tau2-16k-shaped packed trie
-(Qwen3-0.6B head geometry), random data, HIP-event timed.  Usage: python scripts/attn_bench.py [iters] [case]"""
+(Qwen3-0.6B head geometry by default), random data, HIP-event timed.
+Usage: python scripts/attn_bench.py [iters] [case] [Hq/Hkv/D]   e.g. 10 tau2 14/2/64 (Qwen2.5-0.5B heads, head_dim 64)"""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -11,7 +12,7 @@ from dynamictreeattn_amd.tree_training_engine import _PackedTrie
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 case = sys.argv[2] if len(sys.argv) > 2 else "tau2"
 dev = torch.device("cuda:0")
-Hq, Hkv, D = 16, 8, 128
+Hq, Hkv, D = (int(x) for x in (sys.argv[3] if len(sys.argv) > 3 else "16/8/128").split("/"))
 seqs = synth.as_tensors(synth.tau2(0) if case == "tau2" else synth.wide(1, branches=16, depth=8192) if case == "wide" else synth.config1(0))
 trie = TokenTrie(seqs); trie.backward_permute()
 pk = _PackedTrie(trie, dev)
@@ -41,4 +42,4 @@ fin = ms["bwd_dkv_finalize"]
 res["bwd_dkv_finalize"] = {"ms": round(fin[0] / fin[1], 4) if fin[1] else 0.0}
 tot = res["fwd"]["ms"] + res["bwd_dq"]["ms"] + res["bwd_dkv"]["ms"] + res["bwd_dkv_finalize"]["ms"]
 res["all_14HqD"] = {"ms": round(tot, 4), "TFLOPs": round(14 * Hq * D * pairs / (tot * 1e-3) / 1e12, 1)}
-print(json.dumps({"case": case, "T": T, "pairs": pairs, **res}))
+print(json.dumps({"case": case, "heads": f"{Hq}/{Hkv}", "head_dim": D, "T": T, "pairs": pairs, **res}))
