@@ -6,7 +6,6 @@ any number of arrays into ONE reusable page-locked staging buffer per device and
 returned tensors are views of one device buffer, each 16-byte aligned."""
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Sequence
 
 import numpy as np
@@ -24,7 +23,7 @@ def upload(arrays: Sequence[np.ndarray], device, dtype=np.int32) -> List[torch.T
     pads = [(-s) % per16 for s in sizes]
     total = sum(sizes) + sum(pads)
     tdt = torch.from_numpy(np.zeros(0, dt)).dtype
-    pageable = device.type != "cuda" or os.environ.get("DTA_STAGING") == "pageable"      # env: diagnostic A/B switch (blocking copies, as round 1)
+    pageable = device.type != "cuda"
     if pageable:
         flat = np.zeros(total, dt)
         host = torch.from_numpy(flat)

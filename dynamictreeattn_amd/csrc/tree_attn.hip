@@ -25,19 +25,11 @@
 // tile-end barrier, so a tile's DMA has the whole compute phase of the previous tile to land.
 //
 // Lane maps used here were verified on hardware by tests/micro/mfma_layout_probe.hip.
-// The round-1 ablation switches (-DDTA_ABL) and the retired 4-wave dK/dV kernel live in scripts/diag/ (not built).
+// The round-1 ablation switches (-DDTA_ABL) and the retired 4-wave dK/dV kernel live in scripts/diag/ (not built); the A/B forward
+// forms 3 and 4 were removed (last present in b0d42b7).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "dta_common.h"
-
-// Diagnostic build switch (-DDTA_PRIO_HALF=1): static priority for the second-dispatched half of an 8-wave workgroup (waves 4-7 lose every
-// issue arbitration by age; MI355X_MICROARCH.md "Two waves per SIMD", item 4).  Measured in round 3: see DESIGN.md §9c.
-#if defined(DTA_PRIO_HALF) && DTA_PRIO_HALF
-#define DTA_PRIO_YOUNGER_HALF(W) if ((W) >= 4) __builtin_amdgcn_s_setprio(1);
-#else
-#define DTA_PRIO_YOUNGER_HALF(W)
-#endif
 
 // Diagnostic build switch (-DDTA_STAMP=1): in-kernel s_memtime stamps at the segment boundaries of the forward's tile loop, summed per
 // wave in scalar registers and written to a debug buffer of their own (cdna_hip_programming.md §7 "In-kernel stamps"); scripts/fwd_stamps.py
@@ -59,18 +51,6 @@ extern "C" int dta_debug_set_stamp_buffer(void* p) { return hipMemcpyToSymbol(HI
 #define DTA_STAMP_STORE
 #endif
 
-// Waves of a forward / dQ workgroup that ISSUE the K/V tile DMA.  In an 8-wave workgroup the second-dispatched half (waves 4-7) loses every
-// issue arbitration on its SIMD and is the tile's critical path, while the first half waits a quarter of the tile at the barrier (stamps:
-// DESIGN.md §9c): -DDTA_DMA_OLDER_HALF=1 (diagnostic) lets waves 0-3 issue all 32 pieces (8 each) and the critical half none.  Measured:
-// the younger half's time moves from its DMA segment into its softmax / PV segments, the tile takes as long as before (zero-sum).
-#if defined(DTA_DMA_OLDER_HALF) && DTA_DMA_OLDER_HALF
-#define DTA_DMA_WAVES(HPB) 4
-#define DTA_DMA_GUARD(NW) if (wave < (NW))
-#else
-#define DTA_DMA_WAVES(HPB) (4 * (HPB))
-#define DTA_DMA_GUARD(NW)
-#endif
-
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -80,7 +60,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // native vector (HIP's uint4 class kept staging arrays in scratch)
 
 template <int DT> struct Ty;
 template <> struct Ty<DTA_BF16> {
@@ -104,19 +83,11 @@ struct AttnParams {
   float scale; int32_t accumulate; int32_t ktile;
 };
 
-#ifndef DTA_FWD_FORM_DEFAULT
-#define DTA_FWD_FORM_DEFAULT 1
-#endif
-constexpr int TILE_BYTES = 64 * 256;           // 64 rows x 128 x 2 B
 constexpr float LOG2E = 1.4426950408889634f;
 
-// Byte offset of 16-B chunk `ch` (0..15) of row `row` in a [rows][128 x 16-bit] image with 256-B rows.
-// The XOR makes both the 32x32x16 row reads (ds_read_b128) and the transposed reads conflict-free.
-__device__ __forceinline__ int img_off(int row, int ch) {
-  return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
-}
-
-// ---- head_dim 64: the same image with 128-B rows (8 chunks) --------------------------------------------------------
+// Byte offset of 16-B chunk `ch` of row `row` in a [rows][D x 16-bit] image.  head_dim 128: 256-B rows (16 chunks); the XOR makes both the
+// 32x32x16 row reads (ds_read_b128) and the transposed reads conflict-free.
+// head_dim 64: the same image with 128-B rows (8 chunks).
 // 16-B slot of chunk `pc` of row `row` in the 64 banks (256 B): 8 * (row & 1) + pc.  With pc = ch ^ f(row), f a 3-bit function of the row:
 //   ds_read_b128 row reads (lane = row r of a 32-row block, all lanes of a group read the same logical chunk): the four lane groups are the
 //     rows {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (x2 for the lane halves); in each, the 8 rows of one parity have 8 distinct
@@ -125,15 +96,15 @@ __device__ __forceinline__ int img_off(int row, int ch) {
 //     (and 4j+1, 4j+3) have the same parity and XOR the same aligned chunk quad onto itself unless bit 2 of f differs between them, i.e. bit 2
 //     of f must follow row bit 1 -> 16 distinct slots.
 //   f(row) = {row bit 1, row bit 3, row bit 2} (bits 2, 1, 0) meets both; it depends on row bits 1..3 only, so row offsets of 16 rows keep
-//   every lane's swizzle (the FragOffs property below).  The swizzle of the D = 128 image (16 chunks, 4-bit f of row bits 0..3) is unchanged.
+//   every lane's swizzle (the FragOffsT property below).  The swizzle of the D = 128 image (16 chunks, 4-bit f of row bits 0..3) is unchanged.
 __device__ __forceinline__ int swz64(int row) { return ((row & 2) << 1) | ((row >> 2) & 3); }
 template <int D> __device__ __forceinline__ int img_off_d(int row, int ch) {
-  if constexpr (D == 128) return img_off(row, ch);
+  if constexpr (D == 128) return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
   else { static_assert(D == 64, "head_dim 64 or 128"); return row * 128 + ((ch ^ swz64(row)) << 4); }
 }
 template <int D> constexpr int tile_bytes() { return 64 * 2 * D; }   // 64 rows x D x 2 B
 
-template <class V8, int D = 128> __device__ __forceinline__ V8 row_frag(const char* img, int row, int ch) {
+template <class V8, int D> __device__ __forceinline__ V8 row_frag(const char* img, int row, int ch) {
   return *reinterpret_cast<const V8*>(img + img_off_d<D>(row, ch));
 }
 
@@ -144,7 +115,7 @@ __device__ __forceinline__ s16x4 tr_read(const char* p) {
 // A-operand fragment read TRANSPOSED from the image: A[m = 32*mb + (lane&31)][kk], where the 16-deep
 // k-step covers image rows R0..R0+15 in the accumulator-as-operand order
 // (element j of lane half h <-> image row R0 + 8*(j>>2) + 4*h + (j&3)) and m indexes image columns.
-template <class V8, int D = 128> __device__ __forceinline__ V8 tr_frag(const char* img, int R0, int mb, int lane) {
+template <class V8, int D> __device__ __forceinline__ V8 tr_frag(const char* img, int R0, int mb, int lane) {
   const int G = lane >> 4, hh = lane >> 5, i = lane & 15, qd = i >> 2, p = i & 3;
   const int ch = 4 * mb + 2 * (G & 1) + (p >> 1);
   const int ra = R0 + 4 * hh + qd;
@@ -192,25 +163,6 @@ struct TileIter {
   }
 };
 
-// -------------------------------------------------------------------------------------------------
-// Staging macros (no lambdas: captured arrays were demoted to scratch by hipcc).
-// A 64-row x 128-col tile pair (A image + B image, 32 KB) is moved by NT threads; every thread owns
-// CPT 16-byte chunks of each image: chunk id = tid + NT*i -> row = id >> 4, chunk-in-row = id & 15.
-// -------------------------------------------------------------------------------------------------
-#define DTA_STAGE_LOAD(REGA, REGB, BASEA, BASEB, STRIDE_A, STRIDE_B, ROW0, ROWMAX, NT, CPT)                \
-  _Pragma("unroll") for (int i_ = 0; i_ < (CPT); ++i_) {                                                  \
-    const int id_ = tid + (NT) * i_, row_ = id_ >> 4, ch_ = id_ & 15;                                      \
-    int gr_ = (ROW0) + row_; gr_ = gr_ < (ROWMAX) ? gr_ : (ROWMAX) - 1;                                    \
-    REGA[i_] = *reinterpret_cast<const u32x4*>((BASEA) + (int64_t)gr_ * (STRIDE_A) + ch_ * 8);             \
-    REGB[i_] = *reinterpret_cast<const u32x4*>((BASEB) + (int64_t)gr_ * (STRIDE_B) + ch_ * 8);             \
-  }
-#define DTA_STAGE_WRITE(REGA, REGB, IMGA, IMGB, NT, CPT)                                                  \
-  _Pragma("unroll") for (int i_ = 0; i_ < (CPT); ++i_) {                                                  \
-    const int id_ = tid + (NT) * i_, row_ = id_ >> 4, ch_ = id_ & 15;                                      \
-    *reinterpret_cast<u32x4*>((IMGA) + img_off(row_, ch_)) = REGA[i_];                                     \
-    *reinterpret_cast<u32x4*>((IMGB) + img_off(row_, ch_)) = REGB[i_];                                     \
-  }
-
 // Deferred reference maximum of the forward (log2 domain): the running reference follows a tile's row maximum only when that exceeds it by
 // more than this, so P <= 2^THR (fp32 sums; bf16 P keeps its relative precision) and the rescale of O - taken on nine tiles in ten with
 // THR = 0, because ANY of a wave's rows triggers it - becomes rare.  -DDTA_FWD_THR=0 restores the exact-maximum form.
@@ -219,7 +171,6 @@ struct TileIter {
 #endif
 constexpr float FWD_THR = DTA_FWD_THR;
 constexpr int SE_BYTES = 256;                                       // 64 x int32 subtree_end of the staged keys
-constexpr int QK_LDS = 2 * (2 * TILE_BYTES + SE_BYTES);            // double-buffered {K image, V image, se}
 
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 __device__ __forceinline__ float half_max(float x) {      // max(x, value of the lane 32 away) by v_permlane32_swap (no LDS round trip)
@@ -233,8 +184,7 @@ __device__ __forceinline__ float half_max(float x) {      // max(x, value of the
 // loop every ds_read is <lane offset register> + <compile-time immediate>.  row[s]: k-step s (D/16 of them) of a row read;
 // tr[mb], tr[D/32 + mb]: low / high half of the transposed read of 32-column block mb.
 template <int D> struct FragOffsT { int row[D / 16]; int tr[D / 16]; };
-using FragOffs = FragOffsT<128>;
-template <int D = 128> __device__ __forceinline__ FragOffsT<D> frag_offsets(int lane) {
+template <int D> __device__ __forceinline__ FragOffsT<D> frag_offsets(int lane) {
   FragOffsT<D> o;
   const int r = lane & 31, h = lane >> 5;
 #pragma unroll
@@ -270,7 +220,7 @@ template <class V8, int D> __device__ __forceinline__ V8 tr_frag_o(const char* i
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
   return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)(p);
 }
-// pieces {0, 1} of image A (at lds, lds + 1 KiB) and of image B (at lds + TILE_BYTES, + 1 KiB)
+// pieces {0, 1} of image A (at lds, lds + 1 KiB) and of image B (at lds + tile_bytes<128>() = 16 KiB, + 1 KiB): the head_dim 128 tiles
 __device__ __forceinline__ void dma_pair2(uint32_t oa0, uint32_t oa1, const void* ba, uint32_t ob0, uint32_t ob1, const void* bb, uint32_t lds) {
   asm volatile(
       "s_nop 4\n\t"
@@ -294,14 +244,11 @@ __device__ __forceinline__ void dma_dword(uint32_t off, const void* base, uint32
 }
 #define DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
-// Byte offset of this lane's 16-B chunk of image row `row` (rows of `stride` elements of `esz` bytes), swizzled
-__device__ __forceinline__ uint32_t dma_src_off(int row, int img_row, int lane, int64_t stride, int esz) {
-  const int ch = (lane & 15) ^ (((img_row & 3) << 2) | ((img_row >> 2) & 3));
-  return (uint32_t)((row * stride + ch * 8) * (int64_t)esz);
-}
-// head_dim D: a 1-KiB piece is 1024 / (2 D) image rows of D / 8 chunks (D = 64: 8 rows, lane -> row lane >> 3, chunk lane & 7)
+// Byte offset of this lane's 16-B chunk of image row `row` (rows of `stride` elements of `esz` bytes), swizzled as image row `img_row`.
+// head_dim D: a 1-KiB piece is 1024 / (2 D) image rows of D / 8 chunks (D = 128: 4 rows, lane -> row lane >> 4, chunk lane & 15;
+// D = 64: 8 rows, lane -> row lane >> 3, chunk lane & 7)
 template <int D> __device__ __forceinline__ uint32_t dma_src_off_d(int row, int img_row, int lane, int64_t stride, int esz) {
-  if constexpr (D == 128) return dma_src_off(row, img_row, lane, stride, esz);
+  if constexpr (D == 128) return (uint32_t)((row * stride + ((lane & 15) ^ (((img_row & 3) << 2) | ((img_row >> 2) & 3))) * 8) * (int64_t)esz);
   else return (uint32_t)((row * stride + ((lane & 7) ^ swz64(img_row)) * 8) * (int64_t)esz);
 }
 template <int D> constexpr int dma_lane_row_shift() { return D == 128 ? 4 : 3; }
@@ -331,7 +278,7 @@ template <int TB> __device__ __forceinline__ void dma_one2(uint32_t oa, const vo
     voff_k[i_] = dma_src_off_d<DH>(row_, row_, lane, p.kv_st, sizeof(e));                                  \
     voff_v[i_] = dma_src_off_d<DH>(row_, row_, lane, p.v_st, sizeof(e)); }
 #define DTA_KV_DMA(BASE, K0, NW)                                                                           \
-  DTA_DMA_GUARD(NW) { char* base_ = (BASE); const int k0_ = (K0);                                          \
+  { char* base_ = (BASE); const int k0_ = (K0);                                                            \
     if (wave == 0) {                                                                                       \
       if (p.subtree_end) { int ki_ = k0_ + lane; ki_ = ki_ < p.Tk ? ki_ : p.Tk - 1;                        \
         dma_dword((uint32_t)ki_ * 4u, p.subtree_end, lds_addr(base_ + 2 * tile_bytes<DH>())); }           \
@@ -351,27 +298,6 @@ template <int TB> __device__ __forceinline__ void dma_one2(uint32_t oa, const vo
     } else {                                                                                               \
       _Pragma("unroll") for (int i_ = 0; i_ < DTA_KV_PPW(NW); ++i_)                                        \
         dma_one2<tile_bytes<DH>()>(ok_[i_], kb_, ov_[i_], vb_, lds_addr(base_ + (wave * DTA_KV_PPW(NW) + i_) * 1024)); } }
-
-// The same tile DMA in two steps, so that a one-wave-per-SIMD kernel can issue the pieces BETWEEN its MFMAs instead of in one exposed burst
-// (8 pieces cost a wave ~900 cycles of issue): DTA_KV_DMA_PREP declares the bases / offsets (and sends the subtree_end row), DTA_KV_DMA_PAIR(i)
-// issues piece pair i (i = 0 .. 16/NW/2 - 1) of both images.
-#define DTA_KV_DMA_PREP(BASE, K0, NW, COND)                                                                    \
-  char* dbase_ = (BASE); const int dk0_ = (K0);                                                            \
-  if (wave == 0 && (COND)) {                                                                                      \
-    if (p.subtree_end) { int ki_ = dk0_ + lane; ki_ = ki_ < p.Tk ? ki_ : p.Tk - 1;                         \
-      dma_dword((uint32_t)ki_ * 4u, p.subtree_end, lds_addr(dbase_ + 2 * TILE_BYTES)); }                   \
-    else reinterpret_cast<int*>(dbase_ + 2 * TILE_BYTES)[lane] = 0x7fffffff; }                             \
-  const char* dkb_ = reinterpret_cast<const char*>(kbase) + (int64_t)dk0_ * p.kv_st * (int64_t)sizeof(e);  \
-  const char* dvb_ = reinterpret_cast<const char*>(vbase) + (int64_t)dk0_ * p.v_st * (int64_t)sizeof(e);   \
-  uint32_t dok_[16 / (NW)], dov_[16 / (NW)];                                                               \
-  _Pragma("unroll") for (int i_ = 0; i_ < 16 / (NW); ++i_) { dok_[i_] = voff_k[i_]; dov_[i_] = voff_v[i_]; } \
-  if (dk0_ + 64 > p.Tk) {                                                                                  \
-    _Pragma("unroll") for (int i_ = 0; i_ < 16 / (NW); ++i_) {                                             \
-      const int row_ = 4 * (wave * (16 / (NW)) + i_) + (lane >> 4);                                        \
-      const int rr_ = dk0_ + row_ < p.Tk ? row_ : p.Tk - 1 - dk0_;                                         \
-      dok_[i_] = dma_src_off(rr_, row_, lane, p.kv_st, sizeof(e)); dov_[i_] = dma_src_off(rr_, row_, lane, p.v_st, sizeof(e)); } }
-#define DTA_KV_DMA_PAIR(I, NW)                                                                             \
-  dma_pair2(dok_[2 * (I)], dok_[2 * (I) + 1], dkb_, dov_[2 * (I)], dov_[2 * (I) + 1], dvb_, lds_addr(dbase_ + (wave * (16 / (NW)) + 2 * (I)) * 1024));
 
 // The first DTA_V_PRELOAD_N V fragments (k-step by k-step) requested BEFORE the row maximum (they do not depend on the softmax; hipcc otherwise issues them right in
 // front of the first PV MFMA, which then waits an LDS latency).  -DDTA_V_PRELOAD_N=0 disables.
@@ -417,12 +343,11 @@ template <int DT, int HPB, int DH>
 __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32;      // image bytes, k-steps over D, 32-wide accumulator blocks over D
-  constexpr int NW = DTA_DMA_WAVES(HPB), BUF = 2 * TB + SE_BYTES;
+  constexpr int NW = 4 * HPB, BUF = 2 * TB + SE_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // wave-uniform values live in SGPRs
-  DTA_PRIO_YOUNGER_HALF(wave)
   const int hb = wave >> 2, rw = wave & 3;
   const int bid = blockIdx.x;
   const int hgroups = p.hgroups;
@@ -547,358 +472,6 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
 }
 
 // =================================================================================================
-// forward, 8 waves with the two head groups HALF A TILE APART (A/B form 4).  Same work split as tree_attn_fwd_kernel<DT, 2> (waves 0-3 =
-// head 0, waves 4-7 = head 1 of the kv group, sharing the staged tiles, one barrier per tile), but the second group runs its tile body
-// ROTATED: in the interval of tile j it first multiplies P(j-1) - kept packed in 16 registers across the barrier - into V(j-1), then forms
-// S(j) and its softmax.  With both groups in the same order, the two waves of a SIMD meet in the same phase after every barrier (both in
-// the score MFMAs, then both in the exponentials, then both in the PV MFMAs); rotated, a wave's vector phase lies beside its partner's MFMA
-// phase in two of the three thirds of an interval.  V(j-1) has to outlive interval j, so the ring has THREE {K, V, subtree_end} slots
-// (99 KB) and the loop is unrolled over them.
-// =================================================================================================
-constexpr int FWD4_LDS = 3 * (2 * TILE_BYTES + SE_BYTES);
-template <int DT>
-__global__ __launch_bounds__(512, 2) void tree_attn_fwd4_kernel(AttnParams p) {
-  using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
-  constexpr int DH = 128;                                            // the A/B forms exist for head_dim 128 only
-  constexpr int NW = 8, BUF = 2 * TILE_BYTES + SE_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[FWD4_LDS];
-
-  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hb = wave >> 2, rw = wave & 3;
-  const int bid = blockIdx.x;
-  const int hgroups = p.hgroups;
-  const int kvh = bid % p.Hkv; const int rest = bid / p.Hkv; const int hgb = rest % hgroups;
-  const int nqt = (p.Tq + DTA_QTILE - 1) / DTA_QTILE;
-  const int qt = nqt - 1 - rest / hgroups;
-  const int hq = kvh * p.group + p.head0 + hgb * 2 + hb;
-  const int q0 = qt * DTA_QTILE;
-  const int qrow = q0 + rw * 32 + r;
-  const int qrow_c = qrow < p.Tq ? qrow : p.Tq - 1;
-  const int qidx = p.q_offset + qrow;
-
-  TileIter it; it.runs = p.runs; it.diag_first_q = p.subtree_end ? -64 : p.q_offset + q0;
-  if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; if (!it.load_run()) return; }
-  else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; if (it.kend <= 0) return; }
-
-  const e* qp = reinterpret_cast<const e*>(p.q) + (int64_t)qrow_c * p.q_st + (int64_t)hq * p.q_sh;
-  v8 qf[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) qf[s] = *reinterpret_cast<const v8*>(qp + 16 * s + 8 * h);
-
-  const e* kbase = reinterpret_cast<const e*>(p.k) + (int64_t)kvh * p.kv_sh;
-  const e* vbase = reinterpret_cast<const e*>(p.v) + (int64_t)kvh * p.v_sh;
-  const FragOffs offs = frag_offsets(lane);
-  DTA_KV_OFFSETS(NW)
-
-  f32x16 O[4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db)
-#pragma unroll
-    for (int g = 0; g < 16; ++g) O[db][g] = 0.f;
-  float m = -1e30f, lsum = 0.f;
-  const float c = p.scale * LOG2E;
-  v8 pk[4];                                   // group 1: P of the previous tile, packed
-  bool have_prev = false;
-
-  int ck0 = it.k0, ckend = it.kend; bool cmask = it.masked();
-  DTA_KV_DMA(smem, it.k0, NW)
-  bool has_next = it.advance();
-  // The Q fragments must be COMPLETE in hipcc's own book-keeping before the loop: it cannot see the asm DMA, but it does count the plain
-  // global loads of Q, and with them still "pending" at the loop header it put `s_waitcnt vmcnt(7) .. vmcnt(0)` in front of the first eight
-  // score MFMAs of the loop body - where vmcnt(0) also waits for the NEXT tile's DMA issued a few hundred cycles earlier.
-#pragma unroll
-  for (int s = 0; s < 8; ++s) asm volatile("" : "+v"(qf[s]));
-  DMA_WAIT(); __syncthreads();
-
-#define FWD4_SCORES(KS)                                                                                    \
-    const char* Ks = (KS);                                                                                 \
-    const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TILE_BYTES);                                   \
-    f32x16 X[2];                                                                                           \
-    _Pragma("unroll") for (int kb = 0; kb < 2; ++kb) {                                                     \
-      _Pragma("unroll") for (int g = 0; g < 16; ++g) X[kb][g] = 0.f;                                       \
-      _Pragma("unroll") for (int s = 0; s < 8; ++s)                                                        \
-        X[kb] = T::mma(*reinterpret_cast<const v8*>(Ks + 8192 * kb + offs.row[s]), qf[s], X[kb]);         \
-    }                                                                                                      \
-    if (cmask) {                                                                                           \
-      const int qlim = qidx < ckend ? qidx : ckend - 1;                                                    \
-      _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                     \
-        _Pragma("unroll") for (int gq = 0; gq < 4; ++gq) {                                                 \
-          const int kl = 32 * kb + 8 * gq + 4 * h;                                                         \
-          const int4 se4 = *reinterpret_cast<const int4*>(se_s + kl);                                      \
-          const int sev[4] = {se4.x, se4.y, se4.z, se4.w};                                                 \
-          _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                  \
-            const bool ok = (ck0 + kl + j <= qlim) && (qidx < sev[j]);                                     \
-            X[kb][4 * gq + j] = ok ? X[kb][4 * gq + j] : -INFINITY;                                        \
-          }                                                                                                \
-        }                                                                                                  \
-    }                                                                                                      \
-    float mx = max3(X[0][0], X[0][1], X[0][2]), mx1 = max3(X[1][0], X[1][1], X[1][2]);   /* two independent chains */ \
-    _Pragma("unroll") for (int g = 3; g < 15; g += 2) { mx = max3(mx, X[0][g], X[0][g + 1]); mx1 = max3(mx1, X[1][g], X[1][g + 1]); } \
-    mx = max3(mx, X[0][15], mx1);                                                                          \
-    mx = half_max(fmaxf(mx, X[1][15]));        /* v_permlane32_swap: no LDS round trip (ds_bpermute + 6 address instructions before) */ \
-    const float mc = mx * c;                                                                               \
-    if (__builtin_expect(__any(mc > m + FWD_THR), 0)) {                                                    \
-      const float mnew = fmaxf(m, mc);                                                                     \
-      const float alpha = fast_exp2(m - mnew);                                                             \
-      m = mnew; lsum *= alpha;                                                                             \
-      _Pragma("unroll") for (int db = 0; db < 4; ++db)                                                     \
-        _Pragma("unroll") for (int g = 0; g < 16; ++g) O[db][g] *= alpha;                                  \
-    }                                                                                                      \
-    _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                       \
-      _Pragma("unroll") for (int g = 0; g < 16; ++g) { const float pv = fast_exp2(__builtin_fmaf(X[kb][g], c, -m)); lsum += pv; X[kb][g] = pv; }
-#define FWD4_PV(VS, PB)                                                                                    \
-    { const char* vs_ = (VS);                                                                              \
-    _Pragma("unroll") for (int s4 = 0; s4 < 4; ++s4)                                                       \
-      _Pragma("unroll") for (int db = 0; db < 4; ++db) O[db] = T::mma(tr_frag_o<v8>(vs_ + 4096 * s4, offs, db), PB[s4], O[db]); }
-  // single-exit loops over a run-time ring slot (three compile-time slots x early exits made hipcc move the accumulators through scratch)
-  int slot = 0;                               // wave-uniform
-  bool more;
-  if (hb == 0) {
-    do {
-      const int nslot = slot == 2 ? 0 : slot + 1;
-      int nk0_ = 0, nkend_ = 0; bool nmask_ = false;
-      if (has_next) { nk0_ = it.k0; nkend_ = it.kend; nmask_ = it.masked(); DTA_KV_DMA(smem + nslot * BUF, it.k0, NW) }
-      FWD4_SCORES(smem + slot * BUF)
-      v8 pb_[4];
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) pb_[s4] = pack_half<DT>(X[s4 >> 1], s4 & 1);
-      FWD4_PV(smem + slot * BUF + TILE_BYTES, pb_)
-      DMA_WAIT(); __syncthreads();
-      more = has_next;
-      if (more) { ck0 = nk0_; ckend = nkend_; cmask = nmask_; has_next = it.advance(); slot = nslot; }
-    } while (more);
-  } else {
-    int pslot = 0;
-    do {
-      const int nslot = slot == 2 ? 0 : slot + 1;
-      int nk0_ = 0, nkend_ = 0; bool nmask_ = false;
-      if (has_next) { nk0_ = it.k0; nkend_ = it.kend; nmask_ = it.masked(); DTA_KV_DMA(smem + nslot * BUF, it.k0, NW) }
-      if (have_prev) FWD4_PV(smem + pslot * BUF + TILE_BYTES, pk)
-      FWD4_SCORES(smem + slot * BUF)
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) pk[s4] = pack_half<DT>(X[s4 >> 1], s4 & 1);
-      have_prev = true;
-      DMA_WAIT(); __syncthreads();
-      more = has_next;
-      pslot = slot;
-      if (more) { ck0 = nk0_; ckend = nkend_; cmask = nmask_; has_next = it.advance(); slot = nslot; }
-    } while (more);
-    FWD4_PV(smem + pslot * BUF + TILE_BYTES, pk)      // the deferred product of the last tile (its slot is not written again)
-  }
-#undef FWD4_PV
-#undef FWD4_SCORES
-
-  lsum += __shfl_xor(lsum, 32);
-  const float inv = 1.f / lsum;
-  if (qrow < p.Tq) {
-    e* op = reinterpret_cast<e*>(p.out) + (int64_t)qrow * p.o_st + (int64_t)hq * p.o_sh;
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        v4 w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (e)(O[db][4 * gq + j] * inv);
-        *reinterpret_cast<v4*>(op + 32 * db + 8 * gq + 4 * h) = w;
-      }
-    if (h == 0) p.lse_w[(int64_t)hq * p.Tq + qrow] = m + __builtin_amdgcn_logf(lsum);
-  }
-}
-
-// =================================================================================================
-// forward, ONE wave per SIMD: a workgroup = 4 waves = 128 query rows, and every wave carries BOTH query heads of the kv group for its 32
-// rows (512 registers per lane: O 2 x 64, Q fragments 2 x 32, scores 2 x 32).
-//
-// Why: in-kernel stamps of the 8-wave form above show that vector instructions do not run in the shadow of the SIMD
-// PARTNER's MFMAs - a tile costs the SIMD its MFMA cycles PLUS both waves' vector-issue cycles - while they do run in the shadow of the
-// wave's OWN MFMAs.  Here the two heads are two independent instruction chains inside one wave: every K and V fragment read feeds two
-// MFMAs (half the LDS traffic per MFMA), and the exponentials / packs of both heads sit in the same basic block as the 32 PV MFMAs.
-// Same tile iteration, masks, staging (LDS-DMA, double buffer, one barrier per tile) and outputs as the 8-wave form.
-// =================================================================================================
-// Score MFMAs with a VGPR destination, from inline asm: with a 512-register budget hipcc puts the accumulators of EVERY builtin MFMA into
-// accumulation registers - right for O (128 registers nothing but the rare rescale touches), wrong for the scores, which the softmax
-// reads element by element (8 v_accvgpr moves per MFMA in the loop).  hipcc does not know these are MFMAs: the wait states between the
-// last one and the first vector read of its result (8-pass MFMA -> VALU: 11) are ours to provide - mfma_scores_done().
-template <int DT> struct MmaV;
-template <> struct MmaV<DTA_BF16> {
-  static __device__ __forceinline__ void first(f32x16& d, bf16x8 a, bf16x8 b) { asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b)); }
-  static __device__ __forceinline__ void acc(f32x16& d, bf16x8 a, bf16x8 b) { asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b)); }
-};
-template <> struct MmaV<DTA_F16> {
-  static __device__ __forceinline__ void first(f32x16& d, f16x8 a, f16x8 b) { asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b)); }
-  static __device__ __forceinline__ void acc(f32x16& d, f16x8 a, f16x8 b) { asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b)); }
-};
-__device__ __forceinline__ void mfma_scores_done(f32x16& a, f32x16& b, f32x16& c_, f32x16& d) {
-  asm volatile("s_nop 7\n\ts_nop 7" : "+v"(a), "+v"(b), "+v"(c_), "+v"(d));
-}
-constexpr float FWD3_THR = FWD_THR;          // the reference maximum follows a tile's row maximum only when that grew by more than this (log2 domain: P <= 16): the rescale of the 128 O accumulators (AGPR <-> VGPR moves) becomes rare
-
-template <int DT>
-__global__ __launch_bounds__(256, 1) void tree_attn_fwd3_kernel(AttnParams p) {
-  using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
-  constexpr int DH = 128;                                            // the A/B forms exist for head_dim 128 only
-  constexpr int NW = 4, BUF = 2 * TILE_BYTES + SE_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[QK_LDS];
-
-  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int bid = blockIdx.x;
-  const int hgroups = p.hgroups;
-  const int kvh = bid % p.Hkv; const int rest = bid / p.Hkv; const int hgb = rest % hgroups;
-  const int nqt = (p.Tq + DTA_QTILE - 1) / DTA_QTILE;
-  const int qt = nqt - 1 - rest / hgroups;
-  const int hq0 = kvh * p.group + p.head0 + hgb * 2;                 // this workgroup's two query heads: hq0, hq0 + 1
-  const int q0 = qt * DTA_QTILE;
-  const int qrow = q0 + wave * 32 + r;
-  const int qrow_c = qrow < p.Tq ? qrow : p.Tq - 1;
-  const int qidx = p.q_offset + qrow;
-
-  TileIter it; it.runs = p.runs; it.diag_first_q = p.subtree_end ? -64 : p.q_offset + q0;
-  if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; if (!it.load_run()) return; }
-  else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; if (it.kend <= 0) return; }
-
-  v8 qf[2][8];
-#pragma unroll
-  for (int hd = 0; hd < 2; ++hd) {
-    const e* qp = reinterpret_cast<const e*>(p.q) + (int64_t)qrow_c * p.q_st + (int64_t)(hq0 + hd) * p.q_sh;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) { qf[hd][s] = *reinterpret_cast<const v8*>(qp + 16 * s + 8 * h); asm volatile("" : "+a"(qf[hd][s])); }   // Q fragments live in accumulation registers (pure MFMA operands)
-  }
-  const e* kbase = reinterpret_cast<const e*>(p.k) + (int64_t)kvh * p.kv_sh;
-  const e* vbase = reinterpret_cast<const e*>(p.v) + (int64_t)kvh * p.v_sh;
-  const FragOffs offs = frag_offsets(lane);
-  DTA_KV_OFFSETS(NW)
-
-  f32x16 O[2][4];
-#pragma unroll
-  for (int hd = 0; hd < 2; ++hd)
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) O[hd][db][g] = 0.f;
-  float m[2] = {-1e30f, -1e30f}, lsum[2] = {0.f, 0.f};
-  const float c = p.scale * LOG2E;
-
-  int ck0 = it.k0, ckend = it.kend; bool cmask = it.masked();
-  DTA_KV_DMA(smem, it.k0, NW)
-  bool has_next = it.advance();
-  DMA_WAIT(); __syncthreads();
-
-  int cur = 0;
-  bool more = true;
-  do {          // ONE straight-line body with a single exit at the bottom and a run-time buffer toggle: with two unrolled bodies and exits from the
-                // middle hipcc carried the 128 O accumulators in VGPRs between them (128 v_accvgpr moves each way per tile)
-    int nk0_ = 0, nkend_ = 0; bool nmask_ = false;
-    if (has_next) { nk0_ = it.k0; nkend_ = it.kend; nmask_ = it.masked(); }
-    DTA_KV_DMA_PREP(smem + (cur ^ 1) * BUF, has_next ? it.k0 : 0, NW, has_next)
-    const char* Ks = smem + cur * BUF; const char* Vs = Ks + TILE_BYTES;
-    const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TILE_BYTES);
-    f32x16 X[2][2];
-    { v8 kf[2][8];                           /* all 16 K fragments requested up front (64 registers): one LDS latency per tile, not one per MFMA pair */
-      #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        #pragma unroll
-      for (int s = 0; s < 8; ++s) kf[kb][s] = *reinterpret_cast<const v8*>(Ks + 8192 * kb + offs.row[s]);
-      #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        #pragma unroll
-      for (int s = 0; s < 8; ++s) {                    /* one K fragment, two MFMAs */
-          if (s == 0) { MmaV<DT>::first(X[0][kb], kf[kb][s], qf[0][s]); MmaV<DT>::first(X[1][kb], kf[kb][s], qf[1][s]); }
-          else { MmaV<DT>::acc(X[0][kb], kf[kb][s], qf[0][s]); MmaV<DT>::acc(X[1][kb], kf[kb][s], qf[1][s]); }
-          if (s == 3 && has_next) { if (kb == 0) { DTA_KV_DMA_PAIR(0, NW) } else { DTA_KV_DMA_PAIR(1, NW) } }      // the next tile's DMA pieces go out between the MFMAs
-        }
-    }
-    mfma_scores_done(X[0][0], X[0][1], X[1][0], X[1][1]);
-    if (cmask) {
-      const int qlim = qidx < ckend ? qidx : ckend - 1;
-      #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        #pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-          const int kl = 32 * kb + 8 * gq + 4 * h;
-          const int4 se4 = *reinterpret_cast<const int4*>(se_s + kl);
-          const int sev[4] = {se4.x, se4.y, se4.z, se4.w};
-          #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-            const bool ok = (ck0 + kl + j <= qlim) && (qidx < sev[j]);
-            X[0][kb][4 * gq + j] = ok ? X[0][kb][4 * gq + j] : -INFINITY;
-            X[1][kb][4 * gq + j] = ok ? X[1][kb][4 * gq + j] : -INFINITY;
-          }
-        }
-    }
-    float mc[2];
-    #pragma unroll
-      for (int hd = 0; hd < 2; ++hd) {
-      float mx = max3(X[hd][0][0], X[hd][0][1], X[hd][0][2]);
-      #pragma unroll
-      for (int g = 3; g < 15; g += 2) mx = max3(mx, X[hd][0][g], X[hd][0][g + 1]);
-      mx = fmaxf(mx, X[hd][0][15]);
-      #pragma unroll
-      for (int g = 0; g < 16; g += 2) mx = max3(mx, X[hd][1][g], X[hd][1][g + 1]);
-      mc[hd] = half_max(mx) * c;
-    }
-    if (__builtin_expect(__any((mc[0] > m[0] + FWD3_THR) || (mc[1] > m[1] + FWD3_THR)), 0)) {   /* COLD side path, both heads at once: the O <-> VGPR moves belong in here */
-      #pragma unroll
-      for (int hd = 0; hd < 2; ++hd) {
-        const float mnew = fmaxf(m[hd], mc[hd]);
-        const float alpha = fast_exp2(m[hd] - mnew);
-        m[hd] = mnew; lsum[hd] *= alpha;
-        #pragma unroll
-      for (int db = 0; db < 4; ++db)
-          #pragma unroll
-      for (int g = 0; g < 16; ++g) O[hd][db][g] *= alpha;
-      }
-    }
-    /* exponentials / packs of both heads and the 32 PV MFMAs: one basic block, every V fragment read feeds two MFMAs */
-    #pragma unroll
-      for (int hd = 0; hd < 2; ++hd)
-      #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        #pragma unroll
-      for (int g = 0; g < 16; ++g) { const float pv = fast_exp2(__builtin_fmaf(X[hd][kb][g], c, -m[hd])); lsum[hd] += pv; X[hd][kb][g] = pv; }
-    #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) {
-      const v8 pb0 = pack_half<DT>(X[0][s4 >> 1], s4 & 1);
-      const v8 pb1 = pack_half<DT>(X[1][s4 >> 1], s4 & 1);
-      #pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const v8 vf = tr_frag_o<v8>(Vs + 4096 * s4, offs, db);
-        O[0][db] = T::mma(vf, pb0, O[0][db]);
-        O[1][db] = T::mma(vf, pb1, O[1][db]);
-      }
-    }
-    /* the loop-carried home of O is the accumulation file (hipcc otherwise carries it in VGPRs and moves 128 registers each way per tile) */
-    #pragma unroll
-      for (int db = 0; db < 4; ++db) { asm volatile("" : "+a"(O[0][db])); asm volatile("" : "+a"(O[1][db])); }
-    DMA_WAIT(); __syncthreads();
-    more = has_next;
-    ck0 = nk0_; ckend = nkend_; cmask = nmask_; cur ^= 1;
-    if (more) has_next = it.advance();
-  } while (more);
-
-#pragma unroll
-  for (int hd = 0; hd < 2; ++hd) {
-    float l = lsum[hd];
-    l += __shfl_xor(l, 32);
-    const float inv = 1.f / l;
-    if (qrow < p.Tq) {
-      e* op = reinterpret_cast<e*>(p.out) + (int64_t)qrow * p.o_st + (int64_t)(hq0 + hd) * p.o_sh;
-#pragma unroll
-      for (int db = 0; db < 4; ++db)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          v4 w;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) w[j] = (e)(O[hd][db][4 * gq + j] * inv);
-          *reinterpret_cast<v4*>(op + 32 * db + 8 * gq + 4 * h) = w;
-        }
-      if (h == 0) p.lse_w[(int64_t)(hq0 + hd) * p.Tq + qrow] = m[hd] + __builtin_amdgcn_logf(l);
-    }
-  }
-}
-
-// =================================================================================================
 // backward part 1: delta + dQ   (query tile owns the workgroup; same sweep as the forward)
 // =================================================================================================
 template <int DT, int HPB, int DH>
@@ -909,7 +482,6 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // wave-uniform values live in SGPRs
-  DTA_PRIO_YOUNGER_HALF(wave)
   const int hb = wave >> 2, rw = wave & 3;
   const int bid = blockIdx.x;
   const int hgroups = p.hgroups;
@@ -947,7 +519,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 
   const e* kbase = reinterpret_cast<const e*>(p.k) + (int64_t)kvh * p.kv_sh;
   const e* vbase = reinterpret_cast<const e*>(p.v) + (int64_t)kvh * p.v_sh;
-  constexpr int NW = DTA_DMA_WAVES(HPB), BUF = 2 * TB + SE_BYTES;
+  constexpr int NW = 4 * HPB, BUF = 2 * TB + SE_BYTES;
   DTA_KV_OFFSETS(NW)                      // K/V tiles by LDS-DMA as in the forward (no staging registers, no ds_write)
 
   f32x16 DQ[NDB];
@@ -1085,7 +657,6 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
   __shared__ __attribute__((aligned(16))) char smem_all[kv2_lds<DH>()];
   const int tid8 = threadIdx.x, tid = tid8 & 255, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid8 >> 6);       // 0..7
-  DTA_PRIO_YOUNGER_HALF(wave8)
   const int grp = wave8 >> 2, wave = wave8 & 3;
   char* kvs = smem_all + wave * KSLOT;                               // this key slot's K fragments (+KSLOT/2: V)
   char* smem = smem_all + KV2_FRAGS;                                 // the Q/dO buffers
@@ -1412,16 +983,9 @@ extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v,
   if (npair > 0) {
     p.hgroups = npair; p.head0 = 0;
     dim3 grid(nqt * Hkv * npair), block(512);
-    static const int form = [] { const char* e_ = getenv("DTA_FWD_FORM"); return e_ ? atoi(e_) : DTA_FWD_FORM_DEFAULT; }();   // 1: 8 waves, one head each; 3: 4 waves, two heads each, one wave per SIMD; 4: 8 waves, head groups half a tile apart (A/B switch)
-    if (head_dim == 64) {                                      // the A/B forms exist for head_dim 128 only
+    if (head_dim == 64) {
       if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 64>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 64>), grid, block, 0, st, p);
-    } else if (form == 3) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd3_kernel<DTA_BF16>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd3_kernel<DTA_F16>), grid, dim3(256), 0, st, p);
-    } else if (form == 4) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd4_kernel<DTA_BF16>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd4_kernel<DTA_F16>), grid, block, 0, st, p);
     } else {
       if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 128>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 128>), grid, block, 0, st, p);

@@ -12,8 +12,6 @@ torch.  `Qwen3TreeLM` mirrors the HF module/parameter tree (``model.embed_tokens
 """
 from __future__ import annotations
 
-import os
-
 from types import SimpleNamespace
 
 import torch
@@ -21,8 +19,6 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-
-FUSE_PROJECTIONS = os.environ.get("DTA_FUSE_PROJ", "1") != "0"      # diagnostic A/B switch
 
 
 class _Norm(nn.Module):
@@ -119,28 +115,17 @@ def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     a = layer.self_attn
     res, h = ops.add_rms_norm(res, delta, layer.input_layernorm.weight, eps)
     bq, bk, bv = (getattr(m_, "bias", None) for m_ in (a.q_proj, a.k_proj, a.v_proj))
-    if FUSE_PROJECTIONS:
-        # one projection GEMM for q,k,v (and one for gate,up below): the weights stay separate parameters with
-        # their HF names; stacking them is three plain copies whose backward hands out gradient row slices
-        qkv = ops.linear(h, ops.stack_rows(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight),
-                       torch.cat([bq, bk, bv]) if bq is not None else None).view(T, Hq + 2 * Hkv, D)
-        qn = getattr(a, "q_norm", None); kn = getattr(a, "k_norm", None)
-        q, k, v = ops.qkv_prep(qkv, qn.weight if qn is not None else None, kn.weight if kn is not None else None, cos_sin, eps, Hq, Hkv)
-    else:
-        q = ops.linear(h, a.q_proj.weight, bq).view(T, Hq, D)
-        k = ops.linear(h, a.k_proj.weight, bk).view(T, Hkv, D)
-        v = ops.linear(h, a.v_proj.weight, bv).view(T, Hkv, D)
-        qn = getattr(a, "q_norm", None); kn = getattr(a, "k_norm", None)
-        q = ops.qk_norm_rope(q, qn.weight if qn is not None else None, cos_sin, eps)
-        k = ops.qk_norm_rope(k, kn.weight if kn is not None else None, cos_sin, eps)
+    # one projection GEMM for q,k,v (and one for gate,up below): the weights stay separate parameters with
+    # their HF names; stacking them is three plain copies whose backward hands out gradient row slices
+    qkv = ops.linear(h, ops.stack_rows(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight),
+                   torch.cat([bq, bk, bv]) if bq is not None else None).view(T, Hq + 2 * Hkv, D)
+    qn = getattr(a, "q_norm", None); kn = getattr(a, "k_norm", None)
+    q, k, v = ops.qkv_prep(qkv, qn.weight if qn is not None else None, kn.weight if kn is not None else None, cos_sin, eps, Hq, Hkv)
     o = attn(q, k, v)                   # ops.tree_attention over a packed trie, or ops.stack_attention over the KV stack
     attn_out = ops.linear(o.reshape(T, Hq * D), a.o_proj.weight)
     res, h = ops.add_rms_norm(res, attn_out, layer.post_attention_layernorm.weight, eps)
     m = layer.mlp
-    if FUSE_PROJECTIONS:
-        act = ops.swiglu_fused(ops.linear(h, ops.stack_rows(m.gate_proj.weight, m.up_proj.weight)))
-    else:
-        act = ops.swiglu(ops.linear(h, m.gate_proj.weight), ops.linear(h, m.up_proj.weight))
+    act = ops.swiglu_fused(ops.linear(h, ops.stack_rows(m.gate_proj.weight, m.up_proj.weight)))
     return res, ops.linear(act, m.down_proj.weight)
 
 

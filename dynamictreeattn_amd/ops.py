@@ -2,7 +2,6 @@
 and autograd plumbing only; all arithmetic of these ops runs in the HIP kernels."""
 from __future__ import annotations
 
-import os as _os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -213,9 +212,6 @@ class AttentionTape:
         return False
 
 
-ATTN_FUSED_GRAD = _os.environ.get("DTA_ATTN_FUSED_GRAD", "1") != "0"      # diagnostic A/B switch
-
-
 class _TreeAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, meta: TreeAttnMeta, scale: float):
@@ -236,7 +232,7 @@ class _TreeAttention(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
         Hq, Hkv = q.shape[1], k.shape[1]
-        if ATTN_FUSED_GRAD and q.shape[0] == k.shape[0]:
+        if q.shape[0] == k.shape[0]:
             # the three gradients side by side in ONE [T, Hq+2Hkv, D] buffer, the layout of the fused projection's gradient: _QKVPrep's
             # backward then transforms dq and dk in place and hands the buffer on - no gather of dv (0.65 ms per step at tau2 size)
             fused = torch.empty((q.shape[0], Hq + 2 * Hkv, q.shape[2]), dtype=q.dtype, device=q.device)
@@ -452,7 +448,7 @@ class _HeadRows(torch.autograd.Function):
             logprob_entropy_bwd_raw(logits, next_loc[a:b], lse[a:b], ent[a:b] if ctx.want_entropy else None, g_next[a:b],
                                     g_ent[a:b] if ctx.want_entropy else None, 1.0,
                                     xp[a:b + 1] if ctx.has_forks else None, fork_loc if ctx.has_forks else None, g_fork)
-            if DGRAD_TRANSPOSED_W and W.dtype in (torch.bfloat16, torch.float16) and (b - a) >= 4096 and W.shape[0] % 8 == 0 and W.shape[1] % 8 == 0:
+            if W.dtype in (torch.bfloat16, torch.float16) and (b - a) >= 4096 and W.shape[0] % 8 == 0 and W.shape[1] % 8 == 0:
                 torch.mm(logits, _TransposedWeights.get(W).t(), out=dh[a:b])        # contraction index contiguous in both operands (see _dgrad)
             else:
                 torch.mm(logits, W, out=dh[a:b])
@@ -882,20 +878,17 @@ def clear_weight_caches() -> None:
     _TransposedWeights.cache.clear(); _TransposedWeights.nbytes = 0
 
 
-DGRAD_TRANSPOSED_W = _os.environ.get("DTA_DGRAD_TRANSPOSED_W", "1") == "1"      # env: diagnostic A/B switch
-
-
 def _dgrad(dy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """dx[T, in] = dy[T, out] · W[out, in].  With W row-major the contraction index strides by `in`; against a transposed copy (contraction
     index contiguous in both operands) hipBLASLt runs the same product 12-25 % faster on gfx950 (scripts/gemm_dgrad_layout_probe.py:
     q/k/v 0.252 -> 0.202 ms, gate/up 0.322 -> 0.275, down 0.183 -> 0.155, LM head 9.68 -> 8.34 at T = 28 160) - the copy (HIP transpose,
     once per weight version) costs a tenth of that."""
-    if DGRAD_TRANSPOSED_W and dy.is_cuda and w.dtype in (torch.bfloat16, torch.float16) and dy.shape[0] >= 4096 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
+    if dy.is_cuda and w.dtype in (torch.bfloat16, torch.float16) and dy.shape[0] >= 4096 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
         return dy @ _TransposedWeights.get(w).t()
     return dy @ w
 
 
-WGRAD_SPLIT_K = int(_os.environ.get("DTA_WGRAD_SPLIT_K", "4"))      # slices of the packed rows in the weight-gradient GEMM of a small projection (0 / 1: never split; env: diagnostic A/B switch)
+WGRAD_SPLIT_K = 4      # slices of the packed rows in the weight-gradient GEMM of a small projection
 
 
 def _wgrad(x: torch.Tensor, dy: torch.Tensor, transposed: bool) -> torch.Tensor:
@@ -909,8 +902,8 @@ def _wgrad(x: torch.Tensor, dy: torch.Tensor, transposed: bool) -> torch.Tensor:
     a, b = (x, dy) if transposed else (dy, x)                    # result = aᵀ · b
     S = WGRAD_SPLIT_K
     tiles = -(-a.shape[1] // 256) * -(-b.shape[1] // 256)
-    per = (T // S) // 64 * 64 if S > 1 else 0      # packed lengths are multiples of 256 from 2 048 rows on: nothing is left over at S = 4
-    if S <= 1 or tiles > 64 or per < 2048 or not x.is_cuda or x.dtype == torch.float32:
+    per = (T // S) // 64 * 64      # packed lengths are multiples of 256 from 2 048 rows on: nothing is left over at S = 4
+    if tiles > 64 or per < 2048 or not x.is_cuda or x.dtype == torch.float32:
         out = a.t() @ b
     else:
         body = per * S

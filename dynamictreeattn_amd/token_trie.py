@@ -13,7 +13,6 @@ raises.  (tests monkeypatch `_device_trie_arrays` with the oracle to exercise th
 from __future__ import annotations
 
 import contextlib
-import os
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -139,7 +138,7 @@ class TokenTrie:
         # below then waits for these two small kernels only, not for whatever the caller has queued on its own stream (an engine call
         # returns with its backward still running - tree_training_engine.py `_backward` - and the next trie is built under it).
         side = None
-        if device.type == "cuda" and os.environ.get("DTA_TRIE_STREAM", "1") != "0" and not any(isinstance(t, torch.Tensor) and t.is_cuda for t in inputs):
+        if device.type == "cuda" and not any(isinstance(t, torch.Tensor) and t.is_cuda for t in inputs):
             side = _trie_stream(device)
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             self._dev = _DeviceTokens(inputs, device)

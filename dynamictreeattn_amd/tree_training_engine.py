@@ -23,8 +23,6 @@ left to cut (no token is forwarded twice) and is accepted for signature parity.
 """
 from __future__ import annotations
 
-import os
-
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -121,8 +119,8 @@ def sum_loss_terms(terms, device):
 class _PackedTrie:
     """Device-resident packed form of a TokenTrie (in its current leaf order)."""
 
-    # packed lengths from PAD_FROM on are rounded up to PAD_TO rows of filler (packing.pad_plan); the env var is a diagnostic A/B switch
-    PAD_FROM = int(os.environ.get("DTA_PAD_FROM", 2048))
+    # packed lengths from PAD_FROM on are rounded up to PAD_TO rows of filler (packing.pad_plan)
+    PAD_FROM = 2048
     PAD_TO = 256
 
     def __init__(self, trie, device, n_kv_heads: int = 8):
@@ -487,7 +485,7 @@ class TreeTrainingEngine:
         # stream order (an optimizer step, a gradient reduction or the next call simply queue behind them), and the host work of the next
         # call (trie build, packing plan, uploads) overlaps this call's backward instead of leaving the device idle for it
         landed = None
-        if total.is_cuda and os.environ.get("DTA_ASYNC_LOSS", "1") != "0":          # (env: diagnostic A/B switch)
+        if total.is_cuda:
             if self._loss_host is None:
                 self._loss_host = torch.empty(1, dtype=torch.float32).pin_memory()
             self._loss_host.copy_(total.detach().reshape(1).float(), non_blocking=True)
