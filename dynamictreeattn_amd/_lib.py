@@ -20,6 +20,9 @@ _PROTOS = {
     "dta_tree_attn_bwd": ([_vp] * 14 + [_i32] * 6 + [_i64] * 5 + [_f32, _i32, _i32, _vp], C.c_int),
     "dta_tree_attn_fwd_ex": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32, _vp], C.c_int),
     "dta_tree_attn_bwd_ex": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp], C.c_int),
+    "dta_tree_attn_fwd_win": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32, _vp, _i32, _vp], C.c_int),
+    "dta_tree_attn_bwd_win": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp], C.c_int),
+    "dta_window_lo": ([_vp] * 4 + [_i32, _i32, _i32, _vp, _vp], C.c_int),
     "dta_logprob_entropy_fwd": ([_vp] * 8 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_logprob_entropy_shard_stats": ([_vp] * 6 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_logprob_entropy_bwd": ([_vp] * 10 + [_i32, _i32, _i64, _i64, _f32, _i32, _vp], C.c_int),

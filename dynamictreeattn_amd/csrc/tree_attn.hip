@@ -29,6 +29,7 @@
 // forms 3 and 4 were removed (last present in b0d42b7).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "dta_common.h"
 
 // Diagnostic build switch (-DDTA_STAMP=1): in-kernel s_memtime stamps at the segment boundaries of the forward's tile loop, summed per
@@ -82,6 +83,11 @@ struct AttnParams {
   int64_t q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh;
   float scale; int32_t accumulate; int32_t ktile;
 };
+// Sliding-window form (dta_tree_attn_fwd_win / _bwd_win): key s must also be >= the query row's lower bound, win_lo[row] (packed form)
+// or q_offset + row - window + 1 (stack form, win_lo == NULL).  A parameter type of its own: the kernels without a window (WIN = false)
+// keep the parent's kernel arguments, and every WIN term below folds away at compile time, so their device code is unchanged.
+struct AttnParamsW : AttnParams { const int32_t* win_lo; int32_t window; };
+template <bool WIN> using AttnP = typename std::conditional<WIN, AttnParamsW, AttnParams>::type;
 
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -339,8 +345,8 @@ template <int TB> __device__ __forceinline__ void dma_one2(uint32_t oa, const vo
 // they share the staged K/V tiles.  One barrier per 64-key tile, LDS double buffered, tile loop unrolled
 // over the two buffers so that every LDS address is lane-offset + immediate.
 // =================================================================================================
-template <int DT, int HPB, int DH>
-__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams p) {
+template <int DT, int HPB, int DH, bool WIN>
+__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnP<WIN> p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32;      // image bytes, k-steps over D, 32-wide accumulator blocks over D
   constexpr int NW = 4 * HPB, BUF = 2 * TB + SE_BYTES;
@@ -359,10 +365,21 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
   const int qrow = q0 + rw * 32 + r;
   const int qrow_c = qrow < p.Tq ? qrow : p.Tq - 1;
   const int qidx = p.q_offset + qrow;
+  // window: wlo = this row's lowest visible key; wmax = the largest such bound over the tile in the stack form (keys below it need the
+  // mask; the packed form's runs carry that flag from the windowed plan)
+  int wlo = 0, wmax = 0;
+  if constexpr (WIN) {
+    wlo = p.win_lo ? p.win_lo[qrow_c] : (qidx - p.window + 1 > 0 ? qidx - p.window + 1 : 0);
+    wmax = p.win_lo ? 0 : p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq) - p.window;
+  }
 
   TileIter it; it.runs = p.runs; it.diag_first_q = p.subtree_end ? -64 : p.q_offset + q0;
   if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; if (!it.load_run()) return; }
   else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; if (it.kend <= 0) return; }
+  if constexpr (WIN) {                     // stack form: nothing below the first row's bound is visible to the tile
+    const int lo0 = p.q_offset + q0 - p.window + 1;
+    if (!p.runs && !p.win_lo && lo0 > 0) { it.k0 = lo0; if (it.k0 >= it.kend) return; }
+  }
 
   const e* qp = reinterpret_cast<const e*>(p.q) + (int64_t)qrow_c * p.q_st + (int64_t)hq * p.q_sh;
   v8 qf[NKS];
@@ -382,7 +399,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
   float m = -1e30f, lsum = 0.f;
   const float c = p.scale * LOG2E;
 
-  int ck0 = it.k0, ckend = it.kend; bool cmask = it.masked();
+  int ck0 = it.k0, ckend = it.kend; bool cmask = it.masked() || (WIN && it.k0 < wmax);
   DTA_KV_DMA(smem, it.k0, NW)
   bool has_next = it.advance();
   // The Q fragments must be COMPLETE in hipcc's own book-keeping before the loop: it cannot see the asm DMA, but it does count the plain
@@ -397,7 +414,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
   {                                                                                                        \
     int nk0_ = 0, nkend_ = 0; bool nmask_ = false;                                                         \
     DTA_STAMP_AT(5) DTA_STAMP_TILE                                                                         \
-    if (has_next) { nk0_ = it.k0; nkend_ = it.kend; nmask_ = it.masked(); DTA_KV_DMA(smem + (1 - (BUFI)) * BUF, it.k0, NW) } \
+    if (has_next) { nk0_ = it.k0; nkend_ = it.kend; nmask_ = it.masked() || (WIN && it.k0 < wmax); DTA_KV_DMA(smem + (1 - (BUFI)) * BUF, it.k0, NW) } \
     DTA_STAMP_AT(0)                                                                                        \
     const char* Ks = smem + (BUFI) * BUF; const char* Vs = Ks + TB;                                \
     const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TB);                                   \
@@ -414,7 +431,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
           const int4 se4 = *reinterpret_cast<const int4*>(se_s + kl);                                      \
           const int sev[4] = {se4.x, se4.y, se4.z, se4.w};                                                 \
           _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                  \
-            const bool ok = (ck0 + kl + j <= qlim) && (qidx < sev[j]);                                     \
+            const bool ok = (ck0 + kl + j <= qlim) && (qidx < sev[j]) && (!WIN || ck0 + kl + j >= wlo);    \
             X[kb][4 * gq + j] = ok ? X[kb][4 * gq + j] : -INFINITY;                                        \
           }                                                                                                \
         }                                                                                                  \
@@ -474,8 +491,8 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnParams 
 // =================================================================================================
 // backward part 1: delta + dQ   (query tile owns the workgroup; same sweep as the forward)
 // =================================================================================================
-template <int DT, int HPB, int DH>
-__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnParams p) {
+template <int DT, int HPB, int DH, bool WIN>
+__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnP<WIN> p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32;
   __shared__ __attribute__((aligned(16))) char smem[2 * (2 * TB + SE_BYTES)];
@@ -493,6 +510,13 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
   const int qrow = q0 + rw * 32 + r;
   const int qrow_c = qrow < p.Tq ? qrow : p.Tq - 1;
   const int qidx = p.q_offset + qrow;
+  // window: wlo = this row's lowest visible key; wmax = the largest such bound over the tile in the stack form (keys below it need the
+  // mask; the packed form's runs carry that flag from the windowed plan)
+  int wlo = 0, wmax = 0;
+  if constexpr (WIN) {
+    wlo = p.win_lo ? p.win_lo[qrow_c] : (qidx - p.window + 1 > 0 ? qidx - p.window + 1 : 0);
+    wmax = p.win_lo ? 0 : p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq) - p.window;
+  }
 
   const e* qp = reinterpret_cast<const e*>(p.q) + (int64_t)qrow_c * p.q_st + (int64_t)hq * p.q_sh;
   const e* dop = reinterpret_cast<const e*>(p.dout) + (int64_t)qrow_c * p.o_st + (int64_t)hq * p.o_sh;
@@ -516,6 +540,10 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
   bool any = true;
   if (p.runs) { it.ri = p.run_ptr[qt]; it.re = p.run_ptr[qt + 1]; any = it.load_run(); }
   else { it.ri = 0; it.re = 1; it.k0 = 0; it.flag = 1; int last = p.q_offset + (q0 + DTA_QTILE < p.Tq ? q0 + DTA_QTILE : p.Tq); it.kend = last < p.Tk ? last : p.Tk; any = it.kend > 0; }
+  if constexpr (WIN) {                     // stack form: nothing below the first row's bound is visible to the tile
+    const int lo0 = p.q_offset + q0 - p.window + 1;
+    if (!p.runs && !p.win_lo && lo0 > 0) { it.k0 = lo0; any = any && it.k0 < it.kend; }
+  }
 
   const e* kbase = reinterpret_cast<const e*>(p.k) + (int64_t)kvh * p.kv_sh;
   const e* vbase = reinterpret_cast<const e*>(p.v) + (int64_t)kvh * p.v_sh;
@@ -535,14 +563,14 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 #pragma unroll
   for (int g = 0; g < 16; ++g) DI[g] = -delta;
   if (any) {
-    int ck0 = it.k0, ckend = it.kend; bool cmask = it.masked();
+    int ck0 = it.k0, ckend = it.kend; bool cmask = it.masked() || (WIN && it.k0 < wmax);
     DTA_KV_DMA(smem, it.k0, NW)
     bool has_next = it.advance();
     DMA_WAIT(); __syncthreads();
     int cur = 0;
     while (true) {
       int nk0 = 0, nkend = 0; bool nmask = false;
-      if (has_next) { nk0 = it.k0; nkend = it.kend; nmask = it.masked(); DTA_KV_DMA(smem + (cur ^ 1) * BUF, it.k0, NW) }
+      if (has_next) { nk0 = it.k0; nkend = it.kend; nmask = it.masked() || (WIN && it.k0 < wmax); DTA_KV_DMA(smem + (cur ^ 1) * BUF, it.k0, NW) }
       const char* Ks = smem + cur * BUF; const char* Vs = Ks + TB;
       const int* se_s = reinterpret_cast<const int*>(Ks + 2 * TB);
       // one 32-key block at a time keeps S^T/dP^T at 32 live accumulators (2 waves per SIMD need <= 256 registers)
@@ -579,7 +607,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const int g = 4 * gq + j;
-              const bool ok = (ck0 + kl + j <= qlim) && (qidx < sev[j]);
+              const bool ok = (ck0 + kl + j <= qlim) && (qidx < sev[j]) && (!WIN || ck0 + kl + j >= wlo);
               const float pv = ok ? fast_exp2(__builtin_fmaf(X[g], c, -lse2)) : 0.f;
               X[g] = pv * DP[g];
             }
@@ -646,15 +674,15 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnPara
 
 template <int D> constexpr int kv2_slot() { return 2 * (D / 16) * 1024; }    // one key slot: {K: D/16 fragments x 1 KiB, V: D/16 x 1 KiB}
 template <int D> constexpr int kv2_frags() { return 4 * kv2_slot<D>(); }    // 4 key slots
-template <int D> constexpr int kv2_buf() { return 2 * tile_bytes<D>() + 512; }
-template <int D> constexpr int kv2_lds() { return kv2_frags<D>() + 2 * kv2_buf<D>() + 16; }   // + se_min[4]: ONE __shared__ object (a second one makes hipcc drain vmcnt in front of every LDS read)
+template <int D, bool WIN> constexpr int kv2_buf() { return 2 * tile_bytes<D>() + (WIN ? 768 : 512); }   // + row constants lse, -delta (, win_lo)
+template <int D, bool WIN> constexpr int kv2_lds() { return kv2_frags<D>() + 2 * kv2_buf<D, WIN>() + 16; }   // + se_min[4]: ONE __shared__ object (a second one makes hipcc drain vmcnt in front of every LDS read)
 
-template <int DT, int DH>
-__global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p) {
+template <int DT, int DH, bool WIN>
+__global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnP<WIN> p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int KT = 128;
-  constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32, KV2_FRAGS = kv2_frags<DH>(), KV2_BUF = kv2_buf<DH>(), KSLOT = kv2_slot<DH>();
-  __shared__ __attribute__((aligned(16))) char smem_all[kv2_lds<DH>()];
+  constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32, KV2_FRAGS = kv2_frags<DH>(), KV2_BUF = kv2_buf<DH, WIN>(), KSLOT = kv2_slot<DH>();
+  __shared__ __attribute__((aligned(16))) char smem_all[kv2_lds<DH, WIN>()];
   const int tid8 = threadIdx.x, tid = tid8 & 255, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid8 >> 6);       // 0..7
   const int grp = wave8 >> 2, wave = wave8 & 3;
@@ -700,6 +728,9 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
   else {
     qbeg = k0 > p.q_offset ? k0 : p.q_offset;
     qend = p.ktile_qend ? p.ktile_qend[kt] : q_hi; qend = qend < q_hi ? qend : q_hi;
+    if constexpr (WIN) if (!p.win_lo) {          // stack form: query q sees the tile only while q - window + 1 <= its last key
+      const int64_t wl = (int64_t)k0 + KT - 1 + p.window; qend = wl < qend ? (int)wl : qend;
+    }
   }
   const int ntile = qend > qbeg ? (qend - qbeg + 63) / 64 : 0;
   const int total = ntile * p.group;
@@ -728,6 +759,8 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
   { const uint32_t lb_ = lds_tiles + (uint32_t)(B) * KV2_BUF;                                              \
     if (wave8 < 2) { int qr_ = row_n + lane; qr_ = qr_ < p.Tq ? qr_ : p.Tq - 1;   /* wave 0: lse[64], wave 1: delta[64] */ \
       dma_dword((uint32_t)qr_ * 4u, (wave8 == 0 ? p.lse_r : p.delta) + c_cur, lb_ + 2 * TB + wave8 * 256); } \
+    if constexpr (WIN) if (wave8 == 2 && p.win_lo) { int qr_ = row_n + lane; qr_ = qr_ < p.Tq ? qr_ : p.Tq - 1;   /* wave 2: win_lo[64] */ \
+      dma_dword((uint32_t)qr_ * 4u, p.win_lo, lb_ + 2 * TB + 512); }                                       \
     uint32_t oq_[NP], od_[NP];                                                                             \
     _Pragma("unroll") for (int i_ = 0; i_ < NP; ++i_) { oq_[i_] = voff_q[i_]; od_[i_] = voff_d[i_]; }      \
     if (row_n + 64 > p.Tq) {                       /* ragged last tile of the tensor: clamp the row per lane */ \
@@ -757,7 +790,8 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
     const char* tb = smem + (BUFI) * KV2_BUF;                                                              \
     const char* rc = tb + 2 * TB + rc_off;                                                         \
     const int qi0 = qbeg + 64 * ti + 32 * grp;                       /* packed index of this group's first row */ \
-    const bool full = (qbeg + 64 * ti >= k0 + KT - 1) && (qbeg + 64 * ti + 63 < se_min);   /* workgroup-uniform: no mask needed */ \
+    bool full = (qbeg + 64 * ti >= k0 + KT - 1) && (qbeg + 64 * ti + 63 < se_min);   /* workgroup-uniform: no mask needed */ \
+    if constexpr (WIN) full = full && !p.win_lo && qbeg + 64 * ti + 64 - p.window <= k0;   /* window: stack form only */ \
     /* S starts at 0 (inline constant); dP starts at -delta, read from LDS straight into the accumulator registers:    \
        p = exp2(c*S - lse),  dS/scale = p * dP'  with dP' = dO.V^T - delta  (the softmax scale of dS goes onto dK once, in the epilogue) */ \
     f32x16 S, DP;                                                                                          \
@@ -786,9 +820,18 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnParams p
         DP[g] = pv * DP[g];                                                                                \
       }                                                                                                    \
     } else {                                                                                               \
+      int wl[16];                                   /* window: each row's lowest visible key (staged row constant / stack form) */ \
+      if constexpr (WIN) {                                                                                 \
+        if (p.win_lo) {                                                                                    \
+          _Pragma("unroll") for (int gq = 0; gq < 4; ++gq) {                                               \
+            const int4 w4 = *reinterpret_cast<const int4*>(rc + 512 + 32 * gq);                            \
+            wl[4 * gq] = w4.x; wl[4 * gq + 1] = w4.y; wl[4 * gq + 2] = w4.z; wl[4 * gq + 3] = w4.w; }      \
+        } else {                                                                                           \
+          _Pragma("unroll") for (int g = 0; g < 16; ++g) wl[g] = qi0 + 8 * (g >> 2) + 4 * h + (g & 3) - p.window + 1; } \
+      }                                                                                                    \
       _Pragma("unroll") for (int g = 0; g < 16; ++g) {                                                     \
         const int qi = qi0 + 8 * (g >> 2) + 4 * h + (g & 3);                                               \
-        const bool ok = (kidx <= qi) && (qi < se_l);                                                       \
+        const bool ok = (kidx <= qi) && (qi < se_l) && (!WIN || kidx >= wl[g]);                            \
         const float pv = ok ? fast_exp2(__builtin_fmaf(S[g], c, -nl[g])) : 0.f;                            \
         S[g] = pv;                                                                                         \
         DP[g] = pv * DP[g];                                                                                \
@@ -939,26 +982,28 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_finalize_kernel(AttnPar
 }
 
 // the backward launches of one (dtype, head_dim): dQ (head pairs, then the odd head alone), dK/dV, and the slab finalize
-template <int DT, int DH>
-void launch_bwd(const AttnParams& p, const AttnParams& pp, const AttnParams& ps, int npair, dim3 gqp, dim3 gqs, int ndkv, bool fin, int n_splits,
+template <int DT, int DH, bool WIN>
+void launch_bwd(const AttnP<WIN>& p, const AttnP<WIN>& pp, const AttnP<WIN>& ps, int npair, dim3 gqp, dim3 gqs, int ndkv, bool fin, int n_splits,
                 int which, hipStream_t st) {
   if (which & 1) {
-    if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 2, DH>), gqp, dim3(512), 0, st, pp);
-    if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 1, DH>), gqs, dim3(256), 0, st, ps);
+    if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 2, DH, WIN>), gqp, dim3(512), 0, st, pp);
+    if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 1, DH, WIN>), gqs, dim3(256), 0, st, ps);
   }
-  if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DT, DH>), dim3(ndkv * p.Hkv), dim3(512), 0, st, p);
-  if (fin && p.dkv_units && n_splits > 0) hipLaunchKernelGGL((tree_attn_bwd_dkv_finalize_kernel<DT, DH>), dim3(n_splits * p.Hkv, FIN_SPLIT), dim3(256), 0, st, p);
+  if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DT, DH, WIN>), dim3(ndkv * p.Hkv), dim3(512), 0, st, p);
+  if (fin && p.dkv_units && n_splits > 0)   // the slab sums do not depend on visibility: one finalize kernel for both forms
+    hipLaunchKernelGGL((tree_attn_bwd_dkv_finalize_kernel<DT, DH>), dim3(n_splits * p.Hkv, FIN_SPLIT), dim3(256), 0, st, static_cast<const AttnParams&>(p));
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
-extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v, void* out, float* lse,
+template <bool WIN>
+static int attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
                                     const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                                     int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
                                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    float scale, int32_t dtype, void* stream) {
+                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, void* stream) {
   if (!q || !k || !v || !out || !lse || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
   if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
   if ((head_dim != 128 && head_dim != 64) || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32)) return DTA_EUNSUPPORTED;
@@ -966,11 +1011,12 @@ extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v,
   if (dtype == DTA_F32) {                                    // fp32 models: the plain-FMA correctness path (tree_attn_f32.hip)
     DTA_REFUSE_IF_PRIOR_ERROR();
     return dta_attn_fwd_f32(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
-                            scale, static_cast<hipStream_t>(stream));
+                            scale, win_lo, WIN ? window : 0, static_cast<hipStream_t>(stream));
   }
   // the tile DMA addresses a 64-row tile as scalar base + 32-bit lane offset: token strides must keep 64 rows inside 4 GiB
   if (kv_st < 0 || v_st < 0 || kv_st > (1 << 24) || v_st > (1 << 24)) return DTA_EUNSUPPORTED;
-  AttnParams p{};
+  AttnP<WIN> p{};
+  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
   p.q = q; p.k = k; p.v = v; p.out = out; p.lse_w = lse; p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs;
   p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
   p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh; p.scale = scale;
@@ -984,28 +1030,29 @@ extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v,
     p.hgroups = npair; p.head0 = 0;
     dim3 grid(nqt * Hkv * npair), block(512);
     if (head_dim == 64) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 64>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 64>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 64, WIN>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 64, WIN>), grid, block, 0, st, p);
     } else {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 128>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 128>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 128, WIN>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 128, WIN>), grid, block, 0, st, p);
     }
   }
   if (p.group % 2) {
     p.hgroups = 1; p.head0 = p.group - 1;
     dim3 grid(nqt * Hkv), block(256);
     if (head_dim == 64) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 64>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 64>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 64, WIN>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 64, WIN>), grid, block, 0, st, p);
     } else {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 128>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 128>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 128, WIN>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 128, WIN>), grid, block, 0, st, p);
     }
   }
   return DTA_LAUNCH_STATUS();
 }
 
-extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v, const void* out, const void* dout,
+template <bool WIN>
+static int attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
                                     const float* lse, float* delta, void* dq, void* dk, void* dv,
                                     const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                                     const int32_t* ktile_qend,
@@ -1014,7 +1061,7 @@ extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v,
                                     int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
                                     float scale, int32_t dtype, int32_t accumulate, int32_t which,
                                     const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                                    void* stream) {
+                                    const int32_t* win_lo, int32_t window, void* stream) {
   if (!q || !k || !v || !out || !dout || !lse || !delta || !dq || !dk || !dv || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
   if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
   if (dkv_units && (n_units <= 0 || n_splits < 0 || (n_splits > 0 && (!dkv_splits || !dkv_ws)))) return DTA_EINVAL;
@@ -1026,10 +1073,11 @@ extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v,
     DTA_REFUSE_IF_PRIOR_ERROR();
     return dta_attn_bwd_f32(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
                             q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which,
-                            static_cast<hipStream_t>(stream));
+                            win_lo, WIN ? window : 0, static_cast<hipStream_t>(stream));
   }
   if (q_st < 0 || o_st < 0 || q_st > (1 << 24) || o_st > (1 << 24)) return DTA_EUNSUPPORTED;   // 64-row tile = scalar base + 32-bit lane offset
-  AttnParams p{};
+  AttnP<WIN> p{};
+  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
   p.q = q; p.k = k; p.v = v; p.o = out; p.dout = dout; p.lse_r = lse; p.delta = delta; p.dq = dq; p.dk = dk; p.dv = dv;
   p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs; p.ktile_qend = ktile_qend;
   p.dkv_units = dkv_units; p.dkv_splits = dkv_splits; p.dkv_ws = dkv_ws;
@@ -1045,17 +1093,81 @@ extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v,
   const bool fin = ((which & 2) && !(which & 8)) || (which & 4);     // slab finalize: with the dK/dV launch unless bit3, or alone (bit2)
   const int ndkv = dkv_units ? n_units : nkt;
   const int npair = p.group / 2;                                     // as in the forward: head pairs, then the odd head alone
-  AttnParams pp = p, ps = p;
+  AttnP<WIN> pp = p, ps = p;
   pp.hgroups = npair; pp.head0 = 0; ps.hgroups = 1; ps.head0 = p.group - 1;
   const dim3 gqp(nqt * Hkv * (npair > 0 ? npair : 1)), gqs(nqt * Hkv);
   if (head_dim == 64) {
-    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 64>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-    else launch_bwd<DTA_F16, 64>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 64, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    else launch_bwd<DTA_F16, 64, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
   } else {
-    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 128>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-    else launch_bwd<DTA_F16, 128>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 128, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    else launch_bwd<DTA_F16, 128, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
   }
   return DTA_LAUNCH_STATUS();
+}
+
+extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v, void* out, float* lse,
+                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                    float scale, int32_t dtype, void* stream) {
+  return attn_fwd<false>(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh,
+                         o_st, o_sh, scale, dtype, nullptr, 0, stream);
+}
+
+extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                                    const int32_t* ktile_qend,
+                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
+                                    float scale, int32_t dtype, int32_t accumulate, int32_t which,
+                                    const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
+                                    void* stream) {
+  return attn_bwd<false>(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
+                         q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype, accumulate, which,
+                         dkv_units, n_units, dkv_splits, n_splits, dkv_ws, nullptr, 0, stream);
+}
+
+// Sliding window (dta.h): window <= 0 is the _ex call itself; a win_lo without a window, or a packed trie without win_lo, is refused.
+static int window_args(const int32_t* subtree_end, const int32_t* win_lo, int32_t window) {
+  if (window <= 0) return win_lo ? DTA_EINVAL : 0;
+  if (subtree_end && !win_lo) return DTA_EINVAL;
+  return 1;
+}
+
+extern "C" int dta_tree_attn_fwd_win(const void* q, const void* k, const void* v, void* out, float* lse,
+                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, void* stream) {
+  const int w = window_args(subtree_end, win_lo, window);
+  if (w < 0) return w;
+  if (w == 0) return dta_tree_attn_fwd_ex(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh,
+                                          v_st, v_sh, o_st, o_sh, scale, dtype, stream);
+  return attn_fwd<true>(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh,
+                        o_st, o_sh, scale, dtype, win_lo, window, stream);
+}
+
+extern "C" int dta_tree_attn_bwd_win(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                                    const int32_t* ktile_qend,
+                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
+                                    float scale, int32_t dtype, int32_t accumulate, int32_t which,
+                                    const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
+                                    const int32_t* win_lo, int32_t window, void* stream) {
+  const int w = window_args(subtree_end, win_lo, window);
+  if (w < 0) return w;
+  if (w == 0) return dta_tree_attn_bwd_ex(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv,
+                                          head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype,
+                                          accumulate, which, dkv_units, n_units, dkv_splits, n_splits, dkv_ws, stream);
+  return attn_bwd<true>(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
+                        q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype, accumulate, which,
+                        dkv_units, n_units, dkv_splits, n_splits, dkv_ws, win_lo, window, stream);
 }
 
 // Token-major convenience forms declared in dta.h: head stride = 128 elements, so head_dim 128 only (other head dims: the _ex forms).

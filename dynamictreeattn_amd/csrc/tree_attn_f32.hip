@@ -12,6 +12,7 @@
 // no atomics, no slabs - the split-Q work units of the MFMA kernel are ignored here).  Deterministic by construction.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "dta_common.h"
 
 namespace {
@@ -29,6 +30,14 @@ struct P32 {
   int64_t q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh;
   float scale; int32_t accumulate;
 };
+// sliding window: key s also needs s >= win_lo[row] (packed form) or q_offset + row - window + 1 (stack form, win_lo == NULL); a type of its
+// own so that the kernels without a window keep their arguments and code
+struct P32W : P32 { const int32_t* win_lo; int32_t window; };
+template <bool WIN> using P32T = typename std::conditional<WIN, P32W, P32>::type;
+template <bool WIN> __device__ __forceinline__ int win_lo_of(const P32T<WIN>& p, int row) {
+  if constexpr (WIN) { const int lo = p.q_offset + row - p.window + 1; return p.win_lo ? p.win_lo[row] : (lo > 0 ? lo : 0); }
+  else return 0;
+}
 
 __device__ __forceinline__ float quad_sum(float v) { v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); return v; }
 
@@ -62,15 +71,16 @@ struct Runs {
     return false;
   }
 };
-__device__ __forceinline__ Runs runs_of(const P32& p, int q0) {
+template <bool WIN> __device__ __forceinline__ Runs runs_of(const P32T<WIN>& p, int q0) {
   Runs r; r.runs = p.runs;
   if (p.runs) { const int qt = q0 / DTA_QTILE; r.ri = p.run_ptr[qt]; r.re = p.run_ptr[qt + 1]; r.k0 = r.kend = 0; }
   else { r.ri = 0; r.re = 1; r.k0 = 0; const int last = p.q_offset + (q0 + ROWS < p.Tq ? q0 + ROWS : p.Tq); r.kend = last < p.Tk ? last : p.Tk; }
+  if constexpr (WIN) if (!p.runs && !p.win_lo) r.k0 = win_lo_of<WIN>(p, q0);     // stack form: the first row's bound is the block's lowest
   return r;
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32 p) {
+template <int D, bool WIN>
+__global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32T<WIN> p) {
   constexpr int PD = D / 4;                                         // head dims per lane
   __shared__ __attribute__((aligned(16))) float Ks[ST * D];
   __shared__ __attribute__((aligned(16))) float Vs[ST * D];
@@ -78,6 +88,7 @@ __global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32 p) {
   const int tid = threadIdx.x, row = tid >> 2, part = tid & 3;
   const int hq = blockIdx.y, kvh = hq / p.group;
   const int q0 = blockIdx.x * ROWS, qrow = q0 + row, qrow_c = qrow < p.Tq ? qrow : p.Tq - 1, qidx = p.q_offset + qrow;
+  const int wlo = win_lo_of<WIN>(p, qrow_c);
   float q[PD], o[PD];
   load_part<D>(q, p.q + (int64_t)qrow_c * p.q_st + (int64_t)hq * p.q_sh + PD * part);
 #pragma unroll
@@ -85,7 +96,7 @@ __global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32 p) {
   float m = -1e30f, l = 0.f;
   const float c = p.scale * LOG2E;
   const float* kb = p.k + (int64_t)kvh * p.kv_sh; const float* vb = p.v + (int64_t)kvh * p.v_sh;
-  Runs rn = runs_of(p, q0);
+  Runs rn = runs_of<WIN>(p, q0);
   while (rn.next()) {
     for (int k0 = rn.k0; k0 < rn.kend; k0 += ST) {
       __syncthreads();
@@ -100,7 +111,7 @@ __global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32 p) {
         for (int d = 0; d < PD; ++d) s = __builtin_fmaf(q[d], kr[d], s);
         s = quad_sum(s);
         const int key = k0 + j;
-        if (key <= qidx && qidx < se_s[j] && key < p.Tk) {
+        if (key <= qidx && qidx < se_s[j] && key < p.Tk && (!WIN || key >= wlo)) {
           const float sc = s * c, mn = fmaxf(m, sc);
           const float alpha = __builtin_amdgcn_exp2f(m - mn), pj = __builtin_amdgcn_exp2f(sc - mn);
           const float* vr = Vs + j * D + PD * part;
@@ -121,8 +132,8 @@ __global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32 p) {
   }
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32 p) {
+template <int D, bool WIN>
+__global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32T<WIN> p) {
   constexpr int PD = D / 4;                                         // head dims per lane
   __shared__ __attribute__((aligned(16))) float Ks[ST * D];
   __shared__ __attribute__((aligned(16))) float Vs[ST * D];
@@ -130,6 +141,7 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32 p) {
   const int tid = threadIdx.x, row = tid >> 2, part = tid & 3;
   const int hq = blockIdx.y, kvh = hq / p.group;
   const int q0 = blockIdx.x * ROWS, qrow = q0 + row, qrow_c = qrow < p.Tq ? qrow : p.Tq - 1, qidx = p.q_offset + qrow;
+  const int wlo = win_lo_of<WIN>(p, qrow_c);
   float q[PD], dof[PD], dq[PD];
   load_part<D>(q, p.q + (int64_t)qrow_c * p.q_st + (int64_t)hq * p.q_sh + PD * part);
   load_part<D>(dof, p.dout + (int64_t)qrow_c * p.o_st + (int64_t)hq * p.o_sh + PD * part);
@@ -145,7 +157,7 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32 p) {
   if (part == 0 && qrow < p.Tq) p.delta[(int64_t)hq * p.Tq + qrow] = -delta;
   const float c = p.scale * LOG2E;
   const float* kb = p.k + (int64_t)kvh * p.kv_sh; const float* vb = p.v + (int64_t)kvh * p.v_sh;
-  Runs rn = runs_of(p, q0);
+  Runs rn = runs_of<WIN>(p, q0);
   while (rn.next()) {
     for (int k0 = rn.k0; k0 < rn.kend; k0 += ST) {
       __syncthreads();
@@ -160,7 +172,7 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32 p) {
         for (int d = 0; d < PD; ++d) { s = __builtin_fmaf(q[d], kr[d], s); dp = __builtin_fmaf(dof[d], vr[d], dp); }
         s = quad_sum(s); dp = quad_sum(dp);
         const int key = k0 + j;
-        if (key <= qidx && qidx < se_s[j] && key < p.Tk) {
+        if (key <= qidx && qidx < se_s[j] && key < p.Tk && (!WIN || key >= wlo)) {
           const float ds = __builtin_amdgcn_exp2f(__builtin_fmaf(s, c, -lse2)) * (dp - delta);
 #pragma unroll
           for (int d = 0; d < PD; ++d) dq[d] = __builtin_fmaf(ds, kr[d], dq[d]);
@@ -177,8 +189,8 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32 p) {
 }
 
 // key-owned sweep: 64 keys of one kv head x every query that can see them x the heads of the GQA group
-template <int D>
-__global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32 p) {
+template <int D, bool WIN>
+__global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32T<WIN> p) {
   constexpr int PD = D / 4;                                         // head dims per lane
   __shared__ __attribute__((aligned(16))) float Qs[ST * D];
   __shared__ __attribute__((aligned(16))) float Ds[ST * D];
@@ -200,6 +212,9 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32 p) {
     const int qe = p.ktile_qend[k0 / DTA_KTILE];
     t_end = qe < t_end ? qe : t_end;
   }
+  if constexpr (WIN) if (!p.win_lo) {                  // stack form: query t sees this block only while t - window + 1 <= its last key
+    const int64_t wl = (int64_t)k0 + ROWS - 1 + p.window; t_end = wl < t_end ? (int)wl : t_end;
+  }
   for (int g = 0; g < p.group; ++g) {
     const int hq = kvh * p.group + g;
     const float* qb = p.q + (int64_t)hq * p.q_sh; const float* dob = p.dout + (int64_t)hq * p.o_sh;
@@ -217,7 +232,7 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32 p) {
         for (int d = 0; d < PD; ++d) { s = __builtin_fmaf(kf[d], qr[d], s); dp = __builtin_fmaf(vf[d], dr[d], dp); }
         s = quad_sum(s); dp = quad_sum(dp);
         const int t = t0 + i;
-        if (key <= t && t < se && key < p.Tk) {
+        if (key <= t && t < se && key < p.Tk && (!WIN || key >= win_lo_of<WIN>(p, t - p.q_offset))) {
           const float pj = __builtin_amdgcn_exp2f(__builtin_fmaf(s, c, -lse_s[i]));
           const float ds = pj * (dp + nd_s[i]);
 #pragma unroll
@@ -245,27 +260,32 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32 p) {
 
 }  // namespace
 
-int dta_attn_fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
-                     const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                     float scale, hipStream_t st) {
-  P32 p{};
+template <bool WIN>
+static int fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
+                   const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                   int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                   float scale, const int32_t* win_lo, int32_t window, hipStream_t st) {
+  P32T<WIN> p{};
+  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
   p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.out = (float*)out; p.lse_w = lse;
   p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs;
   p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
   p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh; p.scale = scale;
   const dim3 grid((Tq + ROWS - 1) / ROWS, Hq);
-  if (head_dim == 64) hipLaunchKernelGGL(tree_attn_fwd_f32_kernel<64>, grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL(tree_attn_fwd_f32_kernel<128>, grid, dim3(256), 0, st, p);
+  if (head_dim == 64) hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<64, WIN>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<128, WIN>), grid, dim3(256), 0, st, p);
   return DTA_LAUNCH_STATUS();
 }
 
-int dta_attn_bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
-                     void* dq, void* dk, void* dv, const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs, const int32_t* ktile_qend,
-                     int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                     int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which, hipStream_t st) {
-  P32 p{};
+template <bool WIN>
+static int bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
+                   void* dq, void* dk, void* dv, const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs, const int32_t* ktile_qend,
+                   int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                   int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                   int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which,
+                   const int32_t* win_lo, int32_t window, hipStream_t st) {
+  P32T<WIN> p{};
+  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
   p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.o = (const float*)out; p.dout = (const float*)dout;
   p.lse_r = lse; p.delta = delta; p.dq = (float*)dq; p.dk = (float*)dk; p.dv = (float*)dv;
   p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs; p.ktile_qend = ktile_qend;
@@ -274,11 +294,30 @@ int dta_attn_bwd_f32(const void* q, const void* k, const void* v, const void* ou
   p.dq_st = dq_st; p.dq_sh = dq_sh; p.dkv_st = dkv_st; p.dkv_sh = dkv_sh; p.scale = scale; p.accumulate = accumulate;
   const dim3 gq((Tq + ROWS - 1) / ROWS, Hq), gk((Tk + ROWS - 1) / ROWS, Hkv);
   if (head_dim == 64) {
-    if (which & 1) hipLaunchKernelGGL(tree_attn_bwd_dq_f32_kernel<64>, gq, dim3(256), 0, st, p);      // also writes -delta
-    if (which & 2) hipLaunchKernelGGL(tree_attn_bwd_dkv_f32_kernel<64>, gk, dim3(256), 0, st, p);
+    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<64, WIN>), gq, dim3(256), 0, st, p);      // also writes -delta
+    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<64, WIN>), gk, dim3(256), 0, st, p);
   } else {
-    if (which & 1) hipLaunchKernelGGL(tree_attn_bwd_dq_f32_kernel<128>, gq, dim3(256), 0, st, p);
-    if (which & 2) hipLaunchKernelGGL(tree_attn_bwd_dkv_f32_kernel<128>, gk, dim3(256), 0, st, p);
+    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<128, WIN>), gq, dim3(256), 0, st, p);
+    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<128, WIN>), gk, dim3(256), 0, st, p);
   }
   return DTA_LAUNCH_STATUS();                           // (which & 4, the slab finalize of the MFMA path, has nothing to do here)
+}
+
+int dta_attn_fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
+                     const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                     float scale, const int32_t* win_lo, int32_t window, hipStream_t st) {
+  return (window > 0 ? fwd_f32<true> : fwd_f32<false>)(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim,
+                                                       q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, scale, win_lo, window, st);
+}
+
+int dta_attn_bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
+                     void* dq, void* dk, void* dv, const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs, const int32_t* ktile_qend,
+                     int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                     int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which,
+                     const int32_t* win_lo, int32_t window, hipStream_t st) {
+  return (window > 0 ? bwd_f32<true> : bwd_f32<false>)(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk,
+                                                       q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
+                                                       dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which, win_lo, window, st);
 }

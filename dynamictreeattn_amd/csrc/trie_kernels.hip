@@ -2,6 +2,7 @@
 //   dta_lcp_adjacent   — first mismatch of adjacent sorted sequences by wave ballot
 //   dta_leafize        — leafization as a ballot/prefix-scan stream compaction
 //   dta_preorder_meta  — packed pre-order token / depth / parent / subtree_end gather
+//   dta_window_lo      — per-token lower key bound of a sliding attention window, by a walk up the segments
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dta_common.h"
@@ -136,6 +137,46 @@ extern "C" int dta_leafize(const int32_t* lens, const int32_t* lcp, int32_t S,
   if (S > (1 << 20)) return DTA_EUNSUPPORTED;
   DTA_REFUSE_IF_PRIOR_ERROR();
   hipLaunchKernelGGL(leafize_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), lens, lcp, S, out_leaf_pos, out_leaf_lcp, out_seq_leaf, out_M);
+  return DTA_LAUNCH_STATUS();
+}
+
+namespace {
+
+// win_lo[t] = packed index of t's ancestor at depth max(0, depth[t] - window + 1).  Along a root path packed index and depth both
+// increase, so the ancestors of t inside the window are exactly the keys s >= win_lo[t] of its path.  A token's segment is found by
+// binary search over seg_off; a target above the segment's first token moves to the segment of parent_of_seg: the walk visits
+// segments, not tokens (a few hops even for a window of thousands of tokens).
+__device__ __forceinline__ int seg_of(const int32_t* __restrict__ seg_off, int M, int t) {
+  int lo = 0, hi = M - 1;                        // largest i < M with seg_off[i] <= t (empty segments share their successor's offset)
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg_off[mid] <= t) lo = mid; else hi = mid - 1; }
+  return lo;
+}
+__global__ __launch_bounds__(256) void window_lo_kernel(const int32_t* __restrict__ depth, const int32_t* __restrict__ seg_off,
+                                                        const int32_t* __restrict__ seg_depth0, const int32_t* __restrict__ parent_of_seg,
+                                                        int32_t M, int32_t T, int32_t window, int32_t* __restrict__ out) {
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < T; t += gridDim.x * 256) {
+    const int d = depth[t];
+    const int a = d - window + 1 > 0 ? d - window + 1 : 0;
+    int i = seg_of(seg_off, M, t);
+    while (a < seg_depth0[i]) {
+      const int up = parent_of_seg[i];
+      if (up < 0 || up >= T) break;              // inconsistent tables: stop at the segment start rather than read outside them
+      i = seg_of(seg_off, M, up);
+    }
+    const int lo = seg_off[i] + (a > seg_depth0[i] ? a - seg_depth0[i] : 0);
+    out[t] = lo < t ? lo : t;
+  }
+}
+
+}  // namespace
+
+extern "C" int dta_window_lo(const int32_t* depth, const int32_t* seg_off, const int32_t* seg_depth0, const int32_t* parent_of_seg,
+                             int32_t M, int32_t T, int32_t window, int32_t* out_win_lo, void* stream) {
+  if (!depth || !seg_off || !seg_depth0 || !parent_of_seg || !out_win_lo || M < 1 || T < 1 || window <= 0) return DTA_EINVAL;
+  int blocks = (T + 255) / 256; if (blocks > 2048) blocks = 2048;
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  hipLaunchKernelGGL(window_lo_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), depth, seg_off, seg_depth0, parent_of_seg,
+                     M, T, window, out_win_lo);
   return DTA_LAUNCH_STATUS();
 }
 

@@ -18,15 +18,16 @@ def dta_attention_forward(module, query, key, value, attention_mask=None, dropou
                           sliding_window=None, **kwargs):
     if query.shape[0] != 1:
         raise ValueError("dta_mi355x attention handles one sequence per call (batch 1), as the reference engine issues them")
-    if sliding_window is not None or dropout:
-        raise ValueError("dta_mi355x attention: sliding window / dropout are not part of this path")
+    if dropout:
+        raise ValueError("dta_mi355x attention: dropout is not part of this path")
     _, Hq, B, D = query.shape
     S = key.shape[2]
     q = query[0].transpose(0, 1)          # [B, Hq, D] view
     k = key[0].transpose(0, 1)            # [S, Hkv, D] view
     v = value[0].transpose(0, 1)
     scale = D ** -0.5 if scaling is None else scaling
-    out = ops.tree_attention(q, k, v, ops.stack_meta(S - B), scale)      # [B, Hq, D] contiguous
+    # sliding layers (HF: kv_idx > q_idx - sliding_window) are the stack form with a window
+    out = ops.tree_attention(q, k, v, ops.stack_meta(S - B, sliding_window or 0), scale)      # [B, Hq, D] contiguous
     return out.unsqueeze(0), None
 
 

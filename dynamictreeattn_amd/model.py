@@ -107,6 +107,48 @@ def _cfg_of(model):
     return c.num_attention_heads, c.num_key_value_heads, D, float(getattr(c, "rms_norm_eps", 1e-6)), float(theta)
 
 
+def _windows_of(model):
+    """Sliding window of every decoder layer (0 = full attention), as the HF Qwen2 / Qwen3 configurations define it:
+    config.sliding_window where config.layer_types[l] == "sliding_attention"; without layer_types, the rule those config classes
+    apply (use_sliding_window and l >= max_window_layers).  A sliding layer without a sliding_window attends in full, as in HF."""
+    c = model.config
+    n = c.num_hidden_layers
+    W = getattr(c, "sliding_window", None) or 0
+    types = getattr(c, "layer_types", None)
+    if types is not None:
+        if len(types) != n:
+            raise ValueError(f"config.layer_types has {len(types)} entries for {n} layers")
+        bad = [t for t in types if t not in ("full_attention", "sliding_attention")]
+        if bad:
+            raise ValueError(f"unsupported attention layer type {bad[0]!r} (full_attention / sliding_attention)")
+        sliding = [t == "sliding_attention" for t in types]
+    else:
+        first = getattr(c, "max_window_layers", n)
+        sliding = [bool(getattr(c, "use_sliding_window", False)) and l >= (first if first is not None else n) for l in range(n)]
+    # HF keeps sliding_window = None when use_sliding_window is off; its attention then gets no window: full attention here too
+    return [int(W) if s_ else 0 for s_ in sliding]
+
+
+def layer_metas(meta, windows, for_window=None):
+    """Meta of every layer: `meta` for full layers; for a sliding layer of window W, `for_window(W)` (a packed trie: the windowed
+    meta, built once per distinct W - ops.window_meta) or, for a stack-form meta, the same stack form with the window.  A packed
+    meta without `for_window` is refused rather than run without the window."""
+    out, cache = [], {}
+    for W in windows:
+        if W <= 0 or meta is None:
+            out.append(meta)
+            continue
+        if W not in cache:
+            if for_window is not None:
+                cache[W] = for_window(W)
+            elif meta.subtree_end is None and meta.runs is None:
+                cache[W] = ops.stack_meta(meta.q_offset, W)
+            else:
+                raise ValueError("a sliding-window layer needs its windowed meta (ops.window_meta); none was given")
+        out.append(cache[W])
+    return out
+
+
 def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     """One decoder layer over the packed rows.  The hidden state enters as (residual stream, pending update)
     so that each residual add is fused into the RMSNorm that follows it.  hipBLASLt GEMMs through torch;
@@ -167,7 +209,8 @@ class _LayerRecompute(torch.autograd.Function):
 
 
 def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta, checkpoint_layers: bool = False,
-                         attn_keep_bytes: int = 0, attn_of_layer=None, full_layers=0, kept_out=None, embed=None) -> torch.Tensor:
+                         attn_keep_bytes: int = 0, attn_of_layer=None, full_layers=0, kept_out=None, embed=None,
+                         meta_for_window=None) -> torch.Tensor:
     """Final-norm hidden states [T, hidden] of the packed tokens.  `model` is a Qwen3TreeLM or an HF
     Qwen2/Qwen3 *ForCausalLM (duck-typed).  `checkpoint_layers`: recompute each layer in the backward, except the first
     `full_layers`, which keep their activations like the plain pass — an int, or a plan `bytes kept by layer 0 -> number of
@@ -175,15 +218,18 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
     `attn_keep_bytes`: HBM budget for attention outputs kept across that recomputation (layers are served first to last).
     `attn_of_layer(l)` -> callable (q, k, v) -> o replaces the packed tree attention (the block-wise engine passes the
     stack form bound to layer l's KV stack; `meta` is unused then); `embed(tokens)` replaces the plain embedding lookup (the
-    block-wise engine routes the rows' gradients into its fp32 sink instead of a dense [vocab, hidden] gradient per block)."""
+    block-wise engine routes the rows' gradients into its fp32 sink instead of a dense [vocab, hidden] gradient per block).
+    Sliding-window layers (_windows_of) attend with `meta_for_window(W)` (layer_metas); the stack form gets its window from
+    `attn_of_layer`."""
     Hq, Hkv, D, eps, theta = _cfg_of(model)
+    metas = layer_metas(meta, _windows_of(model), meta_for_window) if attn_of_layer is None else None
     body = model.model
     res, delta = (embed(tokens) if embed is not None else F.embedding(tokens, body.embed_tokens.weight)), None
     cos_sin = ops.rope_cos_sin(depth, D, theta)
     per_layer = tokens.shape[0] * Hq * (D * res.element_size() + 4)             # out + lse of one layer
     n_full = full_layers if isinstance(full_layers, int) else 1
     for li, layer in enumerate(body.layers):
-        attn = attn_of_layer(li) if attn_of_layer is not None else (lambda q, k, v: ops.tree_attention(q, k, v, meta))
+        attn = attn_of_layer(li) if attn_of_layer is not None else (lambda m_: lambda q, k, v: ops.tree_attention(q, k, v, m_))(metas[li])
         if li == 0 and callable(full_layers) and checkpoint_layers and torch.is_grad_enabled() and res.is_cuda:
             m0 = torch.cuda.memory_allocated(res.device)
             res, delta = _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)

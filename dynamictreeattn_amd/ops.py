@@ -5,6 +5,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -109,7 +110,9 @@ def _launch(name: str, tensors, *args, nbytes: int = 0):
 
 @dataclass
 class TreeAttnMeta:
-    """Device-resident visibility metadata of one packed trie (or None fields for the stack form)."""
+    """Device-resident visibility metadata of one packed trie (or None fields for the stack form).  window > 0: a sliding-window
+    layer (key s visible to row t only if depth[t] - depth[s] < window); then win_lo [T] holds each row's lowest visible key (packed
+    form; None in the stack form) and run_ptr / runs / ktile_qend / dK/dV units are the windowed plan's (window_meta)."""
     T: int
     subtree_end: Optional[torch.Tensor]      # int32 [T]
     run_ptr: Optional[torch.Tensor]          # int32 [nqt+1]
@@ -119,6 +122,8 @@ class TreeAttnMeta:
     dkv_units: Optional[torch.Tensor] = None     # int32 [n,4] balanced work units of the dK/dV sweep (packing.plan_dkv_units)
     dkv_splits: Optional[torch.Tensor] = None    # int32 [m,4]
     n_slabs: int = 0
+    win_lo: Optional[torch.Tensor] = None        # int32 [T] (packing.window_lo_host / dta_window_lo)
+    window: int = 0
 
 
 def ktile_qend_from(subtree_end: torch.Tensor, tile: int = packing.KTILE) -> torch.Tensor:
@@ -143,11 +148,13 @@ def attn_fwd_raw(q, k, v, meta: TreeAttnMeta, scale: float):
     lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device)          # head-major: rows of one head are contiguous
     (qs, qh), (ks, kh), (vs, vh), (os_, oh) = _strides(q), _strides(k), _strides(v), _strides(out)
     tm = KernelTimer.active
+    win = (ptr(meta.win_lo), int(meta.window)) if meta.window > 0 else ()
     with _on(q, k, v, meta.subtree_end, meta.runs) as stream:
         if tm is not None:
             ev = tm.span("fwd"); ev[0].record()
-        st = lib().dta_tree_attn_fwd_ex(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs),
-                                        Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, float(scale), _DT[q.dtype], stream)
+        st = getattr(lib(), "dta_tree_attn_fwd_win" if win else "dta_tree_attn_fwd_ex")(
+            ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs),
+            Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, float(scale), _DT[q.dtype], *win, stream)
         if tm is not None:
             ev[1].record()
     check(st, "dta_tree_attn_fwd")
@@ -173,14 +180,17 @@ def attn_bwd_raw(q, k, v, out, dout, lse, meta: TreeAttnMeta, scale: float, dk=N
         units = splits = None; n_units = n_splits = 0
     ws = torch.empty((meta.n_slabs, Hkv, 2, packing.KTILE, D), dtype=torch.float32, device=q.device) if (units is not None and meta.n_slabs) else None
 
+    win = (ptr(meta.win_lo), int(meta.window)) if meta.window > 0 else ()
+
     def launch(which, stream):
-        return lib().dta_tree_attn_bwd_ex(ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
-                                          ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs), ptr(meta.ktile_qend),
-                                          Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, dqs, dqh, dks, dkh,
-                                          float(scale), _DT[q.dtype], int(accumulate), which,
-                                          ptr(units), n_units, ptr(splits) if n_splits else None, n_splits, ptr(ws), stream)
+        return getattr(lib(), "dta_tree_attn_bwd_win" if win else "dta_tree_attn_bwd_ex")(
+            ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
+            ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs), ptr(meta.ktile_qend),
+            Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, dqs, dqh, dks, dkh,
+            float(scale), _DT[q.dtype], int(accumulate), which,
+            ptr(units), n_units, ptr(splits) if n_splits else None, n_splits, ptr(ws), *win, stream)
     tm = KernelTimer.active
-    with _on(q, k, v, out, dout, lse, dk, dv, meta.subtree_end, units) as stream:
+    with _on(q, k, v, out, dout, lse, dk, dv, meta.subtree_end, units, meta.win_lo) as stream:
         if tm is None:
             check(launch(3, stream), "dta_tree_attn_bwd")
         else:
@@ -252,11 +262,11 @@ class _StackAttention(torch.autograd.Function):
     contributions of every already-popped descendant plus the block's own."""
 
     @staticmethod
-    def forward(ctx, q, k_new, v_new, kst, vst, gk, gv, start, scale):
+    def forward(ctx, q, k_new, v_new, kst, vst, gk, gv, start, scale, window):
         B = q.shape[0]
         end = start + B
         kst[start:end].copy_(k_new); vst[start:end].copy_(v_new)
-        meta = stack_meta(start)
+        meta = stack_meta(start, window)
         out, lse, _, _ = attn_fwd_raw(q, kst[:end], vst[:end], meta, scale)
         ctx.save_for_backward(q, out, lse)
         ctx.stacks, ctx.meta, ctx.scale, ctx.span = (kst, vst, gk, gv), meta, scale, (start, end)
@@ -268,16 +278,17 @@ class _StackAttention(torch.autograd.Function):
         kst, vst, gk, gv = ctx.stacks
         start, end = ctx.span
         dq, _, _ = attn_bwd_raw(q, kst[:end], vst[:end], out, dout, lse, ctx.meta, ctx.scale, dk=gk[:end], dv=gv[:end], accumulate=2)
-        return dq, gk[start:end].to(q.dtype), gv[start:end].to(q.dtype), None, None, None, None, None, None
+        return dq, gk[start:end].to(q.dtype), gv[start:end].to(q.dtype), None, None, None, None, None, None, None
 
 
-def stack_attention(q, k_new, v_new, kst, vst, gk, gv, start: int, scale: Optional[float] = None):
+def stack_attention(q, k_new, v_new, kst, vst, gk, gv, start: int, scale: Optional[float] = None, window: int = 0):
     """q [B,Hq,D], k_new/v_new [B,Hkv,D] at stack positions start..start+B-1; kst/vst [cap,Hkv,D] (model dtype),
-    gk/gv [cap,Hkv,D] fp32 grad stacks (may be None under no_grad) -> out [B,Hq,D] (D = head_dim, 64 or 128)."""
+    gk/gv [cap,Hkv,D] fp32 grad stacks (may be None under no_grad) -> out [B,Hq,D] (D = head_dim, 64 or 128).
+    window > 0: sliding window, row t sees stack rows (t - window, t] (the whole stack is kept either way)."""
     if q.dtype not in _DT:
         raise TypeError("stack_attention supports bf16 / f16 / f32 (got %s)" % q.dtype)
     scale = q.shape[-1] ** -0.5 if scale is None else scale
-    return _StackAttention.apply(q, k_new, v_new, kst, vst, gk, gv, start, scale)
+    return _StackAttention.apply(q, k_new, v_new, kst, vst, gk, gv, start, scale, int(window))
 
 
 def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, meta: TreeAttnMeta, scale: Optional[float] = None) -> torch.Tensor:
@@ -288,9 +299,10 @@ def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, meta: Tree
     return _TreeAttention.apply(q, k, v, meta, scale)
 
 
-def stack_meta(start: int) -> TreeAttnMeta:
-    """Rectangular-causal stack form: query i sits at stack position start+i (tte:171-186)."""
-    return TreeAttnMeta(T=0, subtree_end=None, run_ptr=None, runs=None, ktile_qend=None, q_offset=start)
+def stack_meta(start: int, window: int = 0) -> TreeAttnMeta:
+    """Rectangular-causal stack form: query i sits at stack position start+i (tte:171-186); window > 0: it sees only the
+    positions (start + i - window, start + i]."""
+    return TreeAttnMeta(T=0, subtree_end=None, run_ptr=None, runs=None, ktile_qend=None, q_offset=start, window=max(int(window), 0))
 
 
 def attach_dkv_units(meta: TreeAttnMeta, Hkv: int) -> TreeAttnMeta:
@@ -310,6 +322,36 @@ def meta_from_plan(plan: packing.SegmentPlan, subtree_end: torch.Tensor, device,
                         run_ptr=torch.from_numpy(rp).to(device), runs=torch.from_numpy(runs).to(device).contiguous(),
                         ktile_qend=ktile_qend_from(subtree_end))
     return attach_dkv_units(meta, Hkv)
+
+
+def window_lo_device(depth: torch.Tensor, seg_off: torch.Tensor, seg_depth0: torch.Tensor, parent_of_seg: torch.Tensor,
+                     window: int) -> torch.Tensor:
+    """win_lo [T] of a packed trie on the device (dta_window_lo): depth from dta_preorder_meta, the segment tables of its plan."""
+    T, M = depth.numel(), parent_of_seg.numel()
+    out = torch.empty(T, dtype=torch.int32, device=depth.device)
+    _launch("dta_window_lo", (depth,), ptr(depth), ptr(seg_off), ptr(seg_depth0), ptr(parent_of_seg), M, T, int(window), ptr(out))
+    return out
+
+
+def window_meta(meta: TreeAttnMeta, plan: packing.SegmentPlan, depth: torch.Tensor, window: int, Hkv: int = 8, seg_tables=None) -> TreeAttnMeta:
+    """The sliding-window meta of a packed trie from its full meta: win_lo on the device (dta_window_lo), the windowed tile plan
+    (packing.plan_qtile_runs_window: query tiles visit O(window) keys), the tighter dK/dV query ends and their work units.  Build
+    it once per distinct window per call and share it between layers.  window <= 0, or wider than the deepest token: `meta`
+    itself (the unwindowed kernels, bit for bit).  seg_tables: (seg_off, seg_depth0, parent_of_seg) already on the device."""
+    if window <= 0 or window > packing.max_depth(plan):
+        return meta
+    dev = depth.device
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+    if seg_tables is None:
+        seg_tables = (up(plan.seg_off), up(plan.seg_depth0), up(plan.parent_of_seg))
+    win_lo = window_lo_device(depth, *seg_tables, window)
+    wl_host = packing.window_lo_host(plan, window)
+    rp, runs = packing.plan_qtile_runs_window(plan, wl_host)
+    kq = packing.ktile_qend_window(packing.ktile_qend_host(plan), wl_host)
+    units, splits, n_slabs = packing.plan_dkv_units(kq, plan.T, plan.T, 0, Hkv)
+    return TreeAttnMeta(T=plan.T, subtree_end=meta.subtree_end, run_ptr=up(rp), runs=up(runs).view(-1, 4), ktile_qend=up(kq),
+                        dkv_units=up(units).view(-1, 4), dkv_splits=up(splits).view(-1, 4) if splits.shape[0] else None, n_slabs=n_slabs,
+                        win_lo=win_lo, window=int(window))
 
 
 # --------------------------------------------------------------------------------------------------

@@ -265,3 +265,115 @@ def plan_dkv_units(ktile_qend: np.ndarray, Tk: int, Tq: int, q_offset: int = 0, 
     first_slab = (np.cumsum(np.where(nsplit > 1, nsplit, 0)) - np.where(nsplit > 1, nsplit, 0))[split_kt]
     splits = np.stack([split_kt, first_slab, nsplit[split_kt], np.zeros_like(split_kt)], axis=1) if split_kt.size else np.zeros((0, 4), np.int64)
     return units[order].astype(np.int32), splits.astype(np.int32), int(is_split.sum())
+
+
+# ---- sliding window ------------------------------------------------------------------------------------------------------
+# A sliding layer lets query t see key s only when depth[t] - depth[s] < W (HF's sliding_window_overlay, per sequence).  Along a
+# root path packed index and depth both increase, so inside t's ancestors that is one lower bound on the index: s >= win_lo[t],
+# the packed index of t's ancestor at depth max(0, depth[t] - W + 1).  dta_window_lo computes the same array on the device.
+
+def window_lo_host(plan: SegmentPlan, window: int) -> np.ndarray:
+    """win_lo[T] (int32) of a window of `window` tokens: walks up segments (vectorised over the tokens still above their target
+    depth), not tokens."""
+    if window <= 0:
+        raise ValueError("window must be > 0")
+    T, M = plan.T, plan.M
+    seg_off = plan.seg_off.astype(np.int64)
+    d0 = plan.seg_depth0.astype(np.int64)
+    seg = np.repeat(np.arange(M, dtype=np.int64), np.diff(seg_off))          # segment of every packed token
+    t = np.arange(T, dtype=np.int64)
+    depth = d0[seg] + t - seg_off[seg]
+    a = np.maximum(depth - window + 1, 0)                                    # target depth
+    i = seg.copy()
+    need = np.flatnonzero(a < d0[i])
+    par = plan.parent_of_seg.astype(np.int64)
+    while need.size:
+        i[need] = seg[par[i[need]]]
+        need = need[a[need] < d0[i[need]]]
+    return (seg_off[i] + a - d0[i]).astype(np.int32)
+
+
+def max_depth(plan: SegmentPlan) -> int:
+    """Largest token depth of the plan (-1 when empty): a window wider than this changes nothing."""
+    n = np.diff(plan.seg_off.astype(np.int64))
+    live = n > 0
+    return int((plan.seg_depth0[live] + n[live] - 1).max()) if live.any() else -1
+
+
+def _clip(ivs, lo):
+    return [(max(b, lo), e) for b, e in ivs if e > max(b, lo)]
+
+
+def plan_qtile_runs_window(plan: SegmentPlan, win_lo: np.ndarray, tile: int = QTILE):
+    """plan_qtile_runs for a sliding window (win_lo from window_lo_host): every run is clipped to the keys some row of the tile can
+    still see — per segment of the tile, at the lowest win_lo of its rows — so a query tile visits O(W) keys instead of its whole
+    root path.  A run stays maskless only if its keys are ancestors of every row AND >= the largest win_lo of the tile; the keys
+    between the two bounds become needs_mask runs.  With a window wider than the deepest token this is plan_qtile_runs."""
+    T = plan.T
+    nqt = (T + tile - 1) // tile
+    seg_off = plan.seg_off
+    starts = np.arange(nqt, dtype=np.int64) * tile
+    ends = np.minimum(starts + tile, T)
+    first = np.searchsorted(seg_off, starts, side="right") - 1
+    last = np.searchsorted(seg_off, ends - 1, side="right") - 1
+    wl = np.asarray(win_lo, np.int64)
+    run_ptr = [0]
+    out: List[Tuple[int, int, int, int]] = []
+    for qt in range(nqt):
+        q0, q1, i0, i1 = int(starts[qt]), int(ends[qt]), int(first[qt]), int(last[qt])
+        lo_min, lo_max = int(wl[q0:q1].min()), int(wl[q0:q1].max())
+        if i0 == i1:
+            full = []                                         # the unwindowed maskless runs of the tile, merged as plan_qtile_runs does
+            for b, e in plan.path_runs[i0]:
+                full.append((b, e))
+            s = int(seg_off[i0])
+            if s < q0:
+                if full and full[-1][1] == s:
+                    full[-1] = (full[-1][0], q0)
+                else:
+                    full.append((s, q0))
+            for b, e in full:
+                b = max(b, lo_min)
+                if b >= e:
+                    continue
+                if min(e, lo_max) > b:
+                    out.append((b, min(e, lo_max), 1, 0))    # ancestors of every row, but below some row's window
+                if e > max(b, lo_max):
+                    out.append((max(b, lo_max), e, 0, 0))
+            out.append((max(q0, lo_min), q1, 1, 0))
+        else:
+            common = None
+            ivs = []
+            for i in range(i0, i1 + 1):
+                s, e = int(seg_off[i]), min(q1, int(seg_off[i + 1]))
+                if e <= s:
+                    continue
+                lo_i = int(wl[max(s, q0):e].min())            # the segment's rows in this tile see nothing below this
+                anc = list(plan.path_runs[i])
+                if s < q0:
+                    anc.append((s, q0))
+                anc = _clip(anc, lo_i)
+                common = anc if common is None else _intersect(common, anc)
+                ivs.extend(_clip(list(plan.path_runs[i]) + [(s, e)], lo_i))
+            common = _merge([(max(b, lo_max), min(e, q0)) for b, e in (common or []) if max(b, lo_max) < min(e, q0)])
+            for b, e in common:
+                out.append((b, e, 0, 0))
+            for b, e in _subtract(_merge(ivs), common):
+                out.append((b, e, 1, 0))
+        run_ptr.append(len(out))
+    return np.asarray(run_ptr, np.int32), np.asarray(out, np.int32).reshape(-1, 4)
+
+
+def ktile_qend_window(ktile_qend: np.ndarray, win_lo: np.ndarray, tile: int = KTILE) -> np.ndarray:
+    """Tighter dK/dV query ends under a window: the keys of tile j are seen only by rows t with win_lo[t] <= its last key, so the sweep
+    may stop after the last such row.  min(ktile_qend, that bound): still an upper bound of every visible row, equal to ktile_qend
+    when the window changes nothing."""
+    wl = np.asarray(win_lo, np.int64)
+    T = wl.shape[0]
+    nkt = ktile_qend.shape[0]
+    if T == 0:
+        return ktile_qend.astype(np.int32)
+    sufmin = np.minimum.accumulate(wl[::-1])[::-1]                         # non-decreasing
+    kmax = np.minimum((np.arange(nkt, dtype=np.int64) + 1) * tile, T) - 1
+    qe = np.searchsorted(sufmin, kmax, side="right")                       # one past the last row whose window reaches the tile
+    return np.minimum(ktile_qend.astype(np.int64), qe).astype(np.int32)

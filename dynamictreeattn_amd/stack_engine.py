@@ -31,7 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .model import _cfg_of, head_weight, packed_hidden_states
+from .model import _cfg_of, _windows_of, head_weight, packed_hidden_states
 from .tree_training_engine import sum_loss_terms
 from .trie import pop_block_starts
 
@@ -153,9 +153,12 @@ class StackWalk:
 
     # ------------------------------------------------------------------------------------------
     def _attn_of_layer(self, start: int, with_grad: bool):
+        windows = _windows_of(self.model)          # sliding layers: the stack form with the window (the whole stack is kept)
+
         def of(l):
+            win = {"window": windows[l]} if windows[l] > 0 else {}
             return lambda q, k, v: ops.stack_attention(q, k, v, self.kst[l], self.vst[l], self.gk[l] if with_grad else None,
-                                                       self.gv[l] if with_grad else None, start)
+                                                       self.gv[l] if with_grad else None, start, **win)
         return of
 
     def _hidden(self, s: int, e: int, with_grad: bool):

@@ -173,6 +173,13 @@ class _PackedTrie:
         self.meta = ops.TreeAttnMeta(T=T, subtree_end=self.subtree_end, run_ptr=run_ptr_d, runs=runs_d.view(-1, 4), ktile_qend=kq_d,
                                      dkv_units=units_d.view(-1, 4), dkv_splits=splits_d.view(-1, 4) if splits.shape[0] else None,
                                      n_slabs=n_slabs)
+        self._seg_tables, self._n_kv_heads, self._win_metas = (seg_off, seg_d0, par_seg), n_kv_heads, {}
+
+    def for_window(self, window: int):
+        """Meta of the sliding-window layers of width `window` (ops.window_meta), built once per distinct window per pass."""
+        if window not in self._win_metas:
+            self._win_metas[window] = ops.window_meta(self.meta, self.plan, self.depth, window, self._n_kv_heads, self._seg_tables)
+        return self._win_metas[window]
 
     def sequence_rows(self, attach_lists):
         """Packed row of every value the loss callbacks see, in callback order (leaf by leaf, the sequences folded onto it in attach-list
@@ -430,7 +437,7 @@ class TreeTrainingEngine:
 
     def _forward(self, model, token_trie):
         packed = self._pack(token_trie)
-        h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, False)
+        h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, False, meta_for_window=packed.for_window)
         lp, _ = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, False, self.head_chunk,
                                        packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev)
         for i, attach_list in enumerate(token_trie.attach_lists):
@@ -472,7 +479,8 @@ class TreeTrainingEngine:
         attn_keep = self._attn_keep_bytes() if ckpt else 0          # before the layer plan: the plan leaves this much alone
         full = self._full_layers(model, packed.plan.T) if ckpt else 0
         kept = []
-        h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, ckpt, attn_keep, None, full, kept)
+        h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, ckpt, attn_keep, None, full, kept,
+                                 meta_for_window=packed.for_window)
         if ckpt and kept:
             self.last_mode = "packed" if kept[0] >= self.n_layers else f"packed+recompute[{self.n_layers - kept[0]}/{self.n_layers}]"
         lp, ent = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, True, max(chunk, 1),

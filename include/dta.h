@@ -158,6 +158,42 @@ int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v, const void
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sliding-window attention (the "sliding_attention" layers of Qwen2 / Qwen3 configurations).  Visibility gains one lower bound:
+ *   packed trie:  key s visible to query row i (t = q_offset + i)  <=>  s <= t < subtree_end[s]  &&  s >= win_lo[i]
+ *                 win_lo[i] = packed index of t's ancestor at depth max(0, depth[t] - window + 1) (dta_window_lo), i.e.
+ *                 depth[t] - depth[s] < window along the path: the mask of HF's sliding_window_overlay for every sequence through t.
+ *   stack form (subtree_end == NULL, win_lo == NULL):  s <= t  &&  t - s < window.
+ * All other arguments are those of the _ex forms.  run_ptr / runs of a packed trie must be planned for the window: a run with
+ * needs_mask == 0 promises that its keys are ancestors of every row of the tile AND >= every row's win_lo (the windowed plan of
+ * packing.plan_qtile_runs_window); ktile_qend and dkv_units may be the windowed, tighter ones.
+ * window <= 0: no window - the call IS the _ex call (bit for bit) and win_lo must be NULL.  DTA_EINVAL: win_lo given with
+ * window <= 0, or subtree_end given (packed trie) with window > 0 and no win_lo. */
+int dta_tree_attn_fwd_win(const void* q, const void* k, const void* v, void* out, float* lse,
+                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
+                          int64_t v_stride_t, int64_t v_stride_h,
+                          int64_t o_stride_t, int64_t o_stride_h, float scale, int32_t dtype,
+                          const int32_t* win_lo, int32_t window, void* stream);
+int dta_tree_attn_bwd_win(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                          const float* lse, float* delta, void* dq, void* dk, void* dv,
+                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                          const int32_t* ktile_qend,
+                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
+                          int64_t v_stride_t, int64_t v_stride_h,
+                          int64_t o_stride_t, int64_t o_stride_h, int64_t dq_stride_t, int64_t dq_stride_h,
+                          int64_t dkv_stride_t, int64_t dkv_stride_h,
+                          float scale, int32_t dtype, int32_t accumulate, int32_t which,
+                          const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
+                          const int32_t* win_lo, int32_t window, void* stream);
+/* out_win_lo[t] for the T packed tokens of a trie: the packed index of t's ancestor at depth max(0, depth[t] - window + 1).  depth[T] as
+ * written by dta_preorder_meta; seg_off[M+1], seg_depth0[M], parent_of_seg[M] as passed to it.  Walks up segments (binary search over
+ * seg_off per hop), not tokens.  window > 0 (DTA_EINVAL otherwise). */
+int dta_window_lo(const int32_t* depth, const int32_t* seg_off, const int32_t* seg_depth0, const int32_t* parent_of_seg,
+                  int32_t M, int32_t T, int32_t window, int32_t* out_win_lo, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Log-prob / entropy over vocabulary rows (HBM-bound).  logits: [R, V] bf16 / f16 / f32 with row_stride elements
  * between rows (multiple of 8; base 16-byte aligned, 32-byte for f32).  All statistics are fp32.
  * fwd writes lse[r] = ln sum_j exp(x_j/T), entropy[r] (may be NULL) and logprob[r] = x[labels[r]]/T - lse[r] (may be
