@@ -36,6 +36,14 @@ _PROTOS = {
     "dta_swiglu_bwd": ([_vp] * 5 + [_i64, _i32, _i64, _i64, _i32, _vp], C.c_int),
     "dta_transpose": ([_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp], C.c_int),
     "dta_sum_slabs": ([_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp], C.c_int),
+    "dta_moe_router_fwd": ([_vp] * 4 + [_i32] * 5 + [_vp], C.c_int),
+    "dta_moe_router_bwd": ([_vp] * 5 + [_i32] * 5 + [_vp], C.c_int),
+    "dta_moe_permute_workspace": ([_i32, _i32], C.c_int),
+    "dta_moe_tile_bound": ([_i32, _i32], C.c_int),
+    "dta_moe_permute": ([_vp, _i32, _i32, _i32] + [_vp] * 5 + [_vp], C.c_int),
+    "dta_moe_grouped_gemm": ([_i32] + [_vp] * 7 + [_i32] * 5 + [_vp], C.c_int),
+    "dta_moe_combine_fwd": ([_vp] * 4 + [_i32] * 4 + [_vp], C.c_int),
+    "dta_moe_combine_bwd": ([_vp] * 6 + [_i32] * 4 + [_vp], C.c_int),
 }
 EXPORTS = tuple(_PROTOS)
 _ERR = {-1: "DTA_EINVAL", -2: "DTA_EUNSUPPORTED", -3: "DTA_EALIGN", -4: "DTA_ELAUNCH", -5: "DTA_EPRIOR"}

@@ -7,7 +7,7 @@ torch.  `Qwen3TreeLM` mirrors the HF module/parameter tree (``model.embed_tokens
 ``model.layers.N.self_attn.q_proj.weight`` …, tied head) so that
 
 * gradients compare name by name with grad/Qwen3-0.6B-TB-vs-DB-bf16.txt (310 tensors), and
-* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3 ``*ForCausalLM`` by duck typing —
+* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE ``*ForCausalLM`` by duck typing —
   its own ``nn.Parameter`` objects are used, so ``param.grad`` lands where the training loop expects.
 """
 from __future__ import annotations
@@ -47,10 +47,40 @@ class _MLP(nn.Module):
         self.gate_proj, self.up_proj, self.down_proj = _Lin(c.hidden_size, c.intermediate_size), _Lin(c.hidden_size, c.intermediate_size), _Lin(c.intermediate_size, c.hidden_size)
 
 
-class _Layer(nn.Module):
+class _Router(nn.Module):
     def __init__(self, c):
         super().__init__()
-        self.self_attn, self.mlp = _Attn(c), _MLP(c)
+        self.top_k, self.num_experts, self.norm_topk_prob = c.num_experts_per_tok, c.num_experts, bool(getattr(c, "norm_topk_prob", False))
+        self.weight = nn.Parameter(torch.empty(c.num_experts, c.hidden_size))
+
+
+class _Experts(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        E, H, I = c.num_experts, c.hidden_size, c.moe_intermediate_size
+        self.gate_up_proj = nn.Parameter(torch.empty(E, 2 * I, H))
+        self.down_proj = nn.Parameter(torch.empty(E, H, I))
+
+
+class _MoE(nn.Module):
+    """HF Qwen3MoeSparseMoeBlock's parameter tree: mlp.gate.weight [E, H], mlp.experts.gate_up_proj [E, 2I, H], mlp.experts.down_proj [E, H, I]."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.gate, self.experts = _Router(c), _Experts(c)
+
+
+def is_moe_layer(c, l: int) -> bool:
+    """The rule of HF Qwen3MoeDecoderLayer: experts unless the layer is in mlp_only_layers, when num_experts > 0 and (l + 1) is a
+    multiple of decoder_sparse_step."""
+    E = getattr(c, "num_experts", 0) or 0
+    return E > 0 and l not in (getattr(c, "mlp_only_layers", None) or []) and (l + 1) % (getattr(c, "decoder_sparse_step", 1) or 1) == 0
+
+
+class _Layer(nn.Module):
+    def __init__(self, c, l=0):
+        super().__init__()
+        self.self_attn, self.mlp = _Attn(c), (_MoE(c) if is_moe_layer(c, l) else _MLP(c))
         self.input_layernorm, self.post_attention_layernorm = _Norm(c.hidden_size), _Norm(c.hidden_size)
 
 
@@ -58,7 +88,7 @@ class _Body(nn.Module):
     def __init__(self, c):
         super().__init__()
         self.embed_tokens = nn.Embedding(c.vocab_size, c.hidden_size)
-        self.layers = nn.ModuleList(_Layer(c) for _ in range(c.num_hidden_layers))
+        self.layers = nn.ModuleList(_Layer(c, l) for l in range(c.num_hidden_layers))
         self.norm = _Norm(c.hidden_size)
 
 
@@ -167,6 +197,9 @@ def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     attn_out = ops.linear(o.reshape(T, Hq * D), a.o_proj.weight)
     res, h = ops.add_rms_norm(res, attn_out, layer.post_attention_layernorm.weight, eps)
     m = layer.mlp
+    if hasattr(m, "experts") and hasattr(m, "gate"):       # Qwen3MoeSparseMoeBlock (duck-typed): router + grouped expert GEMMs
+        g = m.gate
+        return res, ops.moe_mlp(h, g.weight, m.experts.gate_up_proj, m.experts.down_proj, g.top_k, g.norm_topk_prob)
     act = ops.swiglu_fused(ops.linear(h, ops.stack_rows(m.gate_proj.weight, m.up_proj.weight)))
     return res, ops.linear(act, m.down_proj.weight)
 

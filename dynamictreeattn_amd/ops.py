@@ -95,13 +95,14 @@ def free_hbm(device) -> int:
     return max(int(usable), 0)
 
 
-def _launch(name: str, tensors, *args, nbytes: int = 0):
+def _launch(name: str, tensors, *args, nbytes: int = 0, span: Optional[str] = None):
     """One C-ABI call on the device / current stream of `tensors` (see _on); raises on a non-zero status.
-    `nbytes`: algorithmic HBM bytes of the launch (one read of every input, one write of every output) for the roofline leg."""
+    `nbytes`: algorithmic HBM bytes of the launch (one read of every input, one write of every output) for the roofline leg;
+    `span`: the KernelTimer name of the launch (default: the entry point's)."""
     tm = KernelTimer.active
     with _on(*tensors) as stream:
         if tm is not None:
-            a, b = tm.span(name, nbytes); a.record()
+            a, b = tm.span(span or name, nbytes); a.record()
         st = getattr(lib(), name)(*args, stream)
         if tm is not None:
             b.record()
@@ -986,3 +987,170 @@ class _Linear(torch.autograd.Function):
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [rows, in] @ w[out, in]ᵀ."""
     return _Linear.apply(x, w, b)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Mixture of experts (Qwen3MoeSparseMoeBlock): router top-k, permutation by expert, grouped GEMMs, combine - include/dta.h "Mixture of experts"
+# ------------------------------------------------------------------------------------------------------------------------------------
+MOE_FWD, MOE_DGRAD, MOE_WGRAD = 0, 1, 2
+
+
+@dataclass
+class MoeRouting:
+    """Device-side result of the permutation of one layer's T*k (token, slot) pairs: expert_offsets [E+1], row_of_pair [T*k],
+    src_token [T*k] (row -> token), tiles [2 * bound] (the grouped GEMMs' tile table).  Nothing of it is read on the host."""
+    T: int
+    k: int
+    E: int
+    expert_offsets: torch.Tensor
+    row_of_pair: torch.Tensor
+    src_token: torch.Tensor
+    tiles: torch.Tensor
+
+
+def moe_router_fwd_raw(logits: torch.Tensor, k: int, norm: bool):
+    """logits [T, E] -> (ids int32 [T, k], weights [T, k] in the logits' dtype, lse float [T])."""
+    T, E_ = logits.shape
+    logits = logits.contiguous()
+    ids = torch.empty((T, k), dtype=torch.int32, device=logits.device)
+    w = torch.empty((T, k), dtype=logits.dtype, device=logits.device)
+    lse = torch.empty(T, dtype=torch.float32, device=logits.device)
+    _launch("dta_moe_router_fwd", (logits,), ptr(logits), ptr(ids), ptr(w), ptr(lse), T, E_, k, int(bool(norm)), _DT[logits.dtype],
+            nbytes=T * E_ * logits.element_size())
+    return ids, w, lse
+
+
+def moe_router_bwd_raw(logits, lse, ids, dw, norm: bool):
+    T, E_ = logits.shape
+    dw = dw.contiguous().to(logits.dtype)
+    dl = torch.empty_like(logits)
+    _launch("dta_moe_router_bwd", (logits, dw), ptr(logits), ptr(lse), ptr(ids), ptr(dw), ptr(dl), T, E_, ids.shape[1], int(bool(norm)),
+            _DT[logits.dtype], nbytes=2 * T * E_ * logits.element_size())
+    return dl
+
+
+def moe_permute(ids: torch.Tensor, E_: int) -> MoeRouting:
+    """Counting sort of the (token, slot) pairs of ids [T, k] (int32) by expert: rows of an expert in token order, bitwise the same on
+    every call (the layer recomputation re-routes in the backward)."""
+    T, k = ids.shape
+    P = T * k
+    L = lib()
+    dev = ids.device
+    ws = torch.empty(max(int(L.dta_moe_permute_workspace(P, E_)), 1), dtype=torch.int32, device=dev)
+    bound = int(L.dta_moe_tile_bound(P, E_))
+    offs = torch.empty(E_ + 1, dtype=torch.int32, device=dev)
+    rop = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    src = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    tiles = torch.empty(2 * bound, dtype=torch.int32, device=dev)
+    ids = ids.contiguous()
+    _launch("dta_moe_permute", (ids,), ptr(ids), T, k, E_, ptr(ws), ptr(offs), ptr(rop), ptr(src), ptr(tiles), nbytes=12 * P)
+    return MoeRouting(T, k, E_, offs, rop[:P], src[:P], tiles)
+
+
+def moe_grouped_gemm(mode: int, route: MoeRouting, w_shape, out_dtype, x=None, w=None, dy=None, gather: bool = False) -> torch.Tensor:
+    """One grouped GEMM over the expert-sorted rows (dta_moe_grouped_gemm); w_shape = (E, N, K) of the expert weights."""
+    E_, N, K = w_shape
+    R = route.T * route.k
+    ref = x if x is not None else dy
+    shape = (R, N) if mode == MOE_FWD else (R, K) if mode == MOE_DGRAD else (E_, N, K)
+    out = torch.empty(shape, dtype=out_dtype, device=ref.device)
+    if R == 0 and mode != MOE_WGRAD:
+        return out
+    x, w, dy = (None if t is None else t.contiguous() for t in (x, w, dy))
+    esz = out.element_size()
+    _launch("dta_moe_grouped_gemm", tuple(t for t in (x, w, dy) if t is not None), mode, ptr(x), ptr(w), ptr(dy), ptr(out),
+            ptr(route.src_token) if gather else None, ptr(route.expert_offsets), ptr(route.tiles), R, E_, N, K, _DT[out_dtype],
+            nbytes=esz * (R * N + R * K + E_ * N * K), span=f"moe_gemm_{('fwd', 'dgrad', 'wgrad')[mode]}_{N}x{K}")
+    return out
+
+
+def moe_combine_fwd_raw(y, w, route: MoeRouting):
+    """out[t] = Σ_j w[t, j] · y[row(t, j)] (w None: weight 1)."""
+    H = y.shape[1]
+    out = torch.empty((route.T, H), dtype=y.dtype, device=y.device)
+    _launch("dta_moe_combine_fwd", (y,), ptr(y), ptr(w), ptr(route.row_of_pair), ptr(out), route.T, route.k, H, _DT[y.dtype],
+            nbytes=(route.k + 1) * route.T * H * y.element_size())
+    return out
+
+
+def moe_combine_bwd_raw(dout, y, w, route: MoeRouting):
+    H = y.shape[1]
+    dout = dout.contiguous()
+    dy = torch.empty_like(y)
+    dw = torch.empty_like(w)
+    _launch("dta_moe_combine_bwd", (dout, y, w), ptr(dout), ptr(y), ptr(w), ptr(route.row_of_pair), ptr(dy), ptr(dw), route.T, route.k, H,
+            _DT[y.dtype], nbytes=(3 * route.k + 1) * route.T * H * y.element_size())
+    return dy, dw
+
+
+class _MoeRouter(torch.autograd.Function):
+    """logits [T, E] -> top-k weights [T, k] (differentiable) and ids (not)."""
+
+    @staticmethod
+    def forward(ctx, logits, k, norm):
+        ids, w, lse = moe_router_fwd_raw(logits, k, norm)
+        ctx.save_for_backward(logits, lse, ids)
+        ctx.norm = norm
+        ctx.mark_non_differentiable(ids)
+        return w, ids
+
+    @staticmethod
+    def backward(ctx, dw, _dids):
+        logits, lse, ids = ctx.saved_tensors
+        return moe_router_bwd_raw(logits, lse, ids, dw, ctx.norm), None, None
+
+
+class _MoeLinear(torch.autograd.Function):
+    """y [T*k, N] = per-expert x · W_eᵀ over the expert-sorted rows; `gather`: x is [T, K] token rows read through src_token (the MoE
+    block's input), else x is already expert-sorted [T*k, K].  Backward: dgrad (and, for a gathered x, the fixed-order scatter-back onto
+    tokens) and wgrad as grouped GEMMs - no transposed copy of the expert weights."""
+
+    @staticmethod
+    def forward(ctx, x, w, route, gather):
+        ctx.save_for_backward(x, w)
+        ctx.route, ctx.gather = route, gather
+        return moe_grouped_gemm(MOE_FWD, route, w.shape, x.dtype, x=x, w=w, gather=gather)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        route, gather = ctx.route, ctx.gather
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dxs = moe_grouped_gemm(MOE_DGRAD, route, w.shape, x.dtype, w=w, dy=dy)
+            dx = moe_combine_fwd_raw(dxs, None, route) if gather else dxs
+        if ctx.needs_input_grad[1]:
+            dw = moe_grouped_gemm(MOE_WGRAD, route, w.shape, w.dtype, x=x, dy=dy, gather=gather)
+        return dx, dw, None, None
+
+
+class _MoeCombine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, w, route):
+        ctx.save_for_backward(y, w)
+        ctx.route = route
+        return moe_combine_fwd_raw(y, w, route)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, w = ctx.saved_tensors
+        dy, dw = moe_combine_bwd_raw(dout, y, w, ctx.route)
+        return dy, dw, None
+
+
+def moe_mlp(h: torch.Tensor, router_w: torch.Tensor, gate_up_w: torch.Tensor, down_w: torch.Tensor, top_k: int,
+            norm_topk_prob: bool) -> torch.Tensor:
+    """Qwen3MoeSparseMoeBlock over packed rows h [T, H]: router GEMM (ops.linear), top-k routing, expert-sorted grouped GEMMs
+    gate_up_proj [E, 2I, H] -> SwiGLU (swiglu_fused: HF's (gate | up) row halves) -> down_proj [E, H, I], weighted combine.
+    No router auxiliary loss (HF adds it only with output_router_logits)."""
+    if not h.is_cuda:
+        raise RuntimeError("moe_mlp runs on the MI355X only; there is no CPU path")
+    E_ = gate_up_w.shape[0]
+    logits = linear(h, router_w)
+    w, ids = _MoeRouter.apply(logits, int(top_k), bool(norm_topk_prob))
+    route = moe_permute(ids, E_)
+    gu = _MoeLinear.apply(h, gate_up_w, route, True)
+    act = swiglu_fused(gu)
+    y = _MoeLinear.apply(act, down_w, route, False)
+    return _MoeCombine.apply(y, w, route)

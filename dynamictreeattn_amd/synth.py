@@ -32,6 +32,12 @@ QWEN25_0P5B = dict(vocab_size=151936, hidden_size=896, intermediate_size=4864, n
                    num_attention_heads=14, num_key_value_heads=2, head_dim=64, rms_norm_eps=1e-6,
                    rope_theta=1000000.0, qkv_bias=True, qk_norm=False, tie_word_embeddings=True)
 
+# Qwen3-30B-A3B geometry (Qwen3MoeForCausalLM): every layer a mixture of 128 experts of intermediate size 768, 8 routed per token,
+# renormalised top-k weights (the released model has an untied LM head; Qwen3TreeLM ties it - 0.3 B parameters fewer)
+QWEN3_30B_A3B = dict(vocab_size=151936, hidden_size=2048, intermediate_size=6144, moe_intermediate_size=768, num_experts=128,
+                     num_experts_per_tok=8, norm_topk_prob=True, decoder_sparse_step=1, mlp_only_layers=[], num_hidden_layers=48,
+                     num_attention_heads=32, num_key_value_heads=4, head_dim=128, rms_norm_eps=1e-6, rope_theta=1000000.0)
+
 
 def as_tensors(seqs: List[List[int]]) -> List[torch.Tensor]:
     return [torch.tensor(s, dtype=torch.long) for s in seqs]

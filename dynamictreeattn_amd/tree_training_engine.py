@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .model import head_weight, packed_hidden_states
+from .model import head_weight, is_moe_layer, packed_hidden_states
 from .trie import pop_block_starts
 
 __all__ = ["TreeTrainingEngine", "_get_forkpos", "packed_logprob_entropy"]
@@ -201,6 +201,25 @@ class _PackedTrie:
         check(st, "dta_preorder_meta")
 
 
+def _mlp_elems_per_token(c, l: int) -> float:
+    """Elements the MLP of layer l keeps per token for its backward.  Dense SwiGLU: gate|up and the activation (4 I).  MoE
+    (model.is_moe_layer): k expert-sorted rows of gate|up, activation and expert output (k (3 I + H)) plus the router logits and
+    softmax rows (2 E) - at Qwen3-30B-A3B geometry 35.1 k elements where intermediate_size would count 24.6 k."""
+    if is_moe_layer(c, l):
+        return c.num_experts_per_tok * (3 * c.moe_intermediate_size + c.hidden_size) + 2 * c.num_experts
+    return 4 * c.intermediate_size
+
+
+def _has_moe(c) -> bool:
+    return any(is_moe_layer(c, l) for l in range(c.num_hidden_layers))
+
+
+def _stack_sink_fits(model, budget: int) -> bool:
+    """Whether the block-wise walk's fp32 gradient sink (6 bytes per parameter) fits the fifth of `budget` it may take."""
+    n = sum(p.numel() for p in model.parameters() if p.requires_grad)
+    return n * 6 <= budget // 5
+
+
 class TreeTrainingEngine:
     def __init__(self, model_config, device, dtype: torch.dtype, max_seq_len: int, forward_only: bool = False):
         if torch.device(device).type == "cuda" and dtype not in (torch.bfloat16, torch.float16, torch.float32):
@@ -246,10 +265,7 @@ class TreeTrainingEngine:
     def _should_checkpoint(self, model, T: int) -> bool:
         if self.checkpoint_layers is not None:
             return self.checkpoint_layers
-        c = model.config
-        D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
-        per_tok = 2 * (10 * c.hidden_size + 4 * c.intermediate_size + 4 * (c.num_attention_heads + c.num_key_value_heads) * D)
-        need = per_tok * self.n_layers * T
+        need = self._per_token_layer_bytes(model) * self.n_layers * T
         if self.device.type != "cuda":
             return False
         free = self._free_hbm()
@@ -263,9 +279,12 @@ class TreeTrainingEngine:
         return ops.free_hbm(self.device)
 
     def _per_token_layer_bytes(self, model) -> int:
+        """Activation bytes kept per token and layer (the mean over the layers: MoE and dense layers differ), 2-byte elements."""
         c = model.config
         D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
-        return 2 * (10 * c.hidden_size + 4 * c.intermediate_size + 4 * (c.num_attention_heads + c.num_key_value_heads) * D)
+        L = c.num_hidden_layers
+        mlp = sum(_mlp_elems_per_token(c, l) for l in range(L)) / max(L, 1)
+        return int(2 * (10 * c.hidden_size + mlp + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
 
     def _budget(self) -> Optional[int]:
         if self.memory_budget_bytes is not None:
@@ -290,6 +309,10 @@ class TreeTrainingEngine:
             need = T * (2 * 2 * c.hidden_size * self.n_layers + 2 * per_layer)
             if need <= budget:
                 return None
+        if self.mode != "stack" and budget is not None and self.stack_fp32_grads and _has_moe(c) and not _stack_sink_fits(model, budget):
+            # an MoE model whose walk's fp32 gradient sink (stack_engine: 6 bytes per parameter within a fifth of the budget) cannot hold
+            # it (Qwen3-30B-A3B: about 180 GB): the auto mode keeps the packed pass with per-layer recomputation
+            return None
         bs = block_size or 2048
         if budget is None:
             return bs

@@ -262,6 +262,60 @@ int dta_transpose(const void* in, void* out, int64_t rows, int64_t cols, int64_t
  * `part` or `extra`.  Any n; the vector form is taken when slabs <= 16 and n, slab_stride are multiples of 4 with 16-byte aligned pointers. */
 int dta_sum_slabs(const float* part, int64_t slabs, int64_t n, int64_t slab_stride, const float* extra, void* out, int32_t out_dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mixture of experts (Qwen3MoeSparseMoeBlock, transformers 5.x modeling_qwen3_moe.py).  T tokens, E experts (E <= 256), top k
+ * (k <= 16, k <= E); no power-of-two requirement.  dtype DTA_BF16 / DTA_F16 (MFMA GEMMs) or DTA_F32 (plain-FMA GEMMs, the gradient-check
+ * path of fp32 models).  Nothing in the routing path copies to the host: offsets, rows and the GEMM tile table stay on the device.
+ * ------------------------------------------------------------------------------------------- */
+#define DTA_MOE_BM 128       /* rows per tile of the grouped GEMMs (tile table granularity) */
+#define DTA_MOE_FWD 0
+#define DTA_MOE_DGRAD 1
+#define DTA_MOE_WGRAD 2
+
+/* Router.  logits [T, E] (model dtype).  Restates Qwen3MoeTopKRouter.forward:
+ *     router_probs = softmax(router_logits, dtype=float); top_value, indices = topk(router_probs, k)
+ *     if norm_topk_prob: top_value /= top_value.sum(-1); top_value = top_value.to(router_logits.dtype)
+ * Writes topk_ids int32 [T, k] in descending probability, topk_w [T, k] (model dtype, rounded once from fp32) and lse float [T]
+ * (natural log-sum-exp of the logit row, for the backward).  Ties: the LOWER expert index wins (it comes first). */
+int dta_moe_router_fwd(const void* logits, int32_t* topk_ids, void* topk_w, float* lse, int32_t T, int32_t E, int32_t k, int32_t norm_topk,
+                       int32_t dtype, void* stream);
+/* dlogits [T, E] (model dtype) from dtopk_w [T, k] (model dtype) through the renormalisation (norm_topk) and the fp32 softmax: the autograd
+ * backward of the lines above, with p recomputed from logits and lse. */
+int dta_moe_router_bwd(const void* logits, const float* lse, const int32_t* topk_ids, const void* dtopk_w, void* dlogits,
+                       int32_t T, int32_t E, int32_t k, int32_t norm_topk, int32_t dtype, void* stream);
+
+/* Permutation: counting sort of the P = T*k (token, slot) pairs by expert, replacing the one_hot / where / index loop of
+ * Qwen3MoeExperts.forward.  Writes expert_offsets [E+1] (rows of expert e: [off[e], off[e+1])), row_of_pair [P] (pair t*k+j -> its row
+ * in expert order; -1 for an id outside [0, E)), src_token [P] (row -> token) and the tile table tiles [2 * dta_moe_tile_bound(P, E)]:
+ * {expert, first row} per DTA_MOE_BM-row tile of every expert, entries past the last tile {-1, 0}.  Within an expert the rows are in pair
+ * (= token) order; the result is the same bit for bit on every call (no order comes from atomics).  workspace: int32
+ * [dta_moe_permute_workspace(P, E)]. */
+int dta_moe_permute_workspace(int32_t n_pairs, int32_t E);
+int dta_moe_tile_bound(int32_t n_pairs, int32_t E);          /* ceil(P / DTA_MOE_BM) + E */
+int dta_moe_permute(const int32_t* topk_ids, int32_t T, int32_t k, int32_t E, int32_t* workspace,
+                    int32_t* expert_offsets, int32_t* row_of_pair, int32_t* src_token, int32_t* tiles, void* stream);
+
+/* Grouped GEMM over the expert-sorted rows (n_rows = P of the permutation), weights w [E, N, K] (the per-expert nn.functional.linear of
+ * Qwen3MoeExperts.forward; gate_up_proj is [E, 2I, H], down_proj [E, H, I]).  fp32 accumulation, each output rounded once.
+ *   DTA_MOE_FWD:   out[r][n] = sum_k x[g(r)][k] w[e(r)][n][k]           out [n_rows, N]     (Y_e = X_e W_e^T)
+ *   DTA_MOE_DGRAD: out[r][k] = sum_n dy[r][n] w[e(r)][n][k]             out [n_rows, K]     (dX_e = dY_e W_e, sorted rows)
+ *   DTA_MOE_WGRAD: out[e][n][k] = sum_{r of e} dy[r][n] x[g(r)][k]      out [E, N, K]       (dW_e = dY_e^T X_e; empty experts: zero)
+ * g(r) = gather[r] (src_token of the permutation: X read by token inside the operand load) or r when gather is NULL.  x / dy rows are
+ * contiguous (ld = K / N).  The fwd / dgrad grid is sized from the bound of the tile table; workgroups past its last tile exit.
+ * N and K multiples of 16 (DTA_EUNSUPPORTED otherwise); pointers 16-byte aligned (DTA_EALIGN). */
+int dta_moe_grouped_gemm(int32_t mode, const void* x, const void* w, const void* dy, void* out, const int32_t* gather,
+                         const int32_t* expert_offsets, const int32_t* tiles, int32_t n_rows, int32_t E, int32_t N, int32_t K,
+                         int32_t dtype, void* stream);
+
+/* Combine: out[t] = sum_j topk_w[t][j] * y[row_of_pair[t*k+j]], summed in fp32 and rounded once (Qwen3MoeExperts.forward's
+ * `current_hidden_states * top_k_weights` + index_add_).  topk_w == NULL: weight 1 - the fixed-order scatter-back
+ * dX[t] = sum_j dXsorted[row(t, j)] of the gathered GEMM input. */
+int dta_moe_combine_fwd(const void* y, const void* topk_w, const int32_t* row_of_pair, void* out, int32_t T, int32_t k, int32_t H,
+                        int32_t dtype, void* stream);
+/* dy[row(t, j)] = topk_w[t][j] * dout[t];  dtopk_w[t][j] = <dout[t], y[row(t, j)]> (fp32, fixed order).  No float atomics. */
+int dta_moe_combine_bwd(const void* dout, const void* y, const void* topk_w, const int32_t* row_of_pair, void* dy, void* dtopk_w,
+                        int32_t T, int32_t k, int32_t H, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
