@@ -6,14 +6,16 @@ run ``TreeTrainingEngine.backward`` (HIP tree attention fwd+bwd inside the full 
 parameter gradients over the ranks (RCCL, in place, overlapped with the backward).  Timed sync-to-sync like run.py:90-108;
 metric = Σ original-sequence tokens / wall (run_all.py:156-159), MAX over ranks.
 
-Legs of one invocation (all in the ONE JSON line rank 0 prints):
+Legs of one invocation (all in the ONE JSON line rank 0 prints).  A plain run times ``value`` alone: set-up, warm-up, the timed
+steps, ``--dump-outputs`` if given, the line.  The other legs run only under ``--full``; without it their fields are null.
 * ``value``            WEAK scaling: step s gives every rank one tau2-shaped call (N calls merged and split by
                        ``LB_by_DFS_and_TM`` before the clock starts, as data_parallel.py does offline).  No kernel timers run here.
-* ``strong_scaling``   (N > 1) the reference's own DP protocol (exp/exp_dp.py:28-49, exp/calc_time.py:24-42): a FIXED batch of calls,
+* ``tree_forward``     (--full) TokenTrie + forward_permute + engine.forward over the same calls.
+* ``strong_scaling``   (--full, N > 1) the reference's own DP protocol (exp/exp_dp.py:28-49, exp/calc_time.py:24-42): a FIXED batch of calls,
                        each split N ways; throughput = Σ n_tokens / Σ_calls max_rank(time), plus the balance Σ t_k / (N · max t_k).
-* ``roofline``         the same steps once more with HIP events around every C-ABI launch (their cost is reported as
+* ``roofline``         (--full) the same steps once more with HIP events around every C-ABI launch (their cost is reported as
                        ``timer_overhead_frac``): dominant MFMA kernel vs the 2.5 PFLOP/s peak, HBM-bound kernels vs 8 TB/s.
-* ``cpu_baseline``     (N = 1) the oracle's restatement of the reference schedule on the host cores: config 1 and a tau2-shaped sample.
+* ``cpu_baseline``     (--full, N = 1) the oracle's restatement of the reference schedule on the host cores: config 1 and a tau2-shaped sample.
 
 Other workloads: ``--workload wide`` (BASELINE config 5: 64 x 16 384 over a 1 024-token root, fp16), ``--model qwen3-4b | qwen3-8b | qwen3-14b``,
 ``--vocab-parallel`` (BASELINE config 4: the LM-head vocabulary split over the ranks, vocab_parallel.py:82-396).
@@ -205,8 +207,10 @@ def main():
     ap.add_argument("--workload", default="tau2", choices=["tau2", "wide"])
     ap.add_argument("--vocab-parallel", action="store_true", help="BASELINE config 4: split the LM-head vocabulary over the ranks (every rank runs the same batch)")
     ap.add_argument("--engine-mode", default="auto", choices=["auto", "packed", "stack"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling leg at N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the roofline, tree_forward, strong-scaling (N > 1) and CPU-baseline (N = 1) legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its like-for-like GPU legs")
+    ap.add_argument("--no-strong", action="store_true", help="with --full: skip the strong-scaling leg at N > 1")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (loss, gradient norms, a fixed sample of every gradient) to DIR/*.npy")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
@@ -377,6 +381,35 @@ def main():
         dump_outputs(args.dump_outputs, model, acc["last_loss"])
         note(rank, f"outputs of the last timed step written to {args.dump_outputs}")
 
+    workload = ("BASELINE config 5: wide/deep trie, 64 branches x 16 384 deep over a 1 024-token root (1 048 576 tokens, 984 064 tree tokens per call), "
+                f"{MODEL_NAME[args.model]} random-init fp16, loss scale {loss_scale:g}") if wide else \
+               ("tau2-16k-shaped trie batch (8 rollouts x 6 turns, 2000-token shared prompt, 48 seqs ~180k tokens per call), "
+                f"{MODEL_NAME[args.model]} random-init bf16")
+    out = {
+        "metric": f"tree-attn fwd+bwd tokens/sec, {MODEL_NAME[args.model]} {'wide/deep' if wide else 'tau2-16k'} tries", "value": n_tokens / wall, "unit": "tokens/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": wall / steps * 1e3,
+        "higher_is_better": True, "scaling": "strong" if tp else "weak", "vs_baseline": None, "dtype": "f16" if wide else "bf16", "data": "synthetic",
+        "config": {"workload": workload + f", tree fwd+bwd, block_size {args.block_size}, permute=ours; "
+                               + ("every rank runs the SAME call with the LM-head vocabulary split over the ranks (config 4)" if tp else "one call per GPU per step"),
+                   "calls_per_step": 1 if tp else world, "balancer": "LB_by_DFS_and_TM" if (world > 1 and not tp) else "none",
+                   "engine_mode": engine_mode,
+                   "grad_allreduce": ("none (vocabulary-parallel run: body replicated, head rows owned per rank)" if tp else
+                                      (("RCCL" if backend == "nccl" else backend + " (rehearsal)") + (" sum in place on persistent flat buckets, overlapped with backward" if reducer.overlap else " sum in place after backward"))) if world > 1 else "none",
+                   "value_is": "the WEAK-scaling leg (per-GPU work fixed); the reference's fixed-batch protocol is `strong_scaling`"},
+        "tree_tokens_per_s": n_tree / wall, "peak_hbm_gb": peak_hbm / 1e9, "step_ms": acc.get("step_ms"), "step_ms_roofline_leg": None,
+        "strong_scaling": None, "tree_forward": None, "roofline": None, "cpu_baseline": None, "full": args.full,
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:                   # a plain run: the headline figure is complete
+        finish()
+        return
+
     # ---- ROOFLINE leg: the same steps with HIP events on the launch stream around every C-ABI launch
     timer = ops.KernelTimer()
     ops.KernelTimer.active = timer
@@ -496,23 +529,8 @@ def main():
                   "balance": float((sm[1] / (world * mx[1])).mean()), "balance_definition": "mean over calls of sum_k t_k / (N * max_k t_k), t_k = rank k's time up to the reduce",
                   "ms_per_call": float(mx[0].mean()) * 1e3}
 
-    workload = ("BASELINE config 5: wide/deep trie, 64 branches x 16 384 deep over a 1 024-token root (1 048 576 tokens, 984 064 tree tokens per call), "
-                f"{MODEL_NAME[args.model]} random-init fp16, loss scale {loss_scale:g}") if wide else \
-               ("tau2-16k-shaped trie batch (8 rollouts x 6 turns, 2000-token shared prompt, 48 seqs ~180k tokens per call), "
-                f"{MODEL_NAME[args.model]} random-init bf16")
-    out = {
-        "metric": f"tree-attn fwd+bwd tokens/sec, {MODEL_NAME[args.model]} {'wide/deep' if wide else 'tau2-16k'} tries", "value": n_tokens / wall, "unit": "tokens/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": wall / steps * 1e3,
-        "higher_is_better": True, "scaling": "strong" if tp else "weak", "vs_baseline": None, "dtype": "f16" if wide else "bf16", "data": "synthetic",
-        "config": {"workload": workload + f", tree fwd+bwd, block_size {args.block_size}, permute=ours; "
-                               + ("every rank runs the SAME call with the LM-head vocabulary split over the ranks (config 4)" if tp else "one call per GPU per step"),
-                   "calls_per_step": 1 if tp else world, "balancer": "LB_by_DFS_and_TM" if (world > 1 and not tp) else "none",
-                   "engine_mode": engine_mode,
-                   "grad_allreduce": ("none (vocabulary-parallel run: body replicated, head rows owned per rank)" if tp else
-                                      (("RCCL" if backend == "nccl" else backend + " (rehearsal)") + (" sum in place on persistent flat buckets, overlapped with backward" if reducer.overlap else " sum in place after backward"))) if world > 1 else "none",
-                   "value_is": "the WEAK-scaling leg (per-GPU work fixed); the reference's fixed-batch protocol is `strong_scaling`"},
-        "tree_tokens_per_s": n_tree / wall, "peak_hbm_gb": peak_hbm / 1e9, "step_ms": acc.get("step_ms"), "step_ms_roofline_leg": acc_r.get("step_ms"),
-        "strong_scaling": strong, "tree_forward": fwd_leg,
+    out.update({
+        "step_ms_roofline_leg": acc_r.get("step_ms"), "strong_scaling": strong, "tree_forward": fwd_leg,
         "roofline": {"bound": "mfma", "kernel": DKV_KERNEL, "achieved": dkv_tf, "peak": PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": dkv_tf / PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": dkv_ms,
                      "flops_per_pair_per_layer": 8 * Hq * D, "pairs_per_step": pairs_r / max(steps, 1),
@@ -527,22 +545,17 @@ def main():
                                        "tree_attn_bwd_dkv_finalize_kernel": {"avg_launch_ms": (fin[0] / fin[1]) if fin[1] else 0.0},
                                        "attention_fwd+bwd_14HqD": {"bound": "mfma", "achieved": all_tf, "frac": all_tf / PEAK_TFLOPS, "ms_per_step": attn_ms_total / max(steps, 1)},
                                        **hbm_rows}},
-    }
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            cb = cpu_baseline()
-            if same_sample is not None and cb.get("value"):
-                # like for like: the GPU timed on exactly the two workloads the CPU ran (after one warm-up each, as the CPU leg)
-                cb["gpu_same_sample"] = dict(same_sample["gpu_same_sample"], ratio_gpu_over_cpu=same_sample["gpu_same_sample"]["value"] / cb["value"])
-                cb["gpu_config1"] = dict(same_sample["gpu_config1"], ratio_gpu_over_cpu=same_sample["gpu_config1"]["value"] / cb["config1"]["value"])
-                cb["note"] = ("`value` of this object and `gpu_same_sample` are the SAME bounded sample; `config1` and `gpu_config1` the same BASELINE config 1; "
-                              "the headline `value` of the line is the full tau2 call, which the CPU leg does not run (see full_call)")
-            out["cpu_baseline"] = cb
-        else:
-            out["cpu_baseline"] = None
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    })
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cb = cpu_baseline()
+        if same_sample is not None and cb.get("value"):
+            # like for like: the GPU timed on exactly the two workloads the CPU ran (after one warm-up each, as the CPU leg)
+            cb["gpu_same_sample"] = dict(same_sample["gpu_same_sample"], ratio_gpu_over_cpu=same_sample["gpu_same_sample"]["value"] / cb["value"])
+            cb["gpu_config1"] = dict(same_sample["gpu_config1"], ratio_gpu_over_cpu=same_sample["gpu_config1"]["value"] / cb["config1"]["value"])
+            cb["note"] = ("`value` of this object and `gpu_same_sample` are the SAME bounded sample; `config1` and `gpu_config1` the same BASELINE config 1; "
+                          "the headline `value` of the line is the full tau2 call, which the CPU leg does not run (see full_call)")
+        out["cpu_baseline"] = cb
+    finish()
 
 
 if __name__ == "__main__":

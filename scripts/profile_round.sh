@@ -12,9 +12,9 @@ OUT=gpurun_out/prof_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
 echo "[profile] kernel trace"; date
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/trace.err || echo "kernel trace run failed"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py --steps 4 --warmup 2 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/trace.err || echo "kernel trace run failed"
 echo "[profile] hip api trace"; date
-timeout -k 10 400 rocprofv3 --hip-trace --stats --output-format csv -d $OUT/hip -o bench -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline > $OUT/bench_under_hiptrace.json 2> $OUT/hip.err || echo "hip trace run failed"
+timeout -k 10 400 rocprofv3 --hip-trace --stats --output-format csv -d $OUT/hip -o bench -- python3 bench.py --steps 4 --warmup 2 --full --no-cpu-baseline > $OUT/bench_under_hiptrace.json 2> $OUT/hip.err || echo "hip trace run failed"
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_LDS" "SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS" "GRBM_GUI_ACTIVE"; do
   tag=$(echo $grp | tr ' ' '+' | cut -c1-40)
   echo "[profile] pmc $grp"; date
