@@ -8,7 +8,7 @@ from typing import List
 import torch
 
 from . import ops
-from .model import head_weight, packed_hidden_states
+from .model import ensure_supported, head_weight, packed_hidden_states
 from .tree_training_engine import packed_logprob_entropy
 
 
@@ -23,6 +23,7 @@ def _one(model, ids: torch.Tensor, want_entropy: bool, checkpoint_layers: bool):
 @torch.no_grad()
 def forward(model, token_seqs: List[torch.LongTensor], use_tqdm: bool = False) -> List[torch.Tensor]:
     out = []
+    ensure_supported(model)
     with ops.weight_cache():
         for ids in token_seqs:
             lp, _ = _one(model, ids.to(model.device), False, False)
@@ -32,6 +33,7 @@ def forward(model, token_seqs: List[torch.LongTensor], use_tqdm: bool = False) -
 
 def backward(model, token_seqs: List[torch.LongTensor], attachs, loss_fn, act_ckpt: bool = False, use_tqdm: bool = False) -> float:
     total = 0.0
+    ensure_supported(model)
     with ops.weight_cache():
         for ids, att in zip(token_seqs, attachs):
             lp, ent = _one(model, ids.to(model.device), True, act_ckpt)

@@ -7,11 +7,12 @@ torch.  `Qwen3TreeLM` mirrors the HF module/parameter tree (``model.embed_tokens
 ``model.layers.N.self_attn.q_proj.weight`` …, tied head) so that
 
 * gradients compare name by name with grad/Qwen3-0.6B-TB-vs-DB-bf16.txt (310 tensors), and
-* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE ``*ForCausalLM`` by duck typing —
+* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral ``*ForCausalLM`` by duck typing —
   its own ``nn.Parameter`` objects are used, so ``param.grad`` lands where the training loop expects.
 """
 from __future__ import annotations
 
+import weakref
 from types import SimpleNamespace
 
 import torch
@@ -47,17 +48,29 @@ class _MLP(nn.Module):
         self.gate_proj, self.up_proj, self.down_proj = _Lin(c.hidden_size, c.intermediate_size), _Lin(c.hidden_size, c.intermediate_size), _Lin(c.intermediate_size, c.hidden_size)
 
 
+def moe_geometry(c):
+    """(experts, expert intermediate size, renormalise the top-k weights) of an MoE configuration: Qwen3-MoE names them num_experts /
+    moe_intermediate_size / norm_topk_prob; Mixtral num_local_experts / intermediate_size, and its router always renormalises.
+    (0, 0, False) for a dense model."""
+    E = getattr(c, "num_experts", 0) or 0
+    if E and getattr(c, "moe_intermediate_size", None) is not None:      # (MixtralConfig answers num_experts too, as an alias)
+        return E, c.moe_intermediate_size, bool(getattr(c, "norm_topk_prob", False))
+    E = getattr(c, "num_local_experts", 0) or 0
+    return (E, c.intermediate_size, True) if E else (0, 0, False)
+
+
 class _Router(nn.Module):
     def __init__(self, c):
         super().__init__()
-        self.top_k, self.num_experts, self.norm_topk_prob = c.num_experts_per_tok, c.num_experts, bool(getattr(c, "norm_topk_prob", False))
-        self.weight = nn.Parameter(torch.empty(c.num_experts, c.hidden_size))
+        E, _, norm = moe_geometry(c)
+        self.top_k, self.num_experts, self.norm_topk_prob = c.num_experts_per_tok, E, norm
+        self.weight = nn.Parameter(torch.empty(E, c.hidden_size))
 
 
 class _Experts(nn.Module):
     def __init__(self, c):
         super().__init__()
-        E, H, I = c.num_experts, c.hidden_size, c.moe_intermediate_size
+        (E, I, _), H = moe_geometry(c), c.hidden_size
         self.gate_up_proj = nn.Parameter(torch.empty(E, 2 * I, H))
         self.down_proj = nn.Parameter(torch.empty(E, H, I))
 
@@ -72,8 +85,8 @@ class _MoE(nn.Module):
 
 def is_moe_layer(c, l: int) -> bool:
     """The rule of HF Qwen3MoeDecoderLayer: experts unless the layer is in mlp_only_layers, when num_experts > 0 and (l + 1) is a
-    multiple of decoder_sparse_step."""
-    E = getattr(c, "num_experts", 0) or 0
+    multiple of decoder_sparse_step.  A Mixtral configuration (num_local_experts, neither of the two lists) has experts in every layer."""
+    E = moe_geometry(c)[0]
     return E > 0 and l not in (getattr(c, "mlp_only_layers", None) or []) and (l + 1) % (getattr(c, "decoder_sparse_step", 1) or 1) == 0
 
 
@@ -93,6 +106,8 @@ class _Body(nn.Module):
 
 
 def make_config(d: dict) -> SimpleNamespace:
+    """Configuration of a Qwen3TreeLM from a dict of HF field names.  `rope_parameters` is the dict HF configurations keep
+    (rope_type default / linear / llama3 / yarn with the type's fields; its rope_theta goes before the top-level one)."""
     c = SimpleNamespace(**d)
     if not hasattr(c, "head_dim"):
         c.head_dim = c.hidden_size // c.num_attention_heads
@@ -127,23 +142,101 @@ class Qwen3TreeLM(nn.Module):
         return m.to(device=device, dtype=dtype)
 
 
+def _rope_dict(c) -> dict:
+    """The flat RoPE parameter dict of a configuration: config.rope_parameters (transformers 5.x) or the older rope_scaling, with
+    rope_type and rope_theta always present (HF's standardisation: the dict's own rope_theta goes before config.rope_theta, and a
+    top-level original_max_position_embeddings before the dict's).  A dict nested per layer type is refused."""
+    rp = getattr(c, "rope_parameters", None) or getattr(c, "rope_scaling", None) or {}
+    if not isinstance(rp, dict):
+        raise ValueError(f"config.rope_parameters must be a dict, got {type(rp).__name__}")
+    if rp and all(isinstance(v, dict) for v in rp.values()):
+        raise ValueError(f"config.rope_parameters is nested per layer type ({', '.join(map(str, rp))}): one RoPE table per model is supported")
+    rp = dict(rp)
+    rp["rope_type"] = rp.get("rope_type", rp.get("type")) or "default"
+    if rp.get("rope_theta") is None:
+        theta = getattr(c, "rope_theta", None)
+        rp["rope_theta"] = 1e6 if theta is None else theta
+    if getattr(c, "original_max_position_embeddings", None) is not None:
+        rp["original_max_position_embeddings"] = c.original_max_position_embeddings
+    return rp
+
+
+_ROPE: dict = {}
+
+
+def rope_of(c):
+    """(inv_freq [D/2] fp32 on the host, attention_factor) of a configuration (ops.rope_inv_freq), resolved once per distinct
+    parameter set: every consumer of one model - the packed pass, the block-wise walk, dense.py, engine.forward, warm_gemm_shapes -
+    reaches it through packed_hidden_states and so builds its table from the same frequencies."""
+    rp = _rope_dict(c)
+    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    max_pos = getattr(c, "max_position_embeddings", None)
+    key = (D, max_pos, tuple(sorted((k, repr(v)) for k, v in rp.items())))
+    hit = _ROPE.get(key)
+    if hit is None:
+        hit = _ROPE[key] = ops.rope_inv_freq(D, rp, max_pos)
+    return hit
+
+
+_SOFTCAP_SINK_FIELDS = ("attn_logit_softcapping", "final_logit_softcapping", "attn_softcap", "logit_softcap", "attention_sink",
+                        "attention_sinks", "use_attention_sinks", "num_sink_tokens")
+
+
+def check_supported(config, training: bool = True) -> None:
+    """Refuses, with a ValueError that names the field, a configuration whose arithmetic the engine cannot honour - it would run,
+    and compute something else: a rope_type other than default / linear / llama3 / yarn, rope_parameters nested per layer type,
+    partial rotary embedding, an activation other than silu, attention dropout on a model in training mode, router jitter noise,
+    attention soft-capping or sinks."""
+    c = config
+    rp = _rope_dict(c)
+    if rp["rope_type"] not in ops.ROPE_TYPES:
+        raise ValueError(f"config.rope_parameters['rope_type'] = {rp['rope_type']!r} is not supported ({' / '.join(ops.ROPE_TYPES)})")
+    prf = rp.get("partial_rotary_factor", getattr(c, "partial_rotary_factor", None))
+    if prf is not None and float(prf) != 1.0:
+        raise ValueError(f"config partial_rotary_factor = {prf} is not supported: the rotary kernels rotate the whole head")
+    act = getattr(c, "hidden_act", None)
+    if act is not None and act != "silu":
+        raise ValueError(f"config.hidden_act = {act!r} is not supported: the MLP kernels compute silu(gate) * up")
+    if training and float(getattr(c, "attention_dropout", 0.0) or 0.0) > 0:
+        raise ValueError(f"config.attention_dropout = {c.attention_dropout} on a model in training mode is not supported (model.eval(), or set it to 0)")
+    if float(getattr(c, "router_jitter_noise", 0.0) or 0.0) > 0:
+        raise ValueError(f"config.router_jitter_noise = {c.router_jitter_noise} is not supported")
+    for f in _SOFTCAP_SINK_FIELDS:
+        if getattr(c, f, None):
+            raise ValueError(f"config.{f} = {getattr(c, f)!r} is not supported: the attention kernels have neither soft-capping nor sinks")
+
+
+_CHECKED = weakref.WeakKeyDictionary()
+
+
+def ensure_supported(model) -> None:
+    """check_supported(model.config), once per model object and training mode (the engine and dense.py call it per call)."""
+    training = bool(getattr(model, "training", True))
+    try:
+        seen = _CHECKED.setdefault(model, set())
+    except TypeError:                  # a plain namespace standing in for a model: neither hashable nor weakly referenceable
+        return check_supported(model.config, training)
+    if training not in seen:
+        check_supported(model.config, training)
+        seen.add(training)
+
+
 def _cfg_of(model):
     c = model.config
     D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
-    theta = getattr(c, "rope_theta", None)
-    if theta is None:
-        rp = getattr(c, "rope_parameters", None) or {}
-        theta = rp.get("rope_theta", 1e6) if isinstance(rp, dict) else 1e6
-    return c.num_attention_heads, c.num_key_value_heads, D, float(getattr(c, "rms_norm_eps", 1e-6)), float(theta)
+    return c.num_attention_heads, c.num_key_value_heads, D, float(getattr(c, "rms_norm_eps", 1e-6)), rope_of(c)
 
 
 def _windows_of(model):
     """Sliding window of every decoder layer (0 = full attention), as the HF Qwen2 / Qwen3 configurations define it:
     config.sliding_window where config.layer_types[l] == "sliding_attention"; without layer_types, the rule those config classes
-    apply (use_sliding_window and l >= max_window_layers).  A sliding layer without a sliding_window attends in full, as in HF."""
+    apply (use_sliding_window and l >= max_window_layers).  A sliding layer without a sliding_window attends in full, as in HF.
+    Mistral and Mixtral (config.model_type) have neither field: every layer slides whenever config.sliding_window is set."""
     c = model.config
     n = c.num_hidden_layers
     W = getattr(c, "sliding_window", None) or 0
+    if getattr(c, "model_type", None) in ("mistral", "mixtral"):
+        return [int(W)] * n
     types = getattr(c, "layer_types", None)
     if types is not None:
         if len(types) != n:
@@ -179,6 +272,15 @@ def layer_metas(meta, windows, for_window=None):
     return out
 
 
+def _bias(*mods):
+    """The modules' biases concatenated in order (the fused projection GEMMs stack their weights the same way); None when the
+    modules have none (HF builds the projections of one group with one flag)."""
+    bs = [getattr(m_, "bias", None) for m_ in mods]
+    if bs[0] is None:
+        return None
+    return bs[0] if len(bs) == 1 else torch.cat(bs)
+
+
 def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     """One decoder layer over the packed rows.  The hidden state enters as (residual stream, pending update)
     so that each residual add is fused into the RMSNorm that follows it.  hipBLASLt GEMMs through torch;
@@ -186,22 +288,26 @@ def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     T = res.shape[0]
     a = layer.self_attn
     res, h = ops.add_rms_norm(res, delta, layer.input_layernorm.weight, eps)
-    bq, bk, bv = (getattr(m_, "bias", None) for m_ in (a.q_proj, a.k_proj, a.v_proj))
     # one projection GEMM for q,k,v (and one for gate,up below): the weights stay separate parameters with
     # their HF names; stacking them is three plain copies whose backward hands out gradient row slices
     qkv = ops.linear(h, ops.stack_rows(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight),
-                   torch.cat([bq, bk, bv]) if bq is not None else None).view(T, Hq + 2 * Hkv, D)
+                     _bias(a.q_proj, a.k_proj, a.v_proj)).view(T, Hq + 2 * Hkv, D)
     qn = getattr(a, "q_norm", None); kn = getattr(a, "k_norm", None)
     q, k, v = ops.qkv_prep(qkv, qn.weight if qn is not None else None, kn.weight if kn is not None else None, cos_sin, eps, Hq, Hkv)
     o = attn(q, k, v)                   # ops.tree_attention over a packed trie, or ops.stack_attention over the KV stack
-    attn_out = ops.linear(o.reshape(T, Hq * D), a.o_proj.weight)
+    attn_out = ops.linear(o.reshape(T, Hq * D), a.o_proj.weight, _bias(a.o_proj))          # LlamaConfig.attention_bias: o_proj too
     res, h = ops.add_rms_norm(res, attn_out, layer.post_attention_layernorm.weight, eps)
     m = layer.mlp
-    if hasattr(m, "experts") and hasattr(m, "gate"):       # Qwen3MoeSparseMoeBlock (duck-typed): router + grouped expert GEMMs
+    if hasattr(m, "experts") and hasattr(m, "gate"):       # Qwen3Moe / Mixtral SparseMoeBlock (duck-typed): router + grouped expert GEMMs
         g = m.gate
-        return res, ops.moe_mlp(h, g.weight, m.experts.gate_up_proj, m.experts.down_proj, g.top_k, g.norm_topk_prob)
-    act = ops.swiglu_fused(ops.linear(h, ops.stack_rows(m.gate_proj.weight, m.up_proj.weight)))
-    return res, ops.linear(act, m.down_proj.weight)
+        norm = getattr(g, "norm_topk_prob", None)
+        if norm is None:
+            if not hasattr(m, "jitter_noise"):             # MixtralSparseMoeBlock: its router has no flag and always renormalises
+                raise AttributeError(f"{type(g).__name__} has no norm_topk_prob and {type(m).__name__} is not a Mixtral block")
+            norm = True
+        return res, ops.moe_mlp(h, g.weight, m.experts.gate_up_proj, m.experts.down_proj, g.top_k, norm)
+    act = ops.swiglu_fused(ops.linear(h, ops.stack_rows(m.gate_proj.weight, m.up_proj.weight), _bias(m.gate_proj, m.up_proj)))
+    return res, ops.linear(act, m.down_proj.weight, _bias(m.down_proj))                   # LlamaConfig.mlp_bias
 
 
 class _LayerRecompute(torch.autograd.Function):
@@ -245,7 +351,7 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
                          attn_keep_bytes: int = 0, attn_of_layer=None, full_layers=0, kept_out=None, embed=None,
                          meta_for_window=None) -> torch.Tensor:
     """Final-norm hidden states [T, hidden] of the packed tokens.  `model` is a Qwen3TreeLM or an HF
-    Qwen2/Qwen3 *ForCausalLM (duck-typed).  `checkpoint_layers`: recompute each layer in the backward, except the first
+    Qwen2/Qwen3/Llama/Mistral (and their MoE kin) *ForCausalLM (duck-typed).  `checkpoint_layers`: recompute each layer in the backward, except the first
     `full_layers`, which keep their activations like the plain pass — an int, or a plan `bytes kept by layer 0 -> number of
     layers` that is asked once layer 0 has run in full and its footprint has been measured (the number lands in `kept_out`);
     `attn_keep_bytes`: HBM budget for attention outputs kept across that recomputation (layers are served first to last).
@@ -254,11 +360,11 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
     block-wise engine routes the rows' gradients into its fp32 sink instead of a dense [vocab, hidden] gradient per block).
     Sliding-window layers (_windows_of) attend with `meta_for_window(W)` (layer_metas); the stack form gets its window from
     `attn_of_layer`."""
-    Hq, Hkv, D, eps, theta = _cfg_of(model)
+    Hq, Hkv, D, eps, rope = _cfg_of(model)
     metas = layer_metas(meta, _windows_of(model), meta_for_window) if attn_of_layer is None else None
     body = model.model
     res, delta = (embed(tokens) if embed is not None else F.embedding(tokens, body.embed_tokens.weight)), None
-    cos_sin = ops.rope_cos_sin(depth, D, theta)
+    cos_sin = ops.rope_cos_sin(depth, D, rope)
     per_layer = tokens.shape[0] * Hq * (D * res.element_size() + 4)             # out + lse of one layer
     n_full = full_layers if isinstance(full_layers, int) else 1
     for li, layer in enumerate(body.layers):

@@ -2,6 +2,7 @@
 and autograd plumbing only; all arithmetic of these ops runs in the HIP kernels."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -740,21 +741,95 @@ def qk_norm_rope(x: torch.Tensor, w: Optional[torch.Tensor], cos_sin: torch.Tens
     return _QKNormRope.apply(x, w, cos_sin, eps)
 
 
+ROPE_TYPES = ("default", "linear", "llama3", "yarn")
+
+
+def rope_inv_freq(D: int, rope_parameters: dict, max_position_embeddings: Optional[int] = None):
+    """(inv_freq [D/2] fp32 on the host, attention_factor) of a RoPE parameter dict (`rope_type` default / linear / llama3 / yarn,
+    `rope_theta` and the type's own fields - the dict transformers keeps in config.rope_parameters).  The formulas are those of
+    transformers' modeling_rope_utils (_compute_linear_scaling_rope_parameters, _compute_llama3_parameters, _compute_yarn_parameters)
+    restated with the same fp32 host operations in the same order, so that the frequencies come out bit for bit (see rope_cos_sin for
+    what one ulp costs).  `max_position_embeddings` stands in for an absent `original_max_position_embeddings` and for YaRN's absent
+    `factor`, as there."""
+    rp = rope_parameters
+    kind = rp.get("rope_type", rp.get("type")) or "default"
+    if kind not in ROPE_TYPES:
+        raise ValueError(f"rope_parameters: rope_type {kind!r} is not supported ({' / '.join(ROPE_TYPES)})")
+    base = float(rp["rope_theta"])
+    steps = torch.arange(0, D, 2, dtype=torch.int64).to(torch.float32)
+    if kind == "default":
+        return 1.0 / (base ** (steps / D)), 1.0
+    if kind == "linear":
+        inv = 1.0 / (base ** (steps / D))
+        inv /= rp["factor"]
+        return inv, 1.0
+    orig = rp.get("original_max_position_embeddings") or max_position_embeddings
+    if orig is None:
+        raise ValueError(f"rope_parameters: rope_type {kind!r} needs original_max_position_embeddings (or max_position_embeddings)")
+    if kind == "llama3":
+        inv = 1.0 / (base ** (steps / D))
+        factor, low_f, high_f = rp["factor"], rp["low_freq_factor"], rp["high_freq_factor"]
+        low_wavelen, high_wavelen = orig / low_f, orig / high_f
+        wavelen = 2 * math.pi / inv
+        scaled = torch.where(wavelen > low_wavelen, inv / factor, inv)          # long wavelengths: divided by factor; short ones: kept
+        smooth = (orig / wavelen - low_f) / (high_f - low_f)                    # the band between: interpolated
+        smoothed = (1 - smooth) * scaled / factor + smooth * scaled
+        medium = ~(wavelen < high_wavelen) * ~(wavelen > low_wavelen)
+        return torch.where(medium, smoothed, scaled), 1.0
+    # yarn
+    factor = rp.get("factor")
+    if factor is None:
+        if max_position_embeddings is None:
+            raise ValueError("rope_parameters: yarn needs factor (or max_position_embeddings)")
+        factor = max_position_embeddings / orig
+    mscale_of = lambda scale, m=1: 1.0 if scale <= 1 else 0.1 * m * math.log(scale) + 1.0
+    att = rp.get("attention_factor")
+    if att is None:
+        ms, ms_all = rp.get("mscale"), rp.get("mscale_all_dim")
+        att = float(mscale_of(factor, ms) / mscale_of(factor, ms_all)) if ms and ms_all else mscale_of(factor)
+    beta_fast, beta_slow = rp.get("beta_fast") or 32, rp.get("beta_slow") or 1
+    corr_dim = lambda rot: (D * math.log(orig / (rot * 2 * math.pi))) / (2 * math.log(base))
+    low, high = corr_dim(beta_fast), corr_dim(beta_slow)
+    if rp.get("truncate", True):
+        low, high = math.floor(low), math.ceil(high)
+    low, high = max(low, 0), min(high, D - 1)
+    if low == high:
+        high += 0.001
+    pos_freqs = base ** (steps / D)
+    extrapolation, interpolation = 1.0 / pos_freqs, 1.0 / (factor * pos_freqs)
+    keep = 1 - torch.clamp((torch.arange(D // 2, dtype=torch.float32) - low) / (high - low), 0, 1)
+    return interpolation * (1 - keep) + extrapolation * keep, att
+
+
 _INV_FREQ: dict = {}
 
 
-def rope_cos_sin(depth: torch.Tensor, D: int, theta: float) -> torch.Tensor:
-    """fp32 [T, D] table {cos[D/2], sin[D/2]} of position = trie depth (computed once per trie).  The inverse frequencies are computed ON
+def rope_cos_sin(depth: torch.Tensor, D: int, rope) -> torch.Tensor:
+    """fp32 [T, D] table {cos[D/2], sin[D/2]} * attention_factor of position = trie depth (computed once per trie).  `rope` is the
+    resolved pair (inv_freq [D/2] fp32 on the host, attention_factor) of rope_inv_freq, or a plain theta for the default
+    frequencies.  The inverse frequencies are computed ON
     THE HOST in fp32, exactly as transformers' rotary-embedding init does (`1 / base ** (arange(0, D, 2) / D)`): the GPU's `pow` differs
     from the host's in the last bit, and one ulp of an inverse frequency is 1e-7 x position radians of phase - 5e-5 rad at depth 512,
-    1.6e-3 at 16 384 - which the fp32 engine showed as a 6e-4 deviation of gradient norms from the reference at Qwen3-0.6B size."""
-    key = (D, float(theta), depth.device)
+    1.6e-3 at 16 384 - which the fp32 engine showed as a 6e-4 deviation of gradient norms from the reference at Qwen3-0.6B size.
+    The device copy is cached by the frequencies' VALUE (two configurations with one theta and different scaling do not share it)."""
+    if isinstance(rope, (int, float)):
+        key, host, factor = (D, float(rope), depth.device), None, 1.0
+    else:
+        host, factor = rope
+        if host.shape != (D // 2,) or host.dtype != torch.float32 or host.device.type != "cpu":
+            raise ValueError(f"rope_cos_sin: inv_freq must be a host fp32 [{D // 2}] tensor, got {host.dtype} {tuple(host.shape)} on {host.device}")
+        key = (D, host.numpy().tobytes(), depth.device)
     inv = _INV_FREQ.get(key)
     if inv is None:
-        inv = (1.0 / (float(theta) ** (torch.arange(0, D, 2, dtype=torch.int64).to(torch.float32) / D))).to(depth.device)
+        if host is None:
+            host = rope_inv_freq(D, {"rope_theta": float(rope)})[0]
+        inv = host.to(depth.device)
         _INV_FREQ[key] = inv
     ang = depth.float()[:, None] * inv[None, :]
-    return torch.cat([ang.cos(), ang.sin()], dim=-1).contiguous()
+    table = torch.cat([ang.cos(), ang.sin()], dim=-1)
+    if float(factor) != 1.0:
+        table = table * float(factor)
+    return table.contiguous()
 
 
 class _SwiGLU(torch.autograd.Function):

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .model import head_weight, is_moe_layer, packed_hidden_states
+from .model import ensure_supported, head_weight, is_moe_layer, moe_geometry, packed_hidden_states
 from .trie import pop_block_starts
 
 __all__ = ["TreeTrainingEngine", "_get_forkpos", "packed_logprob_entropy"]
@@ -206,7 +206,8 @@ def _mlp_elems_per_token(c, l: int) -> float:
     (model.is_moe_layer): k expert-sorted rows of gate|up, activation and expert output (k (3 I + H)) plus the router logits and
     softmax rows (2 E) - at Qwen3-30B-A3B geometry 35.1 k elements where intermediate_size would count 24.6 k."""
     if is_moe_layer(c, l):
-        return c.num_experts_per_tok * (3 * c.moe_intermediate_size + c.hidden_size) + 2 * c.num_experts
+        E, I, _ = moe_geometry(c)              # Mixtral: num_local_experts / intermediate_size
+        return c.num_experts_per_tok * (3 * I + c.hidden_size) + 2 * E
     return 4 * c.intermediate_size
 
 
@@ -451,6 +452,7 @@ class TreeTrainingEngine:
     def forward(self, model, token_trie) -> List[torch.Tensor]:
         """Per-sequence logprobs ``[len_i - 1]`` (fp32), indexed by original sequence id (tte:515-553)."""
         self.model = model
+        ensure_supported(model)                  # once per model object: a configuration the kernels cannot honour is refused, not run
         self.returns = [None] * token_trie.n_sequences
         self.forkpos_list = _get_forkpos(None, token_trie.lcp_lens, None)
         if token_trie.n_sequences == 0:
@@ -474,6 +476,7 @@ class TreeTrainingEngine:
         """Accumulates d(sum of per-sequence losses)/d(params) into ``param.grad``; returns the loss sum
         (tte:555-616)."""
         self.model = model
+        ensure_supported(model)
         lens = [int(ids.size(0)) for ids in token_trie.inputs]
         self.forkpos_list = _get_forkpos(lens, token_trie.lcp_lens, block_size)
         if token_trie.n_sequences == 0:          # an empty bin of a data-parallel step: no loss, no gradient (the caller still reduces)
