@@ -44,6 +44,9 @@ _PROTOS = {
     "dta_moe_grouped_gemm": ([_i32] + [_vp] * 7 + [_i32] * 5 + [_vp], C.c_int),
     "dta_moe_combine_fwd": ([_vp] * 4 + [_i32] * 4 + [_vp], C.c_int),
     "dta_moe_combine_bwd": ([_vp] * 6 + [_i32] * 4 + [_vp], C.c_int),
+    "dta_lora_down": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp], C.c_int),
+    "dta_lora_wgrad_slabs": ([_i32, _i32], C.c_int),
+    "dta_lora_wgrad": ([_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp], C.c_int),
 }
 EXPORTS = tuple(_PROTOS)
 _ERR = {-1: "DTA_EINVAL", -2: "DTA_EUNSUPPORTED", -3: "DTA_EALIGN", -4: "DTA_ELAUNCH", -5: "DTA_EPRIOR"}

@@ -184,6 +184,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
       }
     }
   }
+  if (!dw_part) return;                                       // frozen weight: no partials wanted (block-uniform)
   // reduce the 4 waves' dw partials through LDS, one v8-group at a time
   float* out = dw_part + (int64_t)blockIdx.x * H;
 #pragma unroll
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __res
       if (live) *reinterpret_cast<v8*>(dx + h * D) = o;
     }
   }
-  if (w_) {                                              // dw partial [gridDim.x, D]
+  if (w_ && dw_part) {                                   // dw partial [gridDim.x, D]; none for a frozen weight (dw_part NULL)
 #pragma unroll
     for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = acc[j];
     __syncthreads();
@@ -508,11 +509,11 @@ extern "C" int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, 
   return DTA_LAUNCH_STATUS();
 }
 
-/* dw_partial: float [dta_rmsnorm_bwd_blocks(R), H]; the caller sums it over dim 0. */
+/* dw_partial: float [dta_rmsnorm_bwd_blocks(R), H]; the caller sums it over dim 0.  NULL: the weight needs no gradient, dx only. */
 extern "C" int dta_rmsnorm_bwd_blocks(int32_t R) { return row_blocks(R, 4, 2048); }
 extern "C" int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
                                int32_t R, int32_t H, int32_t dtype, void* stream) {
-  if (!x || !w || !dy || !rstd || !dx || !dw_partial || R <= 0 || H <= 0) return DTA_EINVAL;
+  if (!x || !w || !dy || !rstd || !dx || R <= 0 || H <= 0) return DTA_EINVAL;          // dw_partial NULL: dx only (frozen weight)
   if (!row_dtype_ok(dtype) || H % 8 || H > 8192) return DTA_EUNSUPPORTED;
   if (!al16(x) || !al16(w) || !al16(dy) || !al16(dx) || (dres && !al16(dres))) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
@@ -554,7 +555,7 @@ extern "C" int dta_qk_norm_rope_bwd_blocks(int64_t n_heads_total) { return row_b
 extern "C" int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, const void* dy, const float* rstd,
                                     void* dx, float* dw_partial, int32_t T, int32_t NH, int32_t head_dim,
                                     int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t, int32_t dtype, void* stream) {
-  if (!cos_sin || !dy || !dx || T <= 0 || NH <= 0 || (w && (!x || !rstd || !dw_partial))) return DTA_EINVAL;
+  if (!cos_sin || !dy || !dx || T <= 0 || NH <= 0 || (w && (!x || !rstd))) return DTA_EINVAL;     // w with dw_partial NULL: dx only
   if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64)) return DTA_EUNSUPPORTED;
   if (!al16(dy) || !al16(dx) || (w && (!al16(w) || !al16(x))) || x_stride_t % 8 || dy_stride_t % 8 || dy_stride_h % 8 || dx_stride_t % 8) return DTA_EALIGN;
   if (dx_stride_t < (int64_t)NH * head_dim) return DTA_EINVAL;

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import lora, ops
 
 
 class _Norm(nn.Module):
@@ -210,8 +210,12 @@ _CHECKED = weakref.WeakKeyDictionary()
 
 
 def ensure_supported(model) -> None:
-    """check_supported(model.config), once per model object and training mode (the engine and dense.py call it per call)."""
+    """check_supported(model.config), once per model object and training mode, and lora.check_supported(model) on EVERY call (the engine
+    and dense.py call this per call): adapter modules are mutable state - an adapter attached, switched to DoRA or put on lm_head between
+    two calls must be seen - and the walk over the module tree is cheap beside a step."""
     training = bool(getattr(model, "training", True))
+    if hasattr(model, "named_modules"):
+        lora.check_supported(model)
     try:
         seen = _CHECKED.setdefault(model, set())
     except TypeError:                  # a plain namespace standing in for a model: neither hashable nor weakly referenceable
@@ -281,6 +285,25 @@ def _bias(*mods):
     return bs[0] if len(bs) == 1 else torch.cat(bs)
 
 
+def _project(x, *mods):
+    """x through the fused projection of `mods` (q|k|v, gate|up, or one module): ONE base GEMM over the stacked base weights - a module
+    that carries a LoRA adapter (lora.resolve) contributes its base_layer's weight and bias - and, where members carry adapters, their
+    low-rank terms on the members' column ranges of the fused output (ops.lora_linear: some members only, different ranks, a trainable
+    base all work).  Without adapters this is ops.linear, as before."""
+    bases, ads = zip(*(lora.resolve(m_) for m_ in mods))
+    w = bases[0].weight if len(bases) == 1 else ops.stack_rows(*(b_.weight for b_ in bases))
+    bias = _bias(*bases)
+    if not any(a_ is not None for a_ in ads):
+        return ops.linear(x, w, bias)
+    adapters, n0 = [], 0
+    for b_, a_ in zip(bases, ads):
+        n = b_.weight.shape[0]
+        if a_ is not None:
+            adapters.append((n0, n, *a_))
+        n0 += n
+    return ops.lora_linear(x, w, bias, adapters)
+
+
 def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     """One decoder layer over the packed rows.  The hidden state enters as (residual stream, pending update)
     so that each residual add is fused into the RMSNorm that follows it.  hipBLASLt GEMMs through torch;
@@ -290,12 +313,11 @@ def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     res, h = ops.add_rms_norm(res, delta, layer.input_layernorm.weight, eps)
     # one projection GEMM for q,k,v (and one for gate,up below): the weights stay separate parameters with
     # their HF names; stacking them is three plain copies whose backward hands out gradient row slices
-    qkv = ops.linear(h, ops.stack_rows(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight),
-                     _bias(a.q_proj, a.k_proj, a.v_proj)).view(T, Hq + 2 * Hkv, D)
+    qkv = _project(h, a.q_proj, a.k_proj, a.v_proj).view(T, Hq + 2 * Hkv, D)
     qn = getattr(a, "q_norm", None); kn = getattr(a, "k_norm", None)
     q, k, v = ops.qkv_prep(qkv, qn.weight if qn is not None else None, kn.weight if kn is not None else None, cos_sin, eps, Hq, Hkv)
     o = attn(q, k, v)                   # ops.tree_attention over a packed trie, or ops.stack_attention over the KV stack
-    attn_out = ops.linear(o.reshape(T, Hq * D), a.o_proj.weight, _bias(a.o_proj))          # LlamaConfig.attention_bias: o_proj too
+    attn_out = _project(o.reshape(T, Hq * D), a.o_proj)                                    # LlamaConfig.attention_bias: o_proj too
     res, h = ops.add_rms_norm(res, attn_out, layer.post_attention_layernorm.weight, eps)
     m = layer.mlp
     if hasattr(m, "experts") and hasattr(m, "gate"):       # Qwen3Moe / Mixtral SparseMoeBlock (duck-typed): router + grouped expert GEMMs
@@ -306,8 +328,8 @@ def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
                 raise AttributeError(f"{type(g).__name__} has no norm_topk_prob and {type(m).__name__} is not a Mixtral block")
             norm = True
         return res, ops.moe_mlp(h, g.weight, m.experts.gate_up_proj, m.experts.down_proj, g.top_k, norm)
-    act = ops.swiglu_fused(ops.linear(h, ops.stack_rows(m.gate_proj.weight, m.up_proj.weight), _bias(m.gate_proj, m.up_proj)))
-    return res, ops.linear(act, m.down_proj.weight, _bias(m.down_proj))                   # LlamaConfig.mlp_bias
+    act = ops.swiglu_fused(_project(h, m.gate_proj, m.up_proj))
+    return res, _project(act, m.down_proj)                                                # LlamaConfig.mlp_bias
 
 
 class _LayerRecompute(torch.autograd.Function):
@@ -374,7 +396,9 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
             res, delta = _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)
             n_full = int(full_layers(torch.cuda.memory_allocated(res.device) - m0))
             continue
-        if checkpoint_layers and li >= n_full and torch.is_grad_enabled():
+        # (a layer whose input carries no gradient - the first one behind a frozen embedding, LoRA - runs in full: a recomputed layer
+        # whose inputs need no gradient would be cut out of the graph, and its adapters with it)
+        if checkpoint_layers and li >= n_full and torch.is_grad_enabled() and (res.requires_grad or (delta is not None and delta.requires_grad)):
             keep = attn_of_layer is None and attn_keep_bytes >= per_layer
             if keep:
                 attn_keep_bytes -= per_layer

@@ -484,7 +484,8 @@ class _HeadRows(torch.autograd.Function):
         kept = ctx.kept
         step = T if kept is not None else ctx.chunk
         dh = torch.empty_like(h)
-        dW = None if kept is not None else torch.zeros(W.shape, dtype=torch.float32, device=W.device)
+        need_w = ctx.needs_input_grad[1]          # a frozen head (LoRA: the tied embedding or lm_head): no [V, hidden] product, no buffer
+        dW = None if (kept is not None or not need_w) else torch.zeros(W.shape, dtype=torch.float32, device=W.device)
         pending = []
         for a in range(0, T, step):
             b = min(a + step, T)
@@ -499,7 +500,9 @@ class _HeadRows(torch.autograd.Function):
             if ctx.tp_group is not None:       # each rank saw only its vocabulary slice: sum dh while the wgrad GEMM runs
                 import torch.distributed as dist
                 pending.append(dist.all_reduce(dh[a:b], op=dist.ReduceOp.SUM, group=ctx.tp_group, async_op=True))
-            if kept is not None:
+            if not need_w:
+                pass
+            elif kept is not None:
                 dW = torch.mm(logits.t(), h)                 # one wgrad GEMM over all T rows (fp32 accumulate inside)
             elif HEAD_WGRAD_FUSED_ACCUMULATE:
                 dW = torch.addmm(dW, logits.t(), h[a:b], out_dtype=torch.float32)      # hipBLASLt: 16-bit operands, fp32 C/D - no [V, hidden] temporary
@@ -508,7 +511,7 @@ class _HeadRows(torch.autograd.Function):
         ctx.kept = None
         for w in pending:
             w.wait()
-        return dh, dW.to(W.dtype), None, None, None, None, None, None, None, None, None, None
+        return dh, (dW.to(W.dtype) if need_w else None), None, None, None, None, None, None, None, None, None, None
 
 
 def lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes=None, tp_group=None, vocab_offset=0):
@@ -633,11 +636,12 @@ class _RMSNorm(torch.autograd.Function):
         dy2 = dy.contiguous().view(R, H)
         gr = g_res.contiguous().view(R, H) if g_res is not None else None
         dx = torch.empty_like(x2)
-        part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, dtype=torch.float32, device=x2.device)
+        need_w = ctx.needs_input_grad[2]          # a frozen norm weight is still read (dx depends on it) but gets no partials and no sum
+        part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, dtype=torch.float32, device=x2.device) if need_w else None
         _launch("dta_rmsnorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(rstd), ptr(dx), ptr(part), R, H, _DT[x2.dtype],
                 nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
         dx = dx.view(dy.shape)
-        return dx, (dx if ctx.has_delta else None), sum_slabs(part, w.dtype), None
+        return dx, (dx if ctx.has_delta else None), (sum_slabs(part, w.dtype) if need_w else None), None
 
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
@@ -672,12 +676,12 @@ class _QKNormRope(torch.autograd.Function):
             dy = dy.contiguous()
         dx = torch.empty((T, NH, D), dtype=x.dtype, device=x.device)
         part = None
-        if ctx.has_w:
+        if ctx.has_w and ctx.needs_input_grad[1]:
             part = torch.empty(lib().dta_qk_norm_rope_bwd_blocks(T * NH), D, dtype=torch.float32, device=x.device)
         _launch("dta_qk_norm_rope_bwd", (x, cos_sin, dy), ptr(x), ptr(w) if ctx.has_w else None, ptr(cos_sin), ptr(dy), ptr(rstd) if ctx.has_w else None,
                 ptr(dx), ptr(part), T, NH, D, x.stride(0), dy.stride(0), dy.stride(1), dx.stride(0), _DT[x.dtype],
                 nbytes=(3 if ctx.has_w else 2) * T * NH * D * x.element_size() + T * D * 4)
-        return dx, (sum_slabs(part, w.dtype) if ctx.has_w else None), None, None
+        return dx, (sum_slabs(part, w.dtype) if part is not None else None), None, None
 
 
 class _QKVPrep(torch.autograd.Function):
@@ -717,14 +721,15 @@ class _QKVPrep(torch.autograd.Function):
         # 16 bytes per lane (partner values travel through registers), so dx may be dy
         d = base if in_place else torch.empty_like(qkv)
         dws = []
-        for lo, NH, w, rstd, has_w, dy in ((0, Hq, wq, rq, ctx.has_w[0], dq), (Hq, Hkv, wk, rk, ctx.has_w[1], dk)):
+        for lo, NH, w, rstd, has_w, need_w, dy in ((0, Hq, wq, rq, ctx.has_w[0], ctx.needs_input_grad[1], dq),
+                                                   (Hq, Hkv, wk, rk, ctx.has_w[1], ctx.needs_input_grad[2], dk)):
             if dy.stride(2) != 1:
                 dy = dy.contiguous()
-            part = torch.empty(lib().dta_qk_norm_rope_bwd_blocks(T * NH), D, dtype=torch.float32, device=qkv.device) if has_w else None
+            part = torch.empty(lib().dta_qk_norm_rope_bwd_blocks(T * NH), D, dtype=torch.float32, device=qkv.device) if has_w and need_w else None
             _launch("dta_qk_norm_rope_bwd", (qkv, cos_sin, dy), ptr(qkv[:, lo:lo + NH]), ptr(w) if has_w else None, ptr(cos_sin), ptr(dy),
                     ptr(rstd) if has_w else None, ptr(d[:, lo:lo + NH]), ptr(part), T, NH, D, qkv.stride(0), dy.stride(0), dy.stride(1), d.stride(0),
                     _DT[qkv.dtype], nbytes=(3 if has_w else 2) * T * NH * D * qkv.element_size() + T * D * 4)
-            dws.append(sum_slabs(part, w.dtype) if has_w else None)
+            dws.append(sum_slabs(part, w.dtype) if part is not None else None)
         if not in_place:
             d[:, Hq + Hkv:].copy_(dv)
         return d, dws[0], dws[1], None, None, None, None
@@ -1229,3 +1234,162 @@ def moe_mlp(h: torch.Tensor, router_w: torch.Tensor, gate_up_w: torch.Tensor, do
     act = swiglu_fused(gu)
     y = _MoeLinear.apply(act, down_w, route, False)
     return _MoeCombine.apply(y, w, route)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Low-rank adapters (LoRA): y = base(x) + scaling (x Aᵀ) Bᵀ with the base weight frozen - include/dta.h "Low-rank adapters", lora.py
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _host_f32(vals):
+    return None if vals is None else np.ascontiguousarray(vals, np.float32)
+
+
+def lora_down(x: torch.Tensor, m: torch.Tensor, rscale=None) -> torch.Tensor:
+    """out[T, R] = (x[T, K] · m[R, K]ᵀ) * rscale[r] (dta_lora_down): one read of x.  rscale: R host floats or None."""
+    T, K = x.shape
+    R = m.shape[0]
+    assert x.stride(1) == 1 and m.stride(1) == 1 and m.shape[1] == K and m.dtype == x.dtype
+    out = torch.empty((T, R), dtype=x.dtype, device=x.device)
+    rs = _host_f32(rscale)
+    _launch("dta_lora_down", (x, m), ptr(x), x.stride(0), ptr(m), m.stride(0), ptr(out), R, None if rs is None else rs.ctypes.data,
+            T, R, K, _DT[x.dtype], nbytes=(T * K + R * K + T * R) * x.element_size())
+    return out
+
+
+def lora_wgrad(l: torch.Tensor, x: torch.Tensor, out_dtype: torch.dtype, rscale=None) -> torch.Tensor:
+    """G[R, K] = rscale[r] * Σ_t l[t, R]ᵀ x[t, K] (dta_lora_wgrad: fp32 partials per slab of rows, then sum_slabs in slab order, rounded
+    once to `out_dtype`; fp32: the unrounded sum).  One read of x and l."""
+    T, K = x.shape
+    R = l.shape[1]
+    assert l.shape[0] == T and l.stride(1) == 1 and x.stride(1) == 1 and l.dtype == x.dtype
+    S = int(lib().dta_lora_wgrad_slabs(T, K))
+    part = torch.empty((S, R, K), dtype=torch.float32, device=x.device)
+    rs = _host_f32(rscale)
+    _launch("dta_lora_wgrad", (l, x), ptr(l), l.stride(0), ptr(x), x.stride(0), ptr(part), None if rs is None else rs.ctypes.data,
+            T, R, K, _DT[x.dtype], nbytes=(T * K + T * R) * x.element_size() + S * R * K * 4)
+    return part[0] if (S == 1 and out_dtype == torch.float32) else sum_slabs(part, out_dtype)
+
+
+# Which form runs each low-rank product: scripts/lora_probe.py on one MI355X (profiles/lora_probe.json: T = 28 160, bf16, the kernel against
+# the torch / hipBLASLt expression it replaces, alternating in one process).  A kernel is the default where it was at least as fast:
+#   Lᵀ·X          dta_lora_wgrad: faster than dxaᵀ·x and than the manual split-K form up to K = 12 288 (level at 4096), slower at 24 576
+#                 -> the kernel for K <= WGRAD_KERNEL_MAX_K, one fp32-output GEMM beyond
+#   x·Aᵀ / dy·B   dta_lora_down: faster only at K = 1024 with a rank class of 32; slower at every larger K -> the kernel there only
+#   y += s·xa·Bᵀ  an in-place MFMA kernel (scripts/diag/lora_up_add_experiment.hip) lost to addmm_ at every shape: the product ships addmm_
+WGRAD_KERNEL_MAX_K = 12288
+
+
+def _down_by_kernel(K: int, R: int) -> bool:
+    return K <= 1024 and R <= 32
+
+
+def _wgrad_by_kernel(K: int) -> bool:
+    return K <= WGRAD_KERNEL_MAX_K
+
+
+def _lora_wgrad(l: torch.Tensor, x: torch.Tensor, out_dtype: torch.dtype, seg_scale=None) -> torch.Tensor:
+    """G[R, K] = Lᵀ·X over the packed rows, rows r0 .. r0+r of every (r0, r, scale) in seg_scale multiplied by scale.  Either form keeps the
+    sum in fp32 until ONE rounding to `out_dtype` (none for fp32 adapters) and scales the fp32 sum: the HIP kernel (fp32 slabs, summed in
+    slab order), or beyond WGRAD_KERNEL_MAX_K one GEMM with an fp32 result.  The fp32 workspace is S·Σr·K·4 bytes (kernel, S <= 64 slabs)
+    or Σr·K·4 (GEMM) per call - for a fused gate|up output of 24 576 columns and Σr = 32 that is 3 MB."""
+    K = x.shape[1]
+    if _wgrad_by_kernel(K):
+        rs = None
+        if seg_scale is not None:
+            rs = np.ones(l.shape[1], np.float32)
+            for r0, r, sc in seg_scale:
+                rs[r0:r0 + r] = sc
+        return lora_wgrad(l, x, out_dtype, rs)
+    g = torch.mm(l.t(), x, out_dtype=torch.float32)
+    for r0, r, sc in seg_scale or ():
+        if sc != 1.0:
+            g[r0:r0 + r] *= sc
+    return g if out_dtype == torch.float32 else g.to(out_dtype)
+
+
+class _LoraLinear(torch.autograd.Function):
+    """y = x Wᵀ (+ b) + Σ_seg scaling_seg · (x A_segᵀ) B_segᵀ on the segment's columns of y: ONE base GEMM over the (stacked) base weight
+    of a fused projection group and the adapters of its members.  `spec`: per adapter (n0, nlen, r, scaling) - the column range of the
+    member in the fused output - and `ab` = (A_0, B_0, A_1, B_1, ...).  The adapters share the input, so their A matrices are stacked:
+    xa = x·A_catᵀ is one pass over x.  In the backward dy is read once for dxa (each adapter its own column range), once for the dB
+    blocks (formed as the full [Σr, N] product over the fused output, of which each adapter keeps its block: extra FLOPs, no extra pass).  A and B are cast to the model dtype once per call; the scalings multiply fp32 accumulators (a GEMM's alpha, or the kernels'
+    per-rank scale), never a rounded copy of B; gradients come back in each adapter parameter's dtype (fp32 adapters: the fp32 slab sum
+    of the weight-gradient kernel, unrounded).  Each product runs in the form measured faster at its shape (see above).  Saves x, xa."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, spec, *ab):
+        dt = x.dtype
+        As, Bs = ab[0::2], ab[1::2]
+        y = F.linear(x, w, b)
+        a_cat = torch.cat([a.to(dt) for a in As]) if len(As) > 1 else As[0].to(dt)
+        if not a_cat.is_contiguous():
+            a_cat = a_cat.contiguous()
+        xa = lora_down(x, a_cat) if _down_by_kernel(x.shape[1], a_cat.shape[0]) else x @ a_cat.t()
+        bs = [B_.to(dt) for B_ in Bs]
+        r0 = 0
+        for (n0, nlen, r, s), B_ in zip(spec, bs):                      # y_seg += s · xa_seg · B_segᵀ in place (alpha on the fp32 accumulator)
+            y[:, n0:n0 + nlen].addmm_(xa[:, r0:r0 + r], B_.t(), alpha=s); r0 += r
+        ctx.save_for_backward(x, w, xa, a_cat, *bs)
+        ctx.spec, ctx.has_bias, ctx.ab_dtypes = spec, b is not None, [t.dtype for t in ab]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, xa, a_cat = ctx.saved_tensors[:4]
+        bs = ctx.saved_tensors[4:]
+        spec, dt = ctx.spec, x.dtype
+        dy = dy.contiguous()
+        R, N = a_cat.shape[0], dy.shape[1]
+        seg_scale, r0 = [], 0
+        for n0, nlen, r, s in spec:
+            seg_scale.append((r0, r, s)); r0 += r
+        if _down_by_kernel(N, R):          # one pass over dy against the block-diagonal [Σr, N] of the B_iᵀ (the products with zeros are free)
+            bd = torch.zeros((R, N), dtype=dt, device=x.device)
+            rs = np.ones(R, np.float32)
+            for (n0, nlen, r, s), (q0, _, _), B_ in zip(spec, seg_scale, bs):
+                bd[q0:q0 + r, n0:n0 + nlen] = B_.t(); rs[q0:q0 + r] = s
+            dxa = lora_down(dy, bd, rs)
+        else:                              # every adapter reads its own columns of dy: still one pass over dy in all
+            dxa = torch.empty((dy.shape[0], R), dtype=dt, device=x.device)
+            for (n0, nlen, r, s), (q0, _, _), B_ in zip(spec, seg_scale, bs):
+                torch.addmm(dxa[:, q0:q0 + r], dy[:, n0:n0 + nlen], B_, beta=0, alpha=s, out=dxa[:, q0:q0 + r])
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _dgrad(dy, w)
+            dx = dx.addmm_(dxa, a_cat) if dx.is_contiguous() else dx + dxa @ a_cat
+        dw = _wgrad(x, dy, w.shape[1] >= 2 * w.shape[0]) if ctx.needs_input_grad[1] else None
+        db = dy.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        need = ctx.needs_input_grad[4:]
+        g32 = lambda i: torch.float32 if ctx.ab_dtypes[i] == torch.float32 else dt
+        dA = dB = None
+        if any(need[0::2]):
+            dA = _lora_wgrad(dxa, x, torch.float32 if any(ctx.ab_dtypes[i] == torch.float32 for i in range(0, len(need), 2)) else dt)
+        if any(need[1::2]):
+            dB = _lora_wgrad(xa, dy, torch.float32 if any(ctx.ab_dtypes[i] == torch.float32 for i in range(1, len(need), 2)) else dt, seg_scale)
+        out, r0 = [], 0
+        for i, (n0, nlen, r, _) in enumerate(spec):
+            out.append(dA[r0:r0 + r].to(g32(2 * i)) if need[2 * i] else None)
+            out.append(dB[r0:r0 + r, n0:n0 + nlen].t().to(g32(2 * i + 1)).contiguous() if need[2 * i + 1] else None)
+            r0 += r
+        return (dx, dw, db, None, *out)
+
+
+def lora_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], adapters) -> torch.Tensor:
+    """x [rows, in] through a (fused) projection with adapters: `w` [N, in] the base weight (stacked over the group's members), `adapters`
+    a list of (n0, nlen, A [r, in], B [nlen, r], scaling) - one per member that carries one, in column order.  bf16 / f16 on the device:
+    _LoraLinear (the HIP kernels where they are the faster form).  fp32 models (the gradient-check path) and host tensors: the same arithmetic as torch expressions."""
+    if not adapters:
+        return linear(x, w, b)
+    if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16):
+        spec = tuple((int(n0), int(nlen), int(A.shape[0]), float(s)) for n0, nlen, A, B_, s in adapters)
+        ab = [t for _, _, A, B_, _ in adapters for t in (A, B_)]
+        return _LoraLinear.apply(x, w, b, spec, *ab)
+    y = linear(x, w, b)
+    cols, o = [], 0
+    for n0, nlen, A, B_, s in adapters:
+        if n0 > o:
+            cols.append(y[:, o:n0])
+        cols.append(y[:, n0:n0 + nlen] + float(s) * ((x @ A.to(x.dtype).t()) @ B_.to(x.dtype).t()))
+        o = n0 + nlen
+    if o < y.shape[1]:
+        cols.append(y[:, o:])
+    return cols[0] if len(cols) == 1 else torch.cat(cols, dim=1)

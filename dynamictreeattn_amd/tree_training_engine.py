@@ -285,7 +285,9 @@ class TreeTrainingEngine:
         D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
         L = c.num_hidden_layers
         mlp = sum(_mlp_elems_per_token(c, l) for l in range(L)) / max(L, 1)
-        return int(2 * (10 * c.hidden_size + mlp + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
+        from . import lora
+        ranks = lora.rank_elems_per_token(model)        # LoRA: x·Aᵀ of every adapted projection is kept for the backward (Σr elements)
+        return int(2 * (10 * c.hidden_size + mlp + ranks + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
 
     def _budget(self) -> Optional[int]:
         if self.memory_budget_bytes is not None:

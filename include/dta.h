@@ -230,7 +230,8 @@ int dta_logprob_entropy_bwd(const void* logits, void* dlogits, const int64_t* la
  * (x_out of the forward), `dres` (may be NULL) the gradient arriving on the residual stream, added to dx. */
 int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
                     int32_t R, int32_t H, float eps, int32_t dtype, void* stream);
-int dta_rmsnorm_bwd_blocks(int32_t R);   /* rows of the dw_partial workspace [blocks, H] (float); caller sums dim 0.  H % 8 == 0; bwd: H <= 8192 */
+int dta_rmsnorm_bwd_blocks(int32_t R);   /* rows of the dw_partial workspace [blocks, H] (float); caller sums dim 0.  H % 8 == 0; bwd: H <= 8192.
+                                          * dw_partial NULL (here and in dta_qk_norm_rope_bwd): a frozen weight - dx only, no partials written */
 int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
                     int32_t R, int32_t H, int32_t dtype, void* stream);
 /* head_dim D = 128 or 64.  x: [T, NH, D] with token stride x_stride_t; cos_sin: float [T, D] = {cos[D/2], sin[D/2]} of the token's
@@ -315,6 +316,25 @@ int dta_moe_combine_fwd(const void* y, const void* topk_w, const int32_t* row_of
 /* dy[row(t, j)] = topk_w[t][j] * dout[t];  dtopk_w[t][j] = <dout[t], y[row(t, j)]> (fp32, fixed order).  No float atomics. */
 int dta_moe_combine_bwd(const void* dout, const void* y, const void* topk_w, const int32_t* row_of_pair, void* dy, void* dtopk_w,
                         int32_t T, int32_t k, int32_t H, int32_t dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Low-rank adapters (LoRA): y = base(x) + scaling * (x A^T) B^T on a projection whose base weight stays frozen.  The products with
+ * one long operand (T packed rows) and one of rank R <= 256; dtype DTA_BF16 / DTA_F16 (MFMA, fp32 accumulation; fp32 models use torch
+ * expressions - DTA_EUNSUPPORTED here).  ld* are row pitches in elements; a pitch or pointer that is not a multiple of 16 bytes is
+ * served by element loads (a rank-6 operand is [T, 6] in memory: the rank is padded in staging, never in HBM).  T any row count, K and
+ * N multiples of 16, R any integer 1..256 (DTA_EUNSUPPORTED otherwise).  The *_host arguments are HOST arrays, read during the
+ * call (they travel as kernel arguments); NULL rscale_host = all ones.  Scales multiply the fp32 accumulator.  No float atomics: the
+ * same inputs give the same bits on every call.
+ * ------------------------------------------------------------------------------------------- */
+/* out[t][r] = rscale[r] * sum_k x[t][k] m[r][k];  x [T, K], m [R, K], out [T, R] (model dtype).  One read of x. */
+int dta_lora_down(const void* x, int64_t ldx, const void* m, int64_t ldm, void* out, int64_t ldo, const float* rscale_host,
+                  int32_t T, int32_t R, int32_t K, int32_t dtype, void* stream);
+/* part[s][r][k] = rscale[r] * sum_{t in slab s} l[t][r] x[t][k]:  l [T, R], x [T, K], part float [dta_lora_wgrad_slabs(T, K), R, K].  The
+ * slabs are whole 64-row steps of T in order; the caller adds them in slab order (dta_sum_slabs), which also rounds to the gradient's
+ * dtype (fp32 adapters get the fp32 sum unrounded).  One read of x and l. */
+int dta_lora_wgrad_slabs(int32_t T, int32_t K);
+int dta_lora_wgrad(const void* l, int64_t ldl, const void* x, int64_t ldx, float* part, const float* rscale_host,
+                   int32_t T, int32_t R, int32_t K, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }
