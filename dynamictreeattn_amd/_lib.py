@@ -22,18 +22,27 @@ _PROTOS = {
     "dta_tree_attn_bwd_ex": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp], C.c_int),
     "dta_tree_attn_fwd_win": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32, _vp, _i32, _vp], C.c_int),
     "dta_tree_attn_bwd_win": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp], C.c_int),
+    "dta_tree_attn_fwd_cap": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32, _vp, _i32, _f32, _vp], C.c_int),
+    "dta_tree_attn_bwd_cap": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp], C.c_int),
     "dta_window_lo": ([_vp] * 4 + [_i32, _i32, _i32, _vp, _vp], C.c_int),
     "dta_logprob_entropy_fwd": ([_vp] * 8 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_logprob_entropy_shard_stats": ([_vp] * 6 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_logprob_entropy_bwd": ([_vp] * 10 + [_i32, _i32, _i64, _i64, _f32, _i32, _vp], C.c_int),
+    "dta_logprob_entropy_fwd_cap": ([_vp] * 8 + [_i32, _i32, _i64, _f32, _i32, _f32, _vp], C.c_int),
+    "dta_logprob_entropy_shard_stats_cap": ([_vp] * 6 + [_i32, _i32, _i64, _f32, _i32, _f32, _vp], C.c_int),
+    "dta_logprob_entropy_bwd_cap": ([_vp] * 10 + [_i32, _i32, _i64, _i64, _f32, _i32, _f32, _vp], C.c_int),
     "dta_rmsnorm_fwd": ([_vp] * 6 + [_i32, _i32, _f32, _i32, _vp], C.c_int),
     "dta_rmsnorm_bwd_blocks": ([_i32], C.c_int),
     "dta_rmsnorm_bwd": ([_vp] * 7 + [_i32, _i32, _i32, _vp], C.c_int),
+    "dta_rmsnorm_fwd_off": ([_vp] * 6 + [_i32, _i32, _f32, _f32, _i32, _vp], C.c_int),
+    "dta_rmsnorm_bwd_off": ([_vp] * 7 + [_i32, _i32, _f32, _i32, _vp], C.c_int),
     "dta_qk_norm_rope_fwd": ([_vp] * 5 + [_i32, _i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_qk_norm_rope_bwd_blocks": ([_i64], C.c_int),
     "dta_qk_norm_rope_bwd": ([_vp] * 7 + [_i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp], C.c_int),
     "dta_swiglu_fwd": ([_vp] * 3 + [_i64, _i32, _i64, _i32, _vp], C.c_int),
     "dta_swiglu_bwd": ([_vp] * 5 + [_i64, _i32, _i64, _i64, _i32, _vp], C.c_int),
+    "dta_geglu_fwd": ([_vp] * 3 + [_i64, _i32, _i64, _i32, _vp], C.c_int),
+    "dta_geglu_bwd": ([_vp] * 5 + [_i64, _i32, _i64, _i64, _i32, _vp], C.c_int),
     "dta_transpose": ([_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp], C.c_int),
     "dta_sum_slabs": ([_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp], C.c_int),
     "dta_moe_router_fwd": ([_vp] * 4 + [_i32] * 5 + [_vp], C.c_int),

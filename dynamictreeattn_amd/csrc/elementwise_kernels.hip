@@ -42,10 +42,12 @@ __device__ __forceinline__ float wave_sum(float v) {
 // ---------------------------------------------------------------------------------------------
 // RMSNorm over rows of H (H % 8 == 0; forward: any H, backward: H <= 8192).  One wave per row, 4 rows per workgroup, grid-stride.
 // ---------------------------------------------------------------------------------------------
-template <int DT, int NA>
+// OFF (dta_rmsnorm_fwd_off / _bwd_off, the Gemma form): y = cast(x·r·(w_off + w)) - the weight offset is added in fp32 inside the kernel and the
+// product is rounded ONCE (the default form rounds x·r to the storage type first, as Qwen3RMSNorm does).  OFF = false: w_off is unused.
+template <int DT, int NA, bool OFF = false>
 __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const void* __restrict__ x_, const void* __restrict__ delta_, const void* __restrict__ w_,
                                                           void* __restrict__ xout_, void* __restrict__ y_,
-                                                          float* __restrict__ rstd, int R, int H, float eps) {
+                                                          float* __restrict__ rstd, int R, int H, float eps, float w_off = 0.f) {
   // NA > 0: the row (H <= 512*NA elements) stays in registers between the sum-of-squares pass and the scaling pass - ONE read of x (and of
   // delta) per row; NA == 0: any H, second pass re-reads the row (L2-hot).
   using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
@@ -86,7 +88,10 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const void* __restrict
           const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
           v8 o;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { const e t = (e)((float)keep[a][j] * r); o[j] = (e)((float)wv[j] * (float)t); }
+          for (int j = 0; j < 8; ++j) {
+            if constexpr (OFF) o[j] = (e)((float)keep[a][j] * r * (w_off + (float)wv[j]));
+            else { const e t = (e)((float)keep[a][j] * r); o[j] = (e)((float)wv[j] * (float)t); }
+          }
           *reinterpret_cast<v8*>(y + 8 * i) = o;
         }
       }
@@ -118,7 +123,10 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const void* __restrict
         const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
         v8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const e t = (e)((float)v[j] * r); o[j] = (e)((float)wv[j] * (float)t); }
+        for (int j = 0; j < 8; ++j) {
+          if constexpr (OFF) o[j] = (e)((float)v[j] * r * (w_off + (float)wv[j]));
+          else { const e t = (e)((float)v[j] * r); o[j] = (e)((float)wv[j] * (float)t); }
+        }
         *reinterpret_cast<v8*>(y + 8 * i) = o;
       }
     }
@@ -127,11 +135,13 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const void* __restrict
 
 // dx = r·(dt − t̂·mean(dt·t̂)), dt = dy·w, t̂ = x·r ;  dw partial per workgroup: Σ_rows dy·t̂.
 // NA = v8 groups per lane (dw accumulators in registers): 2/4/8 for H <= 1024/2048/4096, 16 for H <= 8192 (Qwen3-14B/32B hidden 5120).
-template <int DT, int NA>
+// OFF: dt = dy·(w_off + w); dw is unchanged (d(w_off + w)/dw = 1).
+template <int DT, int NA, bool OFF = false>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict__ x_, const void* __restrict__ w_, const void* __restrict__ dy_,
                                                           const void* __restrict__ dres_,
                                                           const float* __restrict__ rstd, void* __restrict__ dx_, float* __restrict__ dw_part,
-                                                          int R, int H) {
+                                                          int R, int H, float w_off = 0.f) {
+  auto wof = [&](float w) -> float { if constexpr (OFF) return w_off + w; else return w; };
   using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
   __shared__ float red[4 * 64 * 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -158,7 +168,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
         const v8 v = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(x + 8 * i)); const v8 g = *reinterpret_cast<const v8*>(dy + 8 * i);
         const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const float t = (float)v[j] * r; const float gg = (float)g[j]; dot = __builtin_fmaf(gg * (float)wv[j], t, dot); acc[a][j] = __builtin_fmaf(gg, t, acc[a][j]); }
+        for (int j = 0; j < 8; ++j) { const float t = (float)v[j] * r; const float gg = (float)g[j]; dot = __builtin_fmaf(gg * wof((float)wv[j]), t, dot); acc[a][j] = __builtin_fmaf(gg, t, acc[a][j]); }
         if constexpr (KEEP) { kx[a] = v; kg[a] = g; }
       }
     }
@@ -175,10 +185,10 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
         if (dres_) {                                   // gradient arriving on the residual stream is added here (one pass less)
           const v8 dr = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(dres_) + (int64_t)row * H + 8 * i);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { const float t = (float)v[j] * r; o[j] = (e)(r * ((float)g[j] * (float)wv[j] - t * dot) + (float)dr[j]); }
+          for (int j = 0; j < 8; ++j) { const float t = (float)v[j] * r; o[j] = (e)(r * ((float)g[j] * wof((float)wv[j]) - t * dot) + (float)dr[j]); }
         } else {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { const float t = (float)v[j] * r; o[j] = (e)(r * ((float)g[j] * (float)wv[j] - t * dot)); }
+          for (int j = 0; j < 8; ++j) { const float t = (float)v[j] * r; o[j] = (e)(r * ((float)g[j] * wof((float)wv[j]) - t * dot)); }
         }
         *reinterpret_cast<v8*>(dx + 8 * i) = o;
       }
@@ -377,6 +387,56 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const void* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
+// GeGLU (Gemma): y = cast(gelu_tanh(g)) · u with gelu_tanh(g) = 0.5 g (1 + tanh(√(2/π)(g + 0.044715 g³))) - HF's gelu_pytorch_tanh; same row
+// layout as SwiGLU above.  0.5 (1 + tanh(z)) = sigmoid(2z) = 1 / (1 + e^{-2z}): one exponential and one division, saturating to 0 / 1 for
+// large |z| without an inf / inf.  s = that factor: gelu = g s, gelu' = s + g s (1 − s) · 2 dz/dg.
+__device__ __forceinline__ float gelu_gate(float x, float* dgelu) {
+  constexpr float K0 = 0.7978845608028654f, K1 = 0.044715f;
+  const float x2 = x * x;
+  const float z2 = 2.f * K0 * x * __builtin_fmaf(K1, x2, 1.f);                   // 2z
+  const float E = __expf(fminf(-z2, 80.f));                                     // finite: E s below is never inf * 0
+  const float s = 1.f / (1.f + E);                                              // sigmoid(2z) = 0.5 (1 + tanh z), no cancellation at either end
+  if (dgelu) *dgelu = s + x * s * (E * s) * (2.f * K0 * __builtin_fmaf(3.f * K1, x2, 1.f));      // 1 - s = E s
+  return x * s;
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void geglu_fwd_kernel(const void* __restrict__ g_, const void* __restrict__ u_, void* __restrict__ y_,
+                                                        int64_t n8, int c8, int64_t ld) {
+  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / c8; const int col = (int)(i - row * c8) * 8;
+    const v8 g = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(g_) + row * ld + col);
+    const v8 u = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(u_) + row * ld + col);
+    v8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const e s = (e)gelu_gate((float)g[j], nullptr); o[j] = (e)((float)s * (float)u[j]); }
+    reinterpret_cast<v8*>(y_)[i] = o;
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(const void* __restrict__ g_, const void* __restrict__ u_, const void* __restrict__ dy_,
+                                                        void* __restrict__ dg_, void* __restrict__ du_, int64_t n8, int c8, int64_t ld, int64_t ldg) {
+  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / c8; const int col = (int)(i - row * c8) * 8;
+    const v8 g = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(reinterpret_cast<const e*>(g_) + row * ld + col));
+    const v8 u = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(reinterpret_cast<const e*>(u_) + row * ld + col));
+    const v8 dy = reinterpret_cast<const v8*>(dy_)[i];
+    v8 dg, du;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float dgl; const float ge = gelu_gate((float)g[j], &dgl), d = (float)dy[j];
+      du[j] = (e)(d * ge);
+      dg[j] = (e)(d * (float)u[j] * dgl);
+    }
+    *reinterpret_cast<v8*>(reinterpret_cast<e*>(dg_) + row * ldg + col) = dg;
+    *reinterpret_cast<v8*>(reinterpret_cast<e*>(du_) + row * ldg + col) = du;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // 2-D transpose through a 64x64 LDS tile of 32-bit words, 16-byte global accesses on both sides.
 //   4-byte elements: word[c][r] = in[r][c].
 //   2-byte elements: a lane loads the 8-element chunks of TWO consecutive rows and packs (in[r][c], in[r+1][c]) into one word, so the tile
@@ -489,6 +549,48 @@ inline int row_blocks(int64_t rows, int per_block, int cap) { int64_t b = (rows 
        else hipLaunchKernelGGL(KERNEL<DTA_F32>, dim3(GRID), dim3(256), 0, st_, __VA_ARGS__);               \
        return DTA_LAUNCH_STATUS(); } while (0)
 
+extern "C" int dta_rmsnorm_fwd_off(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
+                                   int32_t R, int32_t H, float eps, float w_offset, int32_t dtype, void* stream) {
+  if (w_offset == 0.f) return dta_rmsnorm_fwd(x, delta, w, x_out, y, rstd, R, H, eps, dtype, stream);      // the default form, bit for bit
+  if (!x || !w || !y || !rstd || R <= 0 || H <= 0 || ((delta != nullptr) != (x_out != nullptr)) || w_offset != w_offset) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || H % 8) return DTA_EUNSUPPORTED;
+  if (!al16(x) || !al16(w) || !al16(y) || (delta && (!al16(delta) || !al16(x_out)))) return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const dim3 grid(row_blocks(R, 4, 8192)), block(256);
+#define DTA_RMS_FWD(NA_)                                                                                                       \
+  do { if (dtype == DTA_BF16) hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_BF16, NA_, true>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps, w_offset); \
+       else if (dtype == DTA_F16) hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_F16, NA_, true>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps, w_offset); \
+       else hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_F32, NA_, true>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps, w_offset); } while (0)
+  if (H <= 1024) DTA_RMS_FWD(2);
+  else if (H <= 2048) DTA_RMS_FWD(4);
+  else if (H <= 4096) DTA_RMS_FWD(8);
+  else DTA_RMS_FWD(0);
+#undef DTA_RMS_FWD
+  return DTA_LAUNCH_STATUS();
+}
+
+extern "C" int dta_rmsnorm_bwd_off(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
+                                   int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream) {
+  if (w_offset == 0.f) return dta_rmsnorm_bwd(x, w, dy, dres, rstd, dx, dw_partial, R, H, dtype, stream);
+  if (!x || !w || !dy || !rstd || !dx || R <= 0 || H <= 0 || w_offset != w_offset) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || H % 8 || H > 8192) return DTA_EUNSUPPORTED;
+  if (!al16(x) || !al16(w) || !al16(dy) || !al16(dx) || (dres && !al16(dres))) return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const dim3 grid(row_blocks(R, 4, 2048)), block(256);
+#define DTA_RMS_BWD(NA_)                                                                                                       \
+  do { if (dtype == DTA_BF16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_BF16, NA_, true>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset); \
+       else if (dtype == DTA_F16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_F16, NA_, true>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset); \
+       else hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_F32, NA_, true>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset); } while (0)
+  if (H <= 1024) DTA_RMS_BWD(2);
+  else if (H <= 2048) DTA_RMS_BWD(4);
+  else if (H <= 4096) DTA_RMS_BWD(8);
+  else DTA_RMS_BWD(16);
+#undef DTA_RMS_BWD
+  return DTA_LAUNCH_STATUS();
+}
+
 extern "C" int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
                                int32_t R, int32_t H, float eps, int32_t dtype, void* stream) {
   if (!x || !w || !y || !rstd || R <= 0 || H <= 0 || ((delta != nullptr) != (x_out != nullptr))) return DTA_EINVAL;
@@ -581,6 +683,23 @@ extern "C" int dta_swiglu_fwd(const void* gate, const void* up, void* y, int64_t
   if (!al16(gate) || !al16(up) || !al16(y)) return DTA_EALIGN;
   const int64_t n8 = rows * (cols / 8);
   DTA_DISPATCH(swiglu_fwd_kernel, row_blocks(n8, 256, 4096), gate, up, y, n8, cols / 8, ld);
+}
+
+extern "C" int dta_geglu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream) {
+  if (!gate || !up || !y || rows <= 0 || cols <= 0 || ld < cols) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8) return DTA_EUNSUPPORTED;
+  if (!al16(gate) || !al16(up) || !al16(y)) return DTA_EALIGN;
+  const int64_t n8 = rows * (cols / 8);
+  DTA_DISPATCH(geglu_fwd_kernel, row_blocks(n8, 256, 4096), gate, up, y, n8, cols / 8, ld);
+}
+
+extern "C" int dta_geglu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void* dup,
+                             int64_t rows, int32_t cols, int64_t ld, int64_t ld_grad, int32_t dtype, void* stream) {
+  if (!gate || !up || !dy || !dgate || !dup || rows <= 0 || cols <= 0 || ld < cols || ld_grad < cols) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8 || ld_grad % 8) return DTA_EUNSUPPORTED;
+  if (!al16(gate) || !al16(up) || !al16(dy) || !al16(dgate) || !al16(dup)) return DTA_EALIGN;
+  const int64_t n8 = rows * (cols / 8);
+  DTA_DISPATCH(geglu_bwd_kernel, row_blocks(n8, 256, 4096), gate, up, dy, dgate, dup, n8, cols / 8, ld, ld_grad);
 }
 
 extern "C" int dta_swiglu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void* dup,

@@ -8,8 +8,12 @@
 //        where G[r] = glp[r] + Σ_e g_extra_lp[e] is the summed gradient of every log-prob picked from row r.
 // One 256-thread workgroup per row, 16-byte loads, online (max, Σexp, Σexp·x) per lane, block reduce.
 // Algorithmic HBM bytes: fwd V·sizeof(e) per row (one read); bwd 2·V·sizeof(e) per row (one read, one write).
+// Final-logit soft-capping (the _cap entries, CAP = true): every statistic and pick is taken on x' = c·tanh(x/c), formed in registers as the
+// raw logit is loaded (no second pass over the logits); the temperature divides x'.  The backward multiplies the gradient with respect to x'
+// by 1 − tanh²(x/c) before the store.  The CAP = false kernels keep their arguments and code.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "dta_common.h"
 
 // The [rows, V] logits are 8.6 GB at the bench's shape: each byte is read once here (and once more by the gradient GEMMs, long after it
@@ -66,21 +70,28 @@ struct FwdArgs {
   float *lse, *ent, *lp, *extra_lp, *stats;
   int R, V; int64_t stride; float inv_temp;
 };
+struct FwdArgsC : FwdArgs { float softcap; };
 
-template <int DT>
-__global__ __launch_bounds__(256) void logprob_entropy_fwd_kernel(FwdArgs a) {
+// tanh(x) from a = 2 log2(e) x: 1 − 2 / (1 + 2^a); saturates to ±1 through 2^a = inf / 0, never inf / inf (see tree_attn.hip)
+__device__ __forceinline__ float cap_tanh(float a) { return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(a)), 1.f); }
+
+template <int DT, bool CAP>
+__global__ __launch_bounds__(256) void logprob_entropy_fwd_kernel(typename std::conditional<CAP, FwdArgsC, FwdArgs>::type a) {
   using e = typename LTy<DT>::e; using v8 = typename LTy<DT>::v8;
   __shared__ Stat sh[4];
   const int row = blockIdx.x, V = a.V;
   const e* x = reinterpret_cast<const e*>(a.logits) + (int64_t)row * a.stride;
-  const float k = LOG2E * a.inv_temp;
+  float k = LOG2E * a.inv_temp;
+  [[maybe_unused]] float kt = 0.f, cs = 1.f;          // CAP: tanh argument factor 2 log2(e) / c; picks are c·t·(1/T)
+  if constexpr (CAP) { kt = 2.f * LOG2E / a.softcap; cs = a.softcap; k *= a.softcap; }
+  auto capped = [&](float xr) -> float { if constexpr (CAP) return cap_tanh(xr * kt); else return xr; };   // x (no cap) or t = tanh(x/c)
   Stat st{-1e30f, 0.f, 0.f};
   const int nv = V >> 3;
   for (int i = threadIdx.x; i < nv; i += 256) {
     const v8 v = DTA_LP_LOAD(reinterpret_cast<const v8*>(x + 8 * i));
     float y[8]; float mx = -1e30f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { y[j] = (float)v[j] * k; mx = fmaxf(mx, y[j]); }
+    for (int j = 0; j < 8; ++j) { y[j] = capped((float)v[j]) * k; mx = fmaxf(mx, y[j]); }
     const float m = fmaxf(st.m, mx);
     const float f = __builtin_amdgcn_exp2f(st.m - m);
     float s = st.s * f, t = st.t * f;
@@ -89,29 +100,30 @@ __global__ __launch_bounds__(256) void logprob_entropy_fwd_kernel(FwdArgs a) {
     st = Stat{m, s, t};
   }
   for (int i = (nv << 3) + threadIdx.x; i < V; i += 256) {            // tail when V % 8 != 0
-    const float y = (float)x[i] * k;
+    const float y = capped((float)x[i]) * k;
     const float m = fmaxf(st.m, y); const float f = __builtin_amdgcn_exp2f(st.m - m); const float p = __builtin_amdgcn_exp2f(y - m);
     st = Stat{m, st.s * f + p, __builtin_fmaf(p, y, st.t * f)};
   }
   st = block_reduce(st, sh);
   const int e0 = a.extra_ptr ? a.extra_ptr[row] : 0, e1 = a.extra_ptr ? a.extra_ptr[row + 1] : 0;
+  auto pick = [&](int64_t lab) -> float { if constexpr (CAP) return cs * capped((float)x[lab]) * a.inv_temp; else return (float)x[lab] * a.inv_temp; };
   if (a.stats) {
     // vocab-sharded use: raw per-shard statistics (log2 domain of the scaled logits) for a cross-rank combine; picked
     // values are the raw x/T of the labels this shard owns (0 otherwise)
     if (threadIdx.x == 0) {
       const int64_t lab = a.labels ? a.labels[row] : -1;
       a.stats[4 * row] = st.m; a.stats[4 * row + 1] = st.s; a.stats[4 * row + 2] = st.t;
-      a.stats[4 * row + 3] = (lab >= 0 && lab < V) ? (float)x[lab] * a.inv_temp : 0.f;
+      a.stats[4 * row + 3] = (lab >= 0 && lab < V) ? pick(lab) : 0.f;
     }
-    for (int f = e0 + threadIdx.x; f < e1; f += 256) { const int64_t lab = a.extra_labels[f]; a.extra_lp[f] = (lab >= 0 && lab < V) ? (float)x[lab] * a.inv_temp : 0.f; }
+    for (int f = e0 + threadIdx.x; f < e1; f += 256) { const int64_t lab = a.extra_labels[f]; a.extra_lp[f] = (lab >= 0 && lab < V) ? pick(lab) : 0.f; }
   } else {
     const float l = (st.m + __builtin_amdgcn_logf(st.s)) * LN2;          // v_log_f32 = log2
     if (threadIdx.x == 0) {
       a.lse[row] = l;
       if (a.ent) a.ent[row] = l - (st.t / st.s) * LN2;                    // H = lse − E[x/T]
-      if (a.lp) { const int64_t lab = a.labels[row]; a.lp[row] = (lab >= 0 && lab < V) ? (float)x[lab] * a.inv_temp - l : 0.f; }
+      if (a.lp) { const int64_t lab = a.labels[row]; a.lp[row] = (lab >= 0 && lab < V) ? pick(lab) - l : 0.f; }
     }
-    for (int f = e0 + threadIdx.x; f < e1; f += 256) { const int64_t lab = a.extra_labels[f]; a.extra_lp[f] = (lab >= 0 && lab < V) ? (float)x[lab] * a.inv_temp - l : 0.f; }
+    for (int f = e0 + threadIdx.x; f < e1; f += 256) { const int64_t lab = a.extra_labels[f]; a.extra_lp[f] = (lab >= 0 && lab < V) ? pick(lab) - l : 0.f; }
   }
 }
 
@@ -120,10 +132,14 @@ struct BwdArgs {
   const float *lse, *ent, *glp, *gextra, *gent;
   int R, V; int64_t stride, out_stride; float inv_temp;
 };
+struct BwdArgsC : BwdArgs { float softcap; };
+constexpr int CAP_STASH = 2048;      // extra picks of ONE row whose 1 − tanh² factors are held in LDS across the in-place sweep (dta.h)
 
-template <int DT>
-__global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(BwdArgs b) {
+template <int DT, bool CAP>
+__global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(typename std::conditional<CAP, BwdArgsC, BwdArgs>::type b) {
   using e = typename LTy<DT>::e; using v8 = typename LTy<DT>::v8;
+  float* stash = nullptr;
+  if constexpr (CAP) { __shared__ float stash_s[CAP_STASH]; stash = stash_s; }
   const int row = blockIdx.x, V = b.V;
   const e* x = reinterpret_cast<const e*>(b.logits) + (int64_t)row * b.stride;
   e* o = reinterpret_cast<e*>(b.out) + (int64_t)row * b.out_stride;
@@ -136,18 +152,34 @@ __global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(BwdArgs b) {
   for (int f = e0; f < e1; ++f) G += b.gextra[f];                    // a handful per fork row, none elsewhere (uniform loop)
   const float a = -G + ge * (l - (b.ent ? b.ent[row] : 0.f));
   const int64_t lab = b.labels ? b.labels[row] : -1;
-  const float k = LOG2E * inv_temp, l2 = l * LOG2E;
+  float k = LOG2E * inv_temp; const float l2 = l * LOG2E;
   const int nv = V >> 3;
+  [[maybe_unused]] float kt = 0.f, cs = 1.f;
+  if constexpr (CAP) {
+    kt = 2.f * LOG2E / b.softcap; cs = b.softcap; k *= b.softcap;
+    // the one-hot terms of the extra picks need 1 − tanh²(x/c) of their own raw logit, which the in-place sweep below overwrites: taken now
+    for (int f = e0 + threadIdx.x; f < e1 && f - e0 < CAP_STASH; f += 256) {
+      const int64_t le = b.extra_labels[f];
+      float w = 0.f;
+      if (le >= 0 && le < V) { const float t = cap_tanh((float)x[le] * kt); w = __builtin_fmaf(-t, t, 1.f); }
+      stash[f - e0] = w;
+    }
+    __syncthreads();
+  }
   // d/dx = (p * (a - ge * x/T) + [label] g1) / T  =  p * (c1 + c2 * x) + [label] g1 / T: two instructions per element besides the exponential's two,
   // and the label test once per 16-byte group (it was a compare and a select per element)
-  const float c1 = a * inv_temp, c2 = -ge * inv_temp * inv_temp, gl = g1 * inv_temp;
+  float c2 = -ge * inv_temp * inv_temp;
+  if constexpr (CAP) c2 *= cs;                                        // x'/T = c·t/T
+  const float c1 = a * inv_temp, gl = g1 * inv_temp;
   const int lab8 = lab >= 0 && lab < ((int64_t)nv << 3) ? (int)(lab >> 3) : -1, labj = (int)(lab & 7);
   for (int i = threadIdx.x; i < nv; i += 256) {
     v8 v = DTA_LP_LOAD(reinterpret_cast<const v8*>(x + 8 * i));
     float g[8];
+    [[maybe_unused]] float sech2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float xf = (float)v[j];
+      float xf = (float)v[j];
+      if constexpr (CAP) { xf = cap_tanh(xf * kt); sech2[j] = __builtin_fmaf(-xf, xf, 1.f); }      // xf := t; k and c2 carry the cap
       const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(xf, k, -l2));
       g[j] = p * __builtin_fmaf(xf, c2, c1);
     }
@@ -155,27 +187,42 @@ __global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(BwdArgs b) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) g[j] += j == labj ? gl : 0.f;
     }
+    if constexpr (CAP) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) g[j] *= sech2[j];
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (e)g[j];
     DTA_LP_STORE(reinterpret_cast<v8*>(o + 8 * i), v);
   }
   for (int i = (nv << 3) + threadIdx.x; i < V; i += 256) {
-    const float xs = (float)x[i] * inv_temp;
-    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf((float)x[i], k, -l2));
+    float xr = (float)x[i], s2 = 1.f;
+    if constexpr (CAP) { xr = cap_tanh(xr * kt); s2 = __builtin_fmaf(-xr, xr, 1.f); }
+    const float xs = xr * cs * inv_temp;
+    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(xr, k, -l2));
     float g = p * (a - ge * xs);
     if (i == lab) g += g1;
+    if constexpr (CAP) g *= s2;
     o[i] = (e)(g * inv_temp);
   }
   if (e1 > e0) {                                                      // one-hot terms of the extra picks (distinct tokens: children of one node)
     __syncthreads();
     for (int f = e0 + threadIdx.x; f < e1; f += 256) {
       const int64_t le = b.extra_labels[f];
+      if constexpr (CAP) {
+        // beyond the stash only an out-of-place call still has the raw logit; in place (dta.h: at most CAP_STASH extra picks per row) the
+        // pick's gradient element becomes NaN - never a silently dropped term
+        float w = __builtin_nanf("");
+        if (f - e0 < CAP_STASH) w = stash[f - e0];
+        else if (le >= 0 && le < V && (const void*)x != (const void*)o) { const float t = cap_tanh((float)x[le] * kt); w = __builtin_fmaf(-t, t, 1.f); }
+        if (le >= 0 && le < V) o[le] = (e)((float)o[le] + b.gextra[f] * inv_temp * w);
+      } else
       if (le >= 0 && le < V) o[le] = (e)((float)o[le] + b.gextra[f] * inv_temp);
     }
   }
 }
 
-int fwd_launch(FwdArgs a, int32_t dtype, float temperature, void* stream) {
+int fwd_launch(FwdArgs a, int32_t dtype, float temperature, void* stream, float softcap = 0.f) {
   if (!a.logits || a.R <= 0 || a.V <= 0 || (a.lp && !a.labels) || !(temperature > 0.f)) return DTA_EINVAL;
   if (a.extra_ptr && (!a.extra_labels || !a.extra_lp)) return DTA_EINVAL;
   if (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) return DTA_EUNSUPPORTED;
@@ -183,9 +230,16 @@ int fwd_launch(FwdArgs a, int32_t dtype, float temperature, void* stream) {
   a.inv_temp = 1.f / temperature;
   hipStream_t st = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
-  if (dtype == DTA_BF16) hipLaunchKernelGGL(logprob_entropy_fwd_kernel<DTA_BF16>, dim3(a.R), dim3(256), 0, st, a);
-  else if (dtype == DTA_F16) hipLaunchKernelGGL(logprob_entropy_fwd_kernel<DTA_F16>, dim3(a.R), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(logprob_entropy_fwd_kernel<DTA_F32>, dim3(a.R), dim3(256), 0, st, a);
+  if (softcap > 0.f) {
+    FwdArgsC c; static_cast<FwdArgs&>(c) = a; c.softcap = softcap;
+    if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_BF16, true>), dim3(a.R), dim3(256), 0, st, c);
+    else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F16, true>), dim3(a.R), dim3(256), 0, st, c);
+    else hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F32, true>), dim3(a.R), dim3(256), 0, st, c);
+    return DTA_LAUNCH_STATUS();
+  }
+  if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_BF16, false>), dim3(a.R), dim3(256), 0, st, a);
+  else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F16, false>), dim3(a.R), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F32, false>), dim3(a.R), dim3(256), 0, st, a);
   return DTA_LAUNCH_STATUS();
 }
 
@@ -207,10 +261,10 @@ extern "C" int dta_logprob_entropy_shard_stats(const void* logits, const int64_t
   return fwd_launch(a, dtype, temperature, stream);
 }
 
-extern "C" int dta_logprob_entropy_bwd(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+static int bwd_launch(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
                                        const float* lse, const float* entropy,
                                        const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
-                                       int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype, void* stream) {
+                                       int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
   if (!logits || !dlogits || !lse || R <= 0 || V <= 0 || (g_entropy && !entropy) || (g_logprob && !labels) || !(temperature > 0.f)) return DTA_EINVAL;
   if (extra_ptr && (!extra_labels || !g_extra_logprob)) return DTA_EINVAL;
   if (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) return DTA_EUNSUPPORTED;
@@ -219,8 +273,52 @@ extern "C" int dta_logprob_entropy_bwd(const void* logits, void* dlogits, const 
   BwdArgs b{logits, dlogits, labels, extra_ptr, extra_labels, lse, entropy, g_logprob, g_extra_logprob, g_entropy, R, V, row_stride, out_row_stride, 1.f / temperature};
   hipStream_t st = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
-  if (dtype == DTA_BF16) hipLaunchKernelGGL(logprob_entropy_bwd_kernel<DTA_BF16>, dim3(R), dim3(256), 0, st, b);
-  else if (dtype == DTA_F16) hipLaunchKernelGGL(logprob_entropy_bwd_kernel<DTA_F16>, dim3(R), dim3(256), 0, st, b);
-  else hipLaunchKernelGGL(logprob_entropy_bwd_kernel<DTA_F32>, dim3(R), dim3(256), 0, st, b);
+  if (softcap > 0.f) {
+    BwdArgsC c; static_cast<BwdArgs&>(c) = b; c.softcap = softcap;
+    if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_BF16, true>), dim3(R), dim3(256), 0, st, c);
+    else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F16, true>), dim3(R), dim3(256), 0, st, c);
+    else hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F32, true>), dim3(R), dim3(256), 0, st, c);
+    return DTA_LAUNCH_STATUS();
+  }
+  if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_BF16, false>), dim3(R), dim3(256), 0, st, b);
+  else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F16, false>), dim3(R), dim3(256), 0, st, b);
+  else hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F32, false>), dim3(R), dim3(256), 0, st, b);
   return DTA_LAUNCH_STATUS();
+}
+
+extern "C" int dta_logprob_entropy_bwd(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+                                       const float* lse, const float* entropy,
+                                       const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
+                                       int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype, void* stream) {
+  return bwd_launch(logits, dlogits, labels, extra_ptr, extra_labels, lse, entropy, g_logprob, g_extra_logprob, g_entropy, R, V, row_stride, out_row_stride,
+                    temperature, dtype, 0.f, stream);
+}
+
+// Final-logit soft-capping: softcap <= 0 is the plain entry, bit for bit; a cap that is not finite is refused.
+static bool cap_ok(float c) { return c == c && c < 3.0e38f; }
+
+extern "C" int dta_logprob_entropy_fwd_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+                                           float* lse, float* entropy, float* logprob, float* extra_logprob,
+                                           int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
+  if (!lse || !cap_ok(softcap)) return DTA_EINVAL;
+  FwdArgs a{logits, labels, extra_ptr, extra_labels, lse, entropy, logprob, extra_logprob, nullptr, R, V, row_stride, 1.f};
+  return fwd_launch(a, dtype, temperature, stream, softcap);
+}
+
+extern "C" int dta_logprob_entropy_shard_stats_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+                                                   float* stats, float* extra_picked,
+                                                   int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
+  if (!stats || !cap_ok(softcap)) return DTA_EINVAL;
+  FwdArgs a{logits, labels, extra_ptr, extra_labels, nullptr, nullptr, nullptr, extra_picked, stats, R, V, row_stride, 1.f};
+  return fwd_launch(a, dtype, temperature, stream, softcap);
+}
+
+extern "C" int dta_logprob_entropy_bwd_cap(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+                                           const float* lse, const float* entropy,
+                                           const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
+                                           int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype,
+                                           float softcap, void* stream) {
+  if (!cap_ok(softcap)) return DTA_EINVAL;
+  return bwd_launch(logits, dlogits, labels, extra_ptr, extra_labels, lse, entropy, g_logprob, g_extra_logprob, g_entropy, R, V, row_stride, out_row_stride,
+                    temperature, dtype, softcap, stream);
 }

@@ -87,7 +87,12 @@ struct AttnParams {
 // or q_offset + row - window + 1 (stack form, win_lo == NULL).  A parameter type of its own: the kernels without a window (WIN = false)
 // keep the parent's kernel arguments, and every WIN term below folds away at compile time, so their device code is unchanged.
 struct AttnParamsW : AttnParams { const int32_t* win_lo; int32_t window; };
-template <bool WIN> using AttnP = typename std::conditional<WIN, AttnParamsW, AttnParams>::type;
+// Soft-capped form (dta_tree_attn_fwd_cap / _bwd_cap): the score is softcap * tanh(scale q.k / softcap), capped BEFORE the visibility
+// mask.  Again parameter types of their own (with and without a window), so that the CAP = false kernels keep their arguments and code.
+struct AttnParamsC : AttnParams { float softcap; };
+struct AttnParamsWC : AttnParamsW { float softcap; };
+template <bool WIN, bool CAP = false> using AttnP = typename std::conditional<CAP, typename std::conditional<WIN, AttnParamsWC, AttnParamsC>::type,
+                                                                              typename std::conditional<WIN, AttnParamsW, AttnParams>::type>::type;
 
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -140,6 +145,20 @@ template <int DT> __device__ __forceinline__ typename Ty<DT>::v8 pack_half(const
 }
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// tanh(x) from a = 2 log2(e) x in fp32: 1 - 2 / (1 + 2^a), one v_exp_f32 and one v_rcp_f32.  2^a overflows to +inf for large a and the
+// reciprocal of inf is 0, so the value saturates to exactly +1 (and to -1 when 2^a underflows to 0): finite for every finite or infinite a
+// - a quotient of two exponentials would be inf / inf there.  Absolute error a few 2^-24 (the cancellation for small |x| is absolute, not
+// relative: the capped score softcap * tanh is off by the order of softcap * 2^-24, the fp32 floor of the score itself).
+__device__ __forceinline__ float cap_tanh(float a) { return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + fast_exp2(a)), 1.f); }
+// The cap's two constants: kcap turns a raw q.k into tanh's argument a (2 log2(e) scale / softcap), and the log2-domain score factor c
+// becomes softcap log2(e).  Without a cap the one statement the kernels had (c = scale log2(e)) is all that is left.
+#define DTA_CAP_CONSTANTS                                                                                  \
+  const float c = (CAP ? cap_of(p) : p.scale) * LOG2E;                                                     \
+  [[maybe_unused]] const float kcap = CAP ? 2.f * LOG2E * p.scale / cap_of(p) : 0.f;
+template <class P> __device__ __forceinline__ float cap_of(const P& p) {
+  if constexpr (std::is_base_of<AttnParamsC, P>::value || std::is_base_of<AttnParamsWC, P>::value) return p.softcap; else return 0.f;
+}
 
 // ---- iterator over the 64-key tiles of a query tile's run list --------------------------------
 struct TileIter {
@@ -345,8 +364,8 @@ template <int TB> __device__ __forceinline__ void dma_one2(uint32_t oa, const vo
 // they share the staged K/V tiles.  One barrier per 64-key tile, LDS double buffered, tile loop unrolled
 // over the two buffers so that every LDS address is lane-offset + immediate.
 // =================================================================================================
-template <int DT, int HPB, int DH, bool WIN>
-__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnP<WIN> p) {
+template <int DT, int HPB, int DH, bool WIN, bool CAP>
+__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnP<WIN, CAP> p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32;      // image bytes, k-steps over D, 32-wide accumulator blocks over D
   constexpr int NW = 4 * HPB, BUF = 2 * TB + SE_BYTES;
@@ -397,7 +416,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnP<WIN> 
 #pragma unroll
     for (int g = 0; g < 16; ++g) O[db][g] = 0.f;
   float m = -1e30f, lsum = 0.f;
-  const float c = p.scale * LOG2E;
+  DTA_CAP_CONSTANTS
 
   int ck0 = it.k0, ckend = it.kend; bool cmask = it.masked() || (WIN && it.k0 < wmax);
   DTA_KV_DMA(smem, it.k0, NW)
@@ -422,6 +441,10 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnP<WIN> 
     _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                       \
       _Pragma("unroll") for (int g = 0; g < 16; ++g) X[kb][g] = 0.f;                                       \
     DTA_SCORE_MFMAS                                                                                        \
+    if constexpr (CAP) {                         /* X := tanh(scale q.k / softcap), before the mask; c carries the softcap */ \
+      _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                     \
+        _Pragma("unroll") for (int g = 0; g < 16; ++g) X[kb][g] = cap_tanh(X[kb][g] * kcap);                 \
+    }                                                                                                      \
     DTA_STAMP_AT(1)                                                                                        \
     if (cmask) {                                                                                           \
       const int qlim = qidx < ckend ? qidx : ckend - 1;      /* keys at or beyond the run end never count */ \
@@ -491,8 +514,8 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_fwd_kernel(AttnP<WIN> 
 // =================================================================================================
 // backward part 1: delta + dQ   (query tile owns the workgroup; same sweep as the forward)
 // =================================================================================================
-template <int DT, int HPB, int DH, bool WIN>
-__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnP<WIN> p) {
+template <int DT, int HPB, int DH, bool WIN, bool CAP>
+__global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnP<WIN, CAP> p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32;
   __shared__ __attribute__((aligned(16))) char smem[2 * (2 * TB + SE_BYTES)];
@@ -555,7 +578,7 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnP<WI
   for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int g = 0; g < 16; ++g) DQ[db][g] = 0.f;
-  const float c = p.scale * LOG2E;
+  DTA_CAP_CONSTANTS
 
   // dP starts at -delta (this lane's query row) instead of 0: dS/scale = p * dP' costs one multiply per element, and the softmax
   // scale goes onto dQ once, in the epilogue (as the dK/dV kernel does for dK)
@@ -597,6 +620,8 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnP<WI
           __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         }
         // dS^T / scale = P ∘ (dP − delta); the interval mask only on tiles of runs flagged partial
+        // CAP: t = tanh(z / softcap) stands for the score and dz / scale = p (dP − delta)(1 − t²), one element at a time (a separate pass
+        // over the 16 scores kept t and 1 − t² live beside X and DP: 256 registers and a spill in the windowed D = 128 form)
         if (cmask) {
           const int qlim = qidx < ckend ? qidx : ckend - 1;      // keys at or beyond the run end never count
 #pragma unroll
@@ -608,13 +633,22 @@ __global__ __launch_bounds__(256 * HPB, 2) void tree_attn_bwd_dq_kernel(AttnP<WI
             for (int j = 0; j < 4; ++j) {
               const int g = 4 * gq + j;
               const bool ok = (ck0 + kl + j <= qlim) && (qidx < sev[j]) && (!WIN || ck0 + kl + j >= wlo);
+              if constexpr (CAP) {
+                const float t = cap_tanh(X[g] * kcap);
+                const float pv = ok ? fast_exp2(__builtin_fmaf(t, c, -lse2)) : 0.f;
+                X[g] = pv * DP[g] * __builtin_fmaf(-t, t, 1.f);
+              } else {
               const float pv = ok ? fast_exp2(__builtin_fmaf(X[g], c, -lse2)) : 0.f;
               X[g] = pv * DP[g];
+              }
             }
           }
         } else {
 #pragma unroll
-          for (int g = 0; g < 16; ++g) X[g] = fast_exp2(__builtin_fmaf(X[g], c, -lse2)) * DP[g];
+          for (int g = 0; g < 16; ++g) {
+            if constexpr (CAP) { const float t = cap_tanh(X[g] * kcap); X[g] = fast_exp2(__builtin_fmaf(t, c, -lse2)) * DP[g] * __builtin_fmaf(-t, t, 1.f); }
+            else X[g] = fast_exp2(__builtin_fmaf(X[g], c, -lse2)) * DP[g];
+          }
         }
         // dQ^T[d][q] += K^T · dS^T
 #pragma unroll
@@ -677,8 +711,8 @@ template <int D> constexpr int kv2_frags() { return 4 * kv2_slot<D>(); }    // 4
 template <int D, bool WIN> constexpr int kv2_buf() { return 2 * tile_bytes<D>() + (WIN ? 768 : 512); }   // + row constants lse, -delta (, win_lo)
 template <int D, bool WIN> constexpr int kv2_lds() { return kv2_frags<D>() + 2 * kv2_buf<D, WIN>() + 16; }   // + se_min[4]: ONE __shared__ object (a second one makes hipcc drain vmcnt in front of every LDS read)
 
-template <int DT, int DH, bool WIN>
-__global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnP<WIN> p) {
+template <int DT, int DH, bool WIN, bool CAP>
+__global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnP<WIN, CAP> p) {
   using T = Ty<DT>; using e = typename T::e; using v8 = typename T::v8; using v4 = typename T::v4;
   constexpr int KT = 128;
   constexpr int TB = tile_bytes<DH>(), NKS = DH / 16, NDB = DH / 32, KV2_FRAGS = kv2_frags<DH>(), KV2_BUF = kv2_buf<DH, WIN>(), KSLOT = kv2_slot<DH>();
@@ -734,7 +768,7 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnP<WIN> p
   }
   const int ntile = qend > qbeg ? (qend - qbeg + 63) / 64 : 0;
   const int total = ntile * p.group;
-  const float c = p.scale * LOG2E;
+  DTA_CAP_CONSTANTS
 
   // tile DMA: DH/8 one-KiB pieces per image over 8 waves = NP = DH/64 per wave per image (D = 128: piece = 2*wave8 + i, rows 8*wave8 + 4*i ..;
   // D = 64: piece = wave8, rows 8*wave8 ..); lse / delta rows (64 floats each) by 4-byte DMA from waves 0 / 1.
@@ -812,6 +846,9 @@ __global__ __launch_bounds__(512, 2) void tree_attn_bwd_dkv2_kernel(AttnP<WIN> p
     _Pragma("unroll") for (int gq = 0; gq < 4; ++gq) {                                                     \
       const float4 l4 = *reinterpret_cast<const float4*>(rc + 32 * gq);                                    \
       nl[4 * gq] = l4.x; nl[4 * gq + 1] = l4.y; nl[4 * gq + 2] = l4.z; nl[4 * gq + 3] = l4.w;              \
+    }                                                                                                      \
+    if constexpr (CAP) {                           /* S := t = tanh(z / softcap); DP := (dP - delta)(1 - t^2): dz / scale = p * DP */ \
+      _Pragma("unroll") for (int g = 0; g < 16; ++g) { const float t = cap_tanh(S[g] * kcap); S[g] = t; DP[g] *= __builtin_fmaf(-t, t, 1.f); } \
     }                                                                                                      \
     if (full) {                                                                                            \
       _Pragma("unroll") for (int g = 0; g < 16; ++g) {                                                     \
@@ -982,14 +1019,14 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_finalize_kernel(AttnPar
 }
 
 // the backward launches of one (dtype, head_dim): dQ (head pairs, then the odd head alone), dK/dV, and the slab finalize
-template <int DT, int DH, bool WIN>
-void launch_bwd(const AttnP<WIN>& p, const AttnP<WIN>& pp, const AttnP<WIN>& ps, int npair, dim3 gqp, dim3 gqs, int ndkv, bool fin, int n_splits,
+template <int DT, int DH, bool WIN, bool CAP>
+void launch_bwd(const AttnP<WIN, CAP>& p, const AttnP<WIN, CAP>& pp, const AttnP<WIN, CAP>& ps, int npair, dim3 gqp, dim3 gqs, int ndkv, bool fin, int n_splits,
                 int which, hipStream_t st) {
   if (which & 1) {
-    if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 2, DH, WIN>), gqp, dim3(512), 0, st, pp);
-    if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 1, DH, WIN>), gqs, dim3(256), 0, st, ps);
+    if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 2, DH, WIN, CAP>), gqp, dim3(512), 0, st, pp);
+    if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 1, DH, WIN, CAP>), gqs, dim3(256), 0, st, ps);
   }
-  if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DT, DH, WIN>), dim3(ndkv * p.Hkv), dim3(512), 0, st, p);
+  if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DT, DH, WIN, CAP>), dim3(ndkv * p.Hkv), dim3(512), 0, st, p);
   if (fin && p.dkv_units && n_splits > 0)   // the slab sums do not depend on visibility: one finalize kernel for both forms
     hipLaunchKernelGGL((tree_attn_bwd_dkv_finalize_kernel<DT, DH>), dim3(n_splits * p.Hkv, FIN_SPLIT), dim3(256), 0, st, static_cast<const AttnParams&>(p));
 }
@@ -998,12 +1035,12 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 }  // namespace
 
-template <bool WIN>
+template <bool WIN, bool CAP = false>
 static int attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
                                     const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                                     int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
                                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, void* stream) {
+                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, void* stream, float softcap = 0.f) {
   if (!q || !k || !v || !out || !lse || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
   if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
   if ((head_dim != 128 && head_dim != 64) || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32)) return DTA_EUNSUPPORTED;
@@ -1011,12 +1048,13 @@ static int attn_fwd(const void* q, const void* k, const void* v, void* out, floa
   if (dtype == DTA_F32) {                                    // fp32 models: the plain-FMA correctness path (tree_attn_f32.hip)
     DTA_REFUSE_IF_PRIOR_ERROR();
     return dta_attn_fwd_f32(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
-                            scale, win_lo, WIN ? window : 0, static_cast<hipStream_t>(stream));
+                            scale, win_lo, WIN ? window : 0, CAP ? softcap : 0.f, static_cast<hipStream_t>(stream));
   }
   // the tile DMA addresses a 64-row tile as scalar base + 32-bit lane offset: token strides must keep 64 rows inside 4 GiB
   if (kv_st < 0 || v_st < 0 || kv_st > (1 << 24) || v_st > (1 << 24)) return DTA_EUNSUPPORTED;
-  AttnP<WIN> p{};
+  AttnP<WIN, CAP> p{};
   if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
+  if constexpr (CAP) p.softcap = softcap;
   p.q = q; p.k = k; p.v = v; p.out = out; p.lse_w = lse; p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs;
   p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
   p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh; p.scale = scale;
@@ -1030,28 +1068,28 @@ static int attn_fwd(const void* q, const void* k, const void* v, void* out, floa
     p.hgroups = npair; p.head0 = 0;
     dim3 grid(nqt * Hkv * npair), block(512);
     if (head_dim == 64) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 64, WIN>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 64, WIN>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 64, WIN, CAP>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 64, WIN, CAP>), grid, block, 0, st, p);
     } else {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 128, WIN>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 128, WIN>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 128, WIN, CAP>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 128, WIN, CAP>), grid, block, 0, st, p);
     }
   }
   if (p.group % 2) {
     p.hgroups = 1; p.head0 = p.group - 1;
     dim3 grid(nqt * Hkv), block(256);
     if (head_dim == 64) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 64, WIN>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 64, WIN>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 64, WIN, CAP>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 64, WIN, CAP>), grid, block, 0, st, p);
     } else {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 128, WIN>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 128, WIN>), grid, block, 0, st, p);
+      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 128, WIN, CAP>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 128, WIN, CAP>), grid, block, 0, st, p);
     }
   }
   return DTA_LAUNCH_STATUS();
 }
 
-template <bool WIN>
+template <bool WIN, bool CAP = false>
 static int attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
                                     const float* lse, float* delta, void* dq, void* dk, void* dv,
                                     const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
@@ -1061,7 +1099,7 @@ static int attn_bwd(const void* q, const void* k, const void* v, const void* out
                                     int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
                                     float scale, int32_t dtype, int32_t accumulate, int32_t which,
                                     const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                                    const int32_t* win_lo, int32_t window, void* stream) {
+                                    const int32_t* win_lo, int32_t window, void* stream, float softcap = 0.f) {
   if (!q || !k || !v || !out || !dout || !lse || !delta || !dq || !dk || !dv || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
   if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
   if (dkv_units && (n_units <= 0 || n_splits < 0 || (n_splits > 0 && (!dkv_splits || !dkv_ws)))) return DTA_EINVAL;
@@ -1073,11 +1111,12 @@ static int attn_bwd(const void* q, const void* k, const void* v, const void* out
     DTA_REFUSE_IF_PRIOR_ERROR();
     return dta_attn_bwd_f32(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
                             q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which,
-                            win_lo, WIN ? window : 0, static_cast<hipStream_t>(stream));
+                            win_lo, WIN ? window : 0, CAP ? softcap : 0.f, static_cast<hipStream_t>(stream));
   }
   if (q_st < 0 || o_st < 0 || q_st > (1 << 24) || o_st > (1 << 24)) return DTA_EUNSUPPORTED;   // 64-row tile = scalar base + 32-bit lane offset
-  AttnP<WIN> p{};
+  AttnP<WIN, CAP> p{};
   if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
+  if constexpr (CAP) p.softcap = softcap;
   p.q = q; p.k = k; p.v = v; p.o = out; p.dout = dout; p.lse_r = lse; p.delta = delta; p.dq = dq; p.dk = dk; p.dv = dv;
   p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs; p.ktile_qend = ktile_qend;
   p.dkv_units = dkv_units; p.dkv_splits = dkv_splits; p.dkv_ws = dkv_ws;
@@ -1093,15 +1132,15 @@ static int attn_bwd(const void* q, const void* k, const void* v, const void* out
   const bool fin = ((which & 2) && !(which & 8)) || (which & 4);     // slab finalize: with the dK/dV launch unless bit3, or alone (bit2)
   const int ndkv = dkv_units ? n_units : nkt;
   const int npair = p.group / 2;                                     // as in the forward: head pairs, then the odd head alone
-  AttnP<WIN> pp = p, ps = p;
+  AttnP<WIN, CAP> pp = p, ps = p;
   pp.hgroups = npair; pp.head0 = 0; ps.hgroups = 1; ps.head0 = p.group - 1;
   const dim3 gqp(nqt * Hkv * (npair > 0 ? npair : 1)), gqs(nqt * Hkv);
   if (head_dim == 64) {
-    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 64, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-    else launch_bwd<DTA_F16, 64, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 64, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    else launch_bwd<DTA_F16, 64, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
   } else {
-    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 128, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-    else launch_bwd<DTA_F16, 128, WIN>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 128, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
+    else launch_bwd<DTA_F16, 128, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
   }
   return DTA_LAUNCH_STATUS();
 }
@@ -1168,6 +1207,49 @@ extern "C" int dta_tree_attn_bwd_win(const void* q, const void* k, const void* v
   return attn_bwd<true>(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
                         q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype, accumulate, which,
                         dkv_units, n_units, dkv_splits, n_splits, dkv_ws, win_lo, window, stream);
+}
+
+// Soft-capped scores (dta.h): softcap <= 0 is the _win call itself, bit for bit; a cap that is not finite is refused.
+extern "C" int dta_tree_attn_fwd_cap(const void* q, const void* k, const void* v, void* out, float* lse,
+                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, float softcap, void* stream) {
+  if (!(softcap > 0.f)) {
+    if (softcap != softcap) return DTA_EINVAL;
+    return dta_tree_attn_fwd_win(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh,
+                                 v_st, v_sh, o_st, o_sh, scale, dtype, win_lo, window, stream);
+  }
+  if (softcap > 3.0e38f) return DTA_EINVAL;
+  const int w = window_args(subtree_end, win_lo, window);
+  if (w < 0) return w;
+  return (w ? attn_fwd<true, true> : attn_fwd<false, true>)(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh,
+                                                            kv_st, kv_sh, v_st, v_sh, o_st, o_sh, scale, dtype, win_lo, window, stream, softcap);
+}
+
+extern "C" int dta_tree_attn_bwd_cap(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                                    const int32_t* ktile_qend,
+                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
+                                    float scale, int32_t dtype, int32_t accumulate, int32_t which,
+                                    const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
+                                    const int32_t* win_lo, int32_t window, float softcap, void* stream) {
+  if (!(softcap > 0.f)) {
+    if (softcap != softcap) return DTA_EINVAL;
+    return dta_tree_attn_bwd_win(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv,
+                                 head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype,
+                                 accumulate, which, dkv_units, n_units, dkv_splits, n_splits, dkv_ws, win_lo, window, stream);
+  }
+  if (softcap > 3.0e38f) return DTA_EINVAL;
+  const int w = window_args(subtree_end, win_lo, window);
+  if (w < 0) return w;
+  return (w ? attn_bwd<true, true> : attn_bwd<false, true>)(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk,
+                                                            q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
+                                                            dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype, accumulate, which,
+                                                            dkv_units, n_units, dkv_splits, n_splits, dkv_ws, win_lo, window, stream, softcap);
 }
 
 // Token-major convenience forms declared in dta.h: head stride = 128 elements, so head_dim 128 only (other head dims: the _ex forms).

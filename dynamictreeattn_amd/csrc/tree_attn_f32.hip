@@ -33,8 +33,26 @@ struct P32 {
 // sliding window: key s also needs s >= win_lo[row] (packed form) or q_offset + row - window + 1 (stack form, win_lo == NULL); a type of its
 // own so that the kernels without a window keep their arguments and code
 struct P32W : P32 { const int32_t* win_lo; int32_t window; };
-template <bool WIN> using P32T = typename std::conditional<WIN, P32W, P32>::type;
-template <bool WIN> __device__ __forceinline__ int win_lo_of(const P32T<WIN>& p, int row) {
+// soft-capped scores (softcap * tanh(scale q.k / softcap), capped before the mask): parameter types of their own again
+struct P32C : P32 { float softcap; };
+struct P32WC : P32W { float softcap; };
+template <bool WIN, bool CAP = false> using P32T = typename std::conditional<CAP, typename std::conditional<WIN, P32WC, P32C>::type,
+                                                                             typename std::conditional<WIN, P32W, P32>::type>::type;
+// t = tanh(x) and 1 - t^2 from a = 2 log2(e) x: with E = 2^min(a, 64) and r = 1 / (1 + E), t = 1 - 2r and 1 - t^2 = 4 E r^2 (no cancellation
+// in the derivative; E stays finite, so E r^2 is never inf * 0 and both saturate cleanly to +-1 and 0)
+__device__ __forceinline__ float cap_tanh32(float a, float* sech2) {
+  const float E = __builtin_amdgcn_exp2f(fminf(a, 64.f)), r = __builtin_amdgcn_rcpf(1.f + E);
+  *sech2 = 4.f * (E * r) * r;
+  return __builtin_fmaf(-2.f, r, 1.f);
+}
+// kt turns a raw q.k into tanh's argument (2 log2(e) scale / softcap); the log2-domain score factor c becomes softcap log2(e)
+template <class P> __device__ __forceinline__ float cap_of(const P& p) {
+  if constexpr (std::is_base_of<P32C, P>::value || std::is_base_of<P32WC, P>::value) return p.softcap; else return 0.f;
+}
+#define DTA_CAP_CONSTANTS                                                                                  \
+  const float c = (CAP ? cap_of(p) : p.scale) * LOG2E;                                                     \
+  [[maybe_unused]] const float kt = CAP ? 2.f * LOG2E * p.scale / cap_of(p) : 0.f;
+template <bool WIN, class P> __device__ __forceinline__ int win_lo_of(const P& p, int row) {
   if constexpr (WIN) { const int lo = p.q_offset + row - p.window + 1; return p.win_lo ? p.win_lo[row] : (lo > 0 ? lo : 0); }
   else return 0;
 }
@@ -71,7 +89,7 @@ struct Runs {
     return false;
   }
 };
-template <bool WIN> __device__ __forceinline__ Runs runs_of(const P32T<WIN>& p, int q0) {
+template <bool WIN, class P> __device__ __forceinline__ Runs runs_of(const P& p, int q0) {
   Runs r; r.runs = p.runs;
   if (p.runs) { const int qt = q0 / DTA_QTILE; r.ri = p.run_ptr[qt]; r.re = p.run_ptr[qt + 1]; r.k0 = r.kend = 0; }
   else { r.ri = 0; r.re = 1; r.k0 = 0; const int last = p.q_offset + (q0 + ROWS < p.Tq ? q0 + ROWS : p.Tq); r.kend = last < p.Tk ? last : p.Tk; }
@@ -79,8 +97,8 @@ template <bool WIN> __device__ __forceinline__ Runs runs_of(const P32T<WIN>& p, 
   return r;
 }
 
-template <int D, bool WIN>
-__global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32T<WIN> p) {
+template <int D, bool WIN, bool CAP>
+__global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32T<WIN, CAP> p) {
   constexpr int PD = D / 4;                                         // head dims per lane
   __shared__ __attribute__((aligned(16))) float Ks[ST * D];
   __shared__ __attribute__((aligned(16))) float Vs[ST * D];
@@ -94,7 +112,7 @@ __global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32T<WIN> p) {
 #pragma unroll
   for (int d = 0; d < PD; ++d) o[d] = 0.f;
   float m = -1e30f, l = 0.f;
-  const float c = p.scale * LOG2E;
+  DTA_CAP_CONSTANTS
   const float* kb = p.k + (int64_t)kvh * p.kv_sh; const float* vb = p.v + (int64_t)kvh * p.v_sh;
   Runs rn = runs_of<WIN>(p, q0);
   while (rn.next()) {
@@ -112,6 +130,7 @@ __global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32T<WIN> p) {
         s = quad_sum(s);
         const int key = k0 + j;
         if (key <= qidx && qidx < se_s[j] && key < p.Tk && (!WIN || key >= wlo)) {
+          if constexpr (CAP) { float unused; s = cap_tanh32(s * kt, &unused); }
           const float sc = s * c, mn = fmaxf(m, sc);
           const float alpha = __builtin_amdgcn_exp2f(m - mn), pj = __builtin_amdgcn_exp2f(sc - mn);
           const float* vr = Vs + j * D + PD * part;
@@ -132,8 +151,8 @@ __global__ __launch_bounds__(256) void tree_attn_fwd_f32_kernel(P32T<WIN> p) {
   }
 }
 
-template <int D, bool WIN>
-__global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32T<WIN> p) {
+template <int D, bool WIN, bool CAP>
+__global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32T<WIN, CAP> p) {
   constexpr int PD = D / 4;                                         // head dims per lane
   __shared__ __attribute__((aligned(16))) float Ks[ST * D];
   __shared__ __attribute__((aligned(16))) float Vs[ST * D];
@@ -155,7 +174,7 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32T<WIN> p) 
   delta = quad_sum(delta);
   const float lse2 = p.lse_r[(int64_t)hq * p.Tq + qrow_c];
   if (part == 0 && qrow < p.Tq) p.delta[(int64_t)hq * p.Tq + qrow] = -delta;
-  const float c = p.scale * LOG2E;
+  DTA_CAP_CONSTANTS
   const float* kb = p.k + (int64_t)kvh * p.kv_sh; const float* vb = p.v + (int64_t)kvh * p.v_sh;
   Runs rn = runs_of<WIN>(p, q0);
   while (rn.next()) {
@@ -173,7 +192,10 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32T<WIN> p) 
         s = quad_sum(s); dp = quad_sum(dp);
         const int key = k0 + j;
         if (key <= qidx && qidx < se_s[j] && key < p.Tk && (!WIN || key >= wlo)) {
-          const float ds = __builtin_amdgcn_exp2f(__builtin_fmaf(s, c, -lse2)) * (dp - delta);
+          float sech2 = 1.f;
+          if constexpr (CAP) s = cap_tanh32(s * kt, &sech2);
+          float ds = __builtin_amdgcn_exp2f(__builtin_fmaf(s, c, -lse2)) * (dp - delta);
+          if constexpr (CAP) ds *= sech2;
 #pragma unroll
           for (int d = 0; d < PD; ++d) dq[d] = __builtin_fmaf(ds, kr[d], dq[d]);
         }
@@ -189,8 +211,8 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dq_f32_kernel(P32T<WIN> p) 
 }
 
 // key-owned sweep: 64 keys of one kv head x every query that can see them x the heads of the GQA group
-template <int D, bool WIN>
-__global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32T<WIN> p) {
+template <int D, bool WIN, bool CAP>
+__global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32T<WIN, CAP> p) {
   constexpr int PD = D / 4;                                         // head dims per lane
   __shared__ __attribute__((aligned(16))) float Qs[ST * D];
   __shared__ __attribute__((aligned(16))) float Ds[ST * D];
@@ -204,7 +226,7 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32T<WIN> p)
 #pragma unroll
   for (int d = 0; d < PD; ++d) { dk[d] = 0.f; dv[d] = 0.f; }
   const int se = (p.subtree_end && key < p.Tk) ? p.subtree_end[key_c] : 0x7fffffff;
-  const float c = p.scale * LOG2E;
+  DTA_CAP_CONSTANTS
   // global query indices [t_begin, t_end) that may see a key of this block
   int t_begin = k0 > p.q_offset ? k0 : p.q_offset;
   int t_end = p.q_offset + p.Tq;
@@ -233,8 +255,11 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32T<WIN> p)
         s = quad_sum(s); dp = quad_sum(dp);
         const int t = t0 + i;
         if (key <= t && t < se && key < p.Tk && (!WIN || key >= win_lo_of<WIN>(p, t - p.q_offset))) {
+          float sech2 = 1.f;
+          if constexpr (CAP) s = cap_tanh32(s * kt, &sech2);
           const float pj = __builtin_amdgcn_exp2f(__builtin_fmaf(s, c, -lse_s[i]));
-          const float ds = pj * (dp + nd_s[i]);
+          float ds = pj * (dp + nd_s[i]);
+          if constexpr (CAP) ds *= sech2;
 #pragma unroll
           for (int d = 0; d < PD; ++d) { dv[d] = __builtin_fmaf(pj, dr[d], dv[d]); dk[d] = __builtin_fmaf(ds, qr[d], dk[d]); }
         }
@@ -260,32 +285,34 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32T<WIN> p)
 
 }  // namespace
 
-template <bool WIN>
+template <bool WIN, bool CAP>
 static int fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
                    const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                   float scale, const int32_t* win_lo, int32_t window, hipStream_t st) {
-  P32T<WIN> p{};
+                   float scale, const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
+  P32T<WIN, CAP> p{};
   if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
+  if constexpr (CAP) p.softcap = softcap;
   p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.out = (float*)out; p.lse_w = lse;
   p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs;
   p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
   p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh; p.scale = scale;
   const dim3 grid((Tq + ROWS - 1) / ROWS, Hq);
-  if (head_dim == 64) hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<64, WIN>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<128, WIN>), grid, dim3(256), 0, st, p);
+  if (head_dim == 64) hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<64, WIN, CAP>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<128, WIN, CAP>), grid, dim3(256), 0, st, p);
   return DTA_LAUNCH_STATUS();
 }
 
-template <bool WIN>
+template <bool WIN, bool CAP>
 static int bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
                    void* dq, void* dk, void* dv, const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs, const int32_t* ktile_qend,
                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which,
-                   const int32_t* win_lo, int32_t window, hipStream_t st) {
-  P32T<WIN> p{};
+                   const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
+  P32T<WIN, CAP> p{};
   if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
+  if constexpr (CAP) p.softcap = softcap;
   p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.o = (const float*)out; p.dout = (const float*)dout;
   p.lse_r = lse; p.delta = delta; p.dq = (float*)dq; p.dk = (float*)dk; p.dv = (float*)dv;
   p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs; p.ktile_qend = ktile_qend;
@@ -294,11 +321,11 @@ static int bwd_f32(const void* q, const void* k, const void* v, const void* out,
   p.dq_st = dq_st; p.dq_sh = dq_sh; p.dkv_st = dkv_st; p.dkv_sh = dkv_sh; p.scale = scale; p.accumulate = accumulate;
   const dim3 gq((Tq + ROWS - 1) / ROWS, Hq), gk((Tk + ROWS - 1) / ROWS, Hkv);
   if (head_dim == 64) {
-    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<64, WIN>), gq, dim3(256), 0, st, p);      // also writes -delta
-    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<64, WIN>), gk, dim3(256), 0, st, p);
+    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<64, WIN, CAP>), gq, dim3(256), 0, st, p);      // also writes -delta
+    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<64, WIN, CAP>), gk, dim3(256), 0, st, p);
   } else {
-    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<128, WIN>), gq, dim3(256), 0, st, p);
-    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<128, WIN>), gk, dim3(256), 0, st, p);
+    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<128, WIN, CAP>), gq, dim3(256), 0, st, p);
+    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<128, WIN, CAP>), gk, dim3(256), 0, st, p);
   }
   return DTA_LAUNCH_STATUS();                           // (which & 4, the slab finalize of the MFMA path, has nothing to do here)
 }
@@ -306,9 +333,10 @@ static int bwd_f32(const void* q, const void* k, const void* v, const void* out,
 int dta_attn_fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
                      const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
                      int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                     float scale, const int32_t* win_lo, int32_t window, hipStream_t st) {
-  return (window > 0 ? fwd_f32<true> : fwd_f32<false>)(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim,
-                                                       q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, scale, win_lo, window, st);
+                     float scale, const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
+  const auto f = softcap > 0.f ? (window > 0 ? fwd_f32<true, true> : fwd_f32<false, true>) : (window > 0 ? fwd_f32<true, false> : fwd_f32<false, false>);
+  return f(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim,
+           q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, scale, win_lo, window, softcap, st);
 }
 
 int dta_attn_bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
@@ -316,8 +344,9 @@ int dta_attn_bwd_f32(const void* q, const void* k, const void* v, const void* ou
                      int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
                      int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
                      int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which,
-                     const int32_t* win_lo, int32_t window, hipStream_t st) {
-  return (window > 0 ? bwd_f32<true> : bwd_f32<false>)(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk,
-                                                       q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
-                                                       dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which, win_lo, window, st);
+                     const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
+  const auto f = softcap > 0.f ? (window > 0 ? bwd_f32<true, true> : bwd_f32<false, true>) : (window > 0 ? bwd_f32<true, false> : bwd_f32<false, false>);
+  return f(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk,
+           q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
+           dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which, win_lo, window, softcap, st);
 }

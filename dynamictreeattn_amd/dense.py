@@ -8,7 +8,7 @@ from typing import List
 import torch
 
 from . import ops
-from .model import ensure_supported, head_weight, packed_hidden_states
+from .model import ensure_supported, final_softcap_of, head_weight, packed_hidden_states
 from .tree_training_engine import packed_logprob_entropy
 
 
@@ -17,7 +17,7 @@ def _one(model, ids: torch.Tensor, want_entropy: bool, checkpoint_layers: bool):
     depth = torch.arange(n, device=ids.device, dtype=torch.int32)
     h = packed_hidden_states(model, ids, depth, ops.stack_meta(0), checkpoint_layers)
     parent = depth.to(torch.long) - 1
-    return packed_logprob_entropy(h, head_weight(model), ids, parent, want_entropy)
+    return packed_logprob_entropy(h, head_weight(model), ids, parent, want_entropy, softcap=final_softcap_of(model))
 
 
 @torch.no_grad()

@@ -15,7 +15,7 @@ NAME = "dta_mi355x"
 
 
 def dta_attention_forward(module, query, key, value, attention_mask=None, dropout: float = 0.0, scaling=None,
-                          sliding_window=None, **kwargs):
+                          sliding_window=None, softcap=None, **kwargs):
     if query.shape[0] != 1:
         raise ValueError("dta_mi355x attention handles one sequence per call (batch 1), as the reference engine issues them")
     if dropout:
@@ -26,8 +26,9 @@ def dta_attention_forward(module, query, key, value, attention_mask=None, dropou
     k = key[0].transpose(0, 1)            # [S, Hkv, D] view
     v = value[0].transpose(0, 1)
     scale = D ** -0.5 if scaling is None else scaling
-    # sliding layers (HF: kv_idx > q_idx - sliding_window) are the stack form with a window
-    out = ops.tree_attention(q, k, v, ops.stack_meta(S - B, sliding_window or 0), scale)      # [B, Hq, D] contiguous
+    # sliding layers (HF: kv_idx > q_idx - sliding_window) are the stack form with a window; Gemma-2's attention passes its
+    # attn_logit_softcapping as `softcap` (and query_pre_attn_scalar ** -0.5 as `scaling`): the capped kernels
+    out = ops.tree_attention(q, k, v, ops.stack_meta(S - B, sliding_window or 0), scale, softcap or 0.0)      # [B, Hq, D] contiguous
     return out.unsqueeze(0), None
 
 

@@ -7,7 +7,7 @@ torch.  `Qwen3TreeLM` mirrors the HF module/parameter tree (``model.embed_tokens
 ``model.layers.N.self_attn.q_proj.weight`` …, tied head) so that
 
 * gradients compare name by name with grad/Qwen3-0.6B-TB-vs-DB-bf16.txt (310 tensors), and
-* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral ``*ForCausalLM`` by duck typing —
+* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral/Gemma-2 ``*ForCausalLM`` by duck typing —
   its own ``nn.Parameter`` objects are used, so ``param.grad`` lands where the training loop expects.
 """
 from __future__ import annotations
@@ -182,12 +182,52 @@ _SOFTCAP_SINK_FIELDS = ("attn_logit_softcapping", "final_logit_softcapping", "at
                         "attention_sinks", "use_attention_sinks", "num_sink_tokens")
 
 
+def is_gemma2(config) -> bool:
+    """Gemma-2 arithmetic (soft-capped attention and final logits, GeGLU, the four `1 + w` sandwich norms, the scaled embedding and
+    query_pre_attn_scalar) is keyed on config.model_type == "gemma2" and on nothing else: the same fields on any other configuration
+    stay refused by check_supported."""
+    return getattr(config, "model_type", None) == "gemma2"
+
+
+def gemma2_arith(config):
+    """(attention scale, attention soft-cap, final-logit soft-cap) of a Gemma-2 configuration; a cap of None or 0 is no cap (0.0)."""
+    c = config
+    return float(c.query_pre_attn_scalar) ** -0.5, float(getattr(c, "attn_logit_softcapping", None) or 0.0), \
+        float(getattr(c, "final_logit_softcapping", None) or 0.0)
+
+
+def final_softcap_of(model) -> float:
+    """The final-logit soft-cap the LM-head kernels apply for `model` (0.0: none)."""
+    return gemma2_arith(model.config)[2] if is_gemma2(model.config) else 0.0
+
+
+def _check_gemma2(c) -> None:
+    act = getattr(c, "hidden_activation", None)
+    if act != "gelu_pytorch_tanh":
+        raise ValueError(f"config.hidden_activation = {act!r} is not supported for gemma2: the MLP kernel computes gelu_pytorch_tanh(gate) * up")
+    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    if D not in (64, 128):
+        raise ValueError(f"config.head_dim = {D} is not supported: the attention kernels cover head_dim 64 and 128 (Gemma-2-27B; the 2B / 9B use 256)")
+    qs = getattr(c, "query_pre_attn_scalar", None)
+    if qs is None or not float(qs) > 0:
+        raise ValueError(f"config.query_pre_attn_scalar = {qs!r} is not supported: gemma2 attention scales by query_pre_attn_scalar ** -0.5")
+    for f in ("attn_logit_softcapping", "final_logit_softcapping"):
+        v = getattr(c, f, None)
+        if v is not None and not (0.0 <= float(v) < float("inf")):
+            raise ValueError(f"config.{f} = {v!r} is not supported: a soft-cap is a finite number >= 0 (None or 0: no cap)")
+
+
 def check_supported(config, training: bool = True) -> None:
     """Refuses, with a ValueError that names the field, a configuration whose arithmetic the engine cannot honour - it would run,
     and compute something else: a rope_type other than default / linear / llama3 / yarn, rope_parameters nested per layer type,
     partial rotary embedding, an activation other than silu, attention dropout on a model in training mode, router jitter noise,
-    attention soft-capping or sinks."""
+    attention soft-capping or sinks.  A Gemma-2 configuration (is_gemma2) is the exception for soft-capping and the activation: its
+    attn_logit_softcapping / final_logit_softcapping and hidden_activation == "gelu_pytorch_tanh" are honoured; any other activation,
+    a head_dim other than 64 / 128 and a missing or non-positive query_pre_attn_scalar are refused."""
     c = config
+    gemma = is_gemma2(c)
+    if gemma:
+        _check_gemma2(c)
     rp = _rope_dict(c)
     if rp["rope_type"] not in ops.ROPE_TYPES:
         raise ValueError(f"config.rope_parameters['rope_type'] = {rp['rope_type']!r} is not supported ({' / '.join(ops.ROPE_TYPES)})")
@@ -195,13 +235,15 @@ def check_supported(config, training: bool = True) -> None:
     if prf is not None and float(prf) != 1.0:
         raise ValueError(f"config partial_rotary_factor = {prf} is not supported: the rotary kernels rotate the whole head")
     act = getattr(c, "hidden_act", None)
-    if act is not None and act != "silu":
+    if not gemma and act is not None and act != "silu":         # (Gemma2Config keeps hidden_act as a legacy field; hidden_activation decides)
         raise ValueError(f"config.hidden_act = {act!r} is not supported: the MLP kernels compute silu(gate) * up")
     if training and float(getattr(c, "attention_dropout", 0.0) or 0.0) > 0:
         raise ValueError(f"config.attention_dropout = {c.attention_dropout} on a model in training mode is not supported (model.eval(), or set it to 0)")
     if float(getattr(c, "router_jitter_noise", 0.0) or 0.0) > 0:
         raise ValueError(f"config.router_jitter_noise = {c.router_jitter_noise} is not supported")
     for f in _SOFTCAP_SINK_FIELDS:
+        if gemma and f in ("attn_logit_softcapping", "final_logit_softcapping"):
+            continue
         if getattr(c, f, None):
             raise ValueError(f"config.{f} = {getattr(c, f)!r} is not supported: the attention kernels have neither soft-capping nor sinks")
 
@@ -304,6 +346,22 @@ def _project(x, *mods):
     return ops.lora_linear(x, w, bias, adapters)
 
 
+def _gemma2_layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
+    """One Gemma-2 decoder layer in the (residual stream, pending update) convention of _layer_forward: sandwich norms - the attention
+    and MLP branch outputs are normalised before they join the residual stream - all with weight offset 1, no q/k norm, no bias, and
+    GeGLU.  `attn` carries the layer's scale (query_pre_attn_scalar ** -0.5), soft-cap and window."""
+    T = res.shape[0]
+    a, m = layer.self_attn, layer.mlp
+    res, h = ops.add_rms_norm(res, delta, layer.input_layernorm.weight, eps, 1.0)
+    qkv = _project(h, a.q_proj, a.k_proj, a.v_proj).view(T, Hq + 2 * Hkv, D)
+    q, k, v = ops.qkv_prep(qkv, None, None, cos_sin, eps, Hq, Hkv)
+    o = attn(q, k, v)
+    delta = ops.rms_norm(_project(o.reshape(T, Hq * D), a.o_proj), layer.post_attention_layernorm.weight, eps, 1.0)
+    res, h = ops.add_rms_norm(res, delta, layer.pre_feedforward_layernorm.weight, eps, 1.0)
+    act = ops.geglu_fused(_project(h, m.gate_proj, m.up_proj))
+    return res, ops.rms_norm(_project(act, m.down_proj), layer.post_feedforward_layernorm.weight, eps, 1.0)
+
+
 def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     """One decoder layer over the packed rows.  The hidden state enters as (residual stream, pending update)
     so that each residual add is fused into the RMSNorm that follows it.  hipBLASLt GEMMs through torch;
@@ -330,6 +388,28 @@ def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
         return res, ops.moe_mlp(h, g.weight, m.experts.gate_up_proj, m.experts.down_proj, g.top_k, norm)
     act = ops.swiglu_fused(_project(h, m.gate_proj, m.up_proj))
     return res, _project(act, m.down_proj)                                                # LlamaConfig.mlp_bias
+
+
+class _ScaleRows(torch.autograd.Function):
+    """x * s with s a Python number rounded to x's dtype first (HF Gemma2: hidden_states * tensor(sqrt(hidden_size), dtype=model dtype))."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        ctx.s = float(torch.tensor(s, dtype=x.dtype))
+        return x * ctx.s
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.s, None
+
+
+def attn_args_of(model):
+    """Per-model keyword arguments of ops.tree_attention / ops.stack_attention: Gemma-2's scale and attention soft-cap; {} otherwise
+    (scale head_dim ** -0.5, no cap)."""
+    if not is_gemma2(model.config):
+        return {}
+    scale, cap, _ = gemma2_arith(model.config)
+    return {"scale": scale, "softcap": cap}
 
 
 class _LayerRecompute(torch.autograd.Function):
@@ -385,15 +465,20 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
     Hq, Hkv, D, eps, rope = _cfg_of(model)
     metas = layer_metas(meta, _windows_of(model), meta_for_window) if attn_of_layer is None else None
     body = model.model
+    gemma = is_gemma2(model.config)
+    layer_fwd = _gemma2_layer_forward if gemma else _layer_forward
+    akw = attn_args_of(model)
     res, delta = (embed(tokens) if embed is not None else F.embedding(tokens, body.embed_tokens.weight)), None
+    if gemma:            # the normaliser, rounded to the model dtype as HF does; on the embed= path too, so the fp32 sink gets the scaled gradient
+        res = _ScaleRows.apply(res, float(model.config.hidden_size) ** 0.5)
     cos_sin = ops.rope_cos_sin(depth, D, rope)
     per_layer = tokens.shape[0] * Hq * (D * res.element_size() + 4)             # out + lse of one layer
     n_full = full_layers if isinstance(full_layers, int) else 1
     for li, layer in enumerate(body.layers):
-        attn = attn_of_layer(li) if attn_of_layer is not None else (lambda m_: lambda q, k, v: ops.tree_attention(q, k, v, m_))(metas[li])
+        attn = attn_of_layer(li) if attn_of_layer is not None else (lambda m_: lambda q, k, v: ops.tree_attention(q, k, v, m_, **akw))(metas[li])
         if li == 0 and callable(full_layers) and checkpoint_layers and torch.is_grad_enabled() and res.is_cuda:
             m0 = torch.cuda.memory_allocated(res.device)
-            res, delta = _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)
+            res, delta = layer_fwd(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)
             n_full = int(full_layers(torch.cuda.memory_allocated(res.device) - m0))
             continue
         # (a layer whose input carries no gradient - the first one behind a frozen embedding, LoRA - runs in full: a recomputed layer
@@ -402,13 +487,13 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
             keep = attn_of_layer is None and attn_keep_bytes >= per_layer
             if keep:
                 attn_keep_bytes -= per_layer
-            fn = (lambda layer_, attn_: lambda r_, d_: _layer_forward(layer_, r_, d_, cos_sin, attn_, Hq, Hkv, D, eps))(layer, attn)
+            fn = (lambda layer_, attn_: lambda r_, d_: layer_fwd(layer_, r_, d_, cos_sin, attn_, Hq, Hkv, D, eps))(layer, attn)
             res, delta = _LayerRecompute.apply(fn, keep, res, delta)
         else:
-            res, delta = _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)
+            res, delta = layer_fwd(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)
     if kept_out is not None:
         kept_out.append(n_full if checkpoint_layers else len(body.layers))
-    return ops.add_rms_norm(res, delta, body.norm.weight, eps)[1]
+    return ops.add_rms_norm(res, delta, body.norm.weight, eps, *((1.0,) if gemma else ()))[1]
 
 
 def head_weight(model) -> torch.Tensor:

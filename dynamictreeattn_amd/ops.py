@@ -142,8 +142,18 @@ def _strides(t):
     return t.stride(0), t.stride(1)
 
 
-def attn_fwd_raw(q, k, v, meta: TreeAttnMeta, scale: float):
+def _cap_of(softcap) -> float:
+    """A model's soft-cap as the kernels take it: None / 0 = no cap (the uncapped kernels); negative, NaN or infinite is refused."""
+    c = float(softcap or 0.0)
+    if not (0.0 <= c < float("inf")):
+        raise ValueError(f"softcap must be a finite number >= 0 (got {softcap!r})")
+    return c
+
+
+def attn_fwd_raw(q, k, v, meta: TreeAttnMeta, scale: float, softcap: float = 0.0):
+    """softcap > 0: scores softcap * tanh(scale q.k / softcap), capped before the visibility mask (dta_tree_attn_fwd_cap)."""
     _require_cuda(q, k, v)
+    softcap = _cap_of(softcap)
     Tq, Hq, D = q.shape
     Tk, Hkv, _ = k.shape
     out = torch.empty((Tq, Hq, D), dtype=q.dtype, device=q.device)
@@ -151,10 +161,13 @@ def attn_fwd_raw(q, k, v, meta: TreeAttnMeta, scale: float):
     (qs, qh), (ks, kh), (vs, vh), (os_, oh) = _strides(q), _strides(k), _strides(v), _strides(out)
     tm = KernelTimer.active
     win = (ptr(meta.win_lo), int(meta.window)) if meta.window > 0 else ()
+    entry = "dta_tree_attn_fwd_win" if win else "dta_tree_attn_fwd_ex"
+    if softcap > 0:
+        entry, win = "dta_tree_attn_fwd_cap", (win or (None, 0)) + (softcap,)
     with _on(q, k, v, meta.subtree_end, meta.runs) as stream:
         if tm is not None:
             ev = tm.span("fwd"); ev[0].record()
-        st = getattr(lib(), "dta_tree_attn_fwd_win" if win else "dta_tree_attn_fwd_ex")(
+        st = getattr(lib(), entry)(
             ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs),
             Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, float(scale), _DT[q.dtype], *win, stream)
         if tm is not None:
@@ -163,8 +176,9 @@ def attn_fwd_raw(q, k, v, meta: TreeAttnMeta, scale: float):
     return out, lse, k, v
 
 
-def attn_bwd_raw(q, k, v, out, dout, lse, meta: TreeAttnMeta, scale: float, dk=None, dv=None, accumulate=False, dq=None):
-    """dq/dk/dv may be given as output buffers (row stride, head stride; dk and dv with the SAME strides)."""
+def attn_bwd_raw(q, k, v, out, dout, lse, meta: TreeAttnMeta, scale: float, dk=None, dv=None, accumulate=False, dq=None, softcap: float = 0.0):
+    """dq/dk/dv may be given as output buffers (row stride, head stride; dk and dv with the SAME strides).  softcap: the forward's."""
+    softcap = _cap_of(softcap)
     Tq, Hq, D = q.shape
     Tk, Hkv, _ = k.shape
     if dout.stride() != out.stride():
@@ -183,9 +197,12 @@ def attn_bwd_raw(q, k, v, out, dout, lse, meta: TreeAttnMeta, scale: float, dk=N
     ws = torch.empty((meta.n_slabs, Hkv, 2, packing.KTILE, D), dtype=torch.float32, device=q.device) if (units is not None and meta.n_slabs) else None
 
     win = (ptr(meta.win_lo), int(meta.window)) if meta.window > 0 else ()
+    entry = "dta_tree_attn_bwd_win" if win else "dta_tree_attn_bwd_ex"
+    if softcap > 0:
+        entry, win = "dta_tree_attn_bwd_cap", (win or (None, 0)) + (softcap,)
 
     def launch(which, stream):
-        return getattr(lib(), "dta_tree_attn_bwd_win" if win else "dta_tree_attn_bwd_ex")(
+        return getattr(lib(), entry)(
             ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
             ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs), ptr(meta.ktile_qend),
             Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, dqs, dqh, dks, dkh,
@@ -208,7 +225,9 @@ class AttentionTape:
     """Keeps the attention outputs (out, lse) of a no-grad forward so that a later recomputation of the same layer
     (per-layer activation recomputation in the engine) does not run the forward attention kernel again: in
     "record" mode `tree_attention` appends what it produced, in "replay" mode it takes the next entry instead of
-    launching the kernel.  q, k, v come from the recomputed projections either way (the backward needs them)."""
+    launching the kernel.  q, k, v come from the recomputed projections either way (the backward needs them), and so do the call's scale
+    and soft-cap: the replayed call's own arguments go into its backward, so a capped layer whose forward kernel was skipped still runs the
+    capped backward (an entry also records the cap it was produced under, and a replay under another cap is refused)."""
     current = None
 
     def __init__(self, mode: str, items=None):
@@ -226,18 +245,20 @@ class AttentionTape:
 
 class _TreeAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, meta: TreeAttnMeta, scale: float):
+    def forward(ctx, q, k, v, meta: TreeAttnMeta, scale: float, softcap: float = 0.0):
         tape = AttentionTape.current
         if tape is not None and tape.mode == "replay" and tape.pos < len(tape.items):
-            out, lse = tape.items[tape.pos]; tape.pos += 1
+            out, lse, *cap = tape.items[tape.pos]; tape.pos += 1
             if out.shape != q.shape:
                 raise RuntimeError("attention replay: recorded output does not match the recomputed query")
+            if cap and cap[0] != softcap:
+                raise RuntimeError(f"attention replay: recorded under softcap {cap[0]}, replayed under {softcap}")
         else:
-            out, lse, k, v = attn_fwd_raw(q, k, v, meta, scale)
+            out, lse, k, v = attn_fwd_raw(q, k, v, meta, scale, softcap)
             if tape is not None and tape.mode == "record":
-                tape.items.append((out, lse))
+                tape.items.append((out, lse, softcap))
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.meta, ctx.scale = meta, scale
+        ctx.meta, ctx.scale, ctx.softcap = meta, scale, softcap
         return out
 
     @staticmethod
@@ -249,10 +270,10 @@ class _TreeAttention(torch.autograd.Function):
             # backward then transforms dq and dk in place and hands the buffer on - no gather of dv (0.65 ms per step at tau2 size)
             fused = torch.empty((q.shape[0], Hq + 2 * Hkv, q.shape[2]), dtype=q.dtype, device=q.device)
             dq, dk, dv = fused[:, :Hq], fused[:, Hq:Hq + Hkv], fused[:, Hq + Hkv:]
-            attn_bwd_raw(q, k, v, out, dout, lse, ctx.meta, ctx.scale, dk=dk, dv=dv, dq=dq)
+            attn_bwd_raw(q, k, v, out, dout, lse, ctx.meta, ctx.scale, dk=dk, dv=dv, dq=dq, softcap=ctx.softcap)
         else:
-            dq, dk, dv = attn_bwd_raw(q, k, v, out, dout, lse, ctx.meta, ctx.scale)
-        return dq, dk, dv, None, None
+            dq, dk, dv = attn_bwd_raw(q, k, v, out, dout, lse, ctx.meta, ctx.scale, softcap=ctx.softcap)
+        return dq, dk, dv, None, None, None
 
 
 class _StackAttention(torch.autograd.Function):
@@ -264,14 +285,14 @@ class _StackAttention(torch.autograd.Function):
     contributions of every already-popped descendant plus the block's own."""
 
     @staticmethod
-    def forward(ctx, q, k_new, v_new, kst, vst, gk, gv, start, scale, window):
+    def forward(ctx, q, k_new, v_new, kst, vst, gk, gv, start, scale, window, softcap=0.0):
         B = q.shape[0]
         end = start + B
         kst[start:end].copy_(k_new); vst[start:end].copy_(v_new)
         meta = stack_meta(start, window)
-        out, lse, _, _ = attn_fwd_raw(q, kst[:end], vst[:end], meta, scale)
+        out, lse, _, _ = attn_fwd_raw(q, kst[:end], vst[:end], meta, scale, softcap)
         ctx.save_for_backward(q, out, lse)
-        ctx.stacks, ctx.meta, ctx.scale, ctx.span = (kst, vst, gk, gv), meta, scale, (start, end)
+        ctx.stacks, ctx.meta, ctx.scale, ctx.span, ctx.softcap = (kst, vst, gk, gv), meta, scale, (start, end), softcap
         return out
 
     @staticmethod
@@ -279,26 +300,30 @@ class _StackAttention(torch.autograd.Function):
         q, out, lse = ctx.saved_tensors
         kst, vst, gk, gv = ctx.stacks
         start, end = ctx.span
-        dq, _, _ = attn_bwd_raw(q, kst[:end], vst[:end], out, dout, lse, ctx.meta, ctx.scale, dk=gk[:end], dv=gv[:end], accumulate=2)
-        return dq, gk[start:end].to(q.dtype), gv[start:end].to(q.dtype), None, None, None, None, None, None, None
+        dq, _, _ = attn_bwd_raw(q, kst[:end], vst[:end], out, dout, lse, ctx.meta, ctx.scale, dk=gk[:end], dv=gv[:end], accumulate=2,
+                                softcap=ctx.softcap)
+        return dq, gk[start:end].to(q.dtype), gv[start:end].to(q.dtype), None, None, None, None, None, None, None, None
 
 
-def stack_attention(q, k_new, v_new, kst, vst, gk, gv, start: int, scale: Optional[float] = None, window: int = 0):
+def stack_attention(q, k_new, v_new, kst, vst, gk, gv, start: int, scale: Optional[float] = None, window: int = 0, softcap: float = 0.0):
     """q [B,Hq,D], k_new/v_new [B,Hkv,D] at stack positions start..start+B-1; kst/vst [cap,Hkv,D] (model dtype),
     gk/gv [cap,Hkv,D] fp32 grad stacks (may be None under no_grad) -> out [B,Hq,D] (D = head_dim, 64 or 128).
-    window > 0: sliding window, row t sees stack rows (t - window, t] (the whole stack is kept either way)."""
+    window > 0: sliding window, row t sees stack rows (t - window, t] (the whole stack is kept either way).
+    softcap > 0: scores softcap * tanh(scale q.k / softcap), capped before the mask."""
     if q.dtype not in _DT:
         raise TypeError("stack_attention supports bf16 / f16 / f32 (got %s)" % q.dtype)
     scale = q.shape[-1] ** -0.5 if scale is None else scale
-    return _StackAttention.apply(q, k_new, v_new, kst, vst, gk, gv, start, scale, int(window))
+    return _StackAttention.apply(q, k_new, v_new, kst, vst, gk, gv, start, scale, int(window), _cap_of(softcap))
 
 
-def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, meta: TreeAttnMeta, scale: Optional[float] = None) -> torch.Tensor:
-    """q [T,Hq,D], k/v [T,Hkv,D] packed in DFS pre-order -> out [T,Hq,D] (D = head_dim, 64 or 128).  Differentiable."""
+def tree_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, meta: TreeAttnMeta, scale: Optional[float] = None,
+                   softcap: float = 0.0) -> torch.Tensor:
+    """q [T,Hq,D], k/v [T,Hkv,D] packed in DFS pre-order -> out [T,Hq,D] (D = head_dim, 64 or 128).  Differentiable.
+    softcap > 0: scores softcap * tanh(scale q.k / softcap), capped before the visibility mask (Gemma-2)."""
     if q.dtype not in _DT:
         raise TypeError("tree_attention supports bf16 / f16 / f32 (got %s)" % q.dtype)
     scale = q.shape[-1] ** -0.5 if scale is None else scale
-    return _TreeAttention.apply(q, k, v, meta, scale)
+    return _TreeAttention.apply(q, k, v, meta, scale, _cap_of(softcap))
 
 
 def stack_meta(start: int, window: int = 0) -> TreeAttnMeta:
@@ -359,7 +384,12 @@ def window_meta(meta: TreeAttnMeta, plan: packing.SegmentPlan, depth: torch.Tens
 # --------------------------------------------------------------------------------------------------
 # LM head + log-prob / entropy over packed rows (HIP statistics kernels around hipBLASLt GEMMs)
 # --------------------------------------------------------------------------------------------------
-def logprob_entropy_fwd_raw(logits, labels, want_entropy=True, temperature=1.0, extra_ptr=None, extra_labels=None, extra_out=None):
+def _lp_entry(name: str, softcap: float):
+    """(entry point, trailing arguments) of a log-prob kernel call: the _cap form with the cap when softcap > 0."""
+    return (name + "_cap", (float(softcap),)) if softcap > 0 else (name, ())
+
+
+def logprob_entropy_fwd_raw(logits, labels, want_entropy=True, temperature=1.0, extra_ptr=None, extra_labels=None, extra_out=None, softcap=0.0):
     """logits [R,V] bf16/f16/f32 (row-contiguous) -> (lse, entropy|None, logprob|None) fp32 [R].
     `extra_ptr` int32 [R+1] / `extra_labels` int64 [F]: further labels per row (CSR, absolute indices); their
     log-probs are written to `extra_out` fp32 [F] (rows of this call only)."""
@@ -367,29 +397,33 @@ def logprob_entropy_fwd_raw(logits, labels, want_entropy=True, temperature=1.0, 
     lse = torch.empty(R, dtype=torch.float32, device=logits.device)
     ent = torch.empty_like(lse) if want_entropy else None
     lp = torch.empty_like(lse) if labels is not None else None
-    _launch("dta_logprob_entropy_fwd", (logits, labels, extra_ptr, extra_labels, extra_out),
+    entry, cap = _lp_entry("dta_logprob_entropy_fwd", softcap)
+    _launch(entry, (logits, labels, extra_ptr, extra_labels, extra_out),
             ptr(logits), ptr(labels), ptr(extra_ptr), ptr(extra_labels), ptr(lse), ptr(ent), ptr(lp), ptr(extra_out),
-            R, V, logits.stride(0), float(temperature), _DT_LOGITS[logits.dtype], nbytes=R * V * logits.element_size())
+            R, V, logits.stride(0), float(temperature), _DT_LOGITS[logits.dtype], *cap, nbytes=R * V * logits.element_size())
     return lse, ent, lp
 
 
-def logprob_entropy_bwd_raw(logits, labels, lse, ent, g_lp, g_ent, temperature=1.0, extra_ptr=None, extra_labels=None, g_extra=None, out=None):
+def logprob_entropy_bwd_raw(logits, labels, lse, ent, g_lp, g_ent, temperature=1.0, extra_ptr=None, extra_labels=None, g_extra=None, out=None,
+                            softcap=0.0):
     """dLoss/dlogits into `out` (None: IN PLACE over `logits`)."""
     R, V = logits.shape
     out = logits if out is None else out
-    _launch("dta_logprob_entropy_bwd", (logits, out, labels, extra_ptr, extra_labels, lse, g_lp, g_extra, g_ent),
+    entry, cap = _lp_entry("dta_logprob_entropy_bwd", softcap)
+    _launch(entry, (logits, out, labels, extra_ptr, extra_labels, lse, g_lp, g_extra, g_ent),
             ptr(logits), ptr(out), ptr(labels), ptr(extra_ptr), ptr(extra_labels), ptr(lse), ptr(ent), ptr(g_lp), ptr(g_extra), ptr(g_ent),
-            R, V, logits.stride(0), out.stride(0), float(temperature), _DT_LOGITS[logits.dtype], nbytes=2 * R * V * logits.element_size())
+            R, V, logits.stride(0), out.stride(0), float(temperature), _DT_LOGITS[logits.dtype], *cap, nbytes=2 * R * V * logits.element_size())
     return out
 
 
-def logprob_entropy_shard_stats_raw(logits, labels_local, temperature=1.0, extra_ptr=None, extra_labels=None, extra_out=None):
+def logprob_entropy_shard_stats_raw(logits, labels_local, temperature=1.0, extra_ptr=None, extra_labels=None, extra_out=None, softcap=0.0):
     """Per-shard statistics [R,4] = {m, s, t, picked} (log2 domain) of logits [R, V/tp]; see dta.h.  Extra picks -> raw x/T or 0."""
     R, V = logits.shape
     stats = torch.empty((R, 4), dtype=torch.float32, device=logits.device)
-    _launch("dta_logprob_entropy_shard_stats", (logits, labels_local, extra_ptr, extra_labels, extra_out),
+    entry, cap = _lp_entry("dta_logprob_entropy_shard_stats", softcap)
+    _launch(entry, (logits, labels_local, extra_ptr, extra_labels, extra_out),
             ptr(logits), ptr(labels_local), ptr(extra_ptr), ptr(extra_labels), ptr(stats), ptr(extra_out),
-            R, V, logits.stride(0), float(temperature), _DT_LOGITS[logits.dtype], nbytes=R * V * logits.element_size())
+            R, V, logits.stride(0), float(temperature), _DT_LOGITS[logits.dtype], *cap, nbytes=R * V * logits.element_size())
     return stats
 
 
@@ -434,7 +468,7 @@ class _HeadRows(torch.autograd.Function):
     chunk and the hidden-state gradient is summed across the group while the weight-gradient GEMM runs."""
 
     @staticmethod
-    def forward(ctx, h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes, tp_group, vocab_offset):
+    def forward(ctx, h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes, tp_group, vocab_offset, softcap=0.0):
         T = h.shape[0]
         dev = h.device
         V = W.shape[0]
@@ -456,11 +490,11 @@ class _HeadRows(torch.autograd.Function):
             logits = torch.mm(h[a:b], W.t())
             if tp_group is None:
                 l, e, p = logprob_entropy_fwd_raw(logits, next_loc[a:b], want_entropy, 1.0,
-                                                  xp[a:b + 1] if F_ else None, fork_loc if F_ else None, lp_fork if F_ else None)
+                                                  xp[a:b + 1] if F_ else None, fork_loc if F_ else None, lp_fork if F_ else None, softcap)
             else:
                 f0, f1 = (0, F_) if keep else (fork_bounds[ci], fork_bounds[ci + 1])
                 stats = logprob_entropy_shard_stats_raw(logits, next_loc[a:b], 1.0, xp[a:b + 1] if F_ else None, fork_loc if F_ else None,
-                                                        lp_fork if F_ else None)
+                                                        lp_fork if F_ else None, softcap)
                 l, e, picked, raw = combine_shard_stats(stats, lp_fork[f0:f1], tp_group)
                 p = picked - l
                 if f1 > f0:
@@ -471,7 +505,7 @@ class _HeadRows(torch.autograd.Function):
             if keep:
                 kept = logits
         ctx.save_for_backward(h, W, next_loc, fork_loc, lse, ent if ent is not None else lse, xp if F_ else lse)
-        ctx.kept, ctx.chunk, ctx.want_entropy, ctx.tp_group, ctx.has_forks = kept, chunk, want_entropy, tp_group, bool(F_)
+        ctx.kept, ctx.chunk, ctx.want_entropy, ctx.tp_group, ctx.has_forks, ctx.softcap = kept, chunk, want_entropy, tp_group, bool(F_), softcap
         return lp_next, lp_fork, (ent if want_entropy else lse.new_zeros(0))
 
     @staticmethod
@@ -492,7 +526,7 @@ class _HeadRows(torch.autograd.Function):
             logits = kept if kept is not None else torch.mm(h[a:b], W.t())
             logprob_entropy_bwd_raw(logits, next_loc[a:b], lse[a:b], ent[a:b] if ctx.want_entropy else None, g_next[a:b],
                                     g_ent[a:b] if ctx.want_entropy else None, 1.0,
-                                    xp[a:b + 1] if ctx.has_forks else None, fork_loc if ctx.has_forks else None, g_fork)
+                                    xp[a:b + 1] if ctx.has_forks else None, fork_loc if ctx.has_forks else None, g_fork, softcap=ctx.softcap)
             if W.dtype in (torch.bfloat16, torch.float16) and (b - a) >= 4096 and W.shape[0] % 8 == 0 and W.shape[1] % 8 == 0:
                 torch.mm(logits, _TransposedWeights.get(W).t(), out=dh[a:b])        # contraction index contiguous in both operands (see _dgrad)
             else:
@@ -511,13 +545,23 @@ class _HeadRows(torch.autograd.Function):
         ctx.kept = None
         for w in pending:
             w.wait()
-        return dh, (dW.to(W.dtype) if need_w else None), None, None, None, None, None, None, None, None, None, None
+        return dh, (dW.to(W.dtype) if need_w else None), None, None, None, None, None, None, None, None, None, None, None
 
 
-def lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes=None, tp_group=None, vocab_offset=0):
+MAX_CAPPED_PICKS_PER_ROW = 2048     # dta.h: extra picks of one row in the in-place backward of the capped log-prob kernel
+
+
+def lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes=None, tp_group=None, vocab_offset=0,
+                 softcap: float = 0.0, max_picks_per_row: Optional[int] = None):
     """See _HeadRows.  `fork_ptr` int32 [T+1]: CSR of the forks over the rows; `fork_rows` int64 [F] their rows (ascending);
-    `fork_bounds[c] .. fork_bounds[c+1]` = the forks whose row lies in chunk c (host list; used by the vocabulary-split path)."""
+    `fork_bounds[c] .. fork_bounds[c+1]` = the forks whose row lies in chunk c (host list; used by the vocabulary-split path).
+    softcap > 0: final-logit soft-capping - every statistic is taken on softcap * tanh(logit / softcap), inside the kernels (the
+    [chunk, V] logits get no extra pass).  `max_picks_per_row`: the largest number of forks on one row, from the caller's host tables;
+    it is checked against the capped kernel's limit (None: unknown - beyond the limit the kernel writes NaN for the pick, dta.h)."""
     _require_cuda(h, W)
+    softcap = _cap_of(softcap)
+    if softcap > 0 and max_picks_per_row is not None and max_picks_per_row > MAX_CAPPED_PICKS_PER_ROW:
+        raise ValueError(f"a row with {max_picks_per_row} fork picks exceeds the capped log-prob kernel's {MAX_CAPPED_PICKS_PER_ROW} per row")
     if keep_bytes is None:
         keep_bytes = free_hbm(h.device) // 4
     if tp_group is not None:
@@ -528,7 +572,7 @@ def lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, wan
         dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=tp_group)
         keep_bytes = (1 << 62) if int(ok.item()) else 0
     lp_next, lp_fork, ent = _HeadRows.apply(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes,
-                                            tp_group, vocab_offset)
+                                            tp_group, vocab_offset, softcap)
     return lp_next, lp_fork, (ent if want_entropy else None)
 
 
@@ -608,10 +652,11 @@ def logprob_entropy(logits2d, labels1d, temperature=1.0, want_entropy=True, tp_g
 # Fused decoder-layer row kernels (RMSNorm, head-norm + RoPE, SwiGLU)
 # --------------------------------------------------------------------------------------------------
 class _RMSNorm(torch.autograd.Function):
-    """(x_out, y) = (x + delta, rmsnorm(x + delta) * w); delta may be None (then x_out is x itself)."""
+    """(x_out, y) = (x + delta, rmsnorm(x + delta) * w); delta may be None (then x_out is x itself).  w_offset != 0 (Gemma: 1):
+    y = rmsnorm(x + delta) * (w_offset + w) with the sum formed in fp32 inside the kernel and one rounding (dta_rmsnorm_fwd_off)."""
 
     @staticmethod
-    def forward(ctx, x, delta, w, eps):
+    def forward(ctx, x, delta, w, eps, w_offset=0.0):
         _require_cuda(x, w)
         x2 = x.contiguous().view(-1, x.shape[-1])
         R, H = x2.shape
@@ -622,11 +667,12 @@ class _RMSNorm(torch.autograd.Function):
             xo = torch.empty_like(x2)
         else:
             d2, xo = None, None
-        _launch("dta_rmsnorm_fwd", (x2, d2, w), ptr(x2), ptr(d2), ptr(w), ptr(xo), ptr(y), ptr(rstd), R, H, float(eps), _DT[x.dtype],
-                nbytes=R * H * x2.element_size() * (4 if delta is not None else 2))
+        off = (float(w_offset),) if w_offset else ()
+        _launch("dta_rmsnorm_fwd_off" if off else "dta_rmsnorm_fwd", (x2, d2, w), ptr(x2), ptr(d2), ptr(w), ptr(xo), ptr(y), ptr(rstd), R, H, float(eps),
+                *off, _DT[x.dtype], nbytes=R * H * x2.element_size() * (4 if delta is not None else 2))
         xin = xo if xo is not None else x2
         ctx.save_for_backward(xin, w, rstd)
-        ctx.has_delta = delta is not None
+        ctx.has_delta, ctx.off = delta is not None, off
         return xin.view(x.shape), y.view(x.shape)
 
     @staticmethod
@@ -638,19 +684,19 @@ class _RMSNorm(torch.autograd.Function):
         dx = torch.empty_like(x2)
         need_w = ctx.needs_input_grad[2]          # a frozen norm weight is still read (dx depends on it) but gets no partials and no sum
         part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, dtype=torch.float32, device=x2.device) if need_w else None
-        _launch("dta_rmsnorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(rstd), ptr(dx), ptr(part), R, H, _DT[x2.dtype],
-                nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
+        _launch("dta_rmsnorm_bwd_off" if ctx.off else "dta_rmsnorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(rstd), ptr(dx),
+                ptr(part), R, H, *ctx.off, _DT[x2.dtype], nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
         dx = dx.view(dy.shape)
-        return dx, (dx if ctx.has_delta else None), (sum_slabs(part, w.dtype) if need_w else None), None
+        return dx, (dx if ctx.has_delta else None), (sum_slabs(part, w.dtype) if need_w else None), None, None
 
 
-def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
-    return _RMSNorm.apply(x, None, w, eps)[1]
+def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float, w_offset: float = 0.0) -> torch.Tensor:
+    return _RMSNorm.apply(x, None, w, eps, float(w_offset))[1]
 
 
-def add_rms_norm(x: torch.Tensor, delta: Optional[torch.Tensor], w: torch.Tensor, eps: float):
-    """Residual-stream update fused with the following RMSNorm: returns (x + delta, rmsnorm(x + delta) * w)."""
-    return _RMSNorm.apply(x, delta, w, eps)
+def add_rms_norm(x: torch.Tensor, delta: Optional[torch.Tensor], w: torch.Tensor, eps: float, w_offset: float = 0.0):
+    """Residual-stream update fused with the following RMSNorm: returns (x + delta, rmsnorm(x + delta) * (w_offset + w))."""
+    return _RMSNorm.apply(x, delta, w, eps, float(w_offset))
 
 
 class _QKNormRope(torch.autograd.Function):
@@ -839,10 +885,11 @@ def rope_cos_sin(depth: torch.Tensor, D: int, rope) -> torch.Tensor:
 
 class _SwiGLU(torch.autograd.Function):
     """y = silu(gate) * up.  `gu` is either the fused [rows, 2C] projection output (gate | up) or None with
-    separate contiguous gate/up."""
+    separate contiguous gate/up.  `kernel`: "dta_swiglu", or "dta_geglu" for y = gelu_tanh(gate) * up (same layouts)."""
 
     @staticmethod
-    def forward(ctx, gu, g, u):
+    def forward(ctx, gu, g, u, kernel="dta_swiglu"):
+        ctx.kernel = kernel
         if gu is not None:
             _require_cuda(gu)
             gu = gu if gu.stride(-1) == 1 and gu.dim() == 2 else gu.contiguous().view(-1, gu.shape[-1])
@@ -854,7 +901,7 @@ class _SwiGLU(torch.autograd.Function):
             C, ld = g.shape[1], g.shape[1]
         rows = g.shape[0]
         y = torch.empty((rows, C), dtype=g.dtype, device=g.device)
-        _launch("dta_swiglu_fwd", (g, u), ptr(g), ptr(u), ptr(y), rows, C, ld, _DT[g.dtype], nbytes=3 * rows * C * g.element_size())
+        _launch(ctx.kernel + "_fwd", (g, u), ptr(g), ptr(u), ptr(y), rows, C, ld, _DT[g.dtype], nbytes=3 * rows * C * g.element_size())
         ctx.save_for_backward(g, u)
         ctx.fused, ctx.ld = gu is not None, ld
         return y
@@ -869,18 +916,28 @@ class _SwiGLU(torch.autograd.Function):
             dg, du, ldg = dgu[:, :C], dgu[:, C:], 2 * C
         else:
             dg, du, ldg = torch.empty_like(g), torch.empty_like(u), C
-        _launch("dta_swiglu_bwd", (g, u, dy), ptr(g), ptr(u), ptr(dy), ptr(dg), ptr(du), rows, C, ctx.ld, ldg, _DT[g.dtype],
+        _launch(ctx.kernel + "_bwd", (g, u, dy), ptr(g), ptr(u), ptr(dy), ptr(dg), ptr(du), rows, C, ctx.ld, ldg, _DT[g.dtype],
                 nbytes=5 * rows * C * g.element_size())
-        return (dgu, None, None) if ctx.fused else (None, dg, du)
+        return (dgu, None, None, None) if ctx.fused else (None, dg, du, None)
 
 
 def swiglu(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
-    return _SwiGLU.apply(None, g, u)
+    return _SwiGLU.apply(None, g, u, "dta_swiglu")
 
 
 def swiglu_fused(gu: torch.Tensor) -> torch.Tensor:
     """gu [rows, 2C] = (gate | up) of one fused projection GEMM -> silu(gate) * up  [rows, C]."""
-    return _SwiGLU.apply(gu, None, None)
+    return _SwiGLU.apply(gu, None, None, "dta_swiglu")
+
+
+def geglu(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """gelu_tanh(g) * u (HF's gelu_pytorch_tanh; Gemma) on the dta_geglu kernels; the layouts of swiglu."""
+    return _SwiGLU.apply(None, g, u, "dta_geglu")
+
+
+def geglu_fused(gu: torch.Tensor) -> torch.Tensor:
+    """gu [rows, 2C] = (gate | up) of one fused projection GEMM -> gelu_tanh(gate) * up  [rows, C]."""
+    return _SwiGLU.apply(gu, None, None, "dta_geglu")
 
 
 class weight_cache:

@@ -31,7 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .model import _cfg_of, _windows_of, head_weight, packed_hidden_states
+from .model import _cfg_of, _windows_of, attn_args_of, final_softcap_of, head_weight, packed_hidden_states
 from .tree_training_engine import sum_loss_terms
 from .trie import pop_block_starts
 
@@ -154,9 +154,10 @@ class StackWalk:
     # ------------------------------------------------------------------------------------------
     def _attn_of_layer(self, start: int, with_grad: bool):
         windows = _windows_of(self.model)          # sliding layers: the stack form with the window (the whole stack is kept)
+        akw = attn_args_of(self.model)             # Gemma-2: the attention scale and soft-cap
 
         def of(l):
-            win = {"window": windows[l]} if windows[l] > 0 else {}
+            win = dict(akw, window=windows[l]) if windows[l] > 0 else akw
             return lambda q, k, v: ops.stack_attention(q, k, v, self.kst[l], self.vst[l], self.gk[l] if with_grad else None,
                                                        self.gv[l] if with_grad else None, start, **win)
         return of
@@ -198,6 +199,9 @@ class StackWalk:
             Vp = W.shape[0] // tp
             W = W[rk * Vp:(rk + 1) * Vp]
             kw = dict(tp_group=self.tp_group, vocab_offset=rk * Vp)
+        cap = final_softcap_of(self.model)
+        if cap:
+            kw.update(softcap=cap, max_picks_per_row=int(np.bincount(rows_np).max()) if F_ else 0)
         lp_next, lp_fork, ent = ops.lm_head_rows(h, W, labels, fork_ptr, fork_tok, fork_rows, bounds, True, self.head_chunk, **kw)
         return lp_next, lp_fork, ent, g_fork
 

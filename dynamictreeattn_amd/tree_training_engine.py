@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .model import ensure_supported, head_weight, is_moe_layer, moe_geometry, packed_hidden_states
+from .model import ensure_supported, final_softcap_of, head_weight, is_gemma2, is_moe_layer, moe_geometry, packed_hidden_states
 from .trie import pop_block_starts
 
 __all__ = ["TreeTrainingEngine", "_get_forkpos", "packed_logprob_entropy"]
@@ -63,14 +63,15 @@ def fork_tables_host(fork_child, fork_parent, T: int):
 
 def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tensor, parent: torch.Tensor,
                            want_entropy: bool, chunk: int = 2048, fork_child: Optional[np.ndarray] = None,
-                           fork_parent: Optional[np.ndarray] = None, tp_group=None, fork_dev=None):
+                           fork_parent: Optional[np.ndarray] = None, tp_group=None, fork_dev=None, softcap: float = 0.0):
     """lp[t] = log softmax(h[parent[t]] Wᵀ)[tokens[t]] (0 for roots), ent[t] = H(softmax(h[t] Wᵀ)); fp32.
     The arithmetic (vocab_parallel.py:13-27; call sites tte:190-193, 256-261, 361-372) runs in
     `ops.lm_head_rows`: hipBLASLt logits GEMM per row chunk + the HIP statistics kernels; at most one
     [chunk, V] block of fp32-free, model-dtype logits per chunk is ever alive.
     `fork_child`/`fork_parent`: host lists of the tokens whose parent is not the preceding packed token (sorted by parent);
     `fork_dev` = their device copies (child int64, parent int64, CSR ptr int32 [T+1]) when the caller uploaded them with the
-    plan tables — otherwise they are uploaded here (a blocking copy in the middle of the step)."""
+    plan tables — otherwise they are uploaded here (a blocking copy in the middle of the step).
+    `softcap` > 0: final-logit soft-capping (config.final_logit_softcapping of a Gemma-2 model), applied inside the statistics kernels."""
     T = h.shape[0]
     dev = h.device
     if fork_child is None:
@@ -87,6 +88,9 @@ def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tenso
         fork_ptr = None
     nxt = torch.cat([tokens[1:], tokens.new_zeros(1)])
     bounds = np.searchsorted(np.asarray(fork_parent), np.arange(0, T + chunk, chunk)).tolist()
+    cap_kw = {}
+    if softcap:
+        cap_kw = dict(softcap=softcap, max_picks_per_row=int(np.bincount(np.asarray(fork_parent, np.int64)).max()) if nF else 0)
     if tp_group is not None:
         # vocabulary split across the group (BASELINE config 4; vocab_parallel.py:128-130): this rank multiplies by
         # its contiguous slice of the (tied) head weight only; labels stay global
@@ -95,9 +99,9 @@ def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tenso
         Vp = W.shape[0] // tp
         assert Vp * tp == W.shape[0], "vocabulary must divide by the tensor-parallel size"
         lp_next, lp_fork, ent = ops.lm_head_rows(h, W[rk * Vp:(rk + 1) * Vp], nxt, fork_ptr, ftok, fp_dev, bounds, want_entropy, chunk,
-                                                 tp_group=tp_group, vocab_offset=rk * Vp)
+                                                 tp_group=tp_group, vocab_offset=rk * Vp, **cap_kw)
     else:
-        lp_next, lp_fork, ent = ops.lm_head_rows(h, W, nxt, fork_ptr, ftok, fp_dev, bounds, want_entropy, chunk)
+        lp_next, lp_fork, ent = ops.lm_head_rows(h, W, nxt, fork_ptr, ftok, fp_dev, bounds, want_entropy, chunk, **cap_kw)
     chain = torch.zeros(T, dtype=torch.bool, device=dev)           # lp_next[r] = log p(tokens[r+1] | node r)
     chain[1:] = parent[1:] == torch.arange(0, T - 1, device=dev, dtype=parent.dtype)
     lp = torch.cat([lp_next.new_zeros(1), lp_next[:-1]]) * chain
@@ -287,7 +291,8 @@ class TreeTrainingEngine:
         mlp = sum(_mlp_elems_per_token(c, l) for l in range(L)) / max(L, 1)
         from . import lora
         ranks = lora.rank_elems_per_token(model)        # LoRA: x·Aᵀ of every adapted projection is kept for the backward (Σr elements)
-        return int(2 * (10 * c.hidden_size + mlp + ranks + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
+        norms = 2 * c.hidden_size if is_gemma2(c) else 0          # Gemma-2: the outputs of the two post-branch norms are kept too
+        return int(2 * (10 * c.hidden_size + norms + mlp + ranks + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
 
     def _budget(self) -> Optional[int]:
         if self.memory_budget_bytes is not None:
@@ -359,7 +364,7 @@ class TreeTrainingEngine:
             parent = torch.arange(-1, T - 1, device=self.device, dtype=torch.int32)
             with torch.enable_grad():
                 h = packed_hidden_states(one, tokens, depth, None, False, 0, ident)
-                lp, ent = packed_logprob_entropy(h, head_weight(model), tokens, parent, True, self.head_chunk)
+                lp, ent = packed_logprob_entropy(h, head_weight(model), tokens, parent, True, self.head_chunk, softcap=final_softcap_of(model))
                 (lp.sum() + ent.sum()).backward()
         for p in model.parameters():
             p.grad = None
@@ -466,7 +471,7 @@ class TreeTrainingEngine:
         packed = self._pack(token_trie)
         h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, False, meta_for_window=packed.for_window)
         lp, _ = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, False, self.head_chunk,
-                                       packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev)
+                                       packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model))
         for i, attach_list in enumerate(token_trie.attach_lists):
             lp_path = lp[packed.paths[i][1:]]
             for attachment, length in attach_list:
@@ -512,7 +517,7 @@ class TreeTrainingEngine:
         if ckpt and kept:
             self.last_mode = "packed" if kept[0] >= self.n_layers else f"packed+recompute[{self.n_layers - kept[0]}/{self.n_layers}]"
         lp, ent = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, True, max(chunk, 1),
-                                         packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev)
+                                         packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model))
         total, leaves = self._path_losses(packed, token_trie, lp, ent, loss_fn)
         if total is None:
             return 0.0

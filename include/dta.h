@@ -187,6 +187,36 @@ int dta_tree_attn_bwd_win(const void* q, const void* k, const void* v, const voi
                           float scale, int32_t dtype, int32_t accumulate, int32_t which,
                           const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
                           const int32_t* win_lo, int32_t window, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * Soft-capped attention (Gemma-2's attn_logit_softcapping).  With z_ij = scale * (q_i . k_j), c = softcap and t_ij = tanh(z_ij / c):
+ *   forward   s_ij = c * t_ij.  The cap comes FIRST, then the visibility mask (ancestor test, window), then the softmax - the order of
+ *             HF's eager_attention_forward.  lse is the log-sum-exp of the CAPPED scores (log2 domain, as in the other forms).
+ *   backward  t is recomputed from Q.K^T as S is; p = exp(s - lse) and dS = p * (dP - delta) as without a cap;
+ *             dz = dS * (1 - t^2);  dq = scale * dz K,  dk = scale * dz^T Q;  dV and delta are unchanged.
+ * tanh is computed in fp32 as 1 - 2 / (1 + 2^(2 log2(e) z / c)): it saturates to +-1 for large |z / c| (no inf / inf) and its absolute
+ * error is a few 2^-24, i.e. the capped score is off by the order of c * 2^-24.
+ * Arguments: those of the _win forms (packed tries, the stack form, windows, head_dim 64 / 128, bf16 / f16 / f32, accumulate 0 / 1 / 2;
+ * the dK/dV sweep stays atomic-free and bitwise reproducible) plus `softcap`.  softcap <= 0: no cap - the call IS the _win call, bit for
+ * bit.  DTA_EINVAL: a softcap that is NaN or infinite, and what the _win forms refuse. */
+int dta_tree_attn_fwd_cap(const void* q, const void* k, const void* v, void* out, float* lse,
+                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
+                          int64_t v_stride_t, int64_t v_stride_h,
+                          int64_t o_stride_t, int64_t o_stride_h, float scale, int32_t dtype,
+                          const int32_t* win_lo, int32_t window, float softcap, void* stream);
+int dta_tree_attn_bwd_cap(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                          const float* lse, float* delta, void* dq, void* dk, void* dv,
+                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
+                          const int32_t* ktile_qend,
+                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
+                          int64_t v_stride_t, int64_t v_stride_h,
+                          int64_t o_stride_t, int64_t o_stride_h, int64_t dq_stride_t, int64_t dq_stride_h,
+                          int64_t dkv_stride_t, int64_t dkv_stride_h,
+                          float scale, int32_t dtype, int32_t accumulate, int32_t which,
+                          const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
+                          const int32_t* win_lo, int32_t window, float softcap, void* stream);
 /* out_win_lo[t] for the T packed tokens of a trie: the packed index of t's ancestor at depth max(0, depth[t] - window + 1).  depth[T] as
  * written by dta_preorder_meta; seg_off[M+1], seg_depth0[M], parent_of_seg[M] as passed to it.  Walks up segments (binary search over
  * seg_off per hop), not tokens.  window > 0 (DTA_EINVAL otherwise). */
@@ -219,6 +249,26 @@ int dta_logprob_entropy_bwd(const void* logits, void* dlogits, const int64_t* la
                             const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
                             int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype, void* stream);
 
+/* Final-logit soft-capping (Gemma-2's final_logit_softcapping): the three entries above on x' = c * tanh(x / c), c = softcap.  The cap is
+ * applied to the raw logit as it is loaded (no second pass over the [R, V] logits); lse, entropy, the label pick and the extra picks
+ * are all statistics of x', and the temperature divides x'.  The backward reads each raw x once (in place: dlogits == logits) and
+ * multiplies the gradient with respect to x' by 1 - tanh^2(x / c) before the store.  The cap is elementwise and comes before the
+ * shard statistics, so the cross-rank combine is unchanged.  softcap <= 0: the plain entry, bit for bit; NaN / infinite: DTA_EINVAL.
+ * In-place backward under a cap: at most 2048 extra picks per row (their 1 - tanh^2 factors are taken before the row is
+ * overwritten and held in LDS); the gradient element of a pick beyond that is written as NaN, so the overrun cannot pass for a
+ * result.  An out-of-place call has no such limit. */
+int dta_logprob_entropy_fwd_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+                                float* lse, float* entropy, float* logprob, float* extra_logprob,
+                                int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream);
+int dta_logprob_entropy_shard_stats_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+                                        float* stats, float* extra_picked,
+                                        int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream);
+int dta_logprob_entropy_bwd_cap(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
+                                const float* lse, const float* entropy,
+                                const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
+                                int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype,
+                                float softcap, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused row kernels of the decoder layer (HBM-bound; bf16/f16 storage, fp32 math).  They restate the
  * arithmetic of the third-party Qwen3 layers the reference calls (tree_training_engine.py:182-186,
@@ -234,6 +284,14 @@ int dta_rmsnorm_bwd_blocks(int32_t R);   /* rows of the dw_partial workspace [bl
                                           * dw_partial NULL (here and in dta_qk_norm_rope_bwd): a frozen weight - dx only, no partials written */
 int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
                     int32_t R, int32_t H, int32_t dtype, void* stream);
+/* RMSNorm with a weight offset (Gemma: offset 1): y = cast(x * rsqrt(mean(x^2)+eps) * (w_offset + w)) - the offset is added to w in fp32
+ * inside the kernel and the product is rounded ONCE (a 1 + w formed in bf16 would lose the low bits of w).  The fused residual add and
+ * every other argument are those of dta_rmsnorm_fwd / _bwd; dw_partial is unchanged (d(w_offset + w)/dw = 1).  w_offset == 0: the plain
+ * entries, bit for bit. */
+int dta_rmsnorm_fwd_off(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
+                        int32_t R, int32_t H, float eps, float w_offset, int32_t dtype, void* stream);
+int dta_rmsnorm_bwd_off(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
+                        int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream);
 /* head_dim D = 128 or 64.  x: [T, NH, D] with token stride x_stride_t; cos_sin: float [T, D] = {cos[D/2], sin[D/2]} of the token's
  * depth (rotate-half pairs element i with i + D/2); y: [T, NH, D] contiguous; w (head-norm weight [D]) may be NULL = RoPE only. */
 int dta_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,
@@ -248,6 +306,11 @@ int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, con
 int dta_swiglu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream);
 int dta_swiglu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void* dup,
                    int64_t rows, int32_t cols, int64_t ld, int64_t ld_grad, int32_t dtype, void* stream);
+/* GeGLU (Gemma): y = cast(gelu_tanh(g)) * u with gelu_tanh(g) = 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))), HF's gelu_pytorch_tanh.
+ * Arguments and layouts of dta_swiglu_fwd / _bwd. */
+int dta_geglu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream);
+int dta_geglu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void* dup,
+                  int64_t rows, int32_t cols, int64_t ld, int64_t ld_grad, int32_t dtype, void* stream);
 
 /* out[c][r] = in[r][c]: `rows` x `cols` elements of `elem_size` bytes (2: bf16 / f16, 4: f32), `ld_in` / `ld_out` elements between rows
  * (`rows`, `cols`, `ld_in` and `ld_out` multiples of 16 / elem_size: 8 for 2-byte types, 4 for f32; pointers 16-byte aligned).  HBM-bound (one read + one write).  Used for transposed copies of the projection and
