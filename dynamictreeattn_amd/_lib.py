@@ -16,14 +16,13 @@ _PROTOS = {
     "dta_lcp_adjacent": ([_vp, _vp, _vp, _i32, _vp, _vp, _vp], C.c_int),
     "dta_leafize": ([_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "dta_preorder_meta": ([_vp] * 8 + [_i32, _i32] + [_vp] * 4 + [_vp], C.c_int),
-    "dta_tree_attn_fwd": ([_vp] * 8 + [_i32] * 6 + [_i64] * 3 + [_f32, _i32, _vp], C.c_int),
-    "dta_tree_attn_bwd": ([_vp] * 14 + [_i32] * 6 + [_i64] * 5 + [_f32, _i32, _i32, _vp], C.c_int),
-    "dta_tree_attn_fwd_ex": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32, _vp], C.c_int),
-    "dta_tree_attn_bwd_ex": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp], C.c_int),
-    "dta_tree_attn_fwd_win": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32, _vp, _i32, _vp], C.c_int),
-    "dta_tree_attn_bwd_win": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp], C.c_int),
-    "dta_tree_attn_fwd_cap": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32, _vp, _i32, _f32, _vp], C.c_int),
-    "dta_tree_attn_bwd_cap": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp], C.c_int),
+    # q k v out lse subtree_end run_ptr runs | Tq Tk q_offset Hq Hkv head_dim | q k v o (token, head) strides | scale dtype |
+    # win_lo window softcap stream
+    "dta_tree_attn_fwd": ([_vp] * 8 + [_i32] * 6 + [_i64] * 8 + [_f32, _i32] + [_vp, _i32, _f32, _vp], C.c_int),
+    # q k v out dout lse delta dq dk dv subtree_end run_ptr runs ktile_qend | sizes | q k v o dq dkv strides | scale dtype accumulate which |
+    # dkv_units n_units dkv_splits n_splits dkv_ws | win_lo window softcap stream
+    "dta_tree_attn_bwd": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32] + [_vp, _i32, _vp, _i32, _vp]
+                          + [_vp, _i32, _f32, _vp], C.c_int),
     "dta_window_lo": ([_vp] * 4 + [_i32, _i32, _i32, _vp, _vp], C.c_int),
     "dta_logprob_entropy_fwd": ([_vp] * 8 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_logprob_entropy_shard_stats": ([_vp] * 6 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),

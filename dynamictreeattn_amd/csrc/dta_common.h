@@ -2,6 +2,7 @@
 #ifndef DTA_COMMON_H
 #define DTA_COMMON_H
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "../../include/dta.h"
 
 // A HIP error that is ALREADY pending when an entry point is called (an earlier asynchronous kernel fault, or a failed
@@ -11,17 +12,35 @@
 // status of THIS launch (configuration errors: invalid grid, too much LDS, no code object for the device ...)
 #define DTA_LAUNCH_STATUS() (hipGetLastError() == hipSuccess ? DTA_OK : DTA_ELAUNCH)
 
-// fp32 tree attention (tree_attn_f32.hip, head_dim 64 or 128): reached through dta_tree_attn_fwd_ex / dta_tree_attn_bwd_ex with dtype DTA_F32, and through the _win forms
-// (window > 0: the sliding-window kernels; win_lo as in dta_tree_attn_fwd_win) and the _cap forms (softcap > 0: the soft-capped kernels)
-int dta_attn_fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
-                     const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                     float scale, const int32_t* win_lo, int32_t window, float softcap, hipStream_t st);
-int dta_attn_bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
-                     void* dq, void* dk, void* dv, const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs, const int32_t* ktile_qend,
-                     int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                     int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which,
-                     const int32_t* win_lo, int32_t window, float softcap, hipStream_t st);
+// The arguments of one dta_tree_attn_fwd / dta_tree_attn_bwd call (include/dta.h), under the field names of the kernel parameter structs.
+// Host side only: the entry fills it once, tree_attn.hip validates it once, and the launch code copies its fields into the parameter
+// struct of the chosen kernel form - it is never a kernel argument itself.  The forward leaves the backward fields null
+// (out / lse_w are the forward's outputs; o / lse_r the same buffers as the backward's inputs).
+struct DtaAttnArgs {
+  const void *q, *k, *v, *o, *dout;
+  void *out, *dq, *dk, *dv;
+  float* lse_w; const float* lse_r; float* delta;
+  const int32_t *subtree_end, *run_ptr, *runs, *ktile_qend;
+  const int32_t *dkv_units, *dkv_splits; float* dkv_ws;
+  int32_t n_units, n_splits;
+  int32_t Tq, Tk, q_offset, Hq, Hkv, head_dim;
+  int64_t q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh;
+  float scale; int32_t dtype, accumulate, which;
+  const int32_t* win_lo; int32_t window; float softcap;
+  hipStream_t stream;
+};
+
+// The kernel form of a call, chosen once: f(WIN, CAP) with std::bool_constant arguments.  window <= 0 / softcap <= 0 select the kernels
+// compiled without those terms.
+template <class F> inline void dta_attn_form(const DtaAttnArgs& a, F&& f) {
+  using Y = std::true_type; using N = std::false_type;
+  if (a.softcap > 0.f) { if (a.window > 0) f(Y{}, Y{}); else f(N{}, Y{}); }
+  else { if (a.window > 0) f(Y{}, N{}); else f(N{}, N{}); }
+}
+
+// fp32 tree attention (tree_attn_f32.hip, head_dim 64 or 128): what dta_tree_attn_fwd / dta_tree_attn_bwd launch for dtype DTA_F32, after
+// their argument checks
+int dta_attn_fwd_f32(const DtaAttnArgs& a);
+int dta_attn_bwd_f32(const DtaAttnArgs& a);
 
 #endif

@@ -25,8 +25,8 @@
 // tile-end barrier, so a tile's DMA has the whole compute phase of the previous tile to land.
 //
 // Lane maps used here were verified on hardware by tests/micro/mfma_layout_probe.hip.
-// The round-1 ablation switches (-DDTA_ABL) and the retired 4-wave dK/dV kernel live in scripts/diag/ (not built); the A/B forward
-// forms 3 and 4 were removed (last present in b0d42b7).
+// The round-1 ablation switches (-DDTA_ABL) and the retired 4-wave dK/dV kernel were frozen copies of this file (last
+// present in 4de734c); the A/B forward forms 3 and 4 were removed (last present in b0d42b7).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -83,11 +83,11 @@ struct AttnParams {
   int64_t q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh;
   float scale; int32_t accumulate; int32_t ktile;
 };
-// Sliding-window form (dta_tree_attn_fwd_win / _bwd_win): key s must also be >= the query row's lower bound, win_lo[row] (packed form)
+// Sliding-window form (window > 0): key s must also be >= the query row's lower bound, win_lo[row] (packed form)
 // or q_offset + row - window + 1 (stack form, win_lo == NULL).  A parameter type of its own: the kernels without a window (WIN = false)
 // keep the parent's kernel arguments, and every WIN term below folds away at compile time, so their device code is unchanged.
 struct AttnParamsW : AttnParams { const int32_t* win_lo; int32_t window; };
-// Soft-capped form (dta_tree_attn_fwd_cap / _bwd_cap): the score is softcap * tanh(scale q.k / softcap), capped BEFORE the visibility
+// Soft-capped form (softcap > 0): the score is softcap * tanh(scale q.k / softcap), capped BEFORE the visibility
 // mask.  Again parameter types of their own (with and without a window), so that the CAP = false kernels keep their arguments and code.
 struct AttnParamsC : AttnParams { float softcap; };
 struct AttnParamsWC : AttnParamsW { float softcap; };
@@ -1018,249 +1018,129 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_finalize_kernel(AttnPar
   }
 }
 
-// the backward launches of one (dtype, head_dim): dQ (head pairs, then the odd head alone), dK/dV, and the slab finalize
-template <int DT, int DH, bool WIN, bool CAP>
-void launch_bwd(const AttnP<WIN, CAP>& p, const AttnP<WIN, CAP>& pp, const AttnP<WIN, CAP>& ps, int npair, dim3 gqp, dim3 gqs, int ndkv, bool fin, int n_splits,
-                int which, hipStream_t st) {
-  if (which & 1) {
-    if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 2, DH, WIN, CAP>), gqp, dim3(512), 0, st, pp);
-    if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 1, DH, WIN, CAP>), gqs, dim3(256), 0, st, ps);
-  }
-  if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DT, DH, WIN, CAP>), dim3(ndkv * p.Hkv), dim3(512), 0, st, p);
-  if (fin && p.dkv_units && n_splits > 0)   // the slab sums do not depend on visibility: one finalize kernel for both forms
-    hipLaunchKernelGGL((tree_attn_bwd_dkv_finalize_kernel<DT, DH>), dim3(n_splits * p.Hkv, FIN_SPLIT), dim3(256), 0, st, static_cast<const AttnParams&>(p));
-}
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
-
-template <bool WIN, bool CAP = false>
-static int attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, void* stream, float softcap = 0.f) {
-  if (!q || !k || !v || !out || !lse || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
-  if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
-  if ((head_dim != 128 && head_dim != 64) || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32)) return DTA_EUNSUPPORTED;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (q_st | q_sh | kv_st | kv_sh | v_st | v_sh | o_st | o_sh) % 8 != 0) return DTA_EALIGN;
-  if (dtype == DTA_F32) {                                    // fp32 models: the plain-FMA correctness path (tree_attn_f32.hip)
-    DTA_REFUSE_IF_PRIOR_ERROR();
-    return dta_attn_fwd_f32(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
-                            scale, win_lo, WIN ? window : 0, CAP ? softcap : 0.f, static_cast<hipStream_t>(stream));
-  }
-  // the tile DMA addresses a 64-row tile as scalar base + 32-bit lane offset: token strides must keep 64 rows inside 4 GiB
-  if (kv_st < 0 || v_st < 0 || kv_st > (1 << 24) || v_st > (1 << 24)) return DTA_EUNSUPPORTED;
+// kernel parameters of the chosen form from the call's arguments (the forward's backward fields are null); hgroups / head0 are set per launch
+template <bool WIN, bool CAP> AttnP<WIN, CAP> kernel_params(const DtaAttnArgs& a) {
   AttnP<WIN, CAP> p{};
-  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
-  if constexpr (CAP) p.softcap = softcap;
-  p.q = q; p.k = k; p.v = v; p.out = out; p.lse_w = lse; p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs;
-  p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
-  p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh; p.scale = scale;
-  const int nqt = (Tq + DTA_QTILE - 1) / DTA_QTILE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
+  if constexpr (WIN) { p.win_lo = a.win_lo; p.window = a.window; }
+  if constexpr (CAP) p.softcap = a.softcap;
+  p.q = a.q; p.k = a.k; p.v = a.v; p.o = a.o; p.dout = a.dout; p.out = a.out; p.dq = a.dq; p.dk = a.dk; p.dv = a.dv;
+  p.lse_w = a.lse_w; p.lse_r = a.lse_r; p.delta = a.delta;
+  p.subtree_end = a.subtree_end; p.run_ptr = a.run_ptr; p.runs = a.runs; p.ktile_qend = a.ktile_qend;
+  p.dkv_units = a.dkv_units; p.dkv_splits = a.dkv_splits; p.dkv_ws = a.dkv_ws;
+  p.Tq = a.Tq; p.Tk = a.Tk; p.q_offset = a.q_offset; p.Hq = a.Hq; p.Hkv = a.Hkv; p.group = a.Hq / a.Hkv;
+  p.q_st = a.q_st; p.q_sh = a.q_sh; p.kv_st = a.kv_st; p.kv_sh = a.kv_sh; p.v_st = a.v_st; p.v_sh = a.v_sh; p.o_st = a.o_st; p.o_sh = a.o_sh;
+  p.dq_st = a.dq_st; p.dq_sh = a.dq_sh; p.dkv_st = a.dkv_st; p.dkv_sh = a.dkv_sh; p.scale = a.scale; p.accumulate = a.accumulate;
+  p.ktile = DTA_KTILE;
+  return p;
+}
+
+// f(DT, DH): the call's 16-bit dtype and head_dim as std::integral_constant
+template <class F> void with_type(const DtaAttnArgs& a, F&& f) {
+  using BF = std::integral_constant<int, DTA_BF16>; using FP = std::integral_constant<int, DTA_F16>;
+  using D64 = std::integral_constant<int, 64>; using D128 = std::integral_constant<int, 128>;
+  if (a.head_dim == 64) { if (a.dtype == DTA_BF16) f(BF{}, D64{}); else f(FP{}, D64{}); }
+  else { if (a.dtype == DTA_BF16) f(BF{}, D128{}); else f(FP{}, D128{}); }
+}
+
+template <bool WIN, bool CAP> void launch_fwd(const DtaAttnArgs& a) {
+  AttnP<WIN, CAP> p = kernel_params<WIN, CAP>(a);
+  const int nqt = (a.Tq + DTA_QTILE - 1) / DTA_QTILE;
   // two query heads of a kv group share the staged K/V tiles (512 threads); an odd group sends its last head through the
   // one-head form in a second launch (Qwen3-14B: 40 query / 8 kv heads = 2 pairs + 1 per group)
   const int npair = p.group / 2;
   if (npair > 0) {
     p.hgroups = npair; p.head0 = 0;
-    dim3 grid(nqt * Hkv * npair), block(512);
-    if (head_dim == 64) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 64, WIN, CAP>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 64, WIN, CAP>), grid, block, 0, st, p);
-    } else {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 2, 128, WIN, CAP>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 2, 128, WIN, CAP>), grid, block, 0, st, p);
-    }
+    with_type(a, [&](auto dt, auto dh) {
+      hipLaunchKernelGGL((tree_attn_fwd_kernel<decltype(dt)::value, 2, decltype(dh)::value, WIN, CAP>), dim3(nqt * a.Hkv * npair), dim3(512), 0, a.stream, p);
+    });
   }
   if (p.group % 2) {
     p.hgroups = 1; p.head0 = p.group - 1;
-    dim3 grid(nqt * Hkv), block(256);
-    if (head_dim == 64) {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 64, WIN, CAP>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 64, WIN, CAP>), grid, block, 0, st, p);
-    } else {
-      if (dtype == DTA_BF16) hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_BF16, 1, 128, WIN, CAP>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((tree_attn_fwd_kernel<DTA_F16, 1, 128, WIN, CAP>), grid, block, 0, st, p);
-    }
+    with_type(a, [&](auto dt, auto dh) {
+      hipLaunchKernelGGL((tree_attn_fwd_kernel<decltype(dt)::value, 1, decltype(dh)::value, WIN, CAP>), dim3(nqt * a.Hkv), dim3(256), 0, a.stream, p);
+    });
   }
-  return DTA_LAUNCH_STATUS();
 }
 
-template <bool WIN, bool CAP = false>
-static int attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    const int32_t* ktile_qend,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
-                                    float scale, int32_t dtype, int32_t accumulate, int32_t which,
-                                    const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                                    const int32_t* win_lo, int32_t window, void* stream, float softcap = 0.f) {
-  if (!q || !k || !v || !out || !dout || !lse || !delta || !dq || !dk || !dv || Tq <= 0 || Tk <= 0 || Hq <= 0 || Hkv <= 0 || q_offset < 0) return DTA_EINVAL;
-  if ((runs == nullptr) != (run_ptr == nullptr)) return DTA_EINVAL;
-  if (dkv_units && (n_units <= 0 || n_splits < 0 || (n_splits > 0 && (!dkv_splits || !dkv_ws)))) return DTA_EINVAL;
-  if ((head_dim != 128 && head_dim != 64) || Hq % Hkv != 0 || (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) || accumulate < 0 || accumulate > 2) return DTA_EUNSUPPORTED;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) || !aligned16(dv) ||
-      (q_st | q_sh | kv_st | kv_sh | v_st | v_sh | o_st | o_sh | dq_st | dq_sh | dkv_st | dkv_sh) % 8 != 0) return DTA_EALIGN;
-  if (dtype == DTA_F32) {
-    if ((which & 7) == 0) return DTA_EINVAL;
-    DTA_REFUSE_IF_PRIOR_ERROR();
-    return dta_attn_bwd_f32(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
-                            q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which,
-                            win_lo, WIN ? window : 0, CAP ? softcap : 0.f, static_cast<hipStream_t>(stream));
-  }
-  if (q_st < 0 || o_st < 0 || q_st > (1 << 24) || o_st > (1 << 24)) return DTA_EUNSUPPORTED;   // 64-row tile = scalar base + 32-bit lane offset
-  AttnP<WIN, CAP> p{};
-  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
-  if constexpr (CAP) p.softcap = softcap;
-  p.q = q; p.k = k; p.v = v; p.o = out; p.dout = dout; p.lse_r = lse; p.delta = delta; p.dq = dq; p.dk = dk; p.dv = dv;
-  p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs; p.ktile_qend = ktile_qend;
-  p.dkv_units = dkv_units; p.dkv_splits = dkv_splits; p.dkv_ws = dkv_ws;
-  p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
-  p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh;
-  p.dq_st = dq_st; p.dq_sh = dq_sh; p.dkv_st = dkv_st; p.dkv_sh = dkv_sh; p.scale = scale; p.accumulate = accumulate;
-  const int nqt = (Tq + DTA_QTILE - 1) / DTA_QTILE;
-  p.ktile = DTA_KTILE;
-  const int nkt = (Tk + p.ktile - 1) / p.ktile;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
-  if ((which & 7) == 0) return DTA_EINVAL;
+// the backward launches: dQ (head pairs, then the odd head alone), dK/dV, and the slab finalize
+template <bool WIN, bool CAP> void launch_bwd(const DtaAttnArgs& a) {
+  const AttnP<WIN, CAP> p = kernel_params<WIN, CAP>(a);
+  const int nqt = (a.Tq + DTA_QTILE - 1) / DTA_QTILE, nkt = (a.Tk + DTA_KTILE - 1) / DTA_KTILE;
+  const int which = a.which;
   const bool fin = ((which & 2) && !(which & 8)) || (which & 4);     // slab finalize: with the dK/dV launch unless bit3, or alone (bit2)
-  const int ndkv = dkv_units ? n_units : nkt;
+  const int ndkv = a.dkv_units ? a.n_units : nkt;
   const int npair = p.group / 2;                                     // as in the forward: head pairs, then the odd head alone
   AttnP<WIN, CAP> pp = p, ps = p;
   pp.hgroups = npair; pp.head0 = 0; ps.hgroups = 1; ps.head0 = p.group - 1;
-  const dim3 gqp(nqt * Hkv * (npair > 0 ? npair : 1)), gqs(nqt * Hkv);
-  if (head_dim == 64) {
-    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 64, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-    else launch_bwd<DTA_F16, 64, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-  } else {
-    if (dtype == DTA_BF16) launch_bwd<DTA_BF16, 128, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-    else launch_bwd<DTA_F16, 128, WIN, CAP>(p, pp, ps, npair, gqp, gqs, ndkv, fin, n_splits, which, st);
-  }
+  const dim3 gqp(nqt * a.Hkv * (npair > 0 ? npair : 1)), gqs(nqt * a.Hkv);
+  with_type(a, [&](auto dt, auto dh) {
+    constexpr int DT = decltype(dt)::value, DH = decltype(dh)::value;
+    if (which & 1) {
+      if (npair > 0) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 2, DH, WIN, CAP>), gqp, dim3(512), 0, a.stream, pp);
+      if (p.group % 2) hipLaunchKernelGGL((tree_attn_bwd_dq_kernel<DT, 1, DH, WIN, CAP>), gqs, dim3(256), 0, a.stream, ps);
+    }
+    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv2_kernel<DT, DH, WIN, CAP>), dim3(ndkv * p.Hkv), dim3(512), 0, a.stream, p);
+    if (fin && p.dkv_units && a.n_splits > 0)   // the slab sums do not depend on visibility: one finalize kernel for both forms
+      hipLaunchKernelGGL((tree_attn_bwd_dkv_finalize_kernel<DT, DH>), dim3(a.n_splits * p.Hkv, FIN_SPLIT), dim3(256), 0, a.stream, static_cast<const AttnParams&>(p));
+  });
+}
+
+// Argument checks of both entries in the order dta.h gives the status codes.  The forward's backward fields are null / 0 and pass.
+int check_args(const DtaAttnArgs& a, bool bwd) {
+  if (a.softcap != a.softcap || a.softcap > 3.0e38f) return DTA_EINVAL;          // a cap <= 0 means no cap
+  // sliding window: a win_lo without a window, or a packed trie with a window and no win_lo, is refused
+  if (a.window <= 0 ? a.win_lo != nullptr : (a.subtree_end && !a.win_lo)) return DTA_EINVAL;
+  if (!a.q || !a.k || !a.v || a.Tq <= 0 || a.Tk <= 0 || a.Hq <= 0 || a.Hkv <= 0 || a.q_offset < 0) return DTA_EINVAL;
+  if (bwd ? (!a.o || !a.dout || !a.lse_r || !a.delta || !a.dq || !a.dk || !a.dv) : (!a.out || !a.lse_w)) return DTA_EINVAL;
+  if ((a.runs == nullptr) != (a.run_ptr == nullptr)) return DTA_EINVAL;
+  if (a.dkv_units && (a.n_units <= 0 || a.n_splits < 0 || (a.n_splits > 0 && (!a.dkv_splits || !a.dkv_ws)))) return DTA_EINVAL;
+  if (bwd && (a.which & 7) == 0) return DTA_EINVAL;
+  if ((a.head_dim != 128 && a.head_dim != 64) || a.Hq % a.Hkv != 0 || (a.dtype != DTA_BF16 && a.dtype != DTA_F16 && a.dtype != DTA_F32) ||
+      a.accumulate < 0 || a.accumulate > 2) return DTA_EUNSUPPORTED;
+  if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.o) || !aligned16(a.out) || !aligned16(a.dout) || !aligned16(a.dq) ||
+      !aligned16(a.dk) || !aligned16(a.dv) ||
+      (a.q_st | a.q_sh | a.kv_st | a.kv_sh | a.v_st | a.v_sh | a.o_st | a.o_sh | a.dq_st | a.dq_sh | a.dkv_st | a.dkv_sh) % 8 != 0) return DTA_EALIGN;
+  if (a.dtype == DTA_F32) return DTA_OK;
+  // the tile DMA addresses a 64-row tile as scalar base + 32-bit lane offset: the token strides of the tiles it stages (K and V in the
+  // forward, Q and dO in the backward) must keep 64 rows inside 4 GiB
+  const int64_t s0 = bwd ? a.q_st : a.kv_st, s1 = bwd ? a.o_st : a.v_st;
+  if (s0 < 0 || s1 < 0 || s0 > (1 << 24) || s1 > (1 << 24)) return DTA_EUNSUPPORTED;
+  return DTA_OK;
+}
+
+// Explicit instantiation in the order the kernels have always had in the device image (uncapped forms: forward then backward of each;
+// capped forms: both forwards, then both backwards).  Without it their order follows the dispatch code above and moves with every edit of it.
+template void launch_fwd<false, false>(const DtaAttnArgs&); template void launch_bwd<false, false>(const DtaAttnArgs&);
+template void launch_fwd<true, false>(const DtaAttnArgs&); template void launch_bwd<true, false>(const DtaAttnArgs&);
+template void launch_fwd<true, true>(const DtaAttnArgs&); template void launch_fwd<false, true>(const DtaAttnArgs&);
+template void launch_bwd<true, true>(const DtaAttnArgs&); template void launch_bwd<false, true>(const DtaAttnArgs&);
+
+int attn_call(const DtaAttnArgs& a, bool bwd) {
+  if (const int e = check_args(a, bwd)) return e;
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  if (a.dtype == DTA_F32)                                    // fp32 models: the plain-FMA correctness path (tree_attn_f32.hip)
+    return bwd ? dta_attn_bwd_f32(a) : dta_attn_fwd_f32(a);
+  dta_attn_form(a, [&](auto win, auto cap) {
+    if (bwd) launch_bwd<decltype(win)::value, decltype(cap)::value>(a); else launch_fwd<decltype(win)::value, decltype(cap)::value>(a);
+  });
   return DTA_LAUNCH_STATUS();
 }
 
-extern "C" int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v, void* out, float* lse,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    float scale, int32_t dtype, void* stream) {
-  return attn_fwd<false>(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh,
-                         o_st, o_sh, scale, dtype, nullptr, 0, stream);
-}
+}  // namespace
 
-extern "C" int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    const int32_t* ktile_qend,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
-                                    float scale, int32_t dtype, int32_t accumulate, int32_t which,
-                                    const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                                    void* stream) {
-  return attn_bwd<false>(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
-                         q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype, accumulate, which,
-                         dkv_units, n_units, dkv_splits, n_splits, dkv_ws, nullptr, 0, stream);
-}
-
-// Sliding window (dta.h): window <= 0 is the _ex call itself; a win_lo without a window, or a packed trie without win_lo, is refused.
-static int window_args(const int32_t* subtree_end, const int32_t* win_lo, int32_t window) {
-  if (window <= 0) return win_lo ? DTA_EINVAL : 0;
-  if (subtree_end && !win_lo) return DTA_EINVAL;
-  return 1;
-}
-
-extern "C" int dta_tree_attn_fwd_win(const void* q, const void* k, const void* v, void* out, float* lse,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, void* stream) {
-  const int w = window_args(subtree_end, win_lo, window);
-  if (w < 0) return w;
-  if (w == 0) return dta_tree_attn_fwd_ex(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh,
-                                          v_st, v_sh, o_st, o_sh, scale, dtype, stream);
-  return attn_fwd<true>(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh,
-                        o_st, o_sh, scale, dtype, win_lo, window, stream);
-}
-
-extern "C" int dta_tree_attn_bwd_win(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    const int32_t* ktile_qend,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
-                                    float scale, int32_t dtype, int32_t accumulate, int32_t which,
-                                    const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                                    const int32_t* win_lo, int32_t window, void* stream) {
-  const int w = window_args(subtree_end, win_lo, window);
-  if (w < 0) return w;
-  if (w == 0) return dta_tree_attn_bwd_ex(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv,
-                                          head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype,
-                                          accumulate, which, dkv_units, n_units, dkv_splits, n_splits, dkv_ws, stream);
-  return attn_bwd<true>(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv, head_dim,
-                        q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype, accumulate, which,
-                        dkv_units, n_units, dkv_splits, n_splits, dkv_ws, win_lo, window, stream);
-}
-
-// Soft-capped scores (dta.h): softcap <= 0 is the _win call itself, bit for bit; a cap that is not finite is refused.
-extern "C" int dta_tree_attn_fwd_cap(const void* q, const void* k, const void* v, void* out, float* lse,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    float scale, int32_t dtype, const int32_t* win_lo, int32_t window, float softcap, void* stream) {
-  if (!(softcap > 0.f)) {
-    if (softcap != softcap) return DTA_EINVAL;
-    return dta_tree_attn_fwd_win(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh,
-                                 v_st, v_sh, o_st, o_sh, scale, dtype, win_lo, window, stream);
-  }
-  if (softcap > 3.0e38f) return DTA_EINVAL;
-  const int w = window_args(subtree_end, win_lo, window);
-  if (w < 0) return w;
-  return (w ? attn_fwd<true, true> : attn_fwd<false, true>)(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim, q_st, q_sh,
-                                                            kv_st, kv_sh, v_st, v_sh, o_st, o_sh, scale, dtype, win_lo, window, stream, softcap);
-}
-
-extern "C" int dta_tree_attn_bwd_cap(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
-                                    const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                                    const int32_t* ktile_qend,
-                                    int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                    int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                                    int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
-                                    float scale, int32_t dtype, int32_t accumulate, int32_t which,
-                                    const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                                    const int32_t* win_lo, int32_t window, float softcap, void* stream) {
-  if (!(softcap > 0.f)) {
-    if (softcap != softcap) return DTA_EINVAL;
-    return dta_tree_attn_bwd_win(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk, q_offset, Hq, Hkv,
-                                 head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype,
-                                 accumulate, which, dkv_units, n_units, dkv_splits, n_splits, dkv_ws, win_lo, window, stream);
-  }
-  if (softcap > 3.0e38f) return DTA_EINVAL;
-  const int w = window_args(subtree_end, win_lo, window);
-  if (w < 0) return w;
-  return (w ? attn_bwd<true, true> : attn_bwd<false, true>)(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk,
-                                                            q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
-                                                            dq_st, dq_sh, dkv_st, dkv_sh, scale, dtype, accumulate, which,
-                                                            dkv_units, n_units, dkv_splits, n_splits, dkv_ws, win_lo, window, stream, softcap);
-}
-
-// Token-major convenience forms declared in dta.h: head stride = 128 elements, so head_dim 128 only (other head dims: the _ex forms).
 extern "C" int dta_tree_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
                                  const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                                  int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                 int64_t q_stride_t, int64_t kv_stride_t, int64_t o_stride_t,
-                                 float scale, int32_t dtype, void* stream) {
-  // any other head_dim goes on as 0: the _ex form's argument checks come first, then DTA_EUNSUPPORTED, as before head_dim 64 existed
-  return dta_tree_attn_fwd_ex(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim == 128 ? 128 : 0,
-                              q_stride_t, 128, kv_stride_t, 128, kv_stride_t, 128, o_stride_t, 128, scale, dtype, stream);
+                                 int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                 float scale, int32_t dtype, const int32_t* win_lo, int32_t window, float softcap, void* stream) {
+  DtaAttnArgs a{};
+  a.q = q; a.k = k; a.v = v; a.out = out; a.lse_w = lse; a.subtree_end = subtree_end; a.run_ptr = run_ptr; a.runs = runs;
+  a.Tq = Tq; a.Tk = Tk; a.q_offset = q_offset; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = head_dim;
+  a.q_st = q_st; a.q_sh = q_sh; a.kv_st = kv_st; a.kv_sh = kv_sh; a.v_st = v_st; a.v_sh = v_sh; a.o_st = o_st; a.o_sh = o_sh;
+  a.scale = scale; a.dtype = dtype; a.win_lo = win_lo; a.window = window; a.softcap = softcap; a.stream = static_cast<hipStream_t>(stream);
+  return attn_call(a, false);
 }
 
 extern "C" int dta_tree_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
@@ -1268,10 +1148,18 @@ extern "C" int dta_tree_attn_bwd(const void* q, const void* k, const void* v, co
                                  const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                                  const int32_t* ktile_qend,
                                  int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                                 int64_t q_stride_t, int64_t kv_stride_t, int64_t o_stride_t,
-                                 int64_t dq_stride_t, int64_t dkv_stride_t,
-                                 float scale, int32_t dtype, int32_t accumulate, void* stream) {
-  return dta_tree_attn_bwd_ex(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend,
-                              Tq, Tk, q_offset, Hq, Hkv, head_dim == 128 ? 128 : 0, q_stride_t, 128, kv_stride_t, 128, kv_stride_t, 128, o_stride_t, 128,
-                              dq_stride_t, 128, dkv_stride_t, 128, scale, dtype, accumulate, 3, nullptr, 0, nullptr, 0, nullptr, stream);
+                                 int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
+                                 int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh,
+                                 float scale, int32_t dtype, int32_t accumulate, int32_t which,
+                                 const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
+                                 const int32_t* win_lo, int32_t window, float softcap, void* stream) {
+  DtaAttnArgs a{};
+  a.q = q; a.k = k; a.v = v; a.o = out; a.dout = dout; a.lse_r = lse; a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
+  a.subtree_end = subtree_end; a.run_ptr = run_ptr; a.runs = runs; a.ktile_qend = ktile_qend;
+  a.dkv_units = dkv_units; a.n_units = n_units; a.dkv_splits = dkv_splits; a.n_splits = n_splits; a.dkv_ws = dkv_ws;
+  a.Tq = Tq; a.Tk = Tk; a.q_offset = q_offset; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = head_dim;
+  a.q_st = q_st; a.q_sh = q_sh; a.kv_st = kv_st; a.kv_sh = kv_sh; a.v_st = v_st; a.v_sh = v_sh; a.o_st = o_st; a.o_sh = o_sh;
+  a.dq_st = dq_st; a.dq_sh = dq_sh; a.dkv_st = dkv_st; a.dkv_sh = dkv_sh; a.scale = scale; a.dtype = dtype; a.accumulate = accumulate; a.which = which;
+  a.win_lo = win_lo; a.window = window; a.softcap = softcap; a.stream = static_cast<hipStream_t>(stream);
+  return attn_call(a, true);
 }

@@ -285,68 +285,46 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_f32_kernel(P32T<WIN, CA
 
 }  // namespace
 
-template <bool WIN, bool CAP>
-static int fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
-                   const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                   int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                   float scale, const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
+// kernel parameters of the chosen form from the call's arguments (the forward's backward fields are null)
+template <bool WIN, bool CAP> static P32T<WIN, CAP> kernel_params(const DtaAttnArgs& a) {
   P32T<WIN, CAP> p{};
-  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
-  if constexpr (CAP) p.softcap = softcap;
-  p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.out = (float*)out; p.lse_w = lse;
-  p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs;
-  p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
-  p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh; p.scale = scale;
-  const dim3 grid((Tq + ROWS - 1) / ROWS, Hq);
-  if (head_dim == 64) hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<64, WIN, CAP>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<128, WIN, CAP>), grid, dim3(256), 0, st, p);
+  if constexpr (WIN) { p.win_lo = a.win_lo; p.window = a.window; }
+  if constexpr (CAP) p.softcap = a.softcap;
+  p.q = (const float*)a.q; p.k = (const float*)a.k; p.v = (const float*)a.v; p.o = (const float*)a.o; p.dout = (const float*)a.dout;
+  p.out = (float*)a.out; p.dq = (float*)a.dq; p.dk = (float*)a.dk; p.dv = (float*)a.dv; p.lse_w = a.lse_w; p.lse_r = a.lse_r; p.delta = a.delta;
+  p.subtree_end = a.subtree_end; p.run_ptr = a.run_ptr; p.runs = a.runs; p.ktile_qend = a.ktile_qend;
+  p.Tq = a.Tq; p.Tk = a.Tk; p.q_offset = a.q_offset; p.Hq = a.Hq; p.Hkv = a.Hkv; p.group = a.Hq / a.Hkv;
+  p.q_st = a.q_st; p.q_sh = a.q_sh; p.kv_st = a.kv_st; p.kv_sh = a.kv_sh; p.v_st = a.v_st; p.v_sh = a.v_sh; p.o_st = a.o_st; p.o_sh = a.o_sh;
+  p.dq_st = a.dq_st; p.dq_sh = a.dq_sh; p.dkv_st = a.dkv_st; p.dkv_sh = a.dkv_sh; p.scale = a.scale; p.accumulate = a.accumulate;
+  return p;
+}
+
+// f(D) with head_dim as a std::integral_constant
+template <class F> static void with_head_dim(const DtaAttnArgs& a, F&& f) {
+  if (a.head_dim == 64) f(std::integral_constant<int, 64>{}); else f(std::integral_constant<int, 128>{});
+}
+
+int dta_attn_fwd_f32(const DtaAttnArgs& a) {
+  dta_attn_form(a, [&](auto win, auto cap) {
+    constexpr bool WIN = decltype(win)::value, CAP = decltype(cap)::value;
+    const P32T<WIN, CAP> p = kernel_params<WIN, CAP>(a);
+    with_head_dim(a, [&](auto d) {
+      hipLaunchKernelGGL((tree_attn_fwd_f32_kernel<decltype(d)::value, WIN, CAP>), dim3((a.Tq + ROWS - 1) / ROWS, a.Hq), dim3(256), 0, a.stream, p);
+    });
+  });
   return DTA_LAUNCH_STATUS();
 }
 
-template <bool WIN, bool CAP>
-static int bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
-                   void* dq, void* dk, void* dv, const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs, const int32_t* ktile_qend,
-                   int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                   int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                   int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which,
-                   const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
-  P32T<WIN, CAP> p{};
-  if constexpr (WIN) { p.win_lo = win_lo; p.window = window; }
-  if constexpr (CAP) p.softcap = softcap;
-  p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.o = (const float*)out; p.dout = (const float*)dout;
-  p.lse_r = lse; p.delta = delta; p.dq = (float*)dq; p.dk = (float*)dk; p.dv = (float*)dv;
-  p.subtree_end = subtree_end; p.run_ptr = run_ptr; p.runs = runs; p.ktile_qend = ktile_qend;
-  p.Tq = Tq; p.Tk = Tk; p.q_offset = q_offset; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
-  p.q_st = q_st; p.q_sh = q_sh; p.kv_st = kv_st; p.kv_sh = kv_sh; p.v_st = v_st; p.v_sh = v_sh; p.o_st = o_st; p.o_sh = o_sh;
-  p.dq_st = dq_st; p.dq_sh = dq_sh; p.dkv_st = dkv_st; p.dkv_sh = dkv_sh; p.scale = scale; p.accumulate = accumulate;
-  const dim3 gq((Tq + ROWS - 1) / ROWS, Hq), gk((Tk + ROWS - 1) / ROWS, Hkv);
-  if (head_dim == 64) {
-    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<64, WIN, CAP>), gq, dim3(256), 0, st, p);      // also writes -delta
-    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<64, WIN, CAP>), gk, dim3(256), 0, st, p);
-  } else {
-    if (which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<128, WIN, CAP>), gq, dim3(256), 0, st, p);
-    if (which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<128, WIN, CAP>), gk, dim3(256), 0, st, p);
-  }
+int dta_attn_bwd_f32(const DtaAttnArgs& a) {
+  dta_attn_form(a, [&](auto win, auto cap) {
+    constexpr bool WIN = decltype(win)::value, CAP = decltype(cap)::value;
+    const P32T<WIN, CAP> p = kernel_params<WIN, CAP>(a);
+    const dim3 gq((a.Tq + ROWS - 1) / ROWS, a.Hq), gk((a.Tk + ROWS - 1) / ROWS, a.Hkv);
+    with_head_dim(a, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      if (a.which & 1) hipLaunchKernelGGL((tree_attn_bwd_dq_f32_kernel<D, WIN, CAP>), gq, dim3(256), 0, a.stream, p);      // also writes -delta
+      if (a.which & 2) hipLaunchKernelGGL((tree_attn_bwd_dkv_f32_kernel<D, WIN, CAP>), gk, dim3(256), 0, a.stream, p);
+    });
+  });
   return DTA_LAUNCH_STATUS();                           // (which & 4, the slab finalize of the MFMA path, has nothing to do here)
-}
-
-int dta_attn_fwd_f32(const void* q, const void* k, const void* v, void* out, float* lse, const int32_t* subtree_end, const int32_t* run_ptr,
-                     const int32_t* runs, int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                     float scale, const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
-  const auto f = softcap > 0.f ? (window > 0 ? fwd_f32<true, true> : fwd_f32<false, true>) : (window > 0 ? fwd_f32<true, false> : fwd_f32<false, false>);
-  return f(q, k, v, out, lse, subtree_end, run_ptr, runs, Tq, Tk, q_offset, Hq, Hkv, head_dim,
-           q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh, scale, win_lo, window, softcap, st);
-}
-
-int dta_attn_bwd_f32(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta,
-                     void* dq, void* dk, void* dv, const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs, const int32_t* ktile_qend,
-                     int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                     int64_t q_st, int64_t q_sh, int64_t kv_st, int64_t kv_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh,
-                     int64_t dq_st, int64_t dq_sh, int64_t dkv_st, int64_t dkv_sh, float scale, int32_t accumulate, int32_t which,
-                     const int32_t* win_lo, int32_t window, float softcap, hipStream_t st) {
-  const auto f = softcap > 0.f ? (window > 0 ? bwd_f32<true, true> : bwd_f32<false, true>) : (window > 0 ? bwd_f32<true, false> : bwd_f32<false, false>);
-  return f(q, k, v, out, dout, lse, delta, dq, dk, dv, subtree_end, run_ptr, runs, ktile_qend, Tq, Tk,
-           q_offset, Hq, Hkv, head_dim, q_st, q_sh, kv_st, kv_sh, v_st, v_sh, o_st, o_sh,
-           dq_st, dq_sh, dkv_st, dkv_sh, scale, accumulate, which, win_lo, window, softcap, st);
 }

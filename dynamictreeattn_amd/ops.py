@@ -151,28 +151,17 @@ def _cap_of(softcap) -> float:
 
 
 def attn_fwd_raw(q, k, v, meta: TreeAttnMeta, scale: float, softcap: float = 0.0):
-    """softcap > 0: scores softcap * tanh(scale q.k / softcap), capped before the visibility mask (dta_tree_attn_fwd_cap)."""
-    _require_cuda(q, k, v)
+    """softcap > 0: scores softcap * tanh(scale q.k / softcap), capped before the visibility mask."""
     softcap = _cap_of(softcap)
     Tq, Hq, D = q.shape
     Tk, Hkv, _ = k.shape
     out = torch.empty((Tq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device)          # head-major: rows of one head are contiguous
     (qs, qh), (ks, kh), (vs, vh), (os_, oh) = _strides(q), _strides(k), _strides(v), _strides(out)
-    tm = KernelTimer.active
-    win = (ptr(meta.win_lo), int(meta.window)) if meta.window > 0 else ()
-    entry = "dta_tree_attn_fwd_win" if win else "dta_tree_attn_fwd_ex"
-    if softcap > 0:
-        entry, win = "dta_tree_attn_fwd_cap", (win or (None, 0)) + (softcap,)
-    with _on(q, k, v, meta.subtree_end, meta.runs) as stream:
-        if tm is not None:
-            ev = tm.span("fwd"); ev[0].record()
-        st = getattr(lib(), entry)(
+    _launch("dta_tree_attn_fwd", (q, k, v, meta.subtree_end, meta.runs, meta.win_lo),
             ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs),
-            Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, float(scale), _DT[q.dtype], *win, stream)
-        if tm is not None:
-            ev[1].record()
-    check(st, "dta_tree_attn_fwd")
+            Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, float(scale), _DT[q.dtype],
+            ptr(meta.win_lo) if meta.window > 0 else None, int(meta.window), softcap, span="fwd")
     return out, lse, k, v
 
 
@@ -196,28 +185,20 @@ def attn_bwd_raw(q, k, v, out, dout, lse, meta: TreeAttnMeta, scale: float, dk=N
         units = splits = None; n_units = n_splits = 0
     ws = torch.empty((meta.n_slabs, Hkv, 2, packing.KTILE, D), dtype=torch.float32, device=q.device) if (units is not None and meta.n_slabs) else None
 
-    win = (ptr(meta.win_lo), int(meta.window)) if meta.window > 0 else ()
-    entry = "dta_tree_attn_bwd_win" if win else "dta_tree_attn_bwd_ex"
-    if softcap > 0:
-        entry, win = "dta_tree_attn_bwd_cap", (win or (None, 0)) + (softcap,)
-
-    def launch(which, stream):
-        return getattr(lib(), entry)(
-            ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
-            ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs), ptr(meta.ktile_qend),
-            Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, dqs, dqh, dks, dkh,
-            float(scale), _DT[q.dtype], int(accumulate), which,
-            ptr(units), n_units, ptr(splits) if n_splits else None, n_splits, ptr(ws), *win, stream)
-    tm = KernelTimer.active
-    with _on(q, k, v, out, dout, lse, dk, dv, meta.subtree_end, units, meta.win_lo) as stream:
-        if tm is None:
-            check(launch(3, stream), "dta_tree_attn_bwd")
-        else:
-            for which, name in ((1, "bwd_dq"), (2 | 8, "bwd_dkv"), (4, "bwd_dkv_finalize")):
-                if which == 4 and not n_splits:
-                    continue
-                a, b = tm.span(name); a.record(); st = launch(which, stream); b.record()
-                check(st, "dta_tree_attn_bwd")
+    def launch(which, span=None):
+        _launch("dta_tree_attn_bwd", (q, k, v, out, dout, lse, dk, dv, meta.subtree_end, units, meta.win_lo),
+                ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
+                ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs), ptr(meta.ktile_qend),
+                Tq, Tk, meta.q_offset, Hq, Hkv, D, qs, qh, ks, kh, vs, vh, os_, oh, dqs, dqh, dks, dkh,
+                float(scale), _DT[q.dtype], int(accumulate), which,
+                ptr(units), n_units, ptr(splits) if n_splits else None, n_splits, ptr(ws),
+                ptr(meta.win_lo) if meta.window > 0 else None, int(meta.window), softcap, span=span)
+    if KernelTimer.active is None:
+        launch(3)
+    else:                                   # one launch per span, so that the timer's events bracket each kernel
+        launch(1, "bwd_dq"); launch(2 | 8, "bwd_dkv")
+        if n_splits:
+            launch(4, "bwd_dkv_finalize")
     return dq, dk, dv
 
 

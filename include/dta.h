@@ -25,7 +25,7 @@ extern "C" {
 
 #define DTA_OK 0
 #define DTA_EINVAL (-1)      /* null pointer / negative size / inconsistent sizes */
-#define DTA_EUNSUPPORTED (-2)/* head_dim not 64 / 128 (token-major attention forms: not 128), dtype not bf16/f16, Hq % Hkv != 0 ... */
+#define DTA_EUNSUPPORTED (-2)/* head_dim not 64 / 128, dtype not bf16/f16/f32, Hq % Hkv != 0, accumulate not 0..2 ... */
 #define DTA_EALIGN (-3)      /* pointer or stride not 16-byte aligned */
 #define DTA_ELAUNCH (-4)     /* hipGetLastError() after the launch was not hipSuccess */
 #define DTA_EPRIOR (-5)      /* a HIP error was ALREADY pending on this thread when the entry point was called (an earlier
@@ -85,138 +85,92 @@ int dta_preorder_meta(const int64_t* tokens, const int64_t* leaf_tok_off,
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Tree attention (MFMA-bound).  head_dim 128 or 64 (the _ex forms; the token-major forms dta_tree_attn_fwd / _bwd below take
- * 128 only and return DTA_EUNSUPPORTED for any other head_dim); dtype DTA_BF16 or DTA_F16 (MFMA kernels), or DTA_F32 (every
- * buffer fp32; plain fp32 FMAs, one workgroup per 64 rows, split-Q work units ignored - the correctness path of fp32 models).
- * Alignment: every base pointer 16 bytes, every stride a multiple of 8 elements - a head row is 256 B (D = 128) or 128 B (D = 64),
- * i.e. whole 16-byte chunks either way.
+ * Tree attention (MFMA-bound).  One forward / backward pair serves packed tries and the stack form, with or without a sliding window
+ * and a soft-cap: window <= 0 and softcap <= 0 select the kernels compiled without those terms.
+ * head_dim 128 or 64; dtype DTA_BF16 or DTA_F16 (MFMA kernels), or DTA_F32 (every buffer fp32; plain fp32 FMAs, one workgroup per
+ * 64 rows, split-Q work units ignored - the correctness path of fp32 models).
  *
- * Token-major forms: q/out/dout/dq: [Tq, Hq, 128] with element strides (q_stride_t, 128); k/v/dk/dv: [Tk, Hkv, 128]
- * with (kv_stride_t, 128).  The _ex forms take every head stride explicitly ([.., H, D] rows of head_dim elements).
- * Query row i has packed index q_offset + i.  It attends key s iff
- * s <= q_offset+i  &&  q_offset+i < subtree_end[s]   (subtree_end == NULL: no upper bound, i.e. the
- * rectangular-causal stack form of tree_training_engine.py:171-186 with q_offset = start).
+ * Layout.  q/out/dout/dq: [Tq, Hq, head_dim], k/v/dk/dv: [Tk, Hkv, head_dim], rows of head_dim contiguous elements; every token and
+ * head stride is explicit (elements), so that head-major layouts such as the reference's [1, H, S, D] KV stack
+ * (tree_training_engine.py:108-131) work in place.  Alignment: every base pointer 16 bytes, every stride a multiple of 8 elements
+ * (DTA_EALIGN otherwise) - a head row is 256 B (D = 128) or 128 B (D = 64), i.e. whole 16-byte chunks either way.  Token strides of k
+ * and v (forward) and of q and dout (backward) must be in [0, 2^24] elements on the MFMA path: a 64-row tile is addressed as scalar
+ * base + 32-bit lane offset by the tile DMA (DTA_EUNSUPPORTED otherwise).
+ *
+ * Visibility.  Query row i has packed index t = q_offset + i.  It attends key s iff
+ *   packed trie:  s <= t  &&  t < subtree_end[s]  (the ancestor test)
+ *   stack form (subtree_end == NULL): s <= t, no upper bound - the rectangular-causal form of tree_training_engine.py:171-186 with
+ *                 q_offset = start
+ * and, with window > 0 (the "sliding_attention" layers of Qwen2 / Qwen3 configurations), one lower bound more:
+ *   packed trie:  s >= win_lo[i],  win_lo[i] = packed index of t's ancestor at depth max(0, depth[t] - window + 1) (dta_window_lo), i.e.
+ *                 depth[t] - depth[s] < window along the path: the mask of HF's sliding_window_overlay for every sequence through t.
+ *   stack form (win_lo == NULL):  t - s < window.
+ * window <= 0: no window, and win_lo must be NULL.  DTA_EINVAL: win_lo given with window <= 0, or subtree_end given (packed trie)
+ * with window > 0 and no win_lo.
  *
  * Query tiles are DTA_QTILE rows.  Tile j visits the key runs runs[run_ptr[j] .. run_ptr[j+1]),
  * each run = 4 int32 {key_begin, key_end, needs_mask, 0}; runs == NULL: one run [0, last row + 1).
- * A run with needs_mask == 0 promises that every key in it is visible to every row of the tile.
- * lse: [Hq, Tq] float (head-major), log2-domain log-sum-exp of the scaled scores (natural lse = lse * ln 2).
+ * A run with needs_mask == 0 promises that every key in it is visible to every row of the tile.  With a window, run_ptr / runs of a
+ * packed trie must be planned for the window: needs_mask == 0 then promises that the run's keys are ancestors of every row of the tile
+ * AND >= every row's win_lo (the windowed plan of packing.plan_qtile_runs_window); ktile_qend and dkv_units may be the windowed,
+ * tighter ones.
+ *
+ * Soft-cap (Gemma-2's attn_logit_softcapping), softcap > 0.  With z_ij = scale * (q_i . k_j), c = softcap and t_ij = tanh(z_ij / c):
+ *   forward   s_ij = c * t_ij.  The cap comes FIRST, then the visibility mask (ancestor test, window), then the softmax - the order of
+ *             HF's eager_attention_forward.
+ *   backward  t is recomputed from Q.K^T as S is; p = exp(s - lse) and dS = p * (dP - delta) as without a cap;
+ *             dz = dS * (1 - t^2);  dq = scale * dz K,  dk = scale * dz^T Q;  dV and delta are unchanged.
+ * tanh is computed in fp32 as 1 - 2 / (1 + 2^(2 log2(e) z / c)): it saturates to +-1 for large |z / c| (no inf / inf) and its absolute
+ * error is a few 2^-24, i.e. the capped score is off by the order of c * 2^-24.  softcap <= 0: no cap.  DTA_EINVAL: a softcap that is
+ * NaN or infinite.
+ *
+ * lse: [Hq, Tq] float (head-major), log2-domain log-sum-exp of the scaled scores - of the CAPPED scores under a soft-cap
+ * (natural lse = lse * ln 2).
+ *
+ * Refusals of both entries come in this order: DTA_EINVAL for the soft-cap, then for the window rules, then for a null pointer, a size
+ * <= 0 or q_offset < 0, runs without run_ptr (or the reverse) and, in the backward, inconsistent dkv_units arguments or a `which`
+ * without any of bits 0-2; DTA_EUNSUPPORTED for head_dim, Hq % Hkv != 0, dtype or accumulate; DTA_EALIGN; DTA_EUNSUPPORTED for the
+ * 2^24 token-stride limit; DTA_EPRIOR.
  * Replaces the attention the reference reaches through the model call,
  * tree_training_engine.py:182-186, 248-252, 351-353 (third-party attention backend).  */
 int dta_tree_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
                       const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                       int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                      int64_t q_stride_t, int64_t kv_stride_t, int64_t o_stride_t,
-                      float scale, int32_t dtype, void* stream);
-
-/* General-stride form of dta_tree_attn_fwd: explicit head strides (elements) so that head-major
- * layouts such as the reference's [1, H, S, D] KV stack (tree_training_engine.py:108-131) work in place.
- * Token strides of k and v (forward) and of q and dout (backward) must be in [0, 2^24] elements: a 64-row tile
- * is addressed as scalar base + 32-bit lane offset by the tile DMA (DTA_EUNSUPPORTED otherwise). */
-int dta_tree_attn_fwd_ex(const void* q, const void* k, const void* v, void* out, float* lse,
-                         const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                         int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                         int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
-                         int64_t v_stride_t, int64_t v_stride_h,
-                         int64_t o_stride_t, int64_t o_stride_h, float scale, int32_t dtype, void* stream);
+                      int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
+                      int64_t v_stride_t, int64_t v_stride_h,
+                      int64_t o_stride_t, int64_t o_stride_h, float scale, int32_t dtype,
+                      const int32_t* win_lo, int32_t window, float softcap, void* stream);
 
 /* Backward.  Two launches on `stream`: (1) per query tile: delta = rowsum(dout*out), dq;
  * (2) per key tile of DTA_KTILE keys: dk, dv summed over the query range
  * [max(key0, q_offset), ktile_qend[tile]) and over the Hq/Hkv query heads of the group — no
- * cross-workgroup reduction, no atomics, bitwise reproducible.  ktile_qend[j] = max subtree_end
+ * cross-workgroup reduction, no atomics, bitwise reproducible (with a window and a soft-cap too).  ktile_qend[j] = max subtree_end
  * over the tile's keys (NULL: q_offset + Tq).  `accumulate`: 0 overwrites dk/dv; 1 adds into them (the grad-KV
  * stack of tree_training_engine.py:447-451; model dtype, rounded after every add as the reference's `+=`); 2 adds into
  * FP32 buffers (dk/dv are float*, strides in floats) so that the hundreds of adds a root-side row receives in the
  * block-wise engine are not rounded to 16 bits each time.  delta: [Hq, Tq] float workspace.
+ * Visibility, window, soft-cap, layout and alignment are the forward's.
  * Replaces torch.autograd.backward through the attention backend, tree_training_engine.py:440.  */
 int dta_tree_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
                       const float* lse, float* delta, void* dq, void* dk, void* dv,
                       const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
                       const int32_t* ktile_qend,
                       int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                      int64_t q_stride_t, int64_t kv_stride_t, int64_t o_stride_t,
-                      int64_t dq_stride_t, int64_t dkv_stride_t,
-                      float scale, int32_t dtype, int32_t accumulate, void* stream);
+                      int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
+                      int64_t v_stride_t, int64_t v_stride_h,
+                      int64_t o_stride_t, int64_t o_stride_h, int64_t dq_stride_t, int64_t dq_stride_h,
+                      int64_t dkv_stride_t, int64_t dkv_stride_h,
+                      float scale, int32_t dtype, int32_t accumulate,
+                      int32_t which /* bit0: delta+dq launch, bit1: dk/dv launch (needs delta) followed by the slab finalize
+                                       unless bit3; bit2: slab finalize alone (lets a profiler bracket each launch);
+                                       none of bits 0-2: DTA_EINVAL */,
+                      /* optional split of the dK/dV sweep into balanced work units (NULL: one per key tile):
+                       * dkv_units[u] = {key tile, q_begin, q_end (packed), slab or -1}; units of a split key tile
+                       * write fp32 slabs [2][DTA_KTILE][head_dim] into dkv_ws (slab-major, then kv head) which a finalize
+                       * launch sums in order: dkv_splits[s] = {key tile, first slab, n slabs, 0}. */
+                      const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
+                      const int32_t* win_lo, int32_t window, float softcap, void* stream);
 
-int dta_tree_attn_bwd_ex(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                         const float* lse, float* delta, void* dq, void* dk, void* dv,
-                         const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                         const int32_t* ktile_qend,
-                         int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                         int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
-                         int64_t v_stride_t, int64_t v_stride_h,
-                         int64_t o_stride_t, int64_t o_stride_h, int64_t dq_stride_t, int64_t dq_stride_h,
-                         int64_t dkv_stride_t, int64_t dkv_stride_h,
-                         float scale, int32_t dtype, int32_t accumulate,
-                         int32_t which /* bit0: delta+dq launch, bit1: dk/dv launch (needs delta) followed by the slab finalize
-                                          unless bit3; bit2: slab finalize alone (lets a profiler bracket each launch) */,
-                         /* optional split of the dK/dV sweep into balanced work units (NULL: one per key tile):
-                          * dkv_units[u] = {key tile, q_begin, q_end (packed), slab or -1}; units of a split key tile
-                          * write fp32 slabs [2][DTA_KTILE][head_dim] into dkv_ws (slab-major, then kv head) which a finalize
-                          * launch sums in order: dkv_splits[s] = {key tile, first slab, n slabs, 0}. */
-                         const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                         void* stream);
-
-/* ---------------------------------------------------------------------------------------------
- * Sliding-window attention (the "sliding_attention" layers of Qwen2 / Qwen3 configurations).  Visibility gains one lower bound:
- *   packed trie:  key s visible to query row i (t = q_offset + i)  <=>  s <= t < subtree_end[s]  &&  s >= win_lo[i]
- *                 win_lo[i] = packed index of t's ancestor at depth max(0, depth[t] - window + 1) (dta_window_lo), i.e.
- *                 depth[t] - depth[s] < window along the path: the mask of HF's sliding_window_overlay for every sequence through t.
- *   stack form (subtree_end == NULL, win_lo == NULL):  s <= t  &&  t - s < window.
- * All other arguments are those of the _ex forms.  run_ptr / runs of a packed trie must be planned for the window: a run with
- * needs_mask == 0 promises that its keys are ancestors of every row of the tile AND >= every row's win_lo (the windowed plan of
- * packing.plan_qtile_runs_window); ktile_qend and dkv_units may be the windowed, tighter ones.
- * window <= 0: no window - the call IS the _ex call (bit for bit) and win_lo must be NULL.  DTA_EINVAL: win_lo given with
- * window <= 0, or subtree_end given (packed trie) with window > 0 and no win_lo. */
-int dta_tree_attn_fwd_win(const void* q, const void* k, const void* v, void* out, float* lse,
-                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
-                          int64_t v_stride_t, int64_t v_stride_h,
-                          int64_t o_stride_t, int64_t o_stride_h, float scale, int32_t dtype,
-                          const int32_t* win_lo, int32_t window, void* stream);
-int dta_tree_attn_bwd_win(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                          const float* lse, float* delta, void* dq, void* dk, void* dv,
-                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                          const int32_t* ktile_qend,
-                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
-                          int64_t v_stride_t, int64_t v_stride_h,
-                          int64_t o_stride_t, int64_t o_stride_h, int64_t dq_stride_t, int64_t dq_stride_h,
-                          int64_t dkv_stride_t, int64_t dkv_stride_h,
-                          float scale, int32_t dtype, int32_t accumulate, int32_t which,
-                          const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                          const int32_t* win_lo, int32_t window, void* stream);
-/* ---------------------------------------------------------------------------------------------
- * Soft-capped attention (Gemma-2's attn_logit_softcapping).  With z_ij = scale * (q_i . k_j), c = softcap and t_ij = tanh(z_ij / c):
- *   forward   s_ij = c * t_ij.  The cap comes FIRST, then the visibility mask (ancestor test, window), then the softmax - the order of
- *             HF's eager_attention_forward.  lse is the log-sum-exp of the CAPPED scores (log2 domain, as in the other forms).
- *   backward  t is recomputed from Q.K^T as S is; p = exp(s - lse) and dS = p * (dP - delta) as without a cap;
- *             dz = dS * (1 - t^2);  dq = scale * dz K,  dk = scale * dz^T Q;  dV and delta are unchanged.
- * tanh is computed in fp32 as 1 - 2 / (1 + 2^(2 log2(e) z / c)): it saturates to +-1 for large |z / c| (no inf / inf) and its absolute
- * error is a few 2^-24, i.e. the capped score is off by the order of c * 2^-24.
- * Arguments: those of the _win forms (packed tries, the stack form, windows, head_dim 64 / 128, bf16 / f16 / f32, accumulate 0 / 1 / 2;
- * the dK/dV sweep stays atomic-free and bitwise reproducible) plus `softcap`.  softcap <= 0: no cap - the call IS the _win call, bit for
- * bit.  DTA_EINVAL: a softcap that is NaN or infinite, and what the _win forms refuse. */
-int dta_tree_attn_fwd_cap(const void* q, const void* k, const void* v, void* out, float* lse,
-                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
-                          int64_t v_stride_t, int64_t v_stride_h,
-                          int64_t o_stride_t, int64_t o_stride_h, float scale, int32_t dtype,
-                          const int32_t* win_lo, int32_t window, float softcap, void* stream);
-int dta_tree_attn_bwd_cap(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                          const float* lse, float* delta, void* dq, void* dk, void* dv,
-                          const int32_t* subtree_end, const int32_t* run_ptr, const int32_t* runs,
-                          const int32_t* ktile_qend,
-                          int32_t Tq, int32_t Tk, int32_t q_offset, int32_t Hq, int32_t Hkv, int32_t head_dim,
-                          int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
-                          int64_t v_stride_t, int64_t v_stride_h,
-                          int64_t o_stride_t, int64_t o_stride_h, int64_t dq_stride_t, int64_t dq_stride_h,
-                          int64_t dkv_stride_t, int64_t dkv_stride_h,
-                          float scale, int32_t dtype, int32_t accumulate, int32_t which,
-                          const int32_t* dkv_units, int32_t n_units, const int32_t* dkv_splits, int32_t n_splits, float* dkv_ws,
-                          const int32_t* win_lo, int32_t window, float softcap, void* stream);
 /* out_win_lo[t] for the T packed tokens of a trie: the packed index of t's ancestor at depth max(0, depth[t] - window + 1).  depth[T] as
  * written by dta_preorder_meta; seg_off[M+1], seg_depth0[M], parent_of_seg[M] as passed to it.  Walks up segments (binary search over
  * seg_off per hop), not tokens.  window > 0 (DTA_EINVAL otherwise). */

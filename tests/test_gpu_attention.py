@@ -130,10 +130,13 @@ def test_golden_attention_samples_from_transformers_eager():
 
 def test_error_codes():
     from dynamictreeattn_amd._lib import lib
-    assert lib().dta_tree_attn_fwd(None, None, None, None, None, None, None, None, 4, 4, 0, 2, 1, 128, 256, 128, 256, 0.1, 0, None) == -1
+    assert lib().dta_tree_attn_fwd(None, None, None, None, None, None, None, None, 4, 4, 0, 2, 1, 128,
+                                   256, 128, 128, 128, 128, 128, 256, 128, 0.1, 0, None, 0, 0.0, None) == -1
     x = torch.zeros(4, 2, 64, dtype=torch.bfloat16, device=DEV); l = torch.zeros(4, 2, device=DEV)
+    y = torch.zeros(4, 2, 96, dtype=torch.bfloat16, device=DEV)
     P = lambda t: t.data_ptr()
-    assert lib().dta_tree_attn_fwd(P(x), P(x), P(x), P(x), P(l), None, None, None, 4, 4, 0, 2, 2, 64, 128, 128, 128, 0.1, 0, None) == -2
+    assert lib().dta_tree_attn_fwd(P(y), P(y), P(y), P(y), P(l), None, None, None, 4, 4, 0, 2, 2, 96,
+                                   192, 96, 192, 96, 192, 96, 192, 96, 0.1, 0, None, 0, 0.0, None) == -2      # head_dim 96
     with pytest.raises(TypeError):
         ops.tree_attention(x.double(), x.double(), x.double(), ops.stack_meta(0))
     with pytest.raises(RuntimeError, match="no CPU path"):

@@ -180,22 +180,16 @@ def test_d64_c_interface_codes():
     for hd, want in ((64, 0), (128, 0), (32, -2), (96, -2), (256, -2)):
         q = torch.zeros(4, Hq, hd, dtype=BF, device=DEV); kv = torch.zeros(4, Hkv, hd, dtype=BF, device=DEV)
         o = torch.empty_like(q); lse = torch.zeros(Hq, 4, device=DEV)
-        st = lib().dta_tree_attn_fwd_ex(P(q), P(kv), P(kv), P(o), P(lse), None, None, None, 4, 4, 0, Hq, Hkv, hd,
-                                        Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, 0.1, 0, None)
+        st = lib().dta_tree_attn_fwd(P(q), P(kv), P(kv), P(o), P(lse), None, None, None, 4, 4, 0, Hq, Hkv, hd,
+                                     Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, 0.1, 0, None, 0, 0.0, None)
         torch.cuda.synchronize()
         assert st == want, (hd, st)
         dl = torch.zeros(Hq, 4, device=DEV); dq = torch.empty_like(q); dk = torch.empty_like(kv); dv = torch.empty_like(kv)
-        st = lib().dta_tree_attn_bwd_ex(P(q), P(kv), P(kv), P(o), P(o), P(lse), P(dl), P(dq), P(dk), P(dv), None, None, None, None,
-                                        4, 4, 0, Hq, Hkv, hd, Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, Hq * hd, hd,
-                                            Hkv * hd, hd, 0.1, 0, 0, 3, None, 0, None, 0, None, None)
+        st = lib().dta_tree_attn_bwd(P(q), P(kv), P(kv), P(o), P(o), P(lse), P(dl), P(dq), P(dk), P(dv), None, None, None, None,
+                                     4, 4, 0, Hq, Hkv, hd, Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, Hq * hd, hd,
+                                     Hkv * hd, hd, 0.1, 0, 0, 3, None, 0, None, 0, None, None, 0, 0.0, None)
         torch.cuda.synchronize()
         assert st == want, ("bwd", hd, st)
-    # the token-major forms keep their head stride of 128 elements: head_dim 64 is refused there
-    x = torch.zeros(4, 2, 64, dtype=BF, device=DEV); l = torch.zeros(4, 2, device=DEV)
-    assert lib().dta_tree_attn_fwd(P(x), P(x), P(x), P(x), P(l), None, None, None, 4, 4, 0, 2, 2, 64, 128, 128, 128, 0.1, 0, None) == -2
-    dl = torch.zeros(2, 4, device=DEV)
-    assert lib().dta_tree_attn_bwd(P(x), P(x), P(x), P(x), P(x), P(l), P(dl), P(x), P(x), P(x), None, None, None, None,
-                                   4, 4, 0, 2, 2, 64, 128, 128, 128, 128, 128, 0.1, 0, 0, None) == -2
 
 
 # ------------------------------------------------------------------------------------------------ full size

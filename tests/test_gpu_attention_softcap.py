@@ -1,9 +1,10 @@
-"""Soft-capped tree attention (dta_tree_attn_fwd_cap / _bwd_cap) against the float64 reference of tests/softcap_ref64.py with the
+"""Soft-capped tree attention (dta_tree_attn_fwd / _bwd with softcap > 0) against the float64 reference of tests/softcap_ref64.py with the
 per-row error bound of tests/attn_ref64.py (check_all and its constants C, unchanged; the limit is err / bound <= 1).  Scores are
 c tanh(scale q.k / c), capped before the visibility mask.  Cases: packed tries whose chain ends and forks sit on the 64 / 128 tile edges
-(the generators of the window tests), the stack form with a non-zero q_offset and 1 .. 200 query rows, D = 64 and 128, (4, 2) and
-(2, 1) heads, bf16 / f16 / fp32, the cap alone and with a window whose edge lies inside a tile; a saturated case (|z| / c about 8);
-softcap = 0 must give the bits of the _win entry; forced dK/dV splits must be bitwise reproducible; accumulate 1 and 2.
+(the generators of the window tests), the stack form with a non-zero q_offset and 1 .. 200 query rows, D = 64 and 128, (4, 2),
+(2, 1) and (3, 1) heads (head pairs; one pair plus the odd head of the one-head launch), bf16 / f16 / fp32, the cap alone and with a
+window whose edge lies inside a tile; a saturated case (|z| / c about 8);
+softcap <= 0 must give the bits of the uncapped run; forced dK/dV splits must be bitwise reproducible; accumulate 1 and 2.
 
 Condition on the inputs: in every counted case the float64 references WITH and WITHOUT the cap differ, for every tensor, by at least
 10 x the bound on some row (softcap_ref64.assert_cap_matters, from the references alone) - otherwise an uncapped kernel would pass.
@@ -35,7 +36,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 CAP = 2.0
-HEADS = [(4, 2), (2, 1)]
+HEADS = [(4, 2), (2, 1), (3, 1)]
 ROWS = [1, 63, 64, 65, 129, 200]
 
 
@@ -134,9 +135,9 @@ def test_cap_saturated_scores_stay_finite(D, dtype):
     _packed(W._prefix_trie(128), 70, 4, 2, D, dtype, seed=11, sigma=4.0)
 
 
-# ------------------------------------------------------------------------------------------------ softcap = 0: the _win entry, bit for bit
+# ------------------------------------------------------------------------------------------------ softcap <= 0: the uncapped run, bit for bit
 def _cap_entry(q, k, v, do, meta, scale, softcap, accumulate=0):
-    """dta_tree_attn_fwd_cap / _bwd_cap called directly (ops routes softcap = 0 to the _win / _ex entries itself)."""
+    """dta_tree_attn_fwd / _bwd called directly (ops refuses a negative cap; the entries take it as no cap)."""
     Tq, Hq, D = q.shape
     Tk, Hkv, _ = k.shape
     out = torch.empty_like(q); lse = torch.empty(Hq, Tq, dtype=F32, device=DEV); delta = torch.empty_like(lse)
@@ -149,13 +150,13 @@ def _cap_entry(q, k, v, do, meta, scale, softcap, accumulate=0):
     nu, ns = (0 if units is None else units.shape[0]), (0 if splits is None else splits.shape[0])
     ws = torch.empty((meta.n_slabs, Hkv, 2, packing.KTILE, D), dtype=F32, device=DEV) if (units is not None and meta.n_slabs) else None
     stream = torch.cuda.current_stream().cuda_stream
-    rc = lib().dta_tree_attn_fwd_cap(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs),
-                                     Tq, Tk, meta.q_offset, Hq, Hkv, D, *st(q), *st(k), *st(v), *st(out), scale, ops._DT[q.dtype], *win, softcap, stream)
+    rc = lib().dta_tree_attn_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs),
+                                 Tq, Tk, meta.q_offset, Hq, Hkv, D, *st(q), *st(k), *st(v), *st(out), scale, ops._DT[q.dtype], *win, softcap, stream)
     assert rc == 0, rc
-    rc = lib().dta_tree_attn_bwd_cap(ptr(q), ptr(k), ptr(v), ptr(out), ptr(do), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
-                                     ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs), ptr(meta.ktile_qend),
-                                     Tq, Tk, meta.q_offset, Hq, Hkv, D, *st(q), *st(k), *st(v), *st(out), *st(dq), *st(dk), scale, ops._DT[q.dtype],
-                                     accumulate, 3, ptr(units), nu, ptr(splits) if ns else None, ns, ptr(ws), *win, softcap, stream)
+    rc = lib().dta_tree_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(do), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
+                                 ptr(meta.subtree_end), ptr(meta.run_ptr), ptr(meta.runs), ptr(meta.ktile_qend),
+                                 Tq, Tk, meta.q_offset, Hq, Hkv, D, *st(q), *st(k), *st(v), *st(out), *st(dq), *st(dk), scale, ops._DT[q.dtype],
+                                 accumulate, 3, ptr(units), nu, ptr(splits) if ns else None, ns, ptr(ws), *win, softcap, stream)
     assert rc == 0, rc
     torch.cuda.synchronize()
     return out, lse, dq, dk, dv
@@ -182,8 +183,8 @@ def test_softcap_zero_is_the_win_entry_bitwise(D, dtype):
     for bad in (float("nan"), float("inf")):
         out = torch.empty_like(q); lse = torch.empty(4, plan.T, dtype=F32, device=DEV)
         st = lambda t: (t.stride(0), t.stride(1))
-        assert lib().dta_tree_attn_fwd_cap(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(full.subtree_end), ptr(full.run_ptr), ptr(full.runs),
-                                           plan.T, plan.T, 0, 4, 2, D, *st(q), *st(k), *st(v), *st(out), scale, ops._DT[dtype], None, 0, bad, None) == -1
+        assert lib().dta_tree_attn_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(full.subtree_end), ptr(full.run_ptr), ptr(full.runs),
+                                       plan.T, plan.T, 0, 4, 2, D, *st(q), *st(k), *st(v), *st(out), scale, ops._DT[dtype], None, 0, bad, None) == -1
 
 
 # ------------------------------------------------------------------------------------------------ forced dK/dV splits

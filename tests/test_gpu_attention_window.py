@@ -1,8 +1,8 @@
-"""Sliding-window tree attention (dta_tree_attn_fwd_win / _bwd_win) against a float64 reference with the per-row error bound of
+"""Sliding-window tree attention (dta_tree_attn_fwd / _bwd with window > 0) against a float64 reference with the per-row error bound of
 tests/attn_ref64.py (its check helpers and constants, imported).  Visibility: key s is seen by row t iff it is an ancestor-or-self
 (s <= t < subtree_end[s]; stack form: s <= t) and depth[t] - depth[s] < W.  The cases put chain ends, forks, stack offsets and the
 window itself on the 64 / 128 tile edges, for D = 64 and 128, bf16 / f16 / fp32 and several GQA geometries; forced dK/dV splits
-must be bitwise reproducible; no window and a window wider than the trie must give the bits of the _ex path."""
+must be bitwise reproducible; no window and a window wider than the trie must give the bits of the run without a window."""
 import dataclasses
 
 import numpy as np
@@ -231,7 +231,7 @@ def test_window_forced_dkv_splits(W, D, dtype):
         assert bool(((a - b).norm(dim=-1) <= 2 * R.U[dtype] * b.norm(dim=-1) + 1e-30).all())
 
 
-# ------------------------------------------------------------------------------------------------ no window = the _ex path, bit for bit
+# ------------------------------------------------------------------------------------------------ no window = the kernels without one, bit for bit
 @pytest.mark.parametrize("dtype", [BF, F32])
 @pytest.mark.parametrize("D", [64, 128])
 def test_no_window_and_wide_window_equal_ex_bitwise(D, dtype):
@@ -266,18 +266,18 @@ def test_window_c_interface_codes():
     dl = torch.zeros(Hq, T, device=DEV); dq = torch.empty_like(q); dk = torch.empty_like(kv); dv = torch.empty_like(kv)
 
     def fwd(se_, wl_, W):
-        return lib().dta_tree_attn_fwd_win(P(q), P(kv), P(kv), P(o), P(lse), P(se_), None, None, T, T, 0, Hq, Hkv, hd,
-                                           Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, 0.1, 0, P(wl_), W, None)
+        return lib().dta_tree_attn_fwd(P(q), P(kv), P(kv), P(o), P(lse), P(se_), None, None, T, T, 0, Hq, Hkv, hd,
+                                       Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, 0.1, 0, P(wl_), W, 0.0, None)
 
     def bwd(se_, wl_, W):
-        return lib().dta_tree_attn_bwd_win(P(q), P(kv), P(kv), P(o), P(o), P(lse), P(dl), P(dq), P(dk), P(dv), P(se_), None, None, None,
-                                           T, T, 0, Hq, Hkv, hd, Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, Hq * hd, hd,
-                                           Hkv * hd, hd, 0.1, 0, 0, 3, None, 0, None, 0, None, P(wl_), W, None)
+        return lib().dta_tree_attn_bwd(P(q), P(kv), P(kv), P(o), P(o), P(lse), P(dl), P(dq), P(dk), P(dv), P(se_), None, None, None,
+                                       T, T, 0, Hq, Hkv, hd, Hq * hd, hd, Hkv * hd, hd, Hkv * hd, hd, Hq * hd, hd, Hq * hd, hd,
+                                       Hkv * hd, hd, 0.1, 0, 0, 3, None, 0, None, 0, None, P(wl_), W, 0.0, None)
     for f in (fwd, bwd):
         assert f(se, wl, 0) == -1              # win_lo without a window
         assert f(None, wl, -3) == -1
         assert f(se, None, 8) == -1            # packed trie without win_lo
-        assert f(se, None, 0) == 0             # no window: the _ex call
+        assert f(se, None, 0) == 0             # no window
         assert f(se, wl, 8) == 0
         assert f(None, None, 8) == 0           # stack form
         torch.cuda.synchronize()
