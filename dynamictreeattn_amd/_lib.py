@@ -24,17 +24,12 @@ _PROTOS = {
     "dta_tree_attn_bwd": ([_vp] * 14 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _i32, _i32] + [_vp, _i32, _vp, _i32, _vp]
                           + [_vp, _i32, _f32, _vp], C.c_int),
     "dta_window_lo": ([_vp] * 4 + [_i32, _i32, _i32, _vp, _vp], C.c_int),
-    "dta_logprob_entropy_fwd": ([_vp] * 8 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
-    "dta_logprob_entropy_shard_stats": ([_vp] * 6 + [_i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
-    "dta_logprob_entropy_bwd": ([_vp] * 10 + [_i32, _i32, _i64, _i64, _f32, _i32, _vp], C.c_int),
-    "dta_logprob_entropy_fwd_cap": ([_vp] * 8 + [_i32, _i32, _i64, _f32, _i32, _f32, _vp], C.c_int),
-    "dta_logprob_entropy_shard_stats_cap": ([_vp] * 6 + [_i32, _i32, _i64, _f32, _i32, _f32, _vp], C.c_int),
-    "dta_logprob_entropy_bwd_cap": ([_vp] * 10 + [_i32, _i32, _i64, _i64, _f32, _i32, _f32, _vp], C.c_int),
-    "dta_rmsnorm_fwd": ([_vp] * 6 + [_i32, _i32, _f32, _i32, _vp], C.c_int),
+    "dta_logprob_entropy_fwd": ([_vp] * 8 + [_i32, _i32, _i64, _f32, _i32, _f32, _vp], C.c_int),
+    "dta_logprob_entropy_shard_stats": ([_vp] * 6 + [_i32, _i32, _i64, _f32, _i32, _f32, _vp], C.c_int),
+    "dta_logprob_entropy_bwd": ([_vp] * 10 + [_i32, _i32, _i64, _i64, _f32, _i32, _f32, _vp], C.c_int),
+    "dta_rmsnorm_fwd": ([_vp] * 6 + [_i32, _i32, _f32, _f32, _i32, _vp], C.c_int),
     "dta_rmsnorm_bwd_blocks": ([_i32], C.c_int),
-    "dta_rmsnorm_bwd": ([_vp] * 7 + [_i32, _i32, _i32, _vp], C.c_int),
-    "dta_rmsnorm_fwd_off": ([_vp] * 6 + [_i32, _i32, _f32, _f32, _i32, _vp], C.c_int),
-    "dta_rmsnorm_bwd_off": ([_vp] * 7 + [_i32, _i32, _f32, _i32, _vp], C.c_int),
+    "dta_rmsnorm_bwd": ([_vp] * 7 + [_i32, _i32, _f32, _i32, _vp], C.c_int),
     "dta_qk_norm_rope_fwd": ([_vp] * 5 + [_i32, _i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_qk_norm_rope_bwd_blocks": ([_i64], C.c_int),
     "dta_qk_norm_rope_bwd": ([_vp] * 7 + [_i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp], C.c_int),

@@ -38,6 +38,14 @@ template <class F> inline void dta_attn_form(const DtaAttnArgs& a, F&& f) {
   else { if (a.window > 0) f(Y{}, N{}); else f(N{}, N{}); }
 }
 
+// The storage type of a row-kernel call, chosen once: f(DT) with DT a std::integral_constant of DTA_BF16 / DTA_F16 / DTA_F32.  The entry
+// has refused every other dtype before.
+template <class F> inline void dta_storage_type(int32_t dtype, F&& f) {
+  if (dtype == DTA_BF16) f(std::integral_constant<int, DTA_BF16>{});
+  else if (dtype == DTA_F16) f(std::integral_constant<int, DTA_F16>{});
+  else f(std::integral_constant<int, DTA_F32>{});
+}
+
 // fp32 tree attention (tree_attn_f32.hip, head_dim 64 or 128): what dta_tree_attn_fwd / dta_tree_attn_bwd launch for dtype DTA_F32, after
 // their argument checks
 int dta_attn_fwd_f32(const DtaAttnArgs& a);

@@ -42,7 +42,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 // ---------------------------------------------------------------------------------------------
 // RMSNorm over rows of H (H % 8 == 0; forward: any H, backward: H <= 8192).  One wave per row, 4 rows per workgroup, grid-stride.
 // ---------------------------------------------------------------------------------------------
-// OFF (dta_rmsnorm_fwd_off / _bwd_off, the Gemma form): y = cast(x·r·(w_off + w)) - the weight offset is added in fp32 inside the kernel and the
+// OFF (w_offset != 0, the Gemma form): y = cast(x·r·(w_off + w)) - the weight offset is added in fp32 inside the kernel and the
 // product is rounded ONCE (the default form rounds x·r to the storage type first, as Qwen3RMSNorm does).  OFF = false: w_off is unused.
 template <int DT, int NA, bool OFF = false>
 __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const void* __restrict__ x_, const void* __restrict__ delta_, const void* __restrict__ w_,
@@ -540,96 +540,91 @@ __global__ __launch_bounds__(256) void sum_slabs_flat_kernel(const float* __rest
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int row_blocks(int64_t rows, int per_block, int cap) { int64_t b = (rows + per_block - 1) / per_block; return (int)(b < cap ? (b > 0 ? b : 1) : cap); }
 
+template <int N> using Int = std::integral_constant<int, N>;
+
+// The kernel form of an RMSNorm call, chosen once for both directions: f(NA, OFF).  NA = 16-byte groups per lane: rows of up to 1 024 /
+// 2 048 / 4 096 elements stay in registers between the two passes (backward: where that fits, see KEEP); WIDE = the NA of longer rows
+// (forward 0: any H, the row is read twice; backward 16: H <= 8192).  w_offset == 0 selects the kernels compiled without the offset.
+template <int WIDE, class F> inline void rms_form(int H, float w_offset, F&& f) {
+  auto by_h = [&](auto off) {
+    if (H <= 1024) f(Int<2>{}, off);
+    else if (H <= 2048) f(Int<4>{}, off);
+    else if (H <= 4096) f(Int<8>{}, off);
+    else f(Int<WIDE>{}, off);
+  };
+  if (w_offset != 0.f) by_h(std::true_type{}); else by_h(std::false_type{});
+}
+
+// The kernel form of a head-norm / RoPE call: f(HPL, D) with HPL = 4 heads per lane group when NH % 4 == 0, and D = head_dim (64 or 128)
+template <class F> inline void qk_form(int NH, int head_dim, F&& f) {
+  if (head_dim == 64) { if (NH % 4 == 0) f(Int<4>{}, Int<64>{}); else f(Int<1>{}, Int<64>{}); }
+  else if (NH % 4 == 0) f(Int<4>{}, Int<128>{}); else f(Int<1>{}, Int<128>{});
+}
+
+// SwiGLU and GeGLU: one checked body per direction; kernel_of(DT) is the entry's kernel for the storage type DT
+template <class K>
+int glu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream, K kernel_of) {
+  if (!gate || !up || !y || rows <= 0 || cols <= 0 || ld < cols) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8) return DTA_EUNSUPPORTED;
+  if (!al16(gate) || !al16(up) || !al16(y)) return DTA_EALIGN;
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const int64_t n8 = rows * (cols / 8);
+  dta_storage_type(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(kernel_of(dt), dim3(row_blocks(n8, 256, 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), gate, up, y, n8, cols / 8, ld);
+  });
+  return DTA_LAUNCH_STATUS();
+}
+
+template <class K>
+int glu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void* dup, int64_t rows, int32_t cols, int64_t ld, int64_t ld_grad,
+            int32_t dtype, void* stream, K kernel_of) {
+  if (!gate || !up || !dy || !dgate || !dup || rows <= 0 || cols <= 0 || ld < cols || ld_grad < cols) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8 || ld_grad % 8) return DTA_EUNSUPPORTED;
+  if (!al16(gate) || !al16(up) || !al16(dy) || !al16(dgate) || !al16(dup)) return DTA_EALIGN;
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const int64_t n8 = rows * (cols / 8);
+  dta_storage_type(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(kernel_of(dt), dim3(row_blocks(n8, 256, 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), gate, up, dy, dgate, dup, n8,
+                       cols / 8, ld, ld_grad);
+  });
+  return DTA_LAUNCH_STATUS();
+}
+
 }  // namespace
 
-#define DTA_DISPATCH(KERNEL, GRID, ...)                                                                    \
-  do { hipStream_t st_ = static_cast<hipStream_t>(stream); DTA_REFUSE_IF_PRIOR_ERROR();                    \
-       if (dtype == DTA_BF16) hipLaunchKernelGGL(KERNEL<DTA_BF16>, dim3(GRID), dim3(256), 0, st_, __VA_ARGS__); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL(KERNEL<DTA_F16>, dim3(GRID), dim3(256), 0, st_, __VA_ARGS__); \
-       else hipLaunchKernelGGL(KERNEL<DTA_F32>, dim3(GRID), dim3(256), 0, st_, __VA_ARGS__);               \
-       return DTA_LAUNCH_STATUS(); } while (0)
-
-extern "C" int dta_rmsnorm_fwd_off(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
-                                   int32_t R, int32_t H, float eps, float w_offset, int32_t dtype, void* stream) {
-  if (w_offset == 0.f) return dta_rmsnorm_fwd(x, delta, w, x_out, y, rstd, R, H, eps, dtype, stream);      // the default form, bit for bit
+extern "C" int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
+                               int32_t R, int32_t H, float eps, float w_offset, int32_t dtype, void* stream) {
   if (!x || !w || !y || !rstd || R <= 0 || H <= 0 || ((delta != nullptr) != (x_out != nullptr)) || w_offset != w_offset) return DTA_EINVAL;
   if (!row_dtype_ok(dtype) || H % 8) return DTA_EUNSUPPORTED;
   if (!al16(x) || !al16(w) || !al16(y) || (delta && (!al16(delta) || !al16(x_out)))) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
   const dim3 grid(row_blocks(R, 4, 8192)), block(256);
-#define DTA_RMS_FWD(NA_)                                                                                                       \
-  do { if (dtype == DTA_BF16) hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_BF16, NA_, true>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps, w_offset); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_F16, NA_, true>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps, w_offset); \
-       else hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_F32, NA_, true>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps, w_offset); } while (0)
-  if (H <= 1024) DTA_RMS_FWD(2);
-  else if (H <= 2048) DTA_RMS_FWD(4);
-  else if (H <= 4096) DTA_RMS_FWD(8);
-  else DTA_RMS_FWD(0);
-#undef DTA_RMS_FWD
-  return DTA_LAUNCH_STATUS();
-}
-
-extern "C" int dta_rmsnorm_bwd_off(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
-                                   int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream) {
-  if (w_offset == 0.f) return dta_rmsnorm_bwd(x, w, dy, dres, rstd, dx, dw_partial, R, H, dtype, stream);
-  if (!x || !w || !dy || !rstd || !dx || R <= 0 || H <= 0 || w_offset != w_offset) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || H % 8 || H > 8192) return DTA_EUNSUPPORTED;
-  if (!al16(x) || !al16(w) || !al16(dy) || !al16(dx) || (dres && !al16(dres))) return DTA_EALIGN;
-  hipStream_t st_ = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
-  const dim3 grid(row_blocks(R, 4, 2048)), block(256);
-#define DTA_RMS_BWD(NA_)                                                                                                       \
-  do { if (dtype == DTA_BF16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_BF16, NA_, true>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_F16, NA_, true>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset); \
-       else hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_F32, NA_, true>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset); } while (0)
-  if (H <= 1024) DTA_RMS_BWD(2);
-  else if (H <= 2048) DTA_RMS_BWD(4);
-  else if (H <= 4096) DTA_RMS_BWD(8);
-  else DTA_RMS_BWD(16);
-#undef DTA_RMS_BWD
-  return DTA_LAUNCH_STATUS();
-}
-
-extern "C" int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
-                               int32_t R, int32_t H, float eps, int32_t dtype, void* stream) {
-  if (!x || !w || !y || !rstd || R <= 0 || H <= 0 || ((delta != nullptr) != (x_out != nullptr))) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || H % 8) return DTA_EUNSUPPORTED;
-  if (!al16(x) || !al16(w) || !al16(y) || (delta && (!al16(delta) || !al16(x_out)))) return DTA_EALIGN;
-  hipStream_t st_ = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
-  const dim3 grid(row_blocks(R, 4, 8192)), block(256);
-#define DTA_RMS_FWD(NA_)                                                                                                       \
-  do { if (dtype == DTA_BF16) hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_BF16, NA_>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_F16, NA_>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps); \
-       else hipLaunchKernelGGL((rmsnorm_fwd_kernel<DTA_F32, NA_>), grid, block, 0, st_, x, delta, w, x_out, y, rstd, R, H, eps); } while (0)
-  if (H <= 1024) DTA_RMS_FWD(2);                 // rows of up to 1 024 / 2 048 / 4 096 elements stay in registers between the two passes
-  else if (H <= 2048) DTA_RMS_FWD(4);
-  else if (H <= 4096) DTA_RMS_FWD(8);
-  else DTA_RMS_FWD(0);
-#undef DTA_RMS_FWD
+  rms_form<0>(H, w_offset, [&](auto na, auto off) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((rmsnorm_fwd_kernel<decltype(dt)::value, decltype(na)::value, decltype(off)::value>), grid, block, 0, st_,
+                         x, delta, w, x_out, y, rstd, R, H, eps, w_offset);
+    });
+  });
   return DTA_LAUNCH_STATUS();
 }
 
 /* dw_partial: float [dta_rmsnorm_bwd_blocks(R), H]; the caller sums it over dim 0.  NULL: the weight needs no gradient, dx only. */
 extern "C" int dta_rmsnorm_bwd_blocks(int32_t R) { return row_blocks(R, 4, 2048); }
 extern "C" int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
-                               int32_t R, int32_t H, int32_t dtype, void* stream) {
-  if (!x || !w || !dy || !rstd || !dx || R <= 0 || H <= 0) return DTA_EINVAL;          // dw_partial NULL: dx only (frozen weight)
+                               int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream) {
+  if (!x || !w || !dy || !rstd || !dx || R <= 0 || H <= 0 || w_offset != w_offset) return DTA_EINVAL;          // dw_partial NULL: dx only (frozen weight)
   if (!row_dtype_ok(dtype) || H % 8 || H > 8192) return DTA_EUNSUPPORTED;
   if (!al16(x) || !al16(w) || !al16(dy) || !al16(dx) || (dres && !al16(dres))) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
   const dim3 grid(row_blocks(R, 4, 2048)), block(256);
-#define DTA_RMS_BWD(NA_)                                                                                                       \
-  do { if (dtype == DTA_BF16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_BF16, NA_>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_F16, NA_>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H); \
-       else hipLaunchKernelGGL((rmsnorm_bwd_kernel<DTA_F32, NA_>), grid, block, 0, st_, x, w, dy, dres, rstd, dx, dw_partial, R, H); } while (0)
-  if (H <= 1024) DTA_RMS_BWD(2);                 // NA = 16-byte groups per lane; the row stays in registers where that fits (see KEEP)
-  else if (H <= 2048) DTA_RMS_BWD(4);
-  else if (H <= 4096) DTA_RMS_BWD(8);
-  else DTA_RMS_BWD(16);
-#undef DTA_RMS_BWD
+  rms_form<16>(H, w_offset, [&](auto na, auto off) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((rmsnorm_bwd_kernel<decltype(dt)::value, decltype(na)::value, decltype(off)::value>), grid, block, 0, st_,
+                         x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset);
+    });
+  });
   return DTA_LAUNCH_STATUS();
 }
 
@@ -640,15 +635,14 @@ extern "C" int dta_qk_norm_rope_fwd(const void* x, const void* w, const float* c
   if (!al16(x) || !al16(y) || (w && !al16(w)) || x_stride_t % 8) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
-#define DTA_QK_FWD(HPL_, D_)                                                                                                   \
-  do { const int64_t n = (int64_t)T * (NH / HPL_); const int upb = 4 * (64 / (D_ / 8));                                        \
-       const dim3 grid((unsigned)((n + upb - 1) / upb)), block(256);                                                          \
-       if (dtype == DTA_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_BF16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_F16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); \
-       else hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<DTA_F32, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps); } while (0)
-  if (head_dim == 64) { if (NH % 4 == 0) DTA_QK_FWD(4, 64); else DTA_QK_FWD(1, 64); }
-  else if (NH % 4 == 0) DTA_QK_FWD(4, 128); else DTA_QK_FWD(1, 128);
-#undef DTA_QK_FWD
+  qk_form(NH, head_dim, [&](auto hpl, auto d) {
+    constexpr int HPL = decltype(hpl)::value, D = decltype(d)::value, UPB = 4 * (64 / (D / 8));       // (token, head group) units per workgroup
+    const int64_t n = (int64_t)T * (NH / HPL);
+    const dim3 grid((unsigned)((n + UPB - 1) / UPB)), block(256);
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<decltype(dt)::value, HPL, D>), grid, block, 0, st_, x, w, cos_sin, y, rstd, n, NH, x_stride_t, eps);
+    });
+  });
   return DTA_LAUNCH_STATUS();
 }
 
@@ -666,51 +660,31 @@ extern "C" int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* c
   // the grid - and with it the number of dw_partial rows the caller sized from dta_qk_norm_rope_bwd_blocks(T*NH) - depends on neither HPL nor
   // head_dim (the grid-stride loop covers any unit count; a D = 64 workgroup takes 32 units per pass instead of 16)
   const dim3 grid(row_blocks((int64_t)T * NH, 16, 1024)), block(256);
-#define DTA_QK_BWD(HPL_, D_)                                                                                                   \
-  do { const int64_t n = (int64_t)T * (NH / HPL_);                                                                            \
-       if (dtype == DTA_BF16) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_BF16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); \
-       else if (dtype == DTA_F16) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_F16, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); \
-       else hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<DTA_F32, HPL_, D_>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t); } while (0)
-  if (head_dim == 64) { if (NH % 4 == 0) DTA_QK_BWD(4, 64); else DTA_QK_BWD(1, 64); }
-  else if (NH % 4 == 0) DTA_QK_BWD(4, 128); else DTA_QK_BWD(1, 128);
-#undef DTA_QK_BWD
+  qk_form(NH, head_dim, [&](auto hpl, auto d) {
+    constexpr int HPL = decltype(hpl)::value, D = decltype(d)::value;
+    const int64_t n = (int64_t)T * (NH / HPL);
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<decltype(dt)::value, HPL, D>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH,
+                         x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t);
+    });
+  });
   return DTA_LAUNCH_STATUS();
 }
 
 extern "C" int dta_swiglu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream) {
-  if (!gate || !up || !y || rows <= 0 || cols <= 0 || ld < cols) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8) return DTA_EUNSUPPORTED;
-  if (!al16(gate) || !al16(up) || !al16(y)) return DTA_EALIGN;
-  const int64_t n8 = rows * (cols / 8);
-  DTA_DISPATCH(swiglu_fwd_kernel, row_blocks(n8, 256, 4096), gate, up, y, n8, cols / 8, ld);
+  return glu_fwd(gate, up, y, rows, cols, ld, dtype, stream, [](auto dt) { return swiglu_fwd_kernel<decltype(dt)::value>; });
 }
-
 extern "C" int dta_geglu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream) {
-  if (!gate || !up || !y || rows <= 0 || cols <= 0 || ld < cols) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8) return DTA_EUNSUPPORTED;
-  if (!al16(gate) || !al16(up) || !al16(y)) return DTA_EALIGN;
-  const int64_t n8 = rows * (cols / 8);
-  DTA_DISPATCH(geglu_fwd_kernel, row_blocks(n8, 256, 4096), gate, up, y, n8, cols / 8, ld);
+  return glu_fwd(gate, up, y, rows, cols, ld, dtype, stream, [](auto dt) { return geglu_fwd_kernel<decltype(dt)::value>; });
 }
-
 extern "C" int dta_geglu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void* dup,
                              int64_t rows, int32_t cols, int64_t ld, int64_t ld_grad, int32_t dtype, void* stream) {
-  if (!gate || !up || !dy || !dgate || !dup || rows <= 0 || cols <= 0 || ld < cols || ld_grad < cols) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8 || ld_grad % 8) return DTA_EUNSUPPORTED;
-  if (!al16(gate) || !al16(up) || !al16(dy) || !al16(dgate) || !al16(dup)) return DTA_EALIGN;
-  const int64_t n8 = rows * (cols / 8);
-  DTA_DISPATCH(geglu_bwd_kernel, row_blocks(n8, 256, 4096), gate, up, dy, dgate, dup, n8, cols / 8, ld, ld_grad);
+  return glu_bwd(gate, up, dy, dgate, dup, rows, cols, ld, ld_grad, dtype, stream, [](auto dt) { return geglu_bwd_kernel<decltype(dt)::value>; });
 }
-
 extern "C" int dta_swiglu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void* dup,
                               int64_t rows, int32_t cols, int64_t ld, int64_t ld_grad, int32_t dtype, void* stream) {
-  if (!gate || !up || !dy || !dgate || !dup || rows <= 0 || cols <= 0 || ld < cols || ld_grad < cols) return DTA_EINVAL;
-  if (!row_dtype_ok(dtype) || cols % 8 || ld % 8 || ld_grad % 8) return DTA_EUNSUPPORTED;
-  if (!al16(gate) || !al16(up) || !al16(dy) || !al16(dgate) || !al16(dup)) return DTA_EALIGN;
-  const int64_t n8 = rows * (cols / 8);
-  DTA_DISPATCH(swiglu_bwd_kernel, row_blocks(n8, 256, 4096), gate, up, dy, dgate, dup, n8, cols / 8, ld, ld_grad);
+  return glu_bwd(gate, up, dy, dgate, dup, rows, cols, ld, ld_grad, dtype, stream, [](auto dt) { return swiglu_bwd_kernel<decltype(dt)::value>; });
 }
-
 
 extern "C" int dta_transpose(const void* in, void* out, int64_t rows, int64_t cols, int64_t ld_in, int64_t ld_out, int32_t elem_size, void* stream) {
   if (!in || !out || rows <= 0 || cols <= 0 || ld_in < cols || ld_out < rows) return DTA_EINVAL;

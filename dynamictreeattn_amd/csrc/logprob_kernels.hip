@@ -8,7 +8,7 @@
 //        where G[r] = glp[r] + Σ_e g_extra_lp[e] is the summed gradient of every log-prob picked from row r.
 // One 256-thread workgroup per row, 16-byte loads, online (max, Σexp, Σexp·x) per lane, block reduce.
 // Algorithmic HBM bytes: fwd V·sizeof(e) per row (one read); bwd 2·V·sizeof(e) per row (one read, one write).
-// Final-logit soft-capping (the _cap entries, CAP = true): every statistic and pick is taken on x' = c·tanh(x/c), formed in registers as the
+// Final-logit soft-capping (softcap > 0, CAP = true): every statistic and pick is taken on x' = c·tanh(x/c), formed in registers as the
 // raw logit is loaded (no second pass over the logits); the temperature divides x'.  The backward multiplies the gradient with respect to x'
 // by 1 − tanh²(x/c) before the store.  The CAP = false kernels keep their arguments and code.
 #include <hip/hip_runtime.h>
@@ -222,24 +222,42 @@ __global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(typename std::
   }
 }
 
-int fwd_launch(FwdArgs a, int32_t dtype, float temperature, void* stream, float softcap = 0.f) {
-  if (!a.logits || a.R <= 0 || a.V <= 0 || (a.lp && !a.labels) || !(temperature > 0.f)) return DTA_EINVAL;
+// Final-logit soft-capping: softcap <= 0 selects the kernels compiled without the cap; a cap that is not finite is refused.
+bool cap_ok(float c) { return c == c && c < 3.0e38f; }
+
+int fwd_launch(FwdArgsC a, int32_t dtype, float temperature, void* stream) {
+  if (!a.logits || a.R <= 0 || a.V <= 0 || (a.lp && !a.labels) || !(temperature > 0.f) || !cap_ok(a.softcap)) return DTA_EINVAL;
   if (a.extra_ptr && (!a.extra_labels || !a.extra_lp)) return DTA_EINVAL;
   if (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) return DTA_EUNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(a.logits) & (dtype == DTA_F32 ? 31 : 15)) || (a.stride % 8)) return DTA_EALIGN;   // 8-element vector loads
   a.inv_temp = 1.f / temperature;
   hipStream_t st = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
-  if (softcap > 0.f) {
-    FwdArgsC c; static_cast<FwdArgs&>(c) = a; c.softcap = softcap;
-    if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_BF16, true>), dim3(a.R), dim3(256), 0, st, c);
-    else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F16, true>), dim3(a.R), dim3(256), 0, st, c);
-    else hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F32, true>), dim3(a.R), dim3(256), 0, st, c);
-    return DTA_LAUNCH_STATUS();
-  }
-  if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_BF16, false>), dim3(a.R), dim3(256), 0, st, a);
-  else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F16, false>), dim3(a.R), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((logprob_entropy_fwd_kernel<DTA_F32, false>), dim3(a.R), dim3(256), 0, st, a);
+  auto launch = [&](auto cap) {                              // the CAP = false kernels take the FwdArgs part of `a`
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((logprob_entropy_fwd_kernel<decltype(dt)::value, decltype(cap)::value>), dim3(a.R), dim3(256), 0, st, a);
+    });
+  };
+  if (a.softcap > 0.f) launch(std::true_type{}); else launch(std::false_type{});
+  return DTA_LAUNCH_STATUS();
+}
+
+int bwd_launch(BwdArgsC b, int32_t dtype, float temperature, void* stream) {
+  if (!b.logits || !b.out || !b.lse || b.R <= 0 || b.V <= 0 || (b.gent && !b.ent) || (b.glp && !b.labels) || !(temperature > 0.f) ||
+      !cap_ok(b.softcap)) return DTA_EINVAL;
+  if (b.extra_ptr && (!b.extra_labels || !b.gextra)) return DTA_EINVAL;
+  if (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) return DTA_EUNSUPPORTED;
+  const uintptr_t am = dtype == DTA_F32 ? 31 : 15;
+  if ((reinterpret_cast<uintptr_t>(b.logits) & am) || (reinterpret_cast<uintptr_t>(b.out) & am) || (b.stride % 8) || (b.out_stride % 8)) return DTA_EALIGN;
+  b.inv_temp = 1.f / temperature;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  auto launch = [&](auto cap) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((logprob_entropy_bwd_kernel<decltype(dt)::value, decltype(cap)::value>), dim3(b.R), dim3(256), 0, st, b);
+    });
+  };
+  if (b.softcap > 0.f) launch(std::true_type{}); else launch(std::false_type{});
   return DTA_LAUNCH_STATUS();
 }
 
@@ -247,78 +265,25 @@ int fwd_launch(FwdArgs a, int32_t dtype, float temperature, void* stream, float 
 
 extern "C" int dta_logprob_entropy_fwd(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
                                        float* lse, float* entropy, float* logprob, float* extra_logprob,
-                                       int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, void* stream) {
+                                       int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
   if (!lse) return DTA_EINVAL;
-  FwdArgs a{logits, labels, extra_ptr, extra_labels, lse, entropy, logprob, extra_logprob, nullptr, R, V, row_stride, 1.f};
-  return fwd_launch(a, dtype, temperature, stream);
+  return fwd_launch({{logits, labels, extra_ptr, extra_labels, lse, entropy, logprob, extra_logprob, nullptr, R, V, row_stride, 1.f}, softcap},
+                    dtype, temperature, stream);
 }
 
 extern "C" int dta_logprob_entropy_shard_stats(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
                                                float* stats, float* extra_picked,
-                                               int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, void* stream) {
+                                               int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
   if (!stats) return DTA_EINVAL;
-  FwdArgs a{logits, labels, extra_ptr, extra_labels, nullptr, nullptr, nullptr, extra_picked, stats, R, V, row_stride, 1.f};
-  return fwd_launch(a, dtype, temperature, stream);
-}
-
-static int bwd_launch(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
-                                       const float* lse, const float* entropy,
-                                       const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
-                                       int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
-  if (!logits || !dlogits || !lse || R <= 0 || V <= 0 || (g_entropy && !entropy) || (g_logprob && !labels) || !(temperature > 0.f)) return DTA_EINVAL;
-  if (extra_ptr && (!extra_labels || !g_extra_logprob)) return DTA_EINVAL;
-  if (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) return DTA_EUNSUPPORTED;
-  const uintptr_t am = dtype == DTA_F32 ? 31 : 15;
-  if ((reinterpret_cast<uintptr_t>(logits) & am) || (reinterpret_cast<uintptr_t>(dlogits) & am) || (row_stride % 8) || (out_row_stride % 8)) return DTA_EALIGN;
-  BwdArgs b{logits, dlogits, labels, extra_ptr, extra_labels, lse, entropy, g_logprob, g_extra_logprob, g_entropy, R, V, row_stride, out_row_stride, 1.f / temperature};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
-  if (softcap > 0.f) {
-    BwdArgsC c; static_cast<BwdArgs&>(c) = b; c.softcap = softcap;
-    if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_BF16, true>), dim3(R), dim3(256), 0, st, c);
-    else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F16, true>), dim3(R), dim3(256), 0, st, c);
-    else hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F32, true>), dim3(R), dim3(256), 0, st, c);
-    return DTA_LAUNCH_STATUS();
-  }
-  if (dtype == DTA_BF16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_BF16, false>), dim3(R), dim3(256), 0, st, b);
-  else if (dtype == DTA_F16) hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F16, false>), dim3(R), dim3(256), 0, st, b);
-  else hipLaunchKernelGGL((logprob_entropy_bwd_kernel<DTA_F32, false>), dim3(R), dim3(256), 0, st, b);
-  return DTA_LAUNCH_STATUS();
+  return fwd_launch({{logits, labels, extra_ptr, extra_labels, nullptr, nullptr, nullptr, extra_picked, stats, R, V, row_stride, 1.f}, softcap},
+                    dtype, temperature, stream);
 }
 
 extern "C" int dta_logprob_entropy_bwd(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
                                        const float* lse, const float* entropy,
                                        const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
-                                       int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype, void* stream) {
-  return bwd_launch(logits, dlogits, labels, extra_ptr, extra_labels, lse, entropy, g_logprob, g_extra_logprob, g_entropy, R, V, row_stride, out_row_stride,
-                    temperature, dtype, 0.f, stream);
-}
-
-// Final-logit soft-capping: softcap <= 0 is the plain entry, bit for bit; a cap that is not finite is refused.
-static bool cap_ok(float c) { return c == c && c < 3.0e38f; }
-
-extern "C" int dta_logprob_entropy_fwd_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
-                                           float* lse, float* entropy, float* logprob, float* extra_logprob,
-                                           int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
-  if (!lse || !cap_ok(softcap)) return DTA_EINVAL;
-  FwdArgs a{logits, labels, extra_ptr, extra_labels, lse, entropy, logprob, extra_logprob, nullptr, R, V, row_stride, 1.f};
-  return fwd_launch(a, dtype, temperature, stream, softcap);
-}
-
-extern "C" int dta_logprob_entropy_shard_stats_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
-                                                   float* stats, float* extra_picked,
-                                                   int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream) {
-  if (!stats || !cap_ok(softcap)) return DTA_EINVAL;
-  FwdArgs a{logits, labels, extra_ptr, extra_labels, nullptr, nullptr, nullptr, extra_picked, stats, R, V, row_stride, 1.f};
-  return fwd_launch(a, dtype, temperature, stream, softcap);
-}
-
-extern "C" int dta_logprob_entropy_bwd_cap(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
-                                           const float* lse, const float* entropy,
-                                           const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
-                                           int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype,
-                                           float softcap, void* stream) {
-  if (!cap_ok(softcap)) return DTA_EINVAL;
-  return bwd_launch(logits, dlogits, labels, extra_ptr, extra_labels, lse, entropy, g_logprob, g_extra_logprob, g_entropy, R, V, row_stride, out_row_stride,
-                    temperature, dtype, softcap, stream);
+                                       int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype,
+                                       float softcap, void* stream) {
+  return bwd_launch({{logits, dlogits, labels, extra_ptr, extra_labels, lse, entropy, g_logprob, g_extra_logprob, g_entropy, R, V, row_stride,
+                      out_row_stride, 1.f}, softcap}, dtype, temperature, stream);
 }

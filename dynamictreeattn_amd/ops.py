@@ -15,7 +15,6 @@ from ._lib import check, lib, ptr
 
 # DTA_BF16 / DTA_F16: the MFMA kernels; DTA_F32: fp32 models (plain-FMA attention of tree_attn_f32.hip, fp32 row kernels)
 _DT = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
-_DT_LOGITS = _DT
 
 
 class _on:
@@ -365,11 +364,6 @@ def window_meta(meta: TreeAttnMeta, plan: packing.SegmentPlan, depth: torch.Tens
 # --------------------------------------------------------------------------------------------------
 # LM head + log-prob / entropy over packed rows (HIP statistics kernels around hipBLASLt GEMMs)
 # --------------------------------------------------------------------------------------------------
-def _lp_entry(name: str, softcap: float):
-    """(entry point, trailing arguments) of a log-prob kernel call: the _cap form with the cap when softcap > 0."""
-    return (name + "_cap", (float(softcap),)) if softcap > 0 else (name, ())
-
-
 def logprob_entropy_fwd_raw(logits, labels, want_entropy=True, temperature=1.0, extra_ptr=None, extra_labels=None, extra_out=None, softcap=0.0):
     """logits [R,V] bf16/f16/f32 (row-contiguous) -> (lse, entropy|None, logprob|None) fp32 [R].
     `extra_ptr` int32 [R+1] / `extra_labels` int64 [F]: further labels per row (CSR, absolute indices); their
@@ -378,10 +372,9 @@ def logprob_entropy_fwd_raw(logits, labels, want_entropy=True, temperature=1.0, 
     lse = torch.empty(R, dtype=torch.float32, device=logits.device)
     ent = torch.empty_like(lse) if want_entropy else None
     lp = torch.empty_like(lse) if labels is not None else None
-    entry, cap = _lp_entry("dta_logprob_entropy_fwd", softcap)
-    _launch(entry, (logits, labels, extra_ptr, extra_labels, extra_out),
+    _launch("dta_logprob_entropy_fwd", (logits, labels, extra_ptr, extra_labels, extra_out),
             ptr(logits), ptr(labels), ptr(extra_ptr), ptr(extra_labels), ptr(lse), ptr(ent), ptr(lp), ptr(extra_out),
-            R, V, logits.stride(0), float(temperature), _DT_LOGITS[logits.dtype], *cap, nbytes=R * V * logits.element_size())
+            R, V, logits.stride(0), float(temperature), _DT[logits.dtype], float(softcap), nbytes=R * V * logits.element_size())
     return lse, ent, lp
 
 
@@ -390,10 +383,9 @@ def logprob_entropy_bwd_raw(logits, labels, lse, ent, g_lp, g_ent, temperature=1
     """dLoss/dlogits into `out` (None: IN PLACE over `logits`)."""
     R, V = logits.shape
     out = logits if out is None else out
-    entry, cap = _lp_entry("dta_logprob_entropy_bwd", softcap)
-    _launch(entry, (logits, out, labels, extra_ptr, extra_labels, lse, g_lp, g_extra, g_ent),
+    _launch("dta_logprob_entropy_bwd", (logits, out, labels, extra_ptr, extra_labels, lse, g_lp, g_extra, g_ent),
             ptr(logits), ptr(out), ptr(labels), ptr(extra_ptr), ptr(extra_labels), ptr(lse), ptr(ent), ptr(g_lp), ptr(g_extra), ptr(g_ent),
-            R, V, logits.stride(0), out.stride(0), float(temperature), _DT_LOGITS[logits.dtype], *cap, nbytes=2 * R * V * logits.element_size())
+            R, V, logits.stride(0), out.stride(0), float(temperature), _DT[logits.dtype], float(softcap), nbytes=2 * R * V * logits.element_size())
     return out
 
 
@@ -401,10 +393,9 @@ def logprob_entropy_shard_stats_raw(logits, labels_local, temperature=1.0, extra
     """Per-shard statistics [R,4] = {m, s, t, picked} (log2 domain) of logits [R, V/tp]; see dta.h.  Extra picks -> raw x/T or 0."""
     R, V = logits.shape
     stats = torch.empty((R, 4), dtype=torch.float32, device=logits.device)
-    entry, cap = _lp_entry("dta_logprob_entropy_shard_stats", softcap)
-    _launch(entry, (logits, labels_local, extra_ptr, extra_labels, extra_out),
+    _launch("dta_logprob_entropy_shard_stats", (logits, labels_local, extra_ptr, extra_labels, extra_out),
             ptr(logits), ptr(labels_local), ptr(extra_ptr), ptr(extra_labels), ptr(stats), ptr(extra_out),
-            R, V, logits.stride(0), float(temperature), _DT_LOGITS[logits.dtype], *cap, nbytes=R * V * logits.element_size())
+            R, V, logits.stride(0), float(temperature), _DT[logits.dtype], float(softcap), nbytes=R * V * logits.element_size())
     return stats
 
 
@@ -616,7 +607,7 @@ def _rows_for_kernel(logits2d):
 def logprob_entropy(logits2d, labels1d, temperature=1.0, want_entropy=True, tp_group=None):
     """(logprob [R], entropy [R] | None) of CUDA logits [R, V] through the HIP kernels; labels1d int64 [R], -1 = none.
     With `tp_group`, logits hold this rank's vocabulary slice (rank * V .. ) and labels are global ids."""
-    if logits2d.dtype not in _DT_LOGITS:
+    if logits2d.dtype not in _DT:
         raise TypeError("logprob_entropy supports bf16 / f16 / f32 logits (got %s)" % logits2d.dtype)
     x = _rows_for_kernel(logits2d)
     if tp_group is None:
@@ -634,7 +625,7 @@ def logprob_entropy(logits2d, labels1d, temperature=1.0, want_entropy=True, tp_g
 # --------------------------------------------------------------------------------------------------
 class _RMSNorm(torch.autograd.Function):
     """(x_out, y) = (x + delta, rmsnorm(x + delta) * w); delta may be None (then x_out is x itself).  w_offset != 0 (Gemma: 1):
-    y = rmsnorm(x + delta) * (w_offset + w) with the sum formed in fp32 inside the kernel and one rounding (dta_rmsnorm_fwd_off)."""
+    y = rmsnorm(x + delta) * (w_offset + w) with the sum formed in fp32 inside the kernel and one rounding."""
 
     @staticmethod
     def forward(ctx, x, delta, w, eps, w_offset=0.0):
@@ -648,9 +639,9 @@ class _RMSNorm(torch.autograd.Function):
             xo = torch.empty_like(x2)
         else:
             d2, xo = None, None
-        off = (float(w_offset),) if w_offset else ()
-        _launch("dta_rmsnorm_fwd_off" if off else "dta_rmsnorm_fwd", (x2, d2, w), ptr(x2), ptr(d2), ptr(w), ptr(xo), ptr(y), ptr(rstd), R, H, float(eps),
-                *off, _DT[x.dtype], nbytes=R * H * x2.element_size() * (4 if delta is not None else 2))
+        off = float(w_offset)
+        _launch("dta_rmsnorm_fwd", (x2, d2, w), ptr(x2), ptr(d2), ptr(w), ptr(xo), ptr(y), ptr(rstd), R, H, float(eps), off, _DT[x.dtype],
+                nbytes=R * H * x2.element_size() * (4 if delta is not None else 2))
         xin = xo if xo is not None else x2
         ctx.save_for_backward(xin, w, rstd)
         ctx.has_delta, ctx.off = delta is not None, off
@@ -665,8 +656,8 @@ class _RMSNorm(torch.autograd.Function):
         dx = torch.empty_like(x2)
         need_w = ctx.needs_input_grad[2]          # a frozen norm weight is still read (dx depends on it) but gets no partials and no sum
         part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, dtype=torch.float32, device=x2.device) if need_w else None
-        _launch("dta_rmsnorm_bwd_off" if ctx.off else "dta_rmsnorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(rstd), ptr(dx),
-                ptr(part), R, H, *ctx.off, _DT[x2.dtype], nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
+        _launch("dta_rmsnorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(rstd), ptr(dx), ptr(part), R, H, ctx.off, _DT[x2.dtype],
+                nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
         dx = dx.view(dy.shape)
         return dx, (dx if ctx.has_delta else None), (sum_slabs(part, w.dtype) if need_w else None), None, None
 
@@ -680,6 +671,29 @@ def add_rms_norm(x: torch.Tensor, delta: Optional[torch.Tensor], w: torch.Tensor
     return _RMSNorm.apply(x, delta, w, eps, float(w_offset))
 
 
+def _qk_norm_rope_fwd(x, w, cos_sin, eps):
+    """One dta_qk_norm_rope_fwd launch over x [T, NH, D] (rows of D contiguous, any token stride): (y contiguous, rstd | None without w)."""
+    T, NH, D = x.shape
+    y = torch.empty((T, NH, D), dtype=x.dtype, device=x.device)
+    rstd = torch.empty(T * NH, dtype=torch.float32, device=x.device) if w is not None else None
+    _launch("dta_qk_norm_rope_fwd", (x, w, cos_sin), ptr(x), ptr(w), ptr(cos_sin), ptr(y), ptr(rstd), T, NH, D, x.stride(0), float(eps),
+            _DT[x.dtype], nbytes=2 * T * NH * D * x.element_size() + T * D * 4)
+    return y, rstd
+
+
+def _qk_norm_rope_bwd(x, w, cos_sin, dy, rstd, dx, need_w):
+    """One dta_qk_norm_rope_bwd launch into dx [T, NH, D] (any token stride; may be dy); w None: RoPE only.  Returns dw (None unless
+    w is given and need_w)."""
+    T, NH, D = x.shape
+    if dy.stride(2) != 1:
+        dy = dy.contiguous()
+    part = torch.empty(lib().dta_qk_norm_rope_bwd_blocks(T * NH), D, dtype=torch.float32, device=x.device) if w is not None and need_w else None
+    _launch("dta_qk_norm_rope_bwd", (x, cos_sin, dy), ptr(x), ptr(w), ptr(cos_sin), ptr(dy), ptr(rstd) if w is not None else None,
+            ptr(dx), ptr(part), T, NH, D, x.stride(0), dy.stride(0), dy.stride(1), dx.stride(0), _DT[x.dtype],
+            nbytes=(3 if w is not None else 2) * T * NH * D * x.element_size() + T * D * 4)
+    return sum_slabs(part, w.dtype) if part is not None else None
+
+
 class _QKNormRope(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, cos_sin, eps):
@@ -687,10 +701,7 @@ class _QKNormRope(torch.autograd.Function):
         T, NH, D = x.shape
         if x.stride(2) != 1 or x.stride(1) != D:
             x = x.contiguous()
-        y = torch.empty((T, NH, D), dtype=x.dtype, device=x.device)
-        rstd = torch.empty(T * NH, dtype=torch.float32, device=x.device) if w is not None else None
-        _launch("dta_qk_norm_rope_fwd", (x, w, cos_sin), ptr(x), ptr(w), ptr(cos_sin), ptr(y), ptr(rstd), T, NH, D, x.stride(0), float(eps),
-                _DT[x.dtype], nbytes=2 * T * NH * D * x.element_size() + T * D * 4)
+        y, rstd = _qk_norm_rope_fwd(x, w, cos_sin, eps)
         ctx.save_for_backward(x, w if w is not None else cos_sin, cos_sin, rstd if rstd is not None else cos_sin)
         ctx.has_w = w is not None
         return y
@@ -698,17 +709,9 @@ class _QKNormRope(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, cos_sin, rstd = ctx.saved_tensors
-        T, NH, D = x.shape
-        if dy.stride(2) != 1:
-            dy = dy.contiguous()
-        dx = torch.empty((T, NH, D), dtype=x.dtype, device=x.device)
-        part = None
-        if ctx.has_w and ctx.needs_input_grad[1]:
-            part = torch.empty(lib().dta_qk_norm_rope_bwd_blocks(T * NH), D, dtype=torch.float32, device=x.device)
-        _launch("dta_qk_norm_rope_bwd", (x, cos_sin, dy), ptr(x), ptr(w) if ctx.has_w else None, ptr(cos_sin), ptr(dy), ptr(rstd) if ctx.has_w else None,
-                ptr(dx), ptr(part), T, NH, D, x.stride(0), dy.stride(0), dy.stride(1), dx.stride(0), _DT[x.dtype],
-                nbytes=(3 if ctx.has_w else 2) * T * NH * D * x.element_size() + T * D * 4)
-        return dx, (sum_slabs(part, w.dtype) if part is not None else None), None, None
+        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        dw = _qk_norm_rope_bwd(x, w if ctx.has_w else None, cos_sin, dy, rstd, dx, ctx.needs_input_grad[1])
+        return dx, dw, None, None
 
 
 class _QKVPrep(torch.autograd.Function):
@@ -723,11 +726,8 @@ class _QKVPrep(torch.autograd.Function):
         T, H3, D = qkv.shape
         assert H3 == Hq + 2 * Hkv and qkv.is_contiguous()
         outs, rstds = [], []
-        for x, w, NH in ((qkv[:, :Hq], wq, Hq), (qkv[:, Hq:Hq + Hkv], wk, Hkv)):
-            y = torch.empty((T, NH, D), dtype=qkv.dtype, device=qkv.device)
-            rstd = torch.empty(T * NH, dtype=torch.float32, device=qkv.device) if w is not None else None
-            _launch("dta_qk_norm_rope_fwd", (qkv, w, cos_sin), ptr(x), ptr(w), ptr(cos_sin), ptr(y), ptr(rstd), T, NH, D, qkv.stride(0), float(eps),
-                    _DT[qkv.dtype], nbytes=2 * T * NH * D * qkv.element_size() + T * D * 4)
+        for x, w in ((qkv[:, :Hq], wq), (qkv[:, Hq:Hq + Hkv], wk)):
+            y, rstd = _qk_norm_rope_fwd(x, w, cos_sin, eps)
             outs.append(y); rstds.append(rstd if rstd is not None else cos_sin)
         ctx.save_for_backward(qkv, wq if wq is not None else cos_sin, wk if wk is not None else cos_sin, cos_sin, rstds[0], rstds[1])
         ctx.has_w = (wq is not None, wk is not None)
@@ -750,13 +750,7 @@ class _QKVPrep(torch.autograd.Function):
         dws = []
         for lo, NH, w, rstd, has_w, need_w, dy in ((0, Hq, wq, rq, ctx.has_w[0], ctx.needs_input_grad[1], dq),
                                                    (Hq, Hkv, wk, rk, ctx.has_w[1], ctx.needs_input_grad[2], dk)):
-            if dy.stride(2) != 1:
-                dy = dy.contiguous()
-            part = torch.empty(lib().dta_qk_norm_rope_bwd_blocks(T * NH), D, dtype=torch.float32, device=qkv.device) if has_w and need_w else None
-            _launch("dta_qk_norm_rope_bwd", (qkv, cos_sin, dy), ptr(qkv[:, lo:lo + NH]), ptr(w) if has_w else None, ptr(cos_sin), ptr(dy),
-                    ptr(rstd) if has_w else None, ptr(d[:, lo:lo + NH]), ptr(part), T, NH, D, qkv.stride(0), dy.stride(0), dy.stride(1), d.stride(0),
-                    _DT[qkv.dtype], nbytes=(3 if has_w else 2) * T * NH * D * qkv.element_size() + T * D * 4)
-            dws.append(sum_slabs(part, w.dtype) if part is not None else None)
+            dws.append(_qk_norm_rope_bwd(qkv[:, lo:lo + NH], w if has_w else None, cos_sin, dy, rstd, d[:, lo:lo + NH], need_w))
         if not in_place:
             d[:, Hq + Hkv:].copy_(dv)
         return d, dws[0], dws[1], None, None, None, None

@@ -36,7 +36,7 @@ def _rows(logits: torch.Tensor, labels: torch.Tensor):
 def _device_logprob_entropy(logits2d, labels1d, temperature, want_entropy, tp_group):
     """(logprob [R], entropy [R] | None): the HIP operator.  Raises for host tensors (ops._on) and when the library is missing."""
     from . import ops
-    if logits2d.dtype not in ops._DT_LOGITS:
+    if logits2d.dtype not in ops._DT:
         if not logits2d.is_floating_point():
             raise TypeError(f"logits must be floating point (got {logits2d.dtype})")
         logits2d = logits2d.float()               # e.g. float64: the reference computes in fp32 whatever comes in (vocab_parallel.py:14,22)

@@ -187,41 +187,33 @@ int dta_window_lo(const int32_t* depth, const int32_t* seg_off, const int32_t* s
  * extra_logprob[f] = x[extra_labels[f]]/T - lse[row of f].
  * bwd writes dLoss/dlogits to `dlogits` (== logits: in place) given g_logprob[r], g_extra_logprob[F] and g_entropy[r]
  * (each may be NULL), including the one-hot terms of every pick.
+ * Final-logit soft-capping (Gemma-2's final_logit_softcapping), softcap > 0: the three entries work on x' = c * tanh(x / c), c = softcap.
+ * The cap is applied to the raw logit as it is loaded (no second pass over the [R, V] logits); lse, entropy, the label pick and the extra
+ * picks are all statistics of x', and the temperature divides x'.  The backward reads each raw x once (in place: dlogits == logits) and
+ * multiplies the gradient with respect to x' by 1 - tanh^2(x / c) before the store.  The cap is elementwise and comes before the
+ * shard statistics, so the cross-rank combine is unchanged.  softcap <= 0 selects the kernels compiled without the cap; NaN / infinite:
+ * DTA_EINVAL.
+ * In-place backward under a cap: at most 2048 extra picks per row (their 1 - tanh^2 factors are taken before the row is
+ * overwritten and held in LDS); the gradient element of a pick beyond that is written as NaN, so the overrun cannot pass for a
+ * result.  An out-of-place call has no such limit.
+ * Refusals come in this order: DTA_EINVAL (a null pointer, a size <= 0, a temperature that is not > 0, the soft-cap), DTA_EUNSUPPORTED
+ * (dtype), DTA_EALIGN, DTA_EPRIOR.
  * Replaces vocab_parallel.py:13-27 (_gather_logprobs[_entropy]) with its autograd backward, and the torch indexing of
  * the fork rows.  */
 int dta_logprob_entropy_fwd(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
                             float* lse, float* entropy, float* logprob, float* extra_logprob,
-                            int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, void* stream);
+                            int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream);
 /* Vocab-sharded forward: raw per-shard statistics stats[R][4] = {m, s, t, picked} (log2 domain of x*log2(e)/T;
  * labels shard-local, -1 = owned by another rank; extra_picked[F] likewise raw x/T or 0) for the cross-rank combine of
  * vocab_parallel.py:125-160, 258-300. */
 int dta_logprob_entropy_shard_stats(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
                                     float* stats, float* extra_picked,
-                                    int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, void* stream);
+                                    int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream);
 int dta_logprob_entropy_bwd(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
                             const float* lse, const float* entropy,
                             const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
-                            int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype, void* stream);
-
-/* Final-logit soft-capping (Gemma-2's final_logit_softcapping): the three entries above on x' = c * tanh(x / c), c = softcap.  The cap is
- * applied to the raw logit as it is loaded (no second pass over the [R, V] logits); lse, entropy, the label pick and the extra picks
- * are all statistics of x', and the temperature divides x'.  The backward reads each raw x once (in place: dlogits == logits) and
- * multiplies the gradient with respect to x' by 1 - tanh^2(x / c) before the store.  The cap is elementwise and comes before the
- * shard statistics, so the cross-rank combine is unchanged.  softcap <= 0: the plain entry, bit for bit; NaN / infinite: DTA_EINVAL.
- * In-place backward under a cap: at most 2048 extra picks per row (their 1 - tanh^2 factors are taken before the row is
- * overwritten and held in LDS); the gradient element of a pick beyond that is written as NaN, so the overrun cannot pass for a
- * result.  An out-of-place call has no such limit. */
-int dta_logprob_entropy_fwd_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
-                                float* lse, float* entropy, float* logprob, float* extra_logprob,
-                                int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream);
-int dta_logprob_entropy_shard_stats_cap(const void* logits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
-                                        float* stats, float* extra_picked,
-                                        int32_t R, int32_t V, int64_t row_stride, float temperature, int32_t dtype, float softcap, void* stream);
-int dta_logprob_entropy_bwd_cap(const void* logits, void* dlogits, const int64_t* labels, const int32_t* extra_ptr, const int64_t* extra_labels,
-                                const float* lse, const float* entropy,
-                                const float* g_logprob, const float* g_extra_logprob, const float* g_entropy,
-                                int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype,
-                                float softcap, void* stream);
+                            int32_t R, int32_t V, int64_t row_stride, int64_t out_row_stride, float temperature, int32_t dtype,
+                            float softcap, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused row kernels of the decoder layer (HBM-bound; bf16/f16 storage, fp32 math).  They restate the
@@ -231,21 +223,19 @@ int dta_logprob_entropy_bwd_cap(const void* logits, void* dlogits, const int64_t
  * ------------------------------------------------------------------------------------------- */
 /* delta/x_out both NULL: y = norm(x).  Both given: x_out = x + delta (the residual-stream update of the decoder
  * layer, rounded to the storage dtype) and y = norm(x_out), in one pass.  bwd: `x` is the normalised input
- * (x_out of the forward), `dres` (may be NULL) the gradient arriving on the residual stream, added to dx. */
+ * (x_out of the forward), `dres` (may be NULL) the gradient arriving on the residual stream, added to dx.
+ * Weight offset (Gemma: offset 1), w_offset != 0: y = cast(x * rsqrt(mean(x^2)+eps) * (w_offset + w)) - the offset is added to w in fp32
+ * inside the kernel and the product is rounded ONCE (a 1 + w formed in bf16 would lose the low bits of w).  The fused residual add and
+ * every other argument are unchanged, and so is dw_partial (d(w_offset + w)/dw = 1).  w_offset == 0 selects the kernels compiled
+ * without the offset; NaN: DTA_EINVAL.
+ * Refusals come in this order: DTA_EINVAL (a null pointer, a size <= 0, delta without x_out or the reverse, the offset),
+ * DTA_EUNSUPPORTED (dtype, H % 8, bwd: H > 8192), DTA_EALIGN, DTA_EPRIOR. */
 int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
-                    int32_t R, int32_t H, float eps, int32_t dtype, void* stream);
+                    int32_t R, int32_t H, float eps, float w_offset, int32_t dtype, void* stream);
 int dta_rmsnorm_bwd_blocks(int32_t R);   /* rows of the dw_partial workspace [blocks, H] (float); caller sums dim 0.  H % 8 == 0; bwd: H <= 8192.
                                           * dw_partial NULL (here and in dta_qk_norm_rope_bwd): a frozen weight - dx only, no partials written */
 int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
-                    int32_t R, int32_t H, int32_t dtype, void* stream);
-/* RMSNorm with a weight offset (Gemma: offset 1): y = cast(x * rsqrt(mean(x^2)+eps) * (w_offset + w)) - the offset is added to w in fp32
- * inside the kernel and the product is rounded ONCE (a 1 + w formed in bf16 would lose the low bits of w).  The fused residual add and
- * every other argument are those of dta_rmsnorm_fwd / _bwd; dw_partial is unchanged (d(w_offset + w)/dw = 1).  w_offset == 0: the plain
- * entries, bit for bit. */
-int dta_rmsnorm_fwd_off(const void* x, const void* delta, const void* w, void* x_out, void* y, float* rstd,
-                        int32_t R, int32_t H, float eps, float w_offset, int32_t dtype, void* stream);
-int dta_rmsnorm_bwd_off(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
-                        int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream);
+                    int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream);
 /* head_dim D = 128 or 64.  x: [T, NH, D] with token stride x_stride_t; cos_sin: float [T, D] = {cos[D/2], sin[D/2]} of the token's
  * depth (rotate-half pairs element i with i + D/2); y: [T, NH, D] contiguous; w (head-norm weight [D]) may be NULL = RoPE only. */
 int dta_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,

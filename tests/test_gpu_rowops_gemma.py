@@ -1,12 +1,12 @@
 """GPU parity of the Gemma-2 row kernels against float64: GeGLU (dta_geglu_fwd / _bwd), RMSNorm with weight offset 1
-(dta_rmsnorm_fwd_off / _bwd_off, with and without the fused residual add) and the final-logit soft-capped log-prob / entropy kernels
-(dta_logprob_entropy_fwd_cap / _shard_stats_cap / _bwd_cap: fork picks, temperature 0.7, labels outside [0, V), V = 256 and 256 000,
+(dta_rmsnorm_fwd / _bwd with w_offset, with and without the fused residual add) and the final-logit soft-capped log-prob / entropy kernels
+(dta_logprob_entropy_fwd / _shard_stats / _bwd with softcap: fork picks, temperature 0.7, labels outside [0, V), V = 256 and 256 000,
 shard statistics over two halves of V combined on the host).
 
 Tolerances are those of the uncapped forms: the value / gradient comparison of tests/test_gpu_rowops.py (its `_pair` and `_rel`,
 imported: relative Frobenius error 8e-3 bf16 / 2e-3 f16, weight gradients 1e-2) and the figures tests/test_gpu_logprob.py applies in
-test_kernels_vs_oracle (it states them inline, so they are named once below).  softcap = 0 and w_offset = 0 must give the bits of the
-existing entries."""
+test_kernels_vs_oracle (it states them inline, so they are named once below).  softcap <= 0 and w_offset = 0 passed to the entries
+must give the bits of the operators' defaults."""
 import math
 
 import pytest
@@ -104,19 +104,21 @@ def test_zero_offset_is_the_plain_entry_bitwise(dtype):
     R, H = 37, 4608
     x, d, dy = (torch.randn(R, H, generator=g).to(dtype).to(DEV) for _ in range(3))
     w = (1 + 0.1 * torch.randn(H, generator=g)).to(dtype).to(DEV)
-    outs = []
-    for name, off in (("dta_rmsnorm_fwd", ()), ("dta_rmsnorm_fwd_off", (0.0,))):
-        xo, y, rstd = torch.empty_like(x), torch.empty_like(x), torch.empty(R, device=DEV)
-        assert getattr(lib(), name)(ptr(x), ptr(d), ptr(w), ptr(xo), ptr(y), ptr(rstd), R, H, 1e-6, *off, ops._DT[dtype], None) == 0
-        dx = torch.empty_like(x); part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, device=DEV)
-        assert getattr(lib(), name.replace("fwd", "bwd"))(ptr(xo), ptr(w), ptr(dy), ptr(d), ptr(rstd), ptr(dx), ptr(part), R, H, *off, ops._DT[dtype], None) == 0
-        torch.cuda.synchronize()
-        outs.append((xo, y, rstd, dx, part))
-    for a, b in zip(*outs):
-        assert torch.equal(a, b)
-    a = ops.add_rms_norm(x, d, w, 1e-6)
-    b = ops.add_rms_norm(x, d, w, 1e-6, 0.0)
-    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[1], outs[0][1])
+    xo, y, rstd = torch.empty_like(x), torch.empty_like(x), torch.empty(R, device=DEV)
+    assert lib().dta_rmsnorm_fwd(ptr(x), ptr(d), ptr(w), ptr(xo), ptr(y), ptr(rstd), R, H, 1e-6, 0.0, ops._DT[dtype], None) == 0
+    dx = torch.empty_like(x); part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, device=DEV)
+    assert lib().dta_rmsnorm_bwd(ptr(xo), ptr(w), ptr(dy), ptr(d), ptr(rstd), ptr(dx), ptr(part), R, H, 0.0, ops._DT[dtype], None) == 0
+    torch.cuda.synchronize()
+    outs = [(xo, y, rstd, dx, ops.sum_slabs(part, dtype))]           # the operator returns the dw partials summed (one fixed-order launch)
+    for off in ((), (0.0,)):                                         # ops.add_rms_norm without an offset and with an explicit 0.0
+        xa, wa = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        xo, y = ops.add_rms_norm(xa, d, wa, 1e-6, *off)
+        rstd = y.grad_fn.saved_tensors[2]
+        dx, dw = torch.autograd.grad([xo, y], [xa, wa], [d, dy])     # the gradient on the residual stream is the entry's dres
+        outs.append((xo.detach(), y.detach(), rstd, dx, dw))
+    for other in outs[1:]:
+        for a, b in zip(outs[0], other):
+            assert torch.equal(a, b)
 
 
 # ------------------------------------------------------------------------------------------------ capped log-prob / entropy
@@ -222,26 +224,32 @@ def test_zero_softcap_is_the_plain_logprob_entry_bitwise(dtype):
     logits, labels, ex_rows, ex_lab, glp, gent, gex = _lp_case(R, V, dtype, 77)
     ld, lab = logits.to(DEV), labels.to(DEV)
     ptr_, exl = _csr(ex_rows, R).to(DEV), ex_lab.to(DEV)
-    res = []
-    for suffix, cap in (("", ()), ("_cap", (0.0,)), ("_cap", (-3.0,))):
+    glp, gex, gent = glp.to(DEV), gex.to(DEV), gent.to(DEV)
+    # the ops raw functions with their default cap ...
+    lp2, pk = (torch.empty(ex_rows.numel(), dtype=F32, device=DEV) for _ in range(2))
+    lse, ent, lp = ops.logprob_entropy_fwd_raw(ld, lab, True, temp, ptr_, exl, lp2)
+    stats = ops.logprob_entropy_shard_stats_raw(ld, lab, temp, ptr_, exl, pk)
+    out = ops.logprob_entropy_bwd_raw(ld, lab, lse, ent, glp, gent, temp, ptr_, exl, gex, out=torch.empty_like(ld))
+    res = [(lse, ent, lp, lp2, stats, pk, out)]
+    for cap in (0.0, -3.0):                                          # ... and the three entries with a zero and a negative cap
         lse, ent, lp, lp2 = (torch.empty(n, dtype=F32, device=DEV) for n in (R, R, R, ex_rows.numel()))
-        assert getattr(lib(), "dta_logprob_entropy_fwd" + suffix)(ptr(ld), ptr(lab), ptr(ptr_), ptr(exl), ptr(lse), ptr(ent), ptr(lp), ptr(lp2),
-                                                                  R, V, ld.stride(0), temp, ops._DT[dtype], *cap, None) == 0
+        assert lib().dta_logprob_entropy_fwd(ptr(ld), ptr(lab), ptr(ptr_), ptr(exl), ptr(lse), ptr(ent), ptr(lp), ptr(lp2),
+                                             R, V, ld.stride(0), temp, ops._DT[dtype], cap, None) == 0
         stats, pk = torch.empty(R, 4, device=DEV), torch.empty(ex_rows.numel(), device=DEV)
-        assert getattr(lib(), "dta_logprob_entropy_shard_stats" + suffix)(ptr(ld), ptr(lab), ptr(ptr_), ptr(exl), ptr(stats), ptr(pk),
-                                                                          R, V, ld.stride(0), temp, ops._DT[dtype], *cap, None) == 0
+        assert lib().dta_logprob_entropy_shard_stats(ptr(ld), ptr(lab), ptr(ptr_), ptr(exl), ptr(stats), ptr(pk),
+                                                     R, V, ld.stride(0), temp, ops._DT[dtype], cap, None) == 0
         out = torch.empty_like(ld)
-        assert getattr(lib(), "dta_logprob_entropy_bwd" + suffix)(ptr(ld), ptr(out), ptr(lab), ptr(ptr_), ptr(exl), ptr(lse), ptr(ent),
-                                                                  ptr(glp.to(DEV)), ptr(gex.to(DEV)), ptr(gent.to(DEV)),
-                                                                  R, V, ld.stride(0), out.stride(0), temp, ops._DT[dtype], *cap, None) == 0
+        assert lib().dta_logprob_entropy_bwd(ptr(ld), ptr(out), ptr(lab), ptr(ptr_), ptr(exl), ptr(lse), ptr(ent), ptr(glp), ptr(gex), ptr(gent),
+                                             R, V, ld.stride(0), out.stride(0), temp, ops._DT[dtype], cap, None) == 0
         torch.cuda.synchronize()
         res.append((lse, ent, lp, lp2, stats, pk, out))
     for other in res[1:]:
         for a, b in zip(res[0], other):
             assert torch.equal(a, b)
     lse = torch.empty(R, device=DEV)
-    assert lib().dta_logprob_entropy_fwd_cap(ptr(ld), None, None, None, ptr(lse), None, None, None, R, V, ld.stride(0), 1.0, ops._DT[dtype],
-                                             float("nan"), None) == -1
+    for bad in (float("nan"), float("inf")):
+        assert lib().dta_logprob_entropy_fwd(ptr(ld), None, None, None, ptr(lse), None, None, None, R, V, ld.stride(0), 1.0, ops._DT[dtype],
+                                             bad, None) == -1
 
 
 def test_lm_head_rows_with_a_cap_matches_float64():
