@@ -6,6 +6,10 @@
 //   bwd: dLoss/dlogits, written to `out` (out == logits: in place):
 //        g[r,j] = ( p_j·(−G[r] + ge[r]·(lse[r] − ent[r] − x_j/T)) + Σ_{picked j} g_picked ) / T
 //        where G[r] = glp[r] + Σ_e g_extra_lp[e] is the summed gradient of every log-prob picked from row r.
+// Masked columns (CAP = false): x = -inf, or x·log2(e)/T below MASKED_Y, has p = 0, adds nothing to (m, s, t) and gets a gradient of exactly 0:
+// the factor p is multiplied by - the scaled logit in the forward, the raw one in the backward - is held at MASKED_Y (one v_max per element),
+// so that p = 0 always meets a FINITE factor (0·inf was NaN in t = Σ p·y and in p·(c1 + c2·x)); p itself is taken of the raw value, so a NaN
+// logit still yields NaN.  A pick of a -inf column is -inf.  A row of masked columns only is undefined.
 // One 256-thread workgroup per row, 16-byte loads, online (max, Σexp, Σexp·x) per lane, block reduce.
 // Algorithmic HBM bytes: fwd V·sizeof(e) per row (one read); bwd 2·V·sizeof(e) per row (one read, one write).
 // Final-logit soft-capping (softcap > 0, CAP = true): every statistic and pick is taken on x' = c·tanh(x/c), formed in registers as the
@@ -19,6 +23,9 @@
 // The [rows, V] logits are 8.6 GB at the bench's shape: each byte is read once here (and once more by the gradient GEMMs, long after it
 // has left every cache).  Default: non-temporal accesses (no cache allocation) - forward 1.389 -> 1.240 ms (6.9 TB/s), backward 3.36 -> 3.31 ms at
 // [28 160, 151 936] bf16; -DDTA_LOGPROB_NT=0: plain.
+// The masked-column v_max (one VALU per element, plain form only): scripts/head_stage_probe.py, kept variant at this shape (the whole stage:
+// logits GEMM + forward / backward + dgrad + wgrad GEMMs), two runs each: forward 8.887, 9.023 ms before -> 8.830, 8.822 ms after; backward
+// 19.954, 20.039 ms before -> 20.057, 19.943 ms after - inside the spread of the two runs before (0.14 / 0.09 ms around 8.955 / 19.996 ms).
 #ifndef DTA_LOGPROB_NT
 #define DTA_LOGPROB_NT 1
 #endif
@@ -43,6 +50,7 @@ template <> struct LTy<DTA_F32> { using e = float; using v8 = f32x8; };
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
+constexpr float MASKED_Y = -1e30f;   // plain form: the factor that meets p (the scaled logit in fwd, the raw one in bwd) is held at this value
 struct Stat { float m, s, t; };   // running max (log2 domain of scaled x), Σ 2^(y−m), Σ 2^(y−m)·y   with y = x·LOG2E/T
 
 __device__ __forceinline__ Stat merge(Stat a, Stat b) {
@@ -85,6 +93,9 @@ __global__ __launch_bounds__(256) void logprob_entropy_fwd_kernel(typename std::
   [[maybe_unused]] float kt = 0.f, cs = 1.f;          // CAP: tanh argument factor 2 log2(e) / c; picks are c·t·(1/T)
   if constexpr (CAP) { kt = 2.f * LOG2E / a.softcap; cs = a.softcap; k *= a.softcap; }
   auto capped = [&](float xr) -> float { if constexpr (CAP) return cap_tanh(xr * kt); else return xr; };   // x (no cap) or t = tanh(x/c)
+  // the factor of p in t = Σ p·y; plain form: held at MASKED_Y, so that a masked column (y = -inf: p = 0) adds 0·finite = 0, never 0·inf.  p itself
+  // is taken of the raw y: a NaN logit still poisons s (fmaxf alone would swallow it)
+  auto finite = [&](float y) -> float { if constexpr (CAP) return y; else return fmaxf(y, MASKED_Y); };
   Stat st{-1e30f, 0.f, 0.f};
   const int nv = V >> 3;
   for (int i = threadIdx.x; i < nv; i += 256) {
@@ -96,13 +107,13 @@ __global__ __launch_bounds__(256) void logprob_entropy_fwd_kernel(typename std::
     const float f = __builtin_amdgcn_exp2f(st.m - m);
     float s = st.s * f, t = st.t * f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { const float p = __builtin_amdgcn_exp2f(y[j] - m); s += p; t = __builtin_fmaf(p, y[j], t); }
+    for (int j = 0; j < 8; ++j) { const float p = __builtin_amdgcn_exp2f(y[j] - m); s += p; t = __builtin_fmaf(p, finite(y[j]), t); }
     st = Stat{m, s, t};
   }
   for (int i = (nv << 3) + threadIdx.x; i < V; i += 256) {            // tail when V % 8 != 0
     const float y = capped((float)x[i]) * k;
     const float m = fmaxf(st.m, y); const float f = __builtin_amdgcn_exp2f(st.m - m); const float p = __builtin_amdgcn_exp2f(y - m);
-    st = Stat{m, st.s * f + p, __builtin_fmaf(p, y, st.t * f)};
+    st = Stat{m, st.s * f + p, __builtin_fmaf(p, finite(y), st.t * f)};
   }
   st = block_reduce(st, sh);
   const int e0 = a.extra_ptr ? a.extra_ptr[row] : 0, e1 = a.extra_ptr ? a.extra_ptr[row + 1] : 0;
@@ -181,6 +192,7 @@ __global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(typename std::
       float xf = (float)v[j];
       if constexpr (CAP) { xf = cap_tanh(xf * kt); sech2[j] = __builtin_fmaf(-xf, xf, 1.f); }      // xf := t; k and c2 carry the cap
       const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(xf, k, -l2));
+      if constexpr (!CAP) xf = fmaxf(xf, MASKED_Y);                     // masked column: p = 0 times a FINITE factor = exactly 0
       g[j] = p * __builtin_fmaf(xf, c2, c1);
     }
     if (i == lab8) {
@@ -198,8 +210,9 @@ __global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(typename std::
   for (int i = (nv << 3) + threadIdx.x; i < V; i += 256) {
     float xr = (float)x[i], s2 = 1.f;
     if constexpr (CAP) { xr = cap_tanh(xr * kt); s2 = __builtin_fmaf(-xr, xr, 1.f); }
-    const float xs = xr * cs * inv_temp;
     const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(xr, k, -l2));
+    if constexpr (!CAP) xr = fmaxf(xr, MASKED_Y);
+    const float xs = xr * cs * inv_temp;
     float g = p * (a - ge * xs);
     if (i == lab) g += g1;
     if constexpr (CAP) g *= s2;

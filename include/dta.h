@@ -187,6 +187,12 @@ int dta_window_lo(const int32_t* depth, const int32_t* seg_off, const int32_t* s
  * extra_logprob[f] = x[extra_labels[f]]/T - lse[row of f].
  * bwd writes dLoss/dlogits to `dlogits` (== logits: in place) given g_logprob[r], g_extra_logprob[F] and g_entropy[r]
  * (each may be NULL), including the one-hot terms of every pick.
+ * Masked columns (no soft-cap): a logit of -inf, or a finite one whose scaled value x * log2(e) / T is below -1e30 (it would overflow
+ * fp32: the storage type's lowest value at T = 1), has probability 0.  It adds nothing to lse, to entropy (the limit p log p -> 0) or to
+ * any shard statistic, and its element of dlogits is exactly 0 (unless it is itself a picked label: then the pick's one-hot term alone);
+ * everything else on the row is what the row without that column gives.  A label on a -inf column yields logprob = -inf.  A row made
+ * only of such columns is undefined.  A NaN logit still yields NaN.  Under a soft-cap a -inf logit is x' = -c like any very negative one, and 1 - tanh^2 = 0 makes its
+ * gradient exactly 0.
  * Final-logit soft-capping (Gemma-2's final_logit_softcapping), softcap > 0: the three entries work on x' = c * tanh(x / c), c = softcap.
  * The cap is applied to the raw logit as it is loaded (no second pass over the [R, V] logits); lse, entropy, the label pick and the extra
  * picks are all statistics of x', and the temperature divides x'.  The backward reads each raw x once (in place: dlogits == logits) and
