@@ -14,7 +14,7 @@ SOURCES = ["tree_attn.hip", "tree_attn_f32.hip", "trie_kernels.hip", "logprob_ke
 
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17"]
-DEPS = SOURCES + ["dta_common.h"]
+DEPS = SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))       # every header of csrc/: a new one is in the digest unasked
 
 
 def _digest() -> str:

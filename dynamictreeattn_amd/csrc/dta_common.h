@@ -45,6 +45,17 @@ template <class F> inline void dta_storage_type(int32_t dtype, F&& f) {
   else if (dtype == DTA_F16) f(std::integral_constant<int, DTA_F16>{});
   else f(std::integral_constant<int, DTA_F32>{});
 }
+inline bool row_dtype_ok(int dtype) { return dtype == DTA_BF16 || dtype == DTA_F16 || dtype == DTA_F32; }
+// The same for the MFMA kernels of MoE and LoRA, which exist for the 16-bit types only: f(DT) with DT = DTA_BF16 / DTA_F16
+template <class F> inline void dta_storage_type16(int32_t dtype, F&& f) {
+  if (dtype == DTA_BF16) f(std::integral_constant<int, DTA_BF16>{});
+  else f(std::integral_constant<int, DTA_F16>{});
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// workgroups that cover n items at `per` each; row_blocks: the same for a grid-stride kernel, at least 1 and at most cap
+inline unsigned ceil_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+inline int row_blocks(int64_t rows, int per_block, int cap) { int64_t b = (rows + per_block - 1) / per_block; return (int)(b < cap ? (b > 0 ? b : 1) : cap); }
 
 // fp32 tree attention (tree_attn_f32.hip, head_dim 64 or 128): what dta_tree_attn_fwd / dta_tree_attn_bwd launch for dtype DTA_F32, after
 // their argument checks

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dta_common.h"
+#include "dta_device.h"
 
 // Saved activations read back in a backward kernel (written a whole forward ago: in no cache) are read non-temporally - swiglu_bwd 150.5 ->
 // 140.2 us (6.2 TB/s), qk_norm_rope_bwd 53.7 -> 51.6, rmsnorm_bwd 45.9 -> 45.4 at 28 160 rows; -DDTA_EW_NT=0: plain loads.
@@ -22,22 +23,7 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-template <int DT> struct ETy;
-template <> struct ETy<DTA_BF16> { using e = __bf16; using v8 = bf16x8; };
-template <> struct ETy<DTA_F16> { using e = _Float16; using v8 = f16x8; };
-// fp32 models (the reference's --dtype fp32, run.py:122-132): same kernels, 8 floats = two 16-byte accesses per lane; the
-// roundings to the storage type `(e)(...)` are then the identity
-typedef float f32x8 __attribute__((ext_vector_type(8), aligned(16)));
-template <> struct ETy<DTA_F32> { using e = float; using v8 = f32x8; };
-inline bool row_dtype_ok(int dtype) { return dtype == DTA_BF16 || dtype == DTA_F16 || dtype == DTA_F32; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+// fp32 models (the reference's --dtype fp32, run.py:122-132): the same kernels with Ty<DTA_F32>
 
 // ---------------------------------------------------------------------------------------------
 // RMSNorm over rows of H (H % 8 == 0; forward: any H, backward: H <= 8192).  One wave per row, 4 rows per workgroup, grid-stride.
@@ -50,7 +36,7 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const void* __restrict
                                                           float* __restrict__ rstd, int R, int H, float eps, float w_off = 0.f) {
   // NA > 0: the row (H <= 512*NA elements) stays in registers between the sum-of-squares pass and the scaling pass - ONE read of x (and of
   // delta) per row; NA == 0: any H, second pass re-reads the row (L2-hot).
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const e* w = reinterpret_cast<const e*>(w_);
   const int nv = H >> 3;
@@ -142,7 +128,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
                                                           const float* __restrict__ rstd, void* __restrict__ dx_, float* __restrict__ dw_part,
                                                           int R, int H, float w_off = 0.f) {
   auto wof = [&](float w) -> float { if constexpr (OFF) return w_off + w; else return w; };
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   __shared__ float red[4 * 64 * 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const e* w = reinterpret_cast<const e*>(w_);
@@ -225,7 +211,7 @@ template <int DT, int HPL, int D>
 __global__ __launch_bounds__(256) void qk_norm_rope_fwd_kernel(const void* __restrict__ x_, const void* __restrict__ w_, const float* __restrict__ cs,
                                                                void* __restrict__ y_, float* __restrict__ rstd, int64_t n_units, int NH,
                                                                int64_t x_st, float eps) {
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   constexpr int LPH = D / 8, LSH = D == 128 ? 4 : 3;              // lanes per head, log2
   const int lane = threadIdx.x & 63, sub = lane & (LPH - 1);
   const int64_t unit = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / LPH) + (lane >> LSH);     // global (token, head group) index
@@ -278,7 +264,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __res
                                                                const void* dy_, const float* __restrict__ rstd,
                                                                void* dx_, float* __restrict__ dw_part, int64_t n_units, int NH,
                                                                int64_t x_st, int64_t dy_st_t, int64_t dy_st_h, int64_t dx_st) {
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   constexpr int LPH = D / 8, LSH = D == 128 ? 4 : 3, UPB = 4 * (64 / LPH);    // lanes per head (log2), (token, head group) units per workgroup pass
   __shared__ float red[256 * 8];
   const int lane = threadIdx.x & 63, sub = lane & (LPH - 1);
@@ -353,7 +339,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __res
 template <int DT>
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const void* __restrict__ g_, const void* __restrict__ u_, void* __restrict__ y_,
                                                          int64_t n8, int c8, int64_t ld) {
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     const int64_t row = i / c8; const int col = (int)(i - row * c8) * 8;
     const v8 g = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(g_) + row * ld + col);
@@ -368,7 +354,7 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const void* __restrict_
 template <int DT>
 __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const void* __restrict__ g_, const void* __restrict__ u_, const void* __restrict__ dy_,
                                                          void* __restrict__ dg_, void* __restrict__ du_, int64_t n8, int c8, int64_t ld, int64_t ldg) {
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     const int64_t row = i / c8; const int col = (int)(i - row * c8) * 8;
     const v8 g = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(reinterpret_cast<const e*>(g_) + row * ld + col));
@@ -403,7 +389,7 @@ __device__ __forceinline__ float gelu_gate(float x, float* dgelu) {
 template <int DT>
 __global__ __launch_bounds__(256) void geglu_fwd_kernel(const void* __restrict__ g_, const void* __restrict__ u_, void* __restrict__ y_,
                                                         int64_t n8, int c8, int64_t ld) {
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     const int64_t row = i / c8; const int col = (int)(i - row * c8) * 8;
     const v8 g = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(g_) + row * ld + col);
@@ -418,7 +404,7 @@ __global__ __launch_bounds__(256) void geglu_fwd_kernel(const void* __restrict__
 template <int DT>
 __global__ __launch_bounds__(256) void geglu_bwd_kernel(const void* __restrict__ g_, const void* __restrict__ u_, const void* __restrict__ dy_,
                                                         void* __restrict__ dg_, void* __restrict__ du_, int64_t n8, int c8, int64_t ld, int64_t ldg) {
-  using e = typename ETy<DT>::e; using v8 = typename ETy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     const int64_t row = i / c8; const int col = (int)(i - row * c8) * 8;
     const v8 g = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(reinterpret_cast<const e*>(g_) + row * ld + col));
@@ -496,7 +482,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const char* __restrict__
 template <int DT>
 __global__ __launch_bounds__(1024) void sum_slabs_tall_kernel(const float* __restrict__ part, int64_t slabs, int64_t n, int64_t stride,
                                                               const float* __restrict__ extra, void* __restrict__ out_) {
-  using e = typename ETy<DT>::e;
+  using e = typename Ty<DT>::e;
   __shared__ float red[16 * 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t col = (int64_t)blockIdx.x * 64 + lane;
@@ -524,7 +510,7 @@ __global__ __launch_bounds__(1024) void sum_slabs_tall_kernel(const float* __res
 template <int DT>
 __global__ __launch_bounds__(256) void sum_slabs_flat_kernel(const float* __restrict__ part, int slabs, int64_t n4, int64_t stride,
                                                              const float* __restrict__ extra, void* __restrict__ out_) {
-  using e = typename ETy<DT>::e;
+  using e = typename Ty<DT>::e;
   typedef float f4 __attribute__((ext_vector_type(4)));
   typedef e e4 __attribute__((ext_vector_type(4)));
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
@@ -536,9 +522,6 @@ __global__ __launch_bounds__(256) void sum_slabs_flat_kernel(const float* __rest
     *reinterpret_cast<e4*>(reinterpret_cast<e*>(out_) + 4 * i) = o;
   }
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline int row_blocks(int64_t rows, int per_block, int cap) { int64_t b = (rows + per_block - 1) / per_block; return (int)(b < cap ? (b > 0 ? b : 1) : cap); }
 
 template <int N> using Int = std::integral_constant<int, N>;
 
@@ -566,7 +549,7 @@ template <class K>
 int glu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream, K kernel_of) {
   if (!gate || !up || !y || rows <= 0 || cols <= 0 || ld < cols) return DTA_EINVAL;
   if (!row_dtype_ok(dtype) || cols % 8 || ld % 8) return DTA_EUNSUPPORTED;
-  if (!al16(gate) || !al16(up) || !al16(y)) return DTA_EALIGN;
+  if (!aligned16(gate) || !aligned16(up) || !aligned16(y)) return DTA_EALIGN;
   DTA_REFUSE_IF_PRIOR_ERROR();
   const int64_t n8 = rows * (cols / 8);
   dta_storage_type(dtype, [&](auto dt) {
@@ -580,7 +563,7 @@ int glu_bwd(const void* gate, const void* up, const void* dy, void* dgate, void*
             int32_t dtype, void* stream, K kernel_of) {
   if (!gate || !up || !dy || !dgate || !dup || rows <= 0 || cols <= 0 || ld < cols || ld_grad < cols) return DTA_EINVAL;
   if (!row_dtype_ok(dtype) || cols % 8 || ld % 8 || ld_grad % 8) return DTA_EUNSUPPORTED;
-  if (!al16(gate) || !al16(up) || !al16(dy) || !al16(dgate) || !al16(dup)) return DTA_EALIGN;
+  if (!aligned16(gate) || !aligned16(up) || !aligned16(dy) || !aligned16(dgate) || !aligned16(dup)) return DTA_EALIGN;
   DTA_REFUSE_IF_PRIOR_ERROR();
   const int64_t n8 = rows * (cols / 8);
   dta_storage_type(dtype, [&](auto dt) {
@@ -596,7 +579,7 @@ extern "C" int dta_rmsnorm_fwd(const void* x, const void* delta, const void* w, 
                                int32_t R, int32_t H, float eps, float w_offset, int32_t dtype, void* stream) {
   if (!x || !w || !y || !rstd || R <= 0 || H <= 0 || ((delta != nullptr) != (x_out != nullptr)) || w_offset != w_offset) return DTA_EINVAL;
   if (!row_dtype_ok(dtype) || H % 8) return DTA_EUNSUPPORTED;
-  if (!al16(x) || !al16(w) || !al16(y) || (delta && (!al16(delta) || !al16(x_out)))) return DTA_EALIGN;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (delta && (!aligned16(delta) || !aligned16(x_out)))) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
   const dim3 grid(row_blocks(R, 4, 8192)), block(256);
@@ -615,7 +598,7 @@ extern "C" int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, con
                                int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream) {
   if (!x || !w || !dy || !rstd || !dx || R <= 0 || H <= 0 || w_offset != w_offset) return DTA_EINVAL;          // dw_partial NULL: dx only (frozen weight)
   if (!row_dtype_ok(dtype) || H % 8 || H > 8192) return DTA_EUNSUPPORTED;
-  if (!al16(x) || !al16(w) || !al16(dy) || !al16(dx) || (dres && !al16(dres))) return DTA_EALIGN;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(dy) || !aligned16(dx) || (dres && !aligned16(dres))) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
   const dim3 grid(row_blocks(R, 4, 2048)), block(256);
@@ -632,7 +615,7 @@ extern "C" int dta_qk_norm_rope_fwd(const void* x, const void* w, const float* c
                                     int32_t T, int32_t NH, int32_t head_dim, int64_t x_stride_t, float eps, int32_t dtype, void* stream) {
   if (!x || !cos_sin || !y || T <= 0 || NH <= 0 || (w && !rstd)) return DTA_EINVAL;
   if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64)) return DTA_EUNSUPPORTED;
-  if (!al16(x) || !al16(y) || (w && !al16(w)) || x_stride_t % 8) return DTA_EALIGN;
+  if (!aligned16(x) || !aligned16(y) || (w && !aligned16(w)) || x_stride_t % 8) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
   qk_form(NH, head_dim, [&](auto hpl, auto d) {
@@ -653,7 +636,7 @@ extern "C" int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* c
                                     int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t, int32_t dtype, void* stream) {
   if (!cos_sin || !dy || !dx || T <= 0 || NH <= 0 || (w && (!x || !rstd))) return DTA_EINVAL;     // w with dw_partial NULL: dx only
   if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64)) return DTA_EUNSUPPORTED;
-  if (!al16(dy) || !al16(dx) || (w && (!al16(w) || !al16(x))) || x_stride_t % 8 || dy_stride_t % 8 || dy_stride_h % 8 || dx_stride_t % 8) return DTA_EALIGN;
+  if (!aligned16(dy) || !aligned16(dx) || (w && (!aligned16(w) || !aligned16(x))) || x_stride_t % 8 || dy_stride_t % 8 || dy_stride_h % 8 || dx_stride_t % 8) return DTA_EALIGN;
   if (dx_stride_t < (int64_t)NH * head_dim) return DTA_EINVAL;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
@@ -691,7 +674,7 @@ extern "C" int dta_transpose(const void* in, void* out, int64_t rows, int64_t co
   if (elem_size != 2 && elem_size != 4) return DTA_EUNSUPPORTED;
   const int V = 16 / elem_size;
   if (rows % V || cols % V || ld_in % V || ld_out % V) return DTA_EUNSUPPORTED;
-  if (!al16(in) || !al16(out)) return DTA_EALIGN;
+  if (!aligned16(in) || !aligned16(out)) return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
   const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64)), block(256);
@@ -707,18 +690,18 @@ extern "C" int dta_sum_slabs(const float* part, int64_t slabs, int64_t n, int64_
   if (!row_dtype_ok(out_dtype)) return DTA_EUNSUPPORTED;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
-  const bool flat = slabs <= 16 && n % 4 == 0 && slab_stride % 4 == 0 && al16(part) && al16(out) && (!extra || al16(extra));
+  const bool flat = slabs <= 16 && n % 4 == 0 && slab_stride % 4 == 0 && aligned16(part) && aligned16(out) && (!extra || aligned16(extra));
   if (flat) {
     const dim3 grid(row_blocks(n / 4, 256, 8192)), block(256);
-    if (out_dtype == DTA_BF16) hipLaunchKernelGGL(sum_slabs_flat_kernel<DTA_BF16>, grid, block, 0, st_, part, (int)slabs, n / 4, slab_stride, extra, out);
-    else if (out_dtype == DTA_F16) hipLaunchKernelGGL(sum_slabs_flat_kernel<DTA_F16>, grid, block, 0, st_, part, (int)slabs, n / 4, slab_stride, extra, out);
-    else hipLaunchKernelGGL(sum_slabs_flat_kernel<DTA_F32>, grid, block, 0, st_, part, (int)slabs, n / 4, slab_stride, extra, out);
+    dta_storage_type(out_dtype, [&](auto dt) {
+      hipLaunchKernelGGL(sum_slabs_flat_kernel<decltype(dt)::value>, grid, block, 0, st_, part, (int)slabs, n / 4, slab_stride, extra, out);
+    });
   } else {
     if ((n + 63) / 64 > 0x7fffffff) return DTA_EUNSUPPORTED;
     const dim3 grid((unsigned)((n + 63) / 64)), block(1024);
-    if (out_dtype == DTA_BF16) hipLaunchKernelGGL(sum_slabs_tall_kernel<DTA_BF16>, grid, block, 0, st_, part, slabs, n, slab_stride, extra, out);
-    else if (out_dtype == DTA_F16) hipLaunchKernelGGL(sum_slabs_tall_kernel<DTA_F16>, grid, block, 0, st_, part, slabs, n, slab_stride, extra, out);
-    else hipLaunchKernelGGL(sum_slabs_tall_kernel<DTA_F32>, grid, block, 0, st_, part, slabs, n, slab_stride, extra, out);
+    dta_storage_type(out_dtype, [&](auto dt) {
+      hipLaunchKernelGGL(sum_slabs_tall_kernel<decltype(dt)::value>, grid, block, 0, st_, part, slabs, n, slab_stride, extra, out);
+    });
   }
   return DTA_LAUNCH_STATUS();
 }

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "dta_common.h"
+#include "dta_device.h"
 
 // The [rows, V] logits are 8.6 GB at the bench's shape: each byte is read once here (and once more by the gradient GEMMs, long after it
 // has left every cache).  Default: non-temporal accesses (no cache allocation) - forward 1.389 -> 1.240 ms (6.9 TB/s), backward 3.36 -> 3.31 ms at
@@ -38,17 +39,6 @@
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-template <int DT> struct LTy;
-template <> struct LTy<DTA_BF16> { using e = __bf16; using v8 = bf16x8; };
-template <> struct LTy<DTA_F16> { using e = _Float16; using v8 = f16x8; };
-template <> struct LTy<DTA_F32> { using e = float; using v8 = f32x8; };
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
 
 constexpr float MASKED_Y = -1e30f;   // plain form: the factor that meets p (the scaled logit in fwd, the raw one in bwd) is held at this value
 struct Stat { float m, s, t; };   // running max (log2 domain of scaled x), Î£ 2^(yâˆ’m), Î£ 2^(yâˆ’m)Â·y   with y = xÂ·LOG2E/T
@@ -80,12 +70,9 @@ struct FwdArgs {
 };
 struct FwdArgsC : FwdArgs { float softcap; };
 
-// tanh(x) from a = 2 log2(e) x: 1 âˆ’ 2 / (1 + 2^a); saturates to Â±1 through 2^a = inf / 0, never inf / inf (see tree_attn.hip)
-__device__ __forceinline__ float cap_tanh(float a) { return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(a)), 1.f); }
-
 template <int DT, bool CAP>
 __global__ __launch_bounds__(256) void logprob_entropy_fwd_kernel(typename std::conditional<CAP, FwdArgsC, FwdArgs>::type a) {
-  using e = typename LTy<DT>::e; using v8 = typename LTy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   __shared__ Stat sh[4];
   const int row = blockIdx.x, V = a.V;
   const e* x = reinterpret_cast<const e*>(a.logits) + (int64_t)row * a.stride;
@@ -148,7 +135,7 @@ constexpr int CAP_STASH = 2048;      // extra picks of ONE row whose 1 âˆ’ tanhÂ
 
 template <int DT, bool CAP>
 __global__ __launch_bounds__(256) void logprob_entropy_bwd_kernel(typename std::conditional<CAP, BwdArgsC, BwdArgs>::type b) {
-  using e = typename LTy<DT>::e; using v8 = typename LTy<DT>::v8;
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
   float* stash = nullptr;
   if constexpr (CAP) { __shared__ float stash_s[CAP_STASH]; stash = stash_s; }
   const int row = blockIdx.x, V = b.V;
@@ -241,7 +228,7 @@ bool cap_ok(float c) { return c == c && c < 3.0e38f; }
 int fwd_launch(FwdArgsC a, int32_t dtype, float temperature, void* stream) {
   if (!a.logits || a.R <= 0 || a.V <= 0 || (a.lp && !a.labels) || !(temperature > 0.f) || !cap_ok(a.softcap)) return DTA_EINVAL;
   if (a.extra_ptr && (!a.extra_labels || !a.extra_lp)) return DTA_EINVAL;
-  if (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) return DTA_EUNSUPPORTED;
+  if (!row_dtype_ok(dtype)) return DTA_EUNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(a.logits) & (dtype == DTA_F32 ? 31 : 15)) || (a.stride % 8)) return DTA_EALIGN;   // 8-element vector loads
   a.inv_temp = 1.f / temperature;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -259,7 +246,7 @@ int bwd_launch(BwdArgsC b, int32_t dtype, float temperature, void* stream) {
   if (!b.logits || !b.out || !b.lse || b.R <= 0 || b.V <= 0 || (b.gent && !b.ent) || (b.glp && !b.labels) || !(temperature > 0.f) ||
       !cap_ok(b.softcap)) return DTA_EINVAL;
   if (b.extra_ptr && (!b.extra_labels || !b.gextra)) return DTA_EINVAL;
-  if (dtype != DTA_BF16 && dtype != DTA_F16 && dtype != DTA_F32) return DTA_EUNSUPPORTED;
+  if (!row_dtype_ok(dtype)) return DTA_EUNSUPPORTED;
   const uintptr_t am = dtype == DTA_F32 ? 31 : 15;
   if ((reinterpret_cast<uintptr_t>(b.logits) & am) || (reinterpret_cast<uintptr_t>(b.out) & am) || (b.stride % 8) || (b.out_stride % 8)) return DTA_EALIGN;
   b.inv_temp = 1.f / temperature;

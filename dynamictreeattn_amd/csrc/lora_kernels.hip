@@ -19,20 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dta_common.h"
+#include "dta_device.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-
-template <int DT> struct E;
-template <> struct E<DTA_BF16> { using e = __bf16; using v8 = bf16x8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); } };
-template <> struct E<DTA_F16> { using e = _Float16; using v8 = f16x8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); } };
 
 constexpr int MAXR = 256;
 constexpr int BM = 128, BK = 64;
@@ -54,22 +43,6 @@ __device__ __forceinline__ uint4 ld8(const uint16_t* base, int64_t row, int64_t 
   return r;
 }
 
-// fragment of k-step s for the 32-row block ob of a k-fast image: lane (r = lane & 31, h = lane >> 5) gets operand[ob*32 + r][16s + 8h + j]
-template <class V8> __device__ __forceinline__ V8 frag_kfast(const char* img, int ob, int s, int lane) {
-  return *reinterpret_cast<const V8*>(img + ((ob * 32 + (lane & 31)) * KF_LD + 16 * s + 8 * (lane >> 5)) * 2);
-}
-__device__ __forceinline__ s16x4 tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-// the same fragment from an outer-fast image [k][ld] by two transposed reads (moe_kernels.hip frag_ofast, with the pitch as an argument)
-template <class V8> __device__ __forceinline__ V8 frag_ofast(const char* img, int ld, int ob, int s, int lane) {
-  const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int col = ob * 32 + 16 * (G & 1) + 4 * p, kr = 16 * s + 8 * (G >> 1) + q;
-  const s16x4 lo = tr_read(img + (kr * ld + col) * 2), hi = tr_read(img + ((kr + 4) * ld + col) * 2);
-  const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(V8, both);
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------------
 // down: out[T, R] = X[T, K] . M[R, K]^T.  A workgroup owns 128 rows; wave w rows 32w .. 32w+31 and all NCB = ceil(R / 32) column blocks.
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -82,7 +55,7 @@ struct DownArgs {
 
 template <int DT, int NCB>
 __global__ __launch_bounds__(256) void down_k(DownArgs a) {
-  using V8 = typename E<DT>::v8;
+  using V8 = typename Ty<DT>::v8;
   __shared__ __attribute__((aligned(16))) char lds_x[BM * KF_LD * 2];
   __shared__ __attribute__((aligned(16))) char lds_m[NCB * 32 * KF_LD * 2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -117,13 +90,13 @@ __global__ __launch_bounds__(256) void down_k(DownArgs a) {
 #pragma unroll
     for (int s = 0; s < BK / 16; ++s) {
       if (kb + 16 * s >= a.K) break;                         // uniform: K is a multiple of 16
-      const V8 fa = frag_kfast<V8>(lds_x, wave, s, lane);
+      const V8 fa = frag_kfast<V8>(lds_x, KF_LD, wave, s, lane);
 #pragma unroll
-      for (int j = 0; j < NCB; ++j) acc[j] = E<DT>::mma(fa, frag_kfast<V8>(lds_m, j, s, lane), acc[j]);
+      for (int j = 0; j < NCB; ++j) acc[j] = Ty<DT>::mma(fa, frag_kfast<V8>(lds_m, KF_LD, j, s, lane), acc[j]);
     }
   }
   // C block j: register r holds row 8(r>>2) + 4(lane>>5) + (r&3), column lane & 31
-  typename E<DT>::e* out = reinterpret_cast<typename E<DT>::e*>(a.out);
+  typename Ty<DT>::e* out = reinterpret_cast<typename Ty<DT>::e*>(a.out);
 #pragma unroll
   for (int j = 0; j < NCB; ++j) {
     const int n = j * 32 + (lane & 31);
@@ -132,7 +105,7 @@ __global__ __launch_bounds__(256) void down_k(DownArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = m0 + wave * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-      if (m < a.T) out[(int64_t)m * a.ldo + n] = (typename E<DT>::e)(acc[j][r] * sc);
+      if (m < a.T) out[(int64_t)m * a.ldo + n] = (typename Ty<DT>::e)(acc[j][r] * sc);
     }
   }
 }
@@ -151,7 +124,7 @@ struct WgradArgs {
 
 template <int DT, int NCB>
 __global__ __launch_bounds__(256) void wgrad_k(WgradArgs a) {
-  using V8 = typename E<DT>::v8;
+  using V8 = typename Ty<DT>::v8;
   constexpr int LLD = NCB * 32 + 8, VPR = NCB * 4;          // pitch of the L image; 16-byte vectors per staged L row
   __shared__ __attribute__((aligned(16))) char lds_l[BK * LLD * 2];
   __shared__ __attribute__((aligned(16))) char lds_x[BK * XF_LD * 2];
@@ -190,7 +163,7 @@ __global__ __launch_bounds__(256) void wgrad_k(WgradArgs a) {
       if (tb + 16 * s >= t1) break;                          // uniform; rows beyond t1 are zero in the images
       const V8 fb = frag_ofast<V8>(lds_x, XF_LD, wave, s, lane);
 #pragma unroll
-      for (int i = 0; i < NCB; ++i) acc[i] = E<DT>::mma(frag_ofast<V8>(lds_l, LLD, i, s, lane), fb, acc[i]);
+      for (int i = 0; i < NCB; ++i) acc[i] = Ty<DT>::mma(frag_ofast<V8>(lds_l, LLD, i, s, lane), fb, acc[i]);
     }
   }
   float* out = a.part + (int64_t)blockIdx.y * a.R * a.K;
@@ -205,10 +178,19 @@ __global__ __launch_bounds__(256) void wgrad_k(WgradArgs a) {
     }
 }
 
-inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline int vec_ok(const void* p, int64_t ld) { return a16(p) && ld % 8 == 0; }
-inline unsigned nblk(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-inline int ncb_of(int R) { return R <= 32 ? 1 : R <= 64 ? 2 : R <= 128 ? 4 : 8; }
+inline int vec_ok(const void* p, int64_t ld) { return aligned16(p) && ld % 8 == 0; }
+
+// The kernel form of a down / wgrad call: f(DT, NCB) with DT the 16-bit storage type and NCB = 1, 2, 4 or 8 the rank class, the number of
+// 32-wide blocks that hold the rank R <= 256
+template <class F> inline void lora_form(int32_t dtype, int R, F&& f) {
+  using std::integral_constant;
+  dta_storage_type16(dtype, [&](auto dt) {
+    if (R <= 32) f(dt, integral_constant<int, 1>{});
+    else if (R <= 64) f(dt, integral_constant<int, 2>{});
+    else if (R <= 128) f(dt, integral_constant<int, 4>{});
+    else f(dt, integral_constant<int, 8>{});
+  });
+}
 
 // rows of one slab of the weight gradient: whole 64-row steps, about 512 workgroups over (K tiles) x (slabs), at most 64 slabs
 inline int slab_rows(int T, int K) {
@@ -234,16 +216,8 @@ int dta_lora_down(const void* x, int64_t ldx, const void* m, int64_t ldm, void* 
   hipStream_t st = (hipStream_t)stream;
   DownArgs a{(const uint16_t*)x, (const uint16_t*)m, out, ldx, ldm, ldo, T, R, K, vec_ok(x, ldx), vec_ok(m, ldm), rscale_host != nullptr, {}};
   fill_scale(a.rs, rscale_host, R);
-  const dim3 g(nblk(T, BM)), b(256);
-#define DTA_DOWN(DT)                                                   \
-  switch (ncb_of(R)) {                                                 \
-    case 1: down_k<DT, 1><<<g, b, 0, st>>>(a); break;                  \
-    case 2: down_k<DT, 2><<<g, b, 0, st>>>(a); break;                  \
-    case 4: down_k<DT, 4><<<g, b, 0, st>>>(a); break;                  \
-    default: down_k<DT, 8><<<g, b, 0, st>>>(a); break;                 \
-  }
-  if (dtype == DTA_BF16) { DTA_DOWN(DTA_BF16) } else { DTA_DOWN(DTA_F16) }
-#undef DTA_DOWN
+  const dim3 g(ceil_blocks(T, BM)), b(256);
+  lora_form(dtype, R, [&](auto dt, auto ncb) { down_k<decltype(dt)::value, decltype(ncb)::value><<<g, b, 0, st>>>(a); });
   return DTA_LAUNCH_STATUS();
 }
 
@@ -262,16 +236,8 @@ int dta_lora_wgrad(const void* l, int64_t ldl, const void* x, int64_t ldx, float
   hipStream_t st = (hipStream_t)stream;
   WgradArgs a{(const uint16_t*)l, (const uint16_t*)x, part, ldl, ldx, T, R, K, slab_rows(T, K), vec_ok(l, ldl), vec_ok(x, ldx), rscale_host != nullptr, {}};
   fill_scale(a.rs, rscale_host, R);
-  const dim3 g(nblk(K, 128), dta_lora_wgrad_slabs(T, K)), b(256);
-#define DTA_WG(DT)                                                     \
-  switch (ncb_of(R)) {                                                 \
-    case 1: wgrad_k<DT, 1><<<g, b, 0, st>>>(a); break;                 \
-    case 2: wgrad_k<DT, 2><<<g, b, 0, st>>>(a); break;                 \
-    case 4: wgrad_k<DT, 4><<<g, b, 0, st>>>(a); break;                 \
-    default: wgrad_k<DT, 8><<<g, b, 0, st>>>(a); break;                \
-  }
-  if (dtype == DTA_BF16) { DTA_WG(DTA_BF16) } else { DTA_WG(DTA_F16) }
-#undef DTA_WG
+  const dim3 g(ceil_blocks(K, 128), dta_lora_wgrad_slabs(T, K)), b(256);
+  lora_form(dtype, R, [&](auto dt, auto ncb) { wgrad_k<decltype(dt)::value, decltype(ncb)::value><<<g, b, 0, st>>>(a); });
   return DTA_LAUNCH_STATUS();
 }
 

@@ -14,27 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dta_common.h"
+#include "dta_device.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-
-template <int DT> struct E;
-template <> struct E<DTA_BF16> { using e = __bf16; using v8 = bf16x8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); } };
-template <> struct E<DTA_F16> { using e = _Float16; using v8 = f16x8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); } };
-template <> struct E<DTA_F32> { using e = float; };
-
-template <int DT> __device__ __forceinline__ float ldf(const void* p, int64_t i) { return (float)reinterpret_cast<const typename E<DT>::e*>(p)[i]; }
-template <int DT> __device__ __forceinline__ void stf(void* p, int64_t i, float v) { reinterpret_cast<typename E<DT>::e*>(p)[i] = (typename E<DT>::e)v; }
-
-__device__ __forceinline__ float wave_max(float v) { for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; }
-__device__ __forceinline__ float wave_sum(float v) { for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o); return v; }
+template <int DT> __device__ __forceinline__ float ldf(const void* p, int64_t i) { return (float)reinterpret_cast<const typename Ty<DT>::e*>(p)[i]; }
+template <int DT> __device__ __forceinline__ void stf(void* p, int64_t i, float v) { reinterpret_cast<typename Ty<DT>::e*>(p)[i] = (typename Ty<DT>::e)v; }
 
 constexpr int MAXE = 256, MAXK = 16, EPL = MAXE / 64;    // experts per lane in the router kernels
 
@@ -230,26 +215,9 @@ __device__ __forceinline__ void store_ofast(const Stage& s, char* img) {
   for (int i = 0; i < 4; ++i) { const int v = threadIdx.x + 256 * i, kk = v >> 4, oc = (v & 15) * 8; *reinterpret_cast<uint4*>(img + (kk * OF_LD + oc) * 2) = s.v[i]; }
 }
 
-// fragment of k-step s for the 32-row/column block ob: lane (r = lane & 31, h = lane >> 5) gets operand[ob*32 + r][16s + 8h + j], j = 0..7
-template <class V8> __device__ __forceinline__ V8 frag_kfast(const char* img, int ob, int s, int lane) {
-  return *reinterpret_cast<const V8*>(img + ((ob * 32 + (lane & 31)) * KF_LD + 16 * s + 8 * (lane >> 5)) * 2);
-}
-__device__ __forceinline__ s16x4 tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-// the same fragment from an outer-fast image by two transposed reads: in 16-lane group G (column half c = G & 1, k half h = G >> 1),
-// lane 4q + p addresses row k = 16s + 8h + q (+4), columns ob*32 + 16c + 4p .. +3; lane i of the group receives column 16c + i
-template <class V8> __device__ __forceinline__ V8 frag_ofast(const char* img, int ob, int s, int lane) {
-  const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int col = ob * 32 + 16 * (G & 1) + 4 * p, kr = 16 * s + 8 * (G >> 1) + q;
-  const s16x4 lo = tr_read(img + (kr * OF_LD + col) * 2), hi = tr_read(img + ((kr + 4) * OF_LD + col) * 2);
-  const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(V8, both);
-}
-
 template <int DT, int MODE>
 __global__ __launch_bounds__(256) void gg_mfma_k(GemmArgs a) {
-  using V8 = typename E<DT>::v8;
+  using V8 = typename Ty<DT>::v8;
   __shared__ __attribute__((aligned(16))) char lds_a[IMG * 2];
   __shared__ __attribute__((aligned(16))) char lds_b[IMG * 2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
@@ -292,17 +260,17 @@ __global__ __launch_bounds__(256) void gg_mfma_k(GemmArgs a) {
       V8 fa[2], fb[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        fa[i] = MODE < 2 ? frag_kfast<V8>(lds_a, 2 * wm + i, s, lane) : frag_ofast<V8>(lds_a, 2 * wm + i, s, lane);
-        fb[i] = MODE == 0 ? frag_kfast<V8>(lds_b, 2 * wn + i, s, lane) : frag_ofast<V8>(lds_b, 2 * wn + i, s, lane);
+        fa[i] = MODE < 2 ? frag_kfast<V8>(lds_a, KF_LD, 2 * wm + i, s, lane) : frag_ofast<V8>(lds_a, OF_LD, 2 * wm + i, s, lane);
+        fb[i] = MODE == 0 ? frag_kfast<V8>(lds_b, KF_LD, 2 * wn + i, s, lane) : frag_ofast<V8>(lds_b, OF_LD, 2 * wn + i, s, lane);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = E<DT>::mma(fa[i], fb[j], acc[i][j]);
+        for (int j = 0; j < 2; ++j) acc[i][j] = Ty<DT>::mma(fa[i], fb[j], acc[i][j]);
     }
   }
   // C block (i, j): register r holds row 8(r>>2) + 4(lane>>5) + (r&3), column lane & 31
-  typename E<DT>::e* out = reinterpret_cast<typename E<DT>::e*>(a.out);
+  typename Ty<DT>::e* out = reinterpret_cast<typename Ty<DT>::e*>(a.out);
   const int64_t ldo = MODE == 0 ? a.N : a.K;
   const int64_t obase = MODE == 2 ? (int64_t)e * a.N * a.K : 0;
 #pragma unroll
@@ -313,7 +281,7 @@ __global__ __launch_bounds__(256) void gg_mfma_k(GemmArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = m0 + wm * 64 + i * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-        if (m < mlim && n < nlim) out[obase + (int64_t)m * ldo + n] = (typename E<DT>::e)acc[i][j][r];
+        if (m < mlim && n < nlim) out[obase + (int64_t)m * ldo + n] = (typename Ty<DT>::e)acc[i][j][r];
       }
     }
 }
@@ -430,9 +398,6 @@ __global__ __launch_bounds__(256) void combine_bwd_dw_k(const void* dout, const 
   if (lane == 0) stf<DT>(dw, p, acc);
 }
 
-inline bool a16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-inline unsigned nblk(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 }  // namespace
 
 extern "C" {
@@ -440,28 +405,26 @@ extern "C" {
 int dta_moe_router_fwd(const void* logits, int32_t* topk_ids, void* topk_w, float* lse, int32_t T, int32_t E_, int32_t k, int32_t norm_topk,
                        int32_t dtype, void* stream) {
   if (T < 0 || E_ <= 0 || k <= 0 || k > E_ || (T > 0 && (!logits || !topk_ids || !topk_w || !lse))) return DTA_EINVAL;
-  if (E_ > MAXE || k > MAXK || dtype < DTA_BF16 || dtype > DTA_F32) return DTA_EUNSUPPORTED;
+  if (E_ > MAXE || k > MAXK || !row_dtype_ok(dtype)) return DTA_EUNSUPPORTED;
   DTA_REFUSE_IF_PRIOR_ERROR();
   if (T == 0) return DTA_OK;
   hipStream_t st = (hipStream_t)stream;
-  dim3 g(nblk(T, 4)), b(256);
-  if (dtype == DTA_BF16) router_fwd_k<DTA_BF16><<<g, b, 0, st>>>(logits, topk_ids, topk_w, lse, T, E_, k, norm_topk);
-  else if (dtype == DTA_F16) router_fwd_k<DTA_F16><<<g, b, 0, st>>>(logits, topk_ids, topk_w, lse, T, E_, k, norm_topk);
-  else router_fwd_k<DTA_F32><<<g, b, 0, st>>>(logits, topk_ids, topk_w, lse, T, E_, k, norm_topk);
+  dim3 g(ceil_blocks(T, 4)), b(256);
+  dta_storage_type(dtype, [&](auto dt) { router_fwd_k<decltype(dt)::value><<<g, b, 0, st>>>(logits, topk_ids, topk_w, lse, T, E_, k, norm_topk); });
   return DTA_LAUNCH_STATUS();
 }
 
 int dta_moe_router_bwd(const void* logits, const float* lse, const int32_t* topk_ids, const void* dtopk_w, void* dlogits,
                        int32_t T, int32_t E_, int32_t k, int32_t norm_topk, int32_t dtype, void* stream) {
   if (T < 0 || E_ <= 0 || k <= 0 || k > E_ || (T > 0 && (!logits || !lse || !topk_ids || !dtopk_w || !dlogits))) return DTA_EINVAL;
-  if (E_ > MAXE || k > MAXK || dtype < DTA_BF16 || dtype > DTA_F32) return DTA_EUNSUPPORTED;
+  if (E_ > MAXE || k > MAXK || !row_dtype_ok(dtype)) return DTA_EUNSUPPORTED;
   DTA_REFUSE_IF_PRIOR_ERROR();
   if (T == 0) return DTA_OK;
   hipStream_t st = (hipStream_t)stream;
-  dim3 g(nblk(T, 4)), b(256);
-  if (dtype == DTA_BF16) router_bwd_k<DTA_BF16><<<g, b, 0, st>>>(logits, lse, topk_ids, dtopk_w, dlogits, T, E_, k, norm_topk);
-  else if (dtype == DTA_F16) router_bwd_k<DTA_F16><<<g, b, 0, st>>>(logits, lse, topk_ids, dtopk_w, dlogits, T, E_, k, norm_topk);
-  else router_bwd_k<DTA_F32><<<g, b, 0, st>>>(logits, lse, topk_ids, dtopk_w, dlogits, T, E_, k, norm_topk);
+  dim3 g(ceil_blocks(T, 4)), b(256);
+  dta_storage_type(dtype, [&](auto dt) {
+    router_bwd_k<decltype(dt)::value><<<g, b, 0, st>>>(logits, lse, topk_ids, dtopk_w, dlogits, T, E_, k, norm_topk);
+  });
   return DTA_LAUNCH_STATUS();
 }
 
@@ -495,58 +458,55 @@ int dta_moe_grouped_gemm(int32_t mode, const void* x, const void* w, const void*
   if (mode < DTA_MOE_FWD || mode > DTA_MOE_WGRAD || n_rows < 0 || E_ <= 0 || N <= 0 || K <= 0 || !out || !expert_offsets) return DTA_EINVAL;
   if ((mode == DTA_MOE_FWD && (!x || !w)) || (mode == DTA_MOE_DGRAD && (!dy || !w)) || (mode == DTA_MOE_WGRAD && (!dy || !x))) return DTA_EINVAL;
   if (mode != DTA_MOE_WGRAD && !tiles) return DTA_EINVAL;
-  if (N % 16 || K % 16 || dtype < DTA_BF16 || dtype > DTA_F32) return DTA_EUNSUPPORTED;
-  if (!a16(x) || !a16(w) || !a16(dy) || !a16(out)) return DTA_EALIGN;
+  if (N % 16 || K % 16 || !row_dtype_ok(dtype)) return DTA_EUNSUPPORTED;
+  if ((x && !aligned16(x)) || (w && !aligned16(w)) || (dy && !aligned16(dy)) || !aligned16(out)) return DTA_EALIGN;   // the operand a mode does not read may be null
   DTA_REFUSE_IF_PRIOR_ERROR();
   hipStream_t st = (hipStream_t)stream;
   GemmArgs a{x, w, dy, out, gather, expert_offsets, tiles, N, K};
   const int bound = (n_rows + BM - 1) / BM + E_;
   if (mode != DTA_MOE_WGRAD && n_rows == 0) return DTA_OK;
   const int nout = mode == DTA_MOE_FWD ? N : K;
+  const dim3 b(256);
   if (dtype == DTA_F32) {
-    dim3 b(256);
-    if (mode == DTA_MOE_FWD) gg_f32_k<0><<<dim3(2 * bound, nblk(nout, FB)), b, 0, st>>>(a);
-    else if (mode == DTA_MOE_DGRAD) gg_f32_k<1><<<dim3(2 * bound, nblk(nout, FB)), b, 0, st>>>(a);
-    else gg_f32_k<2><<<dim3(nblk(K, FB), nblk(N, FB), E_), b, 0, st>>>(a);
+    if (mode == DTA_MOE_FWD) gg_f32_k<0><<<dim3(2 * bound, ceil_blocks(nout, FB)), b, 0, st>>>(a);
+    else if (mode == DTA_MOE_DGRAD) gg_f32_k<1><<<dim3(2 * bound, ceil_blocks(nout, FB)), b, 0, st>>>(a);
+    else gg_f32_k<2><<<dim3(ceil_blocks(K, FB), ceil_blocks(N, FB), E_), b, 0, st>>>(a);
     return DTA_LAUNCH_STATUS();
   }
-  dim3 b(256);
-#define DTA_GG(DT)                                                                                           \
-  if (mode == DTA_MOE_FWD) gg_mfma_k<DT, 0><<<dim3(bound, nblk(nout, BN)), b, 0, st>>>(a);                   \
-  else if (mode == DTA_MOE_DGRAD) gg_mfma_k<DT, 1><<<dim3(bound, nblk(nout, BN)), b, 0, st>>>(a);            \
-  else gg_mfma_k<DT, 2><<<dim3(nblk(K, BN), nblk(N, BM), E_), b, 0, st>>>(a);
-  if (dtype == DTA_BF16) { DTA_GG(DTA_BF16) } else { DTA_GG(DTA_F16) }
-#undef DTA_GG
+  dta_storage_type16(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (mode == DTA_MOE_FWD) gg_mfma_k<DT, 0><<<dim3(bound, ceil_blocks(nout, BN)), b, 0, st>>>(a);
+    else if (mode == DTA_MOE_DGRAD) gg_mfma_k<DT, 1><<<dim3(bound, ceil_blocks(nout, BN)), b, 0, st>>>(a);
+    else gg_mfma_k<DT, 2><<<dim3(ceil_blocks(K, BN), ceil_blocks(N, BM), E_), b, 0, st>>>(a);
+  });
   return DTA_LAUNCH_STATUS();
 }
 
 int dta_moe_combine_fwd(const void* y, const void* topk_w, const int32_t* row_of_pair, void* out, int32_t T, int32_t k, int32_t H,
                         int32_t dtype, void* stream) {
   if (T < 0 || k <= 0 || H <= 0 || (T > 0 && (!y || !row_of_pair || !out))) return DTA_EINVAL;
-  if (dtype < DTA_BF16 || dtype > DTA_F32) return DTA_EUNSUPPORTED;
+  if (!row_dtype_ok(dtype)) return DTA_EUNSUPPORTED;
   DTA_REFUSE_IF_PRIOR_ERROR();
   if (T == 0) return DTA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned g = nblk((int64_t)T * H, 256);
-  if (dtype == DTA_BF16) combine_fwd_k<DTA_BF16><<<g, 256, 0, st>>>(y, topk_w, row_of_pair, out, T, k, H);
-  else if (dtype == DTA_F16) combine_fwd_k<DTA_F16><<<g, 256, 0, st>>>(y, topk_w, row_of_pair, out, T, k, H);
-  else combine_fwd_k<DTA_F32><<<g, 256, 0, st>>>(y, topk_w, row_of_pair, out, T, k, H);
+  const unsigned g = ceil_blocks((int64_t)T * H, 256);
+  dta_storage_type(dtype, [&](auto dt) { combine_fwd_k<decltype(dt)::value><<<g, 256, 0, st>>>(y, topk_w, row_of_pair, out, T, k, H); });
   return DTA_LAUNCH_STATUS();
 }
 
 int dta_moe_combine_bwd(const void* dout, const void* y, const void* topk_w, const int32_t* row_of_pair, void* dy, void* dtopk_w,
                         int32_t T, int32_t k, int32_t H, int32_t dtype, void* stream) {
   if (T < 0 || k <= 0 || H <= 0 || (T > 0 && (!dout || !y || !topk_w || !row_of_pair || !dy || !dtopk_w))) return DTA_EINVAL;
-  if (dtype < DTA_BF16 || dtype > DTA_F32) return DTA_EUNSUPPORTED;
+  if (!row_dtype_ok(dtype)) return DTA_EUNSUPPORTED;
   DTA_REFUSE_IF_PRIOR_ERROR();
   if (T == 0) return DTA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned g1 = nblk((int64_t)T * k * H, 256), g2 = nblk((int64_t)T * k, 4);
-#define DTA_CB(DT)                                                                                    \
-  combine_bwd_dy_k<DT><<<g1, 256, 0, st>>>(dout, topk_w, row_of_pair, dy, T, k, H);                   \
-  combine_bwd_dw_k<DT><<<g2, 256, 0, st>>>(dout, y, row_of_pair, dtopk_w, T, k, H);
-  if (dtype == DTA_BF16) { DTA_CB(DTA_BF16) } else if (dtype == DTA_F16) { DTA_CB(DTA_F16) } else { DTA_CB(DTA_F32) }
-#undef DTA_CB
+  const unsigned g1 = ceil_blocks((int64_t)T * k * H, 256), g2 = ceil_blocks((int64_t)T * k, 4);
+  dta_storage_type(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    combine_bwd_dy_k<DT><<<g1, 256, 0, st>>>(dout, topk_w, row_of_pair, dy, T, k, H);
+    combine_bwd_dw_k<DT><<<g2, 256, 0, st>>>(dout, y, row_of_pair, dtopk_w, T, k, H);
+  });
   return DTA_LAUNCH_STATUS();
 }
 

@@ -31,6 +31,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "dta_common.h"
+#include "dta_device.h"
 
 // Diagnostic build switch (-DDTA_STAMP=1): in-kernel s_memtime stamps at the segment boundaries of the forward's tile loop, summed per
 // wave in scalar registers and written to a debug buffer of their own (cdna_hip_programming.md §7 "In-kernel stamps"); scripts/fwd_stamps.py
@@ -54,24 +55,6 @@ extern "C" int dta_debug_set_stamp_buffer(void* p) { return hipMemcpyToSymbol(HI
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-
-template <int DT> struct Ty;
-template <> struct Ty<DTA_BF16> {
-  using e = __bf16; using v8 = bf16x8; using v4 = bf16x4;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Ty<DTA_F16> {
-  using e = _Float16; using v8 = f16x8; using v4 = f16x4;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 struct AttnParams {
   const void *q, *k, *v, *o, *dout;
   void *out, *dq, *dk, *dv;
@@ -94,8 +77,6 @@ struct AttnParamsWC : AttnParamsW { float softcap; };
 template <bool WIN, bool CAP = false> using AttnP = typename std::conditional<CAP, typename std::conditional<WIN, AttnParamsWC, AttnParamsC>::type,
                                                                               typename std::conditional<WIN, AttnParamsW, AttnParams>::type>::type;
 
-constexpr float LOG2E = 1.4426950408889634f;
-
 // Byte offset of 16-B chunk `ch` of row `row` in a [rows][D x 16-bit] image.  head_dim 128: 256-B rows (16 chunks); the XOR makes both the
 // 32x32x16 row reads (ds_read_b128) and the transposed reads conflict-free.
 // head_dim 64: the same image with 128-B rows (8 chunks).
@@ -117,10 +98,6 @@ template <int D> constexpr int tile_bytes() { return 64 * 2 * D; }   // 64 rows 
 
 template <class V8, int D> __device__ __forceinline__ V8 row_frag(const char* img, int row, int ch) {
   return *reinterpret_cast<const V8*>(img + img_off_d<D>(row, ch));
-}
-
-__device__ __forceinline__ s16x4 tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
 // A-operand fragment read TRANSPOSED from the image: A[m = 32*mb + (lane&31)][kk], where the 16-deep
@@ -146,11 +123,6 @@ template <int DT> __device__ __forceinline__ typename Ty<DT>::v8 pack_half(const
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// tanh(x) from a = 2 log2(e) x in fp32: 1 - 2 / (1 + 2^a), one v_exp_f32 and one v_rcp_f32.  2^a overflows to +inf for large a and the
-// reciprocal of inf is 0, so the value saturates to exactly +1 (and to -1 when 2^a underflows to 0): finite for every finite or infinite a
-// - a quotient of two exponentials would be inf / inf there.  Absolute error a few 2^-24 (the cancellation for small |x| is absolute, not
-// relative: the capped score softcap * tanh is off by the order of softcap * 2^-24, the fp32 floor of the score itself).
-__device__ __forceinline__ float cap_tanh(float a) { return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + fast_exp2(a)), 1.f); }
 // The cap's two constants: kcap turns a raw q.k into tanh's argument a (2 log2(e) scale / softcap), and the log2-domain score factor c
 // becomes softcap log2(e).  Without a cap the one statement the kernels had (c = scale log2(e)) is all that is left.
 #define DTA_CAP_CONSTANTS                                                                                  \
@@ -1017,8 +989,6 @@ __global__ __launch_bounds__(256) void tree_attn_bwd_dkv_finalize_kernel(AttnPar
     *reinterpret_cast<v4*>(out) = w;
   }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // kernel parameters of the chosen form from the call's arguments (the forward's backward fields are null); hgroups / head0 are set per launch
 template <bool WIN, bool CAP> AttnP<WIN, CAP> kernel_params(const DtaAttnArgs& a) {

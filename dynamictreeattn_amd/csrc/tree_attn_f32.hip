@@ -14,10 +14,10 @@
 #include <stdint.h>
 #include <type_traits>
 #include "dta_common.h"
+#include "dta_device.h"
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int ROWS = 64;        // rows owned by a workgroup (4 lanes each -> 256 threads)
 constexpr int ST = 32;          // rows of the other side staged per LDS tile
 

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 DTYPES = [torch.bfloat16, torch.float16]
 TS = [1, 63, 257, 4099, 28160]
-RS = [1, 4, 6, 16, 64, 200, 256]
+RS = [1, 4, 6, 16, 64, 96, 200, 256]
 KS = [16, 1024, 4096 + 16]
 
 

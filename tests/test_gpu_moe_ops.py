@@ -24,7 +24,7 @@ def _within(out, ref, bnd, what):
 
 @pytest.mark.parametrize("E,k", [(8, 1), (8, 2), (60, 2), (60, 8), (128, 8), (128, 1), (256, 16)])
 @pytest.mark.parametrize("norm", [True, False])
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
 def test_router_forward_backward(E, k, norm, dtype):
     g = torch.Generator().manual_seed(E * 31 + k)
     T = 301
