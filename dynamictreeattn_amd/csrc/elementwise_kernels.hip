@@ -1,6 +1,8 @@
 // Fused row kernels of the decoder layer for gfx950 — HBM-bound, 16-byte accesses, fp32 math.
 //   dta_rmsnorm_fwd/bwd        y = w · cast(x · rsqrt(mean(x²)+eps))                 (Qwen3RMSNorm arithmetic)
 //   dta_qk_norm_rope_fwd/bwd   per (token, head) of 128 or 64: optional RMSNorm, then RoPE at position = trie depth
+//   dta_wide_qk_norm_rope_fwd/bwd  per token: RMSNorm over the whole [NH·D] projection row (OLMo), then RoPE per head
+//   dta_rmsnorm_add_fwd        out = res + cast(w · y · rsqrt(mean(y²)+eps)): OLMo's post-norm branch end
 //   dta_swiglu_fwd/bwd         y = cast(silu(g)) · u
 // These replace ~40 torch elementwise launches per layer (fp32 up-casts included); together they are ~18 ms of a
 // 250 ms step (profiles/r1_bench_kernel_stats.csv).  Reference call sites: the model call of
@@ -334,6 +336,259 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __res
 }
 
 // ---------------------------------------------------------------------------------------------
+// OLMo-2 / OLMo-3: q/k RMSNorm over the WHOLE projection row (NH*D <= 8192 elements, weight [NH*D]), then RoPE per head.
+// WPT = waves per token.  Rows of up to 2 048 elements: one wave per token, 4 tokens per workgroup (WPT 1); longer rows: the 4 waves of
+// a workgroup share one token (WPT 4) - at most 4 groups per lane either way, where one wave holding a row of 8 192 (16 groups per lane)
+// ran at 2 waves / SIMD forward and 1 backward and reached 0.36 / 0.23 of 8 TB/s at 5 120.  Grid-stride over tokens.  Lane l of the
+// L = 64 WPT lanes of a token owns the 16-byte groups i = l + L a (a < NA) of the row: group i is elements 8i .. 8i+7 of head 8i / D.
+// L is a multiple of LPH = D / 8, so a lane's position inside its head (sub = l % LPH) - and with it its 8 cos / 8 sin values - is the
+// same for every a: the token's table row is fetched once and reused across its heads; the rotate_half partner of group i is group
+// i ^ (LPH/2) = lane l ^ (LPH/2) of the same wave at the same a (an NH*D row is a whole number of heads, so both are live or neither
+// is).  The row stays in registers between the sum of squares and the scaling: one read of x.  The row sums are wave shuffles, and
+// with WPT 4 one LDS word per wave.
+// ---------------------------------------------------------------------------------------------
+// sum of v over the lanes of one token: the wave's shuffles, and for WPT 4 the four waves' sums through `slot` (4 floats of LDS; the two
+// barriers make the slot reusable by the next call - every wave of the workgroup runs the same token loop, so they are uniform)
+template <int WPT> __device__ __forceinline__ float token_sum(float v, float* slot) {
+  v = wave_sum(v);
+  if constexpr (WPT == 1) return v;
+  else {
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float t = (slot[0] + slot[1]) + (slot[2] + slot[3]);
+    __syncthreads();
+    return t;
+  }
+}
+
+template <int DT, int NA, int D, int WPT>
+__global__ __launch_bounds__(256) void wide_qk_norm_rope_fwd_kernel(const void* __restrict__ x_, const void* __restrict__ w_, const float* __restrict__ cs,
+                                                                    void* __restrict__ y_, float* __restrict__ rstd, int T, int n,
+                                                                    int64_t x_st, float eps) {
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
+  constexpr int LPH = D / 8, L = 64 * WPT, TPB = 4 / WPT;     // lanes per head, lanes per token, tokens per workgroup pass
+  __shared__ float slot[4];
+  const int lane = WPT == 1 ? (threadIdx.x & 63) : threadIdx.x, sub = lane & (LPH - 1);
+  const e* w = reinterpret_cast<const e*>(w_);
+  const int nv = n >> 3;
+  const int per_lane = (nv + L - 1) / L;                    // <= NA, workgroup-uniform
+  for (int tok = blockIdx.x * TPB + (WPT == 1 ? (threadIdx.x >> 6) : 0); tok < T; tok += gridDim.x * TPB) {
+    const e* x = reinterpret_cast<const e*>(x_) + (int64_t)tok * x_st;
+    e* y = reinterpret_cast<e*>(y_) + (int64_t)tok * n;
+    const float* c = cs + (int64_t)tok * D + 8 * (sub & (LPH / 2 - 1));
+    float cj[8], sj[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { cj[j] = c[j]; sj[j] = sub < LPH / 2 ? -c[D / 2 + j] : c[D / 2 + j]; }
+    v8 keep[NA];
+    float ss = 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int i = lane + L * a;
+      if (a < per_lane && i < nv) {
+        const v8 v = *reinterpret_cast<const v8*>(x + 8 * i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; ss = __builtin_fmaf(f, f, ss); }
+        keep[a] = v;
+      }
+    }
+    ss = token_sum<WPT>(ss, slot);
+    const float r = __builtin_amdgcn_rsqf(ss / (float)n + eps);
+    if (lane == 0) rstd[tok] = r;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      if (a < per_lane) {                                   // wave-uniform: every lane takes part in the shuffles
+        const int i = lane + L * a;
+        const bool live = i < nv;
+        float av[8];
+        if (live) {
+          const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) av[j] = (float)(e)((float)wv[j] * ((float)keep[a][j] * r));      // Olmo2RMSNorm: w · x · r in fp32, ONE rounding
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) av[j] = 0.f;
+        }
+        v8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float other = __shfl_xor(av[j], LPH / 2);
+          o[j] = (e)(av[j] * cj[j] + other * sj[j]);
+        }
+        if (live) *reinterpret_cast<v8*>(y + 8 * i) = o;
+      }
+    }
+  }
+}
+
+// da = un-rotated dy in fp32 (never rounded); dx = r·(da·w − t̂·mean_n(da·w·t̂)), t̂ = x·r; dw partial per workgroup: Σ_tokens da·t̂.
+// dx_ may be dy_ (in place): a lane writes exactly the 16-byte groups it read; its partner's values arrive through registers.  x and dy
+// of the row stay in registers between the two passes (NA <= 4 groups per lane: at most 64 VGPRs).
+template <int DT, int NA, int D, int WPT>
+__global__ __launch_bounds__(256) void wide_qk_norm_rope_bwd_kernel(const void* __restrict__ x_, const void* __restrict__ w_, const float* __restrict__ cs,
+                                                                    const void* dy_, const float* __restrict__ rstd, void* dx_,
+                                                                    float* __restrict__ dw_part, int T, int n, int64_t x_st, int64_t dy_st_t,
+                                                                    int64_t dy_st_h, int64_t dx_st) {
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
+  constexpr int LPH = D / 8, LSH = D == 128 ? 4 : 3, L = 64 * WPT, TPB = 4 / WPT;
+  __shared__ float red[WPT == 1 ? 4 * 64 * 8 : 4];          // WPT 1: the 4 waves' dw partials; WPT 4: the row sum's slot
+  const int lane = WPT == 1 ? (threadIdx.x & 63) : threadIdx.x, wave = threadIdx.x >> 6, sub = lane & (LPH - 1);
+  const e* w = reinterpret_cast<const e*>(w_);
+  const int nv = n >> 3;
+  const int per_lane = (nv + L - 1) / L;                    // <= NA, block-uniform
+  float acc[NA][8];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[a][j] = 0.f;
+  for (int tok = blockIdx.x * TPB + (WPT == 1 ? wave : 0); tok < T; tok += gridDim.x * TPB) {
+    const e* x = reinterpret_cast<const e*>(x_) + (int64_t)tok * x_st;
+    const e* dy = reinterpret_cast<const e*>(dy_) + (int64_t)tok * dy_st_t + 8 * sub;
+    e* dx = reinterpret_cast<e*>(dx_) + (int64_t)tok * dx_st;
+    const float* c = cs + (int64_t)tok * D + 8 * (sub & (LPH / 2 - 1));
+    float cj[8], sj[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { cj[j] = c[j]; sj[j] = sub < LPH / 2 ? c[D / 2 + j] : -c[D / 2 + j]; }
+    const float r = rstd[tok];
+    float dot = 0.f;
+    v8 kx[NA], kg[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      if (a < per_lane) {
+        const int i = lane + L * a;
+        const bool live = i < nv;
+        v8 v, g;
+        if (live) { v = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(x + 8 * i)); g = *reinterpret_cast<const v8*>(dy + (int64_t)(i >> LSH) * dy_st_h); }
+        else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { v[j] = (e)0.f; g[j] = (e)0.f; }
+        }
+        if (live) {
+          const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float gj = (float)g[j];
+            const float da = gj * cj[j] + __shfl_xor(gj, LPH / 2) * sj[j];
+            const float t = (float)v[j] * r;
+            dot = __builtin_fmaf(da * (float)wv[j], t, dot); acc[a][j] = __builtin_fmaf(da, t, acc[a][j]);
+          }
+        }
+        kx[a] = v; kg[a] = g;
+      }
+    }
+    dot = token_sum<WPT>(dot, red) / (float)n;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      if (a < per_lane) {
+        const int i = lane + L * a;
+        const bool live = i < nv;
+        const v8 v = kx[a], g = kg[a];
+        float da[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float gj = (float)g[j]; da[j] = gj * cj[j] + __shfl_xor(gj, LPH / 2) * sj[j]; }
+        if (live) {
+          const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
+          v8 o;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { const float t = (float)v[j] * r; o[j] = (e)(r * (da[j] * (float)wv[j] - t * dot)); }
+          *reinterpret_cast<v8*>(dx + 8 * i) = o;
+        }
+      }
+    }
+  }
+  if (!dw_part) return;                                       // frozen weight: no partials wanted (block-uniform)
+  float* out = dw_part + (int64_t)blockIdx.x * n;
+  if constexpr (WPT == 4) {                                   // every lane of the workgroup owns its columns alone
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int i = lane + L * a;
+      if (a < per_lane && i < nv) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[8 * i + j] = acc[a][j];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {                            // as rmsnorm_bwd_kernel: the 4 waves' partials through LDS, one group at a time
+      if (a < per_lane) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[(wave * 64 + lane) * 8 + j] = acc[a][j];
+        __syncthreads();
+        if (wave == 0) {
+          const int i = lane + 64 * a;
+          if (i < nv) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) out[8 * i + j] = red[lane * 8 + j] + red[(64 + lane) * 8 + j] + red[(128 + lane) * 8 + j] + red[(192 + lane) * 8 + j];
+          }
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// OLMo's post-norm branch end: yn = cast(w · y · rsqrt(mean(y²)+eps)) - Olmo2RMSNorm multiplies by the weight in fp32 and rounds ONCE, unlike
+// the Qwen3 / Llama norm above - kept only when yn_ is given; out = cast(res + yn), one pass.
+// The forms of rmsnorm_fwd_kernel: NA > 0 keeps the row in registers, NA == 0 (any H) reads it twice.
+// ---------------------------------------------------------------------------------------------
+template <int DT, int NA>
+__global__ __launch_bounds__(256) void rmsnorm_add_fwd_kernel(const void* __restrict__ y_, const void* __restrict__ w_, const void* __restrict__ res_,
+                                                              void* __restrict__ out_, void* __restrict__ yn_, float* __restrict__ rstd,
+                                                              int R, int H, float eps) {
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const e* w = reinterpret_cast<const e*>(w_);
+  const int nv = H >> 3;
+  for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
+    const e* y = reinterpret_cast<const e*>(y_) + (int64_t)row * H;
+    const e* res = reinterpret_cast<const e*>(res_) + (int64_t)row * H;
+    e* out = reinterpret_cast<e*>(out_) + (int64_t)row * H;
+    e* yn = yn_ ? reinterpret_cast<e*>(yn_) + (int64_t)row * H : nullptr;
+    float ss = 0.f;
+    auto finish = [&](int i, const v8& v, float r) {
+      const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
+      const v8 rv = *reinterpret_cast<const v8*>(res + 8 * i);
+      v8 n8, o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { n8[j] = (e)((float)wv[j] * ((float)v[j] * r)); o[j] = (e)((float)rv[j] + (float)n8[j]); }
+      if (yn) *reinterpret_cast<v8*>(yn + 8 * i) = n8;
+      *reinterpret_cast<v8*>(out + 8 * i) = o;
+    };
+    if constexpr (NA > 0) {
+      v8 keep[NA];
+#pragma unroll
+      for (int a = 0; a < NA; ++a) {
+        const int i = lane + 64 * a;
+        if (i < nv) {
+          const v8 v = *reinterpret_cast<const v8*>(y + 8 * i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; ss = __builtin_fmaf(f, f, ss); }
+          keep[a] = v;
+        }
+      }
+      ss = wave_sum(ss);
+      const float r = __builtin_amdgcn_rsqf(ss / (float)H + eps);
+      if (lane == 0) rstd[row] = r;
+#pragma unroll
+      for (int a = 0; a < NA; ++a) {
+        const int i = lane + 64 * a;
+        if (i < nv) finish(i, keep[a], r);
+      }
+    } else {
+      for (int i = lane; i < nv; i += 64) {
+        const v8 v = *reinterpret_cast<const v8*>(y + 8 * i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; ss = __builtin_fmaf(f, f, ss); }
+      }
+      ss = wave_sum(ss);
+      const float r = __builtin_amdgcn_rsqf(ss / (float)H + eps);
+      if (lane == 0) rstd[row] = r;
+      for (int i = lane; i < nv; i += 64) finish(i, *reinterpret_cast<const v8*>(y + 8 * i), r);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // SwiGLU on rows of C columns; gate/up (and their gradients) may live side by side in one fused
 // [rows, 2C] GEMM output: `ld` = elements between consecutive rows of g/u (dg/du).
 template <int DT>
@@ -544,6 +799,19 @@ template <class F> inline void qk_form(int NH, int head_dim, F&& f) {
   else if (NH % 4 == 0) f(Int<4>{}, Int<128>{}); else f(Int<1>{}, Int<128>{});
 }
 
+// The kernel form of a projection-wide q/k norm + RoPE call: f(NA, D, WPT) for the row of n = NH*D <= 8192 elements - one wave per token
+// (WPT 1) with NA = 2 / 4 16-byte groups per lane up to 1 024 / 2 048, the workgroup's four waves on one token (WPT 4) with NA = 2 / 4
+// up to 4 096 / 8 192 - and D = head_dim (64 or 128)
+template <class F> inline void wide_qk_form(int64_t n, int head_dim, F&& f) {
+  auto by_n = [&](auto d) {
+    if (n <= 1024) f(Int<2>{}, d, Int<1>{});
+    else if (n <= 2048) f(Int<4>{}, d, Int<1>{});
+    else if (n <= 4096) f(Int<2>{}, d, Int<4>{});
+    else f(Int<4>{}, d, Int<4>{});
+  };
+  if (head_dim == 64) by_n(Int<64>{}); else by_n(Int<128>{});
+}
+
 // SwiGLU and GeGLU: one checked body per direction; kernel_of(DT) is the entry's kernel for the storage type DT
 template <class K>
 int glu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream, K kernel_of) {
@@ -649,6 +917,64 @@ extern "C" int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* c
     dta_storage_type(dtype, [&](auto dt) {
       hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<decltype(dt)::value, HPL, D>), grid, block, 0, st_, x, w, cos_sin, dy, rstd, dx, dw_partial, n, NH,
                          x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t);
+    });
+  });
+  return DTA_LAUNCH_STATUS();
+}
+
+extern "C" int dta_wide_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,
+                                         int32_t T, int32_t NH, int32_t head_dim, int64_t x_stride_t, float eps, int32_t dtype, void* stream) {
+  if (!x || !w || !cos_sin || !y || !rstd || T <= 0 || NH <= 0 || eps != eps) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64) || (int64_t)NH * head_dim > 8192) return DTA_EUNSUPPORTED;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(y) || x_stride_t % 8) return DTA_EALIGN;
+  const int n = NH * head_dim;
+  if (x_stride_t < n) return DTA_EINVAL;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const dim3 grid(row_blocks(T, 4, 8192)), block(256);
+  wide_qk_form(n, head_dim, [&](auto na, auto d, auto wpt) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((wide_qk_norm_rope_fwd_kernel<decltype(dt)::value, decltype(na)::value, decltype(d)::value, decltype(wpt)::value>), grid, block, 0, st_,
+                         x, w, cos_sin, y, rstd, T, n, x_stride_t, eps);
+    });
+  });
+  return DTA_LAUNCH_STATUS();
+}
+
+/* dw_partial: float [dta_wide_qk_norm_rope_bwd_blocks(T), NH*head_dim]; the caller sums it over dim 0 (dta_sum_slabs).  NULL: dx only. */
+extern "C" int dta_wide_qk_norm_rope_bwd_blocks(int32_t T) { return row_blocks(T, 4, 2048); }
+extern "C" int dta_wide_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, const void* dy, const float* rstd,
+                                         void* dx, float* dw_partial, int32_t T, int32_t NH, int32_t head_dim,
+                                         int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t, int32_t dtype, void* stream) {
+  if (!x || !w || !cos_sin || !dy || !rstd || !dx || T <= 0 || NH <= 0) return DTA_EINVAL;       // dw_partial NULL: dx only (frozen weight)
+  if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64) || (int64_t)NH * head_dim > 8192) return DTA_EUNSUPPORTED;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(dy) || !aligned16(dx) || x_stride_t % 8 || dy_stride_t % 8 || dy_stride_h % 8 || dx_stride_t % 8)
+    return DTA_EALIGN;
+  const int n = NH * head_dim;
+  if (x_stride_t < n || dx_stride_t < n) return DTA_EINVAL;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const dim3 grid(row_blocks(T, 4, 2048)), block(256);
+  wide_qk_form(n, head_dim, [&](auto na, auto d, auto wpt) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((wide_qk_norm_rope_bwd_kernel<decltype(dt)::value, decltype(na)::value, decltype(d)::value, decltype(wpt)::value>), grid, block, 0, st_,
+                         x, w, cos_sin, dy, rstd, dx, dw_partial, T, n, x_stride_t, dy_stride_t, dy_stride_h, dx_stride_t);
+    });
+  });
+  return DTA_LAUNCH_STATUS();
+}
+
+extern "C" int dta_rmsnorm_add_fwd(const void* y, const void* w, const void* res, void* out, void* yn, float* rstd,
+                                   int32_t R, int32_t H, float eps, int32_t dtype, void* stream) {
+  if (!y || !w || !res || !out || !rstd || R <= 0 || H <= 0 || eps != eps) return DTA_EINVAL;           // yn NULL: only out is wanted
+  if (!row_dtype_ok(dtype) || H % 8) return DTA_EUNSUPPORTED;
+  if (!aligned16(y) || !aligned16(w) || !aligned16(res) || !aligned16(out) || (yn && !aligned16(yn))) return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const dim3 grid(row_blocks(R, 4, 8192)), block(256);
+  rms_form<0>(H, 0.f, [&](auto na, auto) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((rmsnorm_add_fwd_kernel<decltype(dt)::value, decltype(na)::value>), grid, block, 0, st_, y, w, res, out, yn, rstd, R, H, eps);
     });
   });
   return DTA_LAUNCH_STATUS();

@@ -7,7 +7,7 @@ torch.  `Qwen3TreeLM` mirrors the HF module/parameter tree (``model.embed_tokens
 ``model.layers.N.self_attn.q_proj.weight`` …, tied head) so that
 
 * gradients compare name by name with grad/Qwen3-0.6B-TB-vs-DB-bf16.txt (310 tensors), and
-* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral/Gemma-2 ``*ForCausalLM`` by duck typing —
+* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral/Gemma-2/OLMo-2/OLMo-3 ``*ForCausalLM`` by duck typing —
   its own ``nn.Parameter`` objects are used, so ``param.grad`` lands where the training loop expects.
 """
 from __future__ import annotations
@@ -142,14 +142,41 @@ class Qwen3TreeLM(nn.Module):
         return m.to(device=device, dtype=dtype)
 
 
-def _rope_dict(c) -> dict:
+def is_olmo(config) -> bool:
+    """OLMo-2 / OLMo-3 arithmetic (q/k RMSNorm over the whole projection row before RoPE, and the post-norm layer
+    h = x + norm(attn(x)), y = h + norm(mlp(h))) is keyed on config.model_type in ("olmo2", "olmo3") and on nothing else."""
+    return getattr(config, "model_type", None) in ("olmo2", "olmo3")
+
+
+def rope_layer_types(c):
+    """The layer types that carry their own RoPE parameters: for model_type "olmo3" (HF's Olmo3RotaryEmbedding keeps one set of
+    frequencies per layer type) the sorted set of config.layer_types; None for every other model type (one table per model)."""
+    if getattr(c, "model_type", None) != "olmo3":
+        return None
+    types = getattr(c, "layer_types", None)
+    if not types:
+        raise ValueError("config.layer_types is missing: an olmo3 configuration keeps its rope_parameters per layer type")
+    return sorted(set(types))
+
+
+def _rope_dict(c, layer_type=None) -> dict:
     """The flat RoPE parameter dict of a configuration: config.rope_parameters (transformers 5.x) or the older rope_scaling, with
     rope_type and rope_theta always present (HF's standardisation: the dict's own rope_theta goes before config.rope_theta, and a
-    top-level original_max_position_embeddings before the dict's).  A dict nested per layer type is refused."""
+    top-level original_max_position_embeddings before the dict's).  A dict nested per layer type is refused - except for
+    model_type "olmo3" (rope_layer_types), whose dict MUST be nested with exactly the configuration's layer types as its keys:
+    `layer_type` then picks the sub-dict, which goes through the same standardisation."""
     rp = getattr(c, "rope_parameters", None) or getattr(c, "rope_scaling", None) or {}
     if not isinstance(rp, dict):
         raise ValueError(f"config.rope_parameters must be a dict, got {type(rp).__name__}")
-    if rp and all(isinstance(v, dict) for v in rp.values()):
+    types = rope_layer_types(c)
+    if types is not None:
+        if sorted(map(str, rp)) != types or not all(isinstance(v, dict) for v in rp.values()):
+            raise ValueError(f"config.rope_parameters of an olmo3 configuration must be nested per layer type with exactly the keys "
+                             f"{', '.join(types)} (config.layer_types); got {', '.join(map(str, rp)) or 'nothing'}")
+        if layer_type not in rp:
+            raise ValueError(f"config.rope_parameters is nested per layer type ({', '.join(types)}): name one of them, got {layer_type!r}")
+        rp = rp[layer_type]
+    elif rp and all(isinstance(v, dict) for v in rp.values()):
         raise ValueError(f"config.rope_parameters is nested per layer type ({', '.join(map(str, rp))}): one RoPE table per model is supported")
     rp = dict(rp)
     rp["rope_type"] = rp.get("rope_type", rp.get("type")) or "default"
@@ -164,11 +191,12 @@ def _rope_dict(c) -> dict:
 _ROPE: dict = {}
 
 
-def rope_of(c):
+def rope_of(c, layer_type=None):
     """(inv_freq [D/2] fp32 on the host, attention_factor) of a configuration (ops.rope_inv_freq), resolved once per distinct
     parameter set: every consumer of one model - the packed pass, the block-wise walk, dense.py, engine.forward, warm_gemm_shapes -
-    reaches it through packed_hidden_states and so builds its table from the same frequencies."""
-    rp = _rope_dict(c)
+    reaches it through packed_hidden_states and so builds its table from the same frequencies.  `layer_type`: which of the nested
+    parameter sets of an olmo3 configuration (rope_layer_types); two layer types with equal parameters resolve to the same pair."""
+    rp = _rope_dict(c, layer_type)
     D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
     max_pos = getattr(c, "max_position_embeddings", None)
     key = (D, max_pos, tuple(sorted((k, repr(v)) for k, v in rp.items())))
@@ -217,23 +245,41 @@ def _check_gemma2(c) -> None:
             raise ValueError(f"config.{f} = {v!r} is not supported: a soft-cap is a finite number >= 0 (None or 0: no cap)")
 
 
+def _check_olmo(c) -> None:
+    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    if D not in (64, 128):
+        raise ValueError(f"config.head_dim = {D} is not supported for {c.model_type}: the projection-wide q/k norm kernels cover head_dim 64 and 128")
+    for f in ("num_attention_heads", "num_key_value_heads"):
+        if getattr(c, f) * D > 8192:
+            raise ValueError(f"config.{f} * head_dim = {getattr(c, f)} * {D} is not supported: the projection-wide q/k norm kernels hold "
+                             f"one row of at most 8192 elements")
+
+
 def check_supported(config, training: bool = True) -> None:
     """Refuses, with a ValueError that names the field, a configuration whose arithmetic the engine cannot honour - it would run,
     and compute something else: a rope_type other than default / linear / llama3 / yarn, rope_parameters nested per layer type,
     partial rotary embedding, an activation other than silu, attention dropout on a model in training mode, router jitter noise,
     attention soft-capping or sinks.  A Gemma-2 configuration (is_gemma2) is the exception for soft-capping and the activation: its
     attn_logit_softcapping / final_logit_softcapping and hidden_activation == "gelu_pytorch_tanh" are honoured; any other activation,
-    a head_dim other than 64 / 128 and a missing or non-positive query_pre_attn_scalar are refused."""
+    a head_dim other than 64 / 128 and a missing or non-positive query_pre_attn_scalar are refused.  An OLMo-2 / OLMo-3 configuration
+    (is_olmo) needs head_dim 64 / 128 and num_attention_heads * head_dim, num_key_value_heads * head_dim <= 8192 (the projection-wide
+    q/k norm kernels); for model_type "olmo3" alone rope_parameters nested per layer type is honoured - its keys must be exactly the
+    configuration's layer types, and every sub-dict passes the checks above.  OLMo-1 (model_type "olmo") is refused by name."""
     c = config
     gemma = is_gemma2(c)
     if gemma:
         _check_gemma2(c)
-    rp = _rope_dict(c)
-    if rp["rope_type"] not in ops.ROPE_TYPES:
-        raise ValueError(f"config.rope_parameters['rope_type'] = {rp['rope_type']!r} is not supported ({' / '.join(ops.ROPE_TYPES)})")
-    prf = rp.get("partial_rotary_factor", getattr(c, "partial_rotary_factor", None))
-    if prf is not None and float(prf) != 1.0:
-        raise ValueError(f"config partial_rotary_factor = {prf} is not supported: the rotary kernels rotate the whole head")
+    if getattr(c, "model_type", None) == "olmo":
+        raise ValueError("config.model_type = 'olmo' (OLMo-1: LayerNorm without weights, clip_qkv) is not supported; olmo2 and olmo3 are")
+    if is_olmo(c):
+        _check_olmo(c)
+    for lt in rope_layer_types(c) or [None]:
+        rp = _rope_dict(c, lt)
+        if rp["rope_type"] not in ops.ROPE_TYPES:
+            raise ValueError(f"config.rope_parameters['rope_type'] = {rp['rope_type']!r} is not supported ({' / '.join(ops.ROPE_TYPES)})")
+        prf = rp.get("partial_rotary_factor", getattr(c, "partial_rotary_factor", None))
+        if prf is not None and float(prf) != 1.0:
+            raise ValueError(f"config partial_rotary_factor = {prf} is not supported: the rotary kernels rotate the whole head")
     act = getattr(c, "hidden_act", None)
     if not gemma and act is not None and act != "silu":         # (Gemma2Config keeps hidden_act as a legacy field; hidden_activation decides)
         raise ValueError(f"config.hidden_act = {act!r} is not supported: the MLP kernels compute silu(gate) * up")
@@ -251,6 +297,19 @@ def check_supported(config, training: bool = True) -> None:
 _CHECKED = weakref.WeakKeyDictionary()
 
 
+def _check_olmo_norms(model) -> None:
+    """The q_norm / k_norm weights of an OLMo model span the whole projection row: Hq*D and Hkv*D elements (a per-head [D] weight
+    is another model's arithmetic)."""
+    c = model.config
+    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    for l, layer in enumerate(model.model.layers):
+        for name, heads in (("q_norm", c.num_attention_heads), ("k_norm", c.num_key_value_heads)):
+            w = getattr(getattr(layer.self_attn, name, None), "weight", None)
+            if w is None or w.numel() != heads * D:
+                raise ValueError(f"model.layers.{l}.self_attn.{name}.weight has {None if w is None else w.numel()} elements: "
+                                 f"{c.model_type} normalises the whole projection row of {heads} * {D}")
+
+
 def ensure_supported(model) -> None:
     """check_supported(model.config), once per model object and training mode, and lora.check_supported(model) on EVERY call (the engine
     and dense.py call this per call): adapter modules are mutable state - an adapter attached, switched to DoRA or put on lm_head between
@@ -258,6 +317,8 @@ def ensure_supported(model) -> None:
     training = bool(getattr(model, "training", True))
     if hasattr(model, "named_modules"):
         lora.check_supported(model)
+    if is_olmo(model.config) and hasattr(getattr(model, "model", None), "layers"):
+        _check_olmo_norms(model)
     try:
         seen = _CHECKED.setdefault(model, set())
     except TypeError:                  # a plain namespace standing in for a model: neither hashable nor weakly referenceable
@@ -270,7 +331,9 @@ def ensure_supported(model) -> None:
 def _cfg_of(model):
     c = model.config
     D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
-    return c.num_attention_heads, c.num_key_value_heads, D, float(getattr(c, "rms_norm_eps", 1e-6)), rope_of(c)
+    types = rope_layer_types(c)                  # olmo3: one resolved pair per layer, by the layer's type
+    rope = rope_of(c) if types is None else [rope_of(c, t) for t in c.layer_types]
+    return c.num_attention_heads, c.num_key_value_heads, D, float(getattr(c, "rms_norm_eps", 1e-6)), rope
 
 
 def _windows_of(model):
@@ -362,6 +425,22 @@ def _gemma2_layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     return res, ops.rms_norm(_project(act, m.down_proj), layer.post_feedforward_layernorm.weight, eps, 1.0)
 
 
+def _olmo_layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
+    """One OLMo-2 / OLMo-3 decoder layer in the (residual stream, pending update) convention of _layer_forward: post-norm -
+    h = x + norm(attn(x)), y = h + norm(mlp(h)) - with no norm in front of either branch, and q/k norms over the whole projection row
+    (ops.qkv_prep_wide).  Each branch reads the raw stream, so the stream is materialised once per branch: ops.rms_norm_add normalises
+    the branch output and adds it in one pass, and the layer hands on (y, None)."""
+    T = res.shape[0]
+    a, m = layer.self_attn, layer.mlp
+    x = res if delta is None else res + delta              # (an OLMo layer or the embedding in front never leaves a pending update)
+    qkv = _project(x, a.q_proj, a.k_proj, a.v_proj).view(T, Hq + 2 * Hkv, D)
+    q, k, v = ops.qkv_prep_wide(qkv, a.q_norm.weight, a.k_norm.weight, cos_sin, eps, Hq, Hkv)
+    o = attn(q, k, v)
+    h = ops.rms_norm_add(x, _project(o.reshape(T, Hq * D), a.o_proj), layer.post_attention_layernorm.weight, eps)
+    act = ops.swiglu_fused(_project(h, m.gate_proj, m.up_proj))
+    return ops.rms_norm_add(h, _project(act, m.down_proj), layer.post_feedforward_layernorm.weight, eps), None
+
+
 def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     """One decoder layer over the packed rows.  The hidden state enters as (residual stream, pending update)
     so that each residual add is fused into the RMSNorm that follows it.  hipBLASLt GEMMs through torch;
@@ -445,7 +524,10 @@ class _LayerRecompute(torch.autograd.Function):
             else:
                 o_res, o_delta = ctx.fn(r, d)
         ctx.items = None
-        torch.autograd.backward((o_res, o_delta), (g_res, g_delta))
+        if o_delta is None:                  # a layer that leaves no pending update (OLMo)
+            torch.autograd.backward((o_res,), (g_res,))
+        else:
+            torch.autograd.backward((o_res, o_delta), (g_res, g_delta))
         return None, None, r.grad, (d.grad if d is not None else None)
 
 
@@ -466,15 +548,20 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
     metas = layer_metas(meta, _windows_of(model), meta_for_window) if attn_of_layer is None else None
     body = model.model
     gemma = is_gemma2(model.config)
-    layer_fwd = _gemma2_layer_forward if gemma else _layer_forward
+    layer_fwd = _gemma2_layer_forward if gemma else _olmo_layer_forward if is_olmo(model.config) else _layer_forward
     akw = attn_args_of(model)
     res, delta = (embed(tokens) if embed is not None else F.embedding(tokens, body.embed_tokens.weight)), None
     if gemma:            # the normaliser, rounded to the model dtype as HF does; on the embed= path too, so the fp32 sink gets the scaled gradient
         res = _ScaleRows.apply(res, float(model.config.hidden_size) ** 0.5)
-    cos_sin = ops.rope_cos_sin(depth, D, rope)
+    if isinstance(rope, list):           # olmo3: one table per distinct parameter set (rope_of returns one pair object per set)
+        tables = {id(r_): ops.rope_cos_sin(depth, D, r_) for r_ in {id(r_): r_ for r_ in rope}.values()}
+        cos_sins = [tables[id(r_)] for r_ in rope]
+    else:
+        cos_sins = [ops.rope_cos_sin(depth, D, rope)] * len(body.layers)
     per_layer = tokens.shape[0] * Hq * (D * res.element_size() + 4)             # out + lse of one layer
     n_full = full_layers if isinstance(full_layers, int) else 1
     for li, layer in enumerate(body.layers):
+        cos_sin = cos_sins[li]
         attn = attn_of_layer(li) if attn_of_layer is not None else (lambda m_: lambda q, k, v: ops.tree_attention(q, k, v, m_, **akw))(metas[li])
         if li == 0 and callable(full_layers) and checkpoint_layers and torch.is_grad_enabled() and res.is_cuda:
             m0 = torch.cuda.memory_allocated(res.device)
@@ -487,7 +574,7 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
             keep = attn_of_layer is None and attn_keep_bytes >= per_layer
             if keep:
                 attn_keep_bytes -= per_layer
-            fn = (lambda layer_, attn_: lambda r_, d_: layer_fwd(layer_, r_, d_, cos_sin, attn_, Hq, Hkv, D, eps))(layer, attn)
+            fn = (lambda layer_, attn_, cs_: lambda r_, d_: layer_fwd(layer_, r_, d_, cs_, attn_, Hq, Hkv, D, eps))(layer, attn, cos_sin)
             res, delta = _LayerRecompute.apply(fn, keep, res, delta)
         else:
             res, delta = layer_fwd(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)

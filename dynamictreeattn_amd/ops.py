@@ -671,6 +671,65 @@ def add_rms_norm(x: torch.Tensor, delta: Optional[torch.Tensor], w: torch.Tensor
     return _RMSNorm.apply(x, delta, w, eps, float(w_offset))
 
 
+class _RMSNormAdd(torch.autograd.Function):
+    """out = res + rmsnorm(y) * w in one pass (OLMo's post-norm branch end); the normalised branch itself is not kept.  The backward is
+    the plain RMSNorm backward on (y, w, d out, rstd); d res = d out passes through."""
+
+    @staticmethod
+    def forward(ctx, res, y, w, eps):
+        _require_cuda(res, y, w)
+        H = y.shape[-1]
+        y2, r2 = y.contiguous().view(-1, H), res.contiguous().view(-1, H)
+        R = y2.shape[0]
+        out = torch.empty_like(y2)
+        rstd = torch.empty(R, dtype=torch.float32, device=y.device)
+        _launch("dta_rmsnorm_add_fwd", (y2, w, r2), ptr(y2), ptr(w), ptr(r2), ptr(out), None, ptr(rstd), R, H, float(eps), _DT[y.dtype],
+                nbytes=3 * R * H * y2.element_size())
+        ctx.save_for_backward(y2, w, rstd)
+        return out.view(y.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y2, w, rstd = ctx.saved_tensors
+        R, H = y2.shape
+        d2 = dout.contiguous().view(R, H)
+        dy = torch.empty_like(y2)
+        need_w = ctx.needs_input_grad[2]
+        part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, dtype=torch.float32, device=y2.device) if need_w else None
+        _launch("dta_rmsnorm_bwd", (y2, w, d2), ptr(y2), ptr(w), ptr(d2), None, ptr(rstd), ptr(dy), ptr(part), R, H, 0.0, _DT[y2.dtype],
+                nbytes=3 * R * H * y2.element_size())
+        return dout, dy.view(dout.shape), (sum_slabs(part, w.dtype) if need_w else None), None
+
+
+def rms_norm_add(res: torch.Tensor, y: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
+    """res + rmsnorm(y) * w: the branch output is normalised and joins the residual stream in one pass (norm first, then the add -
+    add_rms_norm is the other order)."""
+    return _RMSNormAdd.apply(res, y, w, eps)
+
+
+def _wide_qk_norm_rope_fwd(x, w, cos_sin, eps):
+    """One dta_wide_qk_norm_rope_fwd launch over x [T, NH, D] (any token stride), w [NH*D]: (y contiguous, rstd [T])."""
+    T, NH, D = x.shape
+    if w.numel() != NH * D:
+        raise ValueError(f"projection-wide norm weight has {w.numel()} elements for {NH} heads of {D}")
+    y = torch.empty((T, NH, D), dtype=x.dtype, device=x.device)
+    rstd = torch.empty(T, dtype=torch.float32, device=x.device)
+    _launch("dta_wide_qk_norm_rope_fwd", (x, w, cos_sin), ptr(x), ptr(w), ptr(cos_sin), ptr(y), ptr(rstd), T, NH, D, x.stride(0), float(eps),
+            _DT[x.dtype], nbytes=2 * T * NH * D * x.element_size() + T * D * 4)
+    return y, rstd
+
+
+def _wide_qk_norm_rope_bwd(x, w, cos_sin, dy, rstd, dx, need_w):
+    """One dta_wide_qk_norm_rope_bwd launch into dx [T, NH, D] (any token stride; may be dy).  Returns dw (None unless need_w)."""
+    T, NH, D = x.shape
+    if dy.stride(2) != 1:
+        dy = dy.contiguous()
+    part = torch.empty(lib().dta_wide_qk_norm_rope_bwd_blocks(T), NH * D, dtype=torch.float32, device=x.device) if need_w else None
+    _launch("dta_wide_qk_norm_rope_bwd", (x, w, cos_sin, dy), ptr(x), ptr(w), ptr(cos_sin), ptr(dy), ptr(rstd), ptr(dx), ptr(part), T, NH, D,
+            x.stride(0), dy.stride(0), dy.stride(1), dx.stride(0), _DT[x.dtype], nbytes=3 * T * NH * D * x.element_size() + T * D * 4)
+    return sum_slabs(part, w.dtype) if part is not None else None
+
+
 def _qk_norm_rope_fwd(x, w, cos_sin, eps):
     """One dta_qk_norm_rope_fwd launch over x [T, NH, D] (rows of D contiguous, any token stride): (y contiguous, rstd | None without w)."""
     T, NH, D = x.shape
@@ -721,13 +780,16 @@ class _QKVPrep(torch.autograd.Function):
     the 200 MB concatenation that `split`'s backward would do per layer disappears."""
 
     @staticmethod
-    def forward(ctx, qkv, wq, wk, cos_sin, eps, Hq, Hkv):
+    def forward(ctx, qkv, wq, wk, cos_sin, eps, Hq, Hkv, wide=False):
         _require_cuda(qkv, cos_sin)
         T, H3, D = qkv.shape
         assert H3 == Hq + 2 * Hkv and qkv.is_contiguous()
+        assert not wide or (wq is not None and wk is not None)
+        ctx.wide = bool(wide)
+        fwd = _wide_qk_norm_rope_fwd if wide else _qk_norm_rope_fwd
         outs, rstds = [], []
         for x, w in ((qkv[:, :Hq], wq), (qkv[:, Hq:Hq + Hkv], wk)):
-            y, rstd = _qk_norm_rope_fwd(x, w, cos_sin, eps)
+            y, rstd = fwd(x, w, cos_sin, eps)
             outs.append(y); rstds.append(rstd if rstd is not None else cos_sin)
         ctx.save_for_backward(qkv, wq if wq is not None else cos_sin, wk if wk is not None else cos_sin, cos_sin, rstds[0], rstds[1])
         ctx.has_w = (wq is not None, wk is not None)
@@ -750,16 +812,24 @@ class _QKVPrep(torch.autograd.Function):
         dws = []
         for lo, NH, w, rstd, has_w, need_w, dy in ((0, Hq, wq, rq, ctx.has_w[0], ctx.needs_input_grad[1], dq),
                                                    (Hq, Hkv, wk, rk, ctx.has_w[1], ctx.needs_input_grad[2], dk)):
-            dws.append(_qk_norm_rope_bwd(qkv[:, lo:lo + NH], w if has_w else None, cos_sin, dy, rstd, d[:, lo:lo + NH], need_w))
+            bwd = _wide_qk_norm_rope_bwd if ctx.wide else _qk_norm_rope_bwd
+            dws.append(bwd(qkv[:, lo:lo + NH], w if has_w else None, cos_sin, dy, rstd, d[:, lo:lo + NH], need_w))
         if not in_place:
             d[:, Hq + Hkv:].copy_(dv)
-        return d, dws[0], dws[1], None, None, None, None
+        return d, dws[0], dws[1], None, None, None, None, None
 
 
 def qkv_prep(qkv: torch.Tensor, wq: Optional[torch.Tensor], wk: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float,
              Hq: int, Hkv: int):
     """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D]."""
     return _QKVPrep.apply(qkv, wq, wk, cos_sin, eps, Hq, Hkv)
+
+
+def qkv_prep_wide(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, cos_sin: torch.Tensor, eps: float, Hq: int, Hkv: int):
+    """qkv_prep with the projection-wide norms of OLMo-2 / OLMo-3: wq [Hq*D] and wk [Hkv*D] normalise the whole q / k row of a token
+    before the heads are rotated (dta_wide_qk_norm_rope_*).  q and k are read in place, v is a view, the three gradients land in one
+    [T, Hq+2Hkv, D] buffer and a frozen weight gets no partials - as qkv_prep."""
+    return _QKVPrep.apply(qkv, wq, wk, cos_sin, eps, Hq, Hkv, True)
 
 
 def qk_norm_rope(x: torch.Tensor, w: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float) -> torch.Tensor:

@@ -284,7 +284,11 @@ class TreeTrainingEngine:
         return ops.free_hbm(self.device)
 
     def _per_token_layer_bytes(self, model) -> int:
-        """Activation bytes kept per token and layer (the mean over the layers: MoE and dense layers differ), 2-byte elements."""
+        """Activation bytes kept per token and layer (the mean over the layers: MoE and dense layers differ), 2-byte elements.
+        Of the 10 hidden-size rows, four are what a pre-norm layer really keeps between its GEMMs: the residual stream in front of
+        each of its two norms and the two norm outputs (the projections' inputs); the rest is slack.  Gemma-2 keeps the outputs of its
+        two post-branch norms on top: 12.  An OLMo layer has no pre-branch norm outputs; it keeps the two branch outputs before their
+        norms (ops.rms_norm_add's saved rows) and one materialised stream per branch (the projections' inputs): the same four, 10."""
         c = model.config
         D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
         L = c.num_hidden_layers

@@ -251,6 +251,34 @@ int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, con
                          void* dx, float* dw_partial, int32_t T, int32_t NH, int32_t head_dim,
                          int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t,
                          int32_t dtype, void* stream);   /* dx: [T, NH, D] with dx_stride_t elements between tokens (>= NH*D); dx == dy (same strides) is allowed: in place */
+/* Projection-wide q/k RMSNorm + RoPE (OLMo-2 / OLMo-3: `q_norm(q_proj(x))` with a weight of [NH*D], then the reshape to heads and
+ * rotate-half RoPE - transformers' Olmo2Attention.forward).  x: [T, NH, D] with token stride x_stride_t (q or k read in place from the
+ * fused projection output); w: [NH*D]; cos_sin as above; y: [T, NH, D] contiguous; rstd: [T].  D = 64 or 128, any NH >= 1 with
+ * NH*D <= 8192.  Arithmetic: r = rsqrt(mean over all NH*D elements of x^2 + eps); a = cast(w x r) - Olmo2RMSNorm multiplies by the
+ * weight in fp32 and rounds ONCE (`(self.weight * hidden_states).to(input_dtype)`), where the Qwen3 / Llama norm of dta_rmsnorm_fwd
+ * rounds x r first; y = cast(a cos + partner(a) sin).  One wave per token - the four waves of a workgroup for rows above 2048 elements - holds the row in
+ * registers: x is read once, the token's table row once.
+ * bwd: da = dy cos + partner'(dy) sin stays in fp32 and is never rounded; dx = r (da w - t^ mean_{NH*D}(da w t^)), t^ = x r;
+ * dw_partial: float [dta_wide_qk_norm_rope_bwd_blocks(T), NH*D], summed over dim 0 by dta_sum_slabs; NULL: a frozen weight, dx only.
+ * dy: token stride dy_stride_t, head stride dy_stride_h; dx: token stride dx_stride_t (>= NH*D); dx == dy (same strides) is allowed:
+ * a lane writes exactly the 16-byte groups it read.
+ * Refusals come in this order: DTA_EINVAL (a null pointer, a size <= 0, a NaN eps), DTA_EUNSUPPORTED (dtype, head_dim, NH*D > 8192),
+ * DTA_EALIGN (a pointer off 16 bytes, a stride off 8 elements), DTA_EINVAL (a token stride below NH*D), DTA_EPRIOR. */
+int dta_wide_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,
+                              int32_t T, int32_t NH, int32_t head_dim, int64_t x_stride_t, float eps, int32_t dtype, void* stream);
+int dta_wide_qk_norm_rope_bwd_blocks(int32_t T);   /* rows of dw_partial [blocks, NH*head_dim] */
+int dta_wide_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, const void* dy, const float* rstd,
+                              void* dx, float* dw_partial, int32_t T, int32_t NH, int32_t head_dim,
+                              int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t,
+                              int32_t dtype, void* stream);
+/* RMSNorm, then the residual add (OLMo's post-norm layer, `residual + post_attention_layernorm(attn_out)` - Olmo2DecoderLayer.forward):
+ * yn = cast(w y r) (one rounding, as Olmo2RMSNorm), r = rsqrt(mean(y^2) + eps), and out = cast(res + yn) in one pass over rows of H (H % 8 == 0, any H: above
+ * 4096 the row is read twice, as in dta_rmsnorm_fwd).  yn may be NULL when only out is wanted; rstd: [R].  No operand may alias an
+ * output.  The backward is dta_rmsnorm_bwd on (y, w, d out, rstd) with dres NULL; d res = d out.
+ * Refusals come in this order: DTA_EINVAL (a null pointer, a size <= 0, a NaN eps), DTA_EUNSUPPORTED (dtype, H % 8), DTA_EALIGN,
+ * DTA_EPRIOR. */
+int dta_rmsnorm_add_fwd(const void* y, const void* w, const void* res, void* out, void* yn, float* rstd,
+                        int32_t R, int32_t H, float eps, int32_t dtype, void* stream);
 /* gate/up: [rows, cols] with `ld` elements between rows (they may be the two halves of one fused [rows, 2*cols]
  * projection output); y/dy: [rows, cols] contiguous; dgate/dup: `ld_grad` between rows. */
 int dta_swiglu_fwd(const void* gate, const void* up, void* y, int64_t rows, int32_t cols, int64_t ld, int32_t dtype, void* stream);
