@@ -1,9 +1,13 @@
-"""CPU stand-ins for the product's three device steps, for `-m "not gpu"` tests of the HOST logic
-only (sorting, leaf grouping, permutation, packing plan, loss assembly, balancers).  They are
-installed by monkeypatching from tests; the product never imports this module or the oracle."""
+"""CPU stand-ins for the product's device steps (the trie kernels, tree / stack attention with scale, soft-cap and window, the LM head,
+the row operators of every model family), for `-m "not gpu"` tests of the HOST logic only (sorting, leaf grouping, permutation,
+packing plan, layer wiring, loss assembly, balancers).  Each is defined once, here; install(monkeypatch) installs all of them.  The
+product never imports this module or the oracle."""
+import dataclasses
+
 import numpy as np
 import torch
 
+from dynamictreeattn_amd import packing
 from oracle import attn_oracle, trie_oracle
 
 
@@ -46,19 +50,36 @@ def _cpu_expand(self, tokens, leaf_off, seg_off, seg_d0, par_seg, brk_ptr, brk_d
     self.tokens.copy_(tokens[torch.from_numpy(src)])
 
 
-def _cpu_attention(q, k, v, meta, scale=None):
+def _cpu_attention(q, k, v, meta, scale=None, softcap=0.0):
+    """Stand-in of ops.tree_attention.  No window and no cap: the oracle's tree attention (what the uncapped, unwindowed families
+    have always run on); otherwise the plain formula of tests/softcap_ref64.py under the visibility mask of the meta."""
     T = q.shape[0]
-    if meta.subtree_end is None:
-        se = torch.full((k.shape[0],), meta.q_offset + T, dtype=torch.long)
-        assert meta.q_offset == 0
-    else:
-        se = meta.subtree_end.long()
-    return attn_oracle.tree_attention(q, k, v, se, scale)[0]
+    assert meta.subtree_end is not None or meta.q_offset == 0
+    if meta.window <= 0 and not softcap:
+        se = torch.full((k.shape[0],), T, dtype=torch.long) if meta.subtree_end is None else meta.subtree_end.long()
+        return attn_oracle.tree_attention(q, k, v, se, scale)[0]
+    import softcap_ref64 as SR
+    s = torch.arange(T)
+    vis = s[None, :] <= s[:, None]
+    if meta.subtree_end is not None:
+        vis = vis & (s[:, None] < meta.subtree_end.long()[None, :])
+    if meta.window > 0:
+        vis = vis & (s[None, :] >= meta.win_lo.long()[:, None]) if meta.win_lo is not None else vis & (s[:, None] - s[None, :] < meta.window)
+    return SR.plain_capped_attention(q, k, v, vis, q.shape[-1] ** -0.5 if scale is None else scale, softcap)[0]
 
 
-def _cpu_lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes=None):
-    """Plain-torch stand-in of ops.lm_head_rows (fp32 log-softmax over the full rows); a label < 0 = no label (0)."""
-    lp_all = torch.log_softmax(torch.nn.functional.linear(h, W).float(), dim=-1)
+def _cpu_window_meta(meta, plan, depth, window, Hkv=8, seg_tables=None):
+    """Stand-in of ops.window_meta: win_lo from the host plan; the tile plans stay the full meta's (no kernel reads them here)."""
+    if window <= 0 or window > packing.max_depth(plan):
+        return meta
+    return dataclasses.replace(meta, win_lo=torch.from_numpy(packing.window_lo_host(plan, window)), window=int(window))
+
+
+def _cpu_lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes=None, softcap=0.0, **kw):
+    """Plain-torch stand-in of ops.lm_head_rows (fp32 log-softmax over the full rows, the logits capped first where softcap > 0); a
+    label < 0 = no label (0)."""
+    x = torch.nn.functional.linear(h, W).float()
+    lp_all = torch.log_softmax(softcap * torch.tanh(x / softcap) if softcap else x, dim=-1)
     ent = -(lp_all.exp() * lp_all).sum(-1) if want_entropy else None
     lp_next = lp_all.gather(-1, next_tok.clamp(min=0)[:, None]).squeeze(-1) * (next_tok >= 0)
     lp_fork = lp_all[fork_rows, fork_tok] if fork_rows.numel() else lp_all.new_zeros(0)
@@ -95,15 +116,22 @@ def _cpu_stack_attention(q, k_new, v_new, kst, vst, gk, gv, start, scale=None):
     return _CpuStackAttention.apply(q, k_new, v_new, kst, vst, gk, gv, start, scale)
 
 
-def _cpu_rms_norm(x, w, eps):
+def _cpu_rms_norm(x, w, eps, w_offset=0.0):
+    """w_offset 0: normalise, round, multiply by w (two roundings); otherwise Gemma-2's (w_offset + w) in fp32 and one rounding."""
     xf = x.float()
-    return w * (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)).to(x.dtype)
+    xn = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+    return w * xn.to(x.dtype) if w_offset == 0 else (xn * (w_offset + w.float())).to(x.dtype)
 
 
-def _cpu_add_rms_norm(x, delta, w, eps):
+def _cpu_add_rms_norm(x, delta, w, eps, w_offset=0.0):
     if delta is not None:
         x = x + delta
-    return x, _cpu_rms_norm(x, w, eps)
+    return x, _cpu_rms_norm(x, w, eps, w_offset)
+
+
+def _cpu_rms_norm_add(res, y, w, eps):
+    yf = y.float()
+    return res + (w * (yf * torch.rsqrt(yf.pow(2).mean(-1, keepdim=True) + eps))).to(y.dtype)
 
 
 def _cpu_qk_norm_rope(x, w, cos_sin, eps):
@@ -120,6 +148,26 @@ def _cpu_qkv_prep(qkv, wq, wk, cos_sin, eps, Hq, Hkv):
     return _cpu_qk_norm_rope(q, wq, cos_sin, eps), _cpu_qk_norm_rope(k, wk, cos_sin, eps), v
 
 
+def _cs(cs, D):
+    c, s = cs[:, :D // 2], cs[:, D // 2:]
+    return torch.cat([c, c], -1)[:, None, :], torch.cat([s, s], -1)[:, None, :]
+
+
+def plain_wide(x, w, cs, eps):
+    """HF's formula in the tensors' own dtype (float64 for autograd): Olmo2RMSNorm over the flattened row, then rotate-half RoPE."""
+    T, NH, D = x.shape
+    cos, sin = _cs(cs.to(x.dtype), D)
+    f = x.reshape(T, NH * D)
+    a = (w * (f * torch.rsqrt(f.pow(2).mean(-1, keepdim=True) + eps))).view(T, NH, D)
+    return a * cos + torch.cat([-a[..., D // 2:], a[..., :D // 2]], -1) * sin
+
+
+def _cpu_qkv_prep_wide(qkv, wq, wk, cos_sin, eps, Hq, Hkv):
+    """fp32 stand-in of ops.qkv_prep_wide: HF's formula (plain_wide) on q and k, v as it is."""
+    q, k, v = qkv.split([Hq, Hkv, Hkv], dim=1)
+    return plain_wide(q, wq, cos_sin, eps), plain_wide(k, wk, cos_sin, eps), v
+
+
 def _cpu_swiglu(g, u):
     return torch.nn.functional.silu(g) * u
 
@@ -127,6 +175,11 @@ def _cpu_swiglu(g, u):
 def _cpu_swiglu_fused(gu):
     C = gu.shape[-1] // 2
     return torch.nn.functional.silu(gu[..., :C]) * gu[..., C:]
+
+
+def _cpu_geglu_fused(gu):
+    C = gu.shape[-1] // 2
+    return torch.nn.functional.gelu(gu[..., :C], approximate="tanh") * gu[..., C:]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -194,11 +247,15 @@ def install(monkeypatch):
     monkeypatch.setattr(token_trie, "_device_trie_arrays", _cpu_trie_arrays)
     monkeypatch.setattr(tree_training_engine._PackedTrie, "_expand", _cpu_expand)
     monkeypatch.setattr(ops, "tree_attention", _cpu_attention)
+    monkeypatch.setattr(ops, "window_meta", _cpu_window_meta)
     monkeypatch.setattr(ops, "stack_attention", _cpu_stack_attention)
     monkeypatch.setattr(ops, "lm_head_rows", _cpu_lm_head_rows)
     monkeypatch.setattr(ops, "rms_norm", _cpu_rms_norm)
     monkeypatch.setattr(ops, "add_rms_norm", _cpu_add_rms_norm)
+    monkeypatch.setattr(ops, "rms_norm_add", _cpu_rms_norm_add)
     monkeypatch.setattr(ops, "qk_norm_rope", _cpu_qk_norm_rope)
     monkeypatch.setattr(ops, "qkv_prep", _cpu_qkv_prep)
+    monkeypatch.setattr(ops, "qkv_prep_wide", _cpu_qkv_prep_wide)
     monkeypatch.setattr(ops, "swiglu", _cpu_swiglu)
     monkeypatch.setattr(ops, "swiglu_fused", _cpu_swiglu_fused)
+    monkeypatch.setattr(ops, "geglu_fused", _cpu_geglu_fused)

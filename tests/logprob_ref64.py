@@ -25,7 +25,7 @@ is a sum of the following named steps of the kernel's arithmetic.
                  cost 3 u32 per step, `steps` = ceil(V / 8 / 256) (+ 1 with a tail) at the most (the ascending row: at every step).
   merge tree     six butterfly steps and three wave merges, each a rescale of both sides and one addition: 3 u32 each, nm = 9.
   sums           a lane adds n = 8 ceil(V / 8 / 256) + 1 positive terms, the tree nm more: C32 sqrt(n + nm) u32 (the statistical growth of
-                 moe_ref64.bound).  Together: an element's weight is off by the relative w u32,
+                 ref64_common.bound).  Together: an element's weight is off by the relative w u32,
                      w = ln 2 (dy / u32 + 2 |y - M|) + 2 + C32 sqrt(n + nm) + 3 (steps + nm).
   lse            ln 2 (m + log2 s): rel(s) = u32 E_p[w], log2 (2 u32 |log2 s|), the sum and the product (3 u32 |lse|).
   entropy        lse - ln 2 t / s, a difference of large terms, bounded on the magnitudes BEFORE the cancellation: t / s is off by
@@ -65,7 +65,7 @@ import math
 import numpy as np
 import torch
 
-from moe_ref64 import C32, TINY, U, U32
+from ref64_common import C32, TINY, U, U32
 
 LN2, LOG2E = math.log(2.0), 1.0 / math.log(2.0)
 KY, KA = 3.25, 3.25

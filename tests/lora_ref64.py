@@ -1,5 +1,5 @@
 """Float64 restatement of the LoRA kernels' products (include/dta.h "Low-rank adapters") for the kernels' ROUNDED inputs, with the operand
-magnitudes of the project's per-element bound moe_ref64.bound(ref, mag, n, dtype):
+magnitudes of the project's per-element bound ref64_common.bound(ref, mag, n, dtype):
 
     |out - ref| <= u |ref| + C32 sqrt(n) u32 mag (+ tiny)        u: the output's rounding, n: the contraction length, mag = |A| |B|
 

@@ -3,19 +3,14 @@ the HIP kernels.
 
 The references take the kernels' rounded inputs, so a kernel's error is its fp32 arithmetic plus the one rounding of its output:
 
-    GEMM / combine element:  |out - ref| <= u |ref| + C32 sqrt(n) u32 (|A| |B|)  (+ tiny)
-        u = 2^-8 bf16, 2^-11 f16, 2^-24 fp32 (output rounding, a relative half-ulp doubled for margin; f16 adds its subnormal
-        spacing 2^-24 as an absolute floor); u32 = 2^-24; n = contraction
-        length; |A| |B| the product of the absolute operands (the magnitude fp32 accumulation errors scale with).
+    GEMM / combine element:  ref64_common.bound (u |ref| + C32 sqrt(n) u32 (|A| |B|) + tiny).
     router weights: u |w| + 1e-6;  lse: 1e-5 (1 + |lse|);  dlogits: u |ref| + 1e-5 p_e (|dp_e| + sum_j |dp_j| p_j) + 1e-7 max|ref|.
 
 Top-k ties: the lower expert index wins (a stable descending sort), as the kernel documents (include/dta.h)."""
 import numpy as np
 import torch
 
-U = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 2.0 ** -24}
-U32 = 2.0 ** -24
-C32 = 4.0
+from ref64_common import C32, TINY, U, U32, bound  # noqa: F401  (the rounding model, shared with the other references)
 
 
 def router_ref(logits: torch.Tensor, k: int, norm: bool):
@@ -88,14 +83,6 @@ def gemm_ref(mode, x, w, dy, offsets, src_token, gather):
         mag[e] = dy[a:b].double().abs().T @ xs[a:b].abs()
         n = max(n, b - a)
     return out, mag, n
-
-
-# absolute floor of the output rounding: f16's subnormal spacing (bf16 and fp32 share fp32's range)
-TINY = {torch.bfloat16: 1e-38, torch.float16: 2.0 ** -24, torch.float32: 1e-38}
-
-
-def bound(ref: torch.Tensor, mag: torch.Tensor, n: int, dtype) -> torch.Tensor:
-    return U[dtype] * ref.abs() + C32 * np.sqrt(max(n, 1)) * U32 * mag + TINY[dtype]
 
 
 def combine_ref(y, w, row_of_pair, T, k):

@@ -9,7 +9,7 @@ a kernel's error is its own arithmetic: the roundings to the storage type it doc
     u = U[dtype], the largest relative error of one rounding to the storage type (2^-8 bf16, 2^-11 f16, 2^-24 fp32); k = roundings to
     the storage type on the output's path; M = the magnitude they apply to (k u is written k u (1 + k u): roundings compound);
     u32 = 2^-24; c u32 M_red = the fp32 part: c counts the fp32 operations on the path (+ C32 sqrt(n) for a sum of n terms, the
-    statistical growth of moe_ref64.bound) and M_red is the magnitude BEFORE any cancellation (sum of absolute terms);
+    statistical growth of ref64_common.bound) and M_red is the magnitude BEFORE any cancellation (sum of absolute terms);
     floor = TINY[dtype] (f16: the subnormal spacing 2^-24) times the factors a rounded intermediate is multiplied by.
 
 For fp32 storage u = u32 and the same formulas hold: k u is then the rounding of the last k fp32 operations.
@@ -59,7 +59,7 @@ import math
 import numpy as np
 import torch
 
-from moe_ref64 import C32, TINY, U, U32
+from ref64_common import C32, TINY, U, U32
 
 RSTD_C = 10.0
 EXP_C = 2.06

@@ -16,10 +16,12 @@ import os
 import pytest
 import torch
 
+import family
 import softcap_ref64 as SR
 from dynamictreeattn_amd import synth
 from dynamictreeattn_amd.model import _windows_of, check_supported, make_config
-from test_llama_family_fixture import LLAMA, MIN_GAP, att, gold_grads  # noqa: F401  (att / gold_grads: shared with the GPU tests)
+from family import _m, att, gold_grads  # noqa: F401  (re-exported: the GPU tests and scripts/make_golden_gemma.py read them here)
+from test_llama_family_fixture import LLAMA, MIN_GAP
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FILE = "engine_gemma2.pt"
@@ -64,11 +66,7 @@ def hf_model(case, off=None, attn="eager", **change):
     """The unmodified transformers Gemma2ForCausalLM of `case` with the seeded weights (fp32, train mode)."""
     import transformers
     m = transformers.Gemma2ForCausalLM(hf_config(case, off, attn, **change))
-    w = weights(m, CASES[case][3], CASE_STD.get(case, STD))
-    with torch.no_grad():
-        for n, p in m.named_parameters():
-            p.copy_(w[n])
-    return m.float().train()
+    return family.load_weights(m, weights(m, CASES[case][3], CASE_STD.get(case, STD)))
 
 
 def seqs_of(case):
@@ -77,10 +75,6 @@ def seqs_of(case):
 
 def gold(case):
     return torch.load(os.path.join(GOLD, FILE), weights_only=True)[CASES[case][0]]
-
-
-def _m(c):
-    return type("M", (), {"config": c})()
 
 
 # ---------------------------------------------------------------------------------------------------------------- fixture
@@ -214,68 +208,6 @@ def test_gemma2_engine_on_cpu_matches_the_reference_fixture(case, monkeypatch):
     every gradient: the layer wiring (sandwich norms with offset 1, GeGLU, the scaled embedding, query_pre_attn_scalar, per-layer
     windows, both caps) is host-side plumbing around the kernels."""
     pytest.importorskip("transformers")
-    import hostmirror
-    from dynamictreeattn_amd import ops
-    from dynamictreeattn_amd.token_trie import TokenTrie
-    from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
-    from oracle import model_oracle as mo
-    hostmirror.install(monkeypatch)
-
-    def attention(q, k, v, meta, scale=None, softcap=0.0):
-        T = q.shape[0]
-        s = torch.arange(T)
-        if meta.subtree_end is None:
-            assert meta.q_offset == 0
-            vis = s[None, :] <= s[:, None]
-        else:
-            vis = (s[None, :] <= s[:, None]) & (s[:, None] < meta.subtree_end.long()[None, :])
-        if meta.window > 0:
-            vis = vis & (s[None, :] >= meta.win_lo.long()[:, None]) if meta.win_lo is not None else vis & (s[:, None] - s[None, :] < meta.window)
-        return SR.plain_capped_attention(q, k, v, vis, q.shape[-1] ** -0.5 if scale is None else scale, softcap)[0]
-
-    def norm(x, w, eps, w_offset=0.0):
-        xf = x.float()
-        return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * (w_offset + w.float())).to(x.dtype)
-
-    def add_norm(x, delta, w, eps, w_offset=0.0):
-        x = x if delta is None else x + delta
-        return x, norm(x, w, eps, w_offset)
-
-    def geglu_fused(gu):
-        C = gu.shape[-1] // 2
-        return torch.nn.functional.gelu(gu[..., :C], approximate="tanh") * gu[..., C:]
-
-    def lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes=None, softcap=0.0, **kw):
-        x = torch.nn.functional.linear(h, W).float()
-        lp_all = torch.log_softmax(softcap * torch.tanh(x / softcap) if softcap else x, dim=-1)
-        ent = -(lp_all.exp() * lp_all).sum(-1) if want_entropy else None
-        lp_next = lp_all.gather(-1, next_tok.clamp(min=0)[:, None]).squeeze(-1) * (next_tok >= 0)
-        return lp_next, (lp_all[fork_rows, fork_tok] if fork_rows.numel() else lp_all.new_zeros(0)), ent
-
-    def window_meta(meta, plan, depth, window, Hkv=8, seg_tables=None):
-        import dataclasses
-        from dynamictreeattn_amd import packing
-        if window <= 0 or window > packing.max_depth(plan):
-            return meta
-        return dataclasses.replace(meta, win_lo=torch.from_numpy(packing.window_lo_host(plan, window)), window=int(window))
-
-    for name, fn in (("tree_attention", attention), ("rms_norm", norm), ("add_rms_norm", add_norm), ("geglu_fused", geglu_fused),
-                     ("lm_head_rows", lm_head_rows), ("window_meta", window_meta)):
-        monkeypatch.setattr(ops, name, fn)
-    cpu = torch.device("cpu")
-    hf = hf_model(case)
     g = gold(case)
-    seqs = synth.as_tensors(seqs_of(case))
-    maxlen = max(map(len, seqs))
-    t = TokenTrie(seqs, device=cpu); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen, forward_only=True).forward(hf, t)
-    for a, b in zip(out, g["fwd_dense"]):
-        assert torch.allclose(a, b, atol=1e-4), float((a - b).abs().max())
-    t = TokenTrie(seqs, att(len(seqs)), device=cpu); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen); e.mode = "packed"
-    loss = e.backward(hf, t, mo.default_loss, 2048)
-    assert abs(loss - g["bwd_dense_loss"]) < 1e-4 * abs(loss)
-    named = dict(hf.named_parameters())
+    named = family.check_cpu_engine_matches_fixture(hf_model(case), synth.as_tensors(seqs_of(case)), g, monkeypatch)
     assert set(named) == set(gold_grads(g))
-    for n, gg in gold_grads(g).items():
-        assert mo.grad_ratio(gg, named[n].grad) <= 1e-3, n                   # fp16-packed golden: 5e-4 per element

@@ -1,6 +1,6 @@
 """LoRA adapters through the engine on the GPU: UNMODIFIED transformers models with adapters (tests/test_lora_fixture.py: all seven
 targets at r = 6 on Llama-3, r = 16 in bf16 on Mistral, q_proj + v_proj with ranks 8 and 4 on the biased Llama, Qwen3 with q/k-norm
-and tied head, Mixtral with attention-only adapters), the protocol of test_gpu_engine_llama.py:
+and tied head, Mixtral with attention-only adapters), the protocol of tests/family.py:
 
 * fp32, packed mode and the block-wise stack walk, against HF's own eager forward / backward in float64 on the card over the same
   wrapped model (the test-side RefLora): logprobs within 1e-4, loss within 1e-5, every adapter gradient within max(1e-4, 1.5 x
@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_engine_llama as gl
+import family
 import test_llama_family_fixture as fx
 import test_lora_fixture as lx
 from dynamictreeattn_amd import dense, lora, ops, synth
@@ -36,30 +36,10 @@ def _seqs(case):
     return synth.as_tensors(lx.seqs_of(case))
 
 
-def _engine32(mine, seqs, mode, monkeypatch):
-    """The fp32 engine on `mine`: (per-sequence logprobs, loss); gradients in .grad."""
-    att = fx.att(len(seqs))
-    t = TokenTrie(seqs); t.forward_permute()
-    out = TreeTrainingEngine(mine.config, DEV, torch.float32, max(map(len, seqs)), forward_only=True).forward(mine, t)
-    t = TokenTrie(seqs, att); t.backward_permute()
-    e = TreeTrainingEngine(mine.config, DEV, torch.float32, max(map(len, seqs))); e.mode = mode
-    if mode == "stack":
-        monkeypatch.setattr(e, "_stack_block_rows", lambda *a: 16)
-    loss = e.backward(mine, t, mo.default_loss, 16)
-    assert e.last_mode.startswith(mode), e.last_mode
-    return [o.cpu() for o in out], loss
-
-
 def _against_hf64(mine, ref64, seqs, mode, monkeypatch):
-    """-> (logprob error, loss, reference loss, {name: ratio} over the parameters HF gave a gradient)."""
-    lps, loss_r = gl._hf_dense(ref64, seqs, fx.att(len(seqs)))
-    out, loss = _engine32(mine, seqs, mode, monkeypatch)
-    lp_err = max(float((a - b).abs().max()) for a, b in zip(out, lps))
-    rg = {n: p.grad for n, p in ref64.named_parameters() if p.grad is not None}
-    named = dict(mine.named_parameters())
-    assert {n for n, p in named.items() if p.grad is not None} == set(rg)
-    assert all(p.grad is None for n, p in named.items() if n not in rg)
-    return lp_err, loss, loss_r, {n: mo.grad_ratio(g.float(), named[n].grad) for n, g in rg.items()}
+    """family.fp32_against_hf64 with the wrapped float64 model as the reference -> (logprob error, loss, reference loss, {name:
+    ratio} over the parameters HF gave a gradient); the engine gave exactly those a gradient, every frozen .grad is None."""
+    return family.fp32_against_hf64(mine, seqs, family.att(len(seqs)), mode, monkeypatch, ref64=ref64)[:4]
 
 
 def _merged_plain(case, attached):
@@ -85,9 +65,7 @@ def test_fp32_against_hf_eager_in_float64(case, mode, monkeypatch):
     assert lp_err < 1e-4
     assert abs(loss - loss_r) <= 1e-5 * abs(loss_r)
     assert abs(lx.gold(case)["bwd_dense_loss_off"] - loss_r) > 1e-5 * abs(loss_r)      # adapters off: another loss - not an inert case
-    ref_c = type(plain)(plain.config).double().to(DEV).train()
-    ref_c.load_state_dict({k: v.double() for k, v in plain.state_dict().items()})
-    _, _, _, control = _against_hf64(plain.to(DEV), ref_c, seqs, mode, monkeypatch)
+    _, _, _, control = _against_hf64(plain, None, seqs, mode, monkeypatch)
     worst_c = max(control.values())
     bad = {n: r for n, r in ratios.items() if r > max(1e-4, 1.5 * worst_c)}
     print(f"{case}/{mode}: control worst {worst_c:.2e}; above the rule: {bad}")
@@ -105,14 +83,8 @@ def _bf16_model(case, trainable_base=False):
 
 
 def _bf16_backward(hf, seqs, mode, bs, monkeypatch, recompute=False):
-    t = TokenTrie(seqs, fx.att(len(seqs))); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, DEV, torch.bfloat16, max(map(len, seqs))); e.mode = mode
-    if recompute:
-        e.checkpoint_layers = True
-    if mode == "stack":
-        monkeypatch.setattr(e, "_stack_block_rows", lambda *a, b=bs: b)
-    loss = e.backward(hf, t, mo.default_loss, bs)
-    torch.cuda.synchronize()
+    _, loss, e = family.run_engine(hf, seqs, family.att(len(seqs)), torch.bfloat16, mode, bs, monkeypatch, forward=False,
+                                   **({"checkpoint_layers": True} if recompute else {}))
     return loss, e.last_mode
 
 
@@ -120,25 +92,9 @@ def _bf16_backward(hf, seqs, mode, bs, monkeypatch, recompute=False):
 @pytest.mark.parametrize("case", list(lx.CASES))
 def test_bf16_against_the_reference_fixture(case, mode, bs, monkeypatch):
     pytest.importorskip("transformers")
-    hf = _bf16_model(case)
     g = lx.gold(case)
-    gold_grads = lx.gold_grads(g)
-    seqs = _seqs(case)
-    t = TokenTrie(seqs); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, DEV, torch.bfloat16, max(map(len, seqs)), forward_only=True).forward(hf, t)
-    err = torch.cat([(a.cpu() - b).abs() for a, b in zip(out, g["fwd_dense"])])
-    loss, last = _bf16_backward(hf, seqs, mode, bs, monkeypatch)
-    assert last.startswith(mode), last
-    named = dict(hf.named_parameters())
-    assert {n for n, p in named.items() if p.grad is not None} == set(gold_grads)
-    assert all(named[n].grad.dtype == named[n].dtype == lx.CASES[case][5] for n in gold_grads)
-    ratios = {n: mo.grad_ratio(gold_grads[n], named[n].grad.float().cpu()) for n in gold_grads}
-    print(f"{case}/{mode}: logprob err max {float(err.max()):.4f} mean {float(err.mean()):.4f}, loss rel "
-          f"{abs(loss - g['bwd_dense_loss']) / abs(loss):.2e}, ratio max {max(ratios.values()):.4f} median {float(np.median(list(ratios.values()))):.4f}")
-    assert float(err.max()) < 0.08 and float(err.mean()) < 0.015
-    assert abs(loss - g["bwd_dense_loss"]) < 1e-2 * abs(loss)
-    assert max(ratios.values()) <= REF_BF16_BOUND, max(ratios.items(), key=lambda kv: kv[1])
-    assert float(np.median(list(ratios.values()))) <= REF_BF16_MEDIAN
+    named = family.check_bf16_against_fixture(_bf16_model(case), _seqs(case), g, mode, bs, monkeypatch, label=case)
+    assert all(named[n].grad.dtype == named[n].dtype == lx.CASES[case][5] for n in lx.gold_grads(g))
 
 
 @pytest.mark.parametrize("mode", ["packed", "packed+recompute", "stack"])
@@ -165,18 +121,10 @@ def test_tree_equals_dense_on_the_device():
     pytest.importorskip("transformers")
     case = "llama3_all7"
     seqs = _seqs(case)
-    att = fx.att(len(seqs))
     a = lx.base_model(case); lx.attach_product(case, a); a = a.to(DEV)
-    loss_d = dense.backward(a, seqs, att, mo.default_loss)
     b = lx.base_model(case); lx.attach_product(case, b); b = b.to(DEV)
-    t = TokenTrie(seqs, att); t.backward_permute()
-    e = TreeTrainingEngine(b.config, DEV, torch.float32, max(map(len, seqs))); e.mode = "packed"
-    loss_t = e.backward(b, t, mo.default_loss, 2048)
-    assert abs(loss_t - loss_d) <= 1e-5 * abs(loss_d)
-    gd = dict(a.named_parameters())
-    ratios = {n: mo.grad_ratio(gd[n].grad, p.grad) for n, p in b.named_parameters() if p.requires_grad}
+    ratios = family.check_tree_equals_dense(a, b, seqs, forward=False)
     assert len(ratios) == 42 and all(p.grad is None for p in a.parameters() if not p.requires_grad)
-    assert max(ratios.values()) <= 1e-4, max(ratios.items(), key=lambda kv: kv[1])
     fwd_d = dense.forward(a, seqs)                                            # dense.py sees the adapters too
     for x, y in zip(fwd_d, lx.gold(case)["fwd_dense"]):
         assert float((x.cpu() - y).abs().max()) < 1e-4

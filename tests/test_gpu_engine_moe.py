@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import family
 import test_qwen3_moe_fixture as fx
 from dynamictreeattn_amd import ops, synth
 from dynamictreeattn_amd.model import Qwen3TreeLM
@@ -85,15 +86,7 @@ def test_fp32_moe_engine_vs_reference(mode, bs, recompute, full, monkeypatch):
         assert a.dtype == F32 and a.shape == b.shape
         assert float((a.cpu() - b).abs().max()) <= 2e-4 * (1 + float(b.abs().max()))
     _check_routing(e0, t, rec.calls, g)
-    t = TokenTrie(seqs, fx.att(len(seqs))); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, DEV, F32, maxlen); e.mode = mode
-    if recompute is not None:
-        e.attn_keep_fraction = recompute
-        monkeypatch.setattr(e, "_should_checkpoint", lambda model, T: True)
-        monkeypatch.setattr(e, "_full_layers", lambda model, T, f=full: f)
-    if mode == "stack":
-        monkeypatch.setattr(e, "_stack_block_rows", lambda *a, b=bs: b)
-    loss = e.backward(hf, t, mo.default_loss, bs)
+    _, loss, e = family.run_engine(hf, seqs, family.att(len(seqs)), F32, mode, bs, monkeypatch, forward=False, recompute=recompute, full_layers=full)
     assert e.last_mode.startswith(mode + ("+recompute" if recompute is not None else "")), e.last_mode
     if mode == "stack" and bs < maxlen:
         assert int(e.last_mode.split("x")[-1]) > 1, e.last_mode
@@ -108,16 +101,9 @@ def test_bf16_moe_engine_vs_reference(mode, bs, monkeypatch):
     g = fx.gold()
     gold_grads = fx.gold_grads(g)
     seqs = _seqs()
-    maxlen = max(map(len, seqs))
-    t = TokenTrie(seqs); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, DEV, torch.bfloat16, maxlen, forward_only=True).forward(hf, t)
+    out, loss, _ = family.run_engine(hf, seqs, family.att(len(seqs)), torch.bfloat16, mode, bs, monkeypatch)
     for a, b in zip(out, g["fwd_dense"]):
-        assert (a.cpu() - b).abs().max() < 0.08 and (a.cpu() - b).abs().mean() < 0.015
-    t = TokenTrie(seqs, fx.att(len(seqs))); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, DEV, torch.bfloat16, maxlen); e.mode = mode
-    if mode == "stack":
-        monkeypatch.setattr(e, "_stack_block_rows", lambda *a, b=bs: b)
-    loss = e.backward(hf, t, mo.default_loss, bs)
+        assert (a - b).abs().max() < 0.08 and (a - b).abs().mean() < 0.015
     assert abs(loss - g["bwd_dense_loss"]) < 1e-2 * abs(loss)
     named = dict(hf.named_parameters())
     ratios = {n: mo.grad_ratio(gold_grads[n], named[n].grad.float().cpu()) for n in gold_grads}

@@ -10,17 +10,14 @@ block-wise stack walk - the protocol and the numeric bounds of tests/test_gpu_en
 * the gradient name set is the model's named_parameters() with lm_head.weight (untied); tree equals dense on the device;
   per-layer recomputation with kept attention outputs gives the gradients of the plain pass bit for bit; LoRA adapters on
   q_proj / v_proj; for olmo3, the full layers forced onto the sliding layers' table miss the fp32 logprob bound."""
-import numpy as np
 import pytest
 import torch
 
+import family
 import test_olmo_fixture as fx
-from dynamictreeattn_amd import dense, lora, ops, synth
+from dynamictreeattn_amd import lora, synth
 from dynamictreeattn_amd.token_trie import TokenTrie
 from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
-from oracle import model_oracle as mo
-from test_gpu_engine import REF_BF16_BOUND, REF_BF16_MEDIAN
-from test_gpu_engine_llama import _hf_dense
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -31,37 +28,16 @@ def _seqs(case):
     return synth.as_tensors(fx.seqs_of(case))
 
 
-def _engine(model, seqs, dtype, mode, bs, monkeypatch, forward=True, **attrs):
-    """(per-sequence logprobs or None, loss, engine) of the engine on `model`; gradients in .grad."""
-    maxlen = max(map(len, seqs))
-    out = None
-    if forward:
-        t = TokenTrie(seqs); t.forward_permute()
-        out = [o.cpu() for o in TreeTrainingEngine(model.config, DEV, dtype, maxlen, forward_only=True).forward(model, t)]
-    t = TokenTrie(seqs, fx.att(len(seqs))); t.backward_permute()
-    e = TreeTrainingEngine(model.config, DEV, dtype, maxlen); e.mode = mode
-    for k, v in attrs.items():
-        setattr(e, k, v)
-    if mode == "stack":
-        monkeypatch.setattr(e, "_stack_block_rows", lambda *a, b=bs: b)
-    loss = e.backward(model, t, mo.default_loss, bs)
-    torch.cuda.synchronize()
-    return out, loss, e
+def _engine(model, seqs, dtype, mode, bs, monkeypatch, forward=True):
+    return family.run_engine(model, seqs, family.att(len(seqs)), dtype, mode, bs, monkeypatch, forward=forward)
 
 
 def _fp32_run(model32, case, mode, monkeypatch):
-    """The engine in fp32 on `model32` against HF eager in float64 on the same state dict: (logprob error, loss, reference loss, ratios)."""
-    ref = type(model32)(model32.config).double().to(DEV).train()
-    ref.load_state_dict({k: v.double() for k, v in model32.state_dict().items()})
-    mine = model32.to(DEV)
+    """family.fp32_against_hf64 on the case's sequences: (logprob error, loss, reference loss, ratios)."""
     seqs = _seqs(case)
-    lps, loss_r = _hf_dense(ref, seqs, fx.att(len(seqs)))
-    out, loss, e = _engine(mine, seqs, torch.float32, mode, 16, monkeypatch)
-    assert e.last_mode.startswith(mode), e.last_mode
-    lp_err = max(float((a - b).abs().max()) for a, b in zip(out, lps))
-    rg = dict(ref.named_parameters())
-    assert {n for n, p in mine.named_parameters() if p.grad is not None} == set(rg) and "lm_head.weight" in rg      # untied head
-    return lp_err, loss, loss_r, {n: mo.grad_ratio(rg[n].grad.float(), p.grad) for n, p in mine.named_parameters()}
+    lp_err, loss, loss_r, ratios, names = family.fp32_against_hf64(model32, seqs, family.att(len(seqs)), mode, monkeypatch)
+    assert "lm_head.weight" in names[1]      # untied head
+    return lp_err, loss, loss_r, ratios
 
 
 @pytest.mark.parametrize("mode", ["packed", "stack"])
@@ -88,41 +64,15 @@ def test_bf16_against_the_reference_fixture(case, mode, bs, monkeypatch):
     pytest.importorskip("transformers")
     hf = fx.hf_model(case).to(device=DEV, dtype=torch.bfloat16).train()
     g = fx.gold(case)
-    gold_grads = fx.gold_grads(g)
-    out, loss, e = _engine(hf, _seqs(case), torch.bfloat16, mode, bs, monkeypatch)
-    assert e.last_mode.startswith(mode), e.last_mode
-    err = torch.cat([(a - b).abs() for a, b in zip(out, g["fwd_dense"])])
-    named = dict(hf.named_parameters())
-    assert {n for n, p in named.items() if p.grad is not None} == set(gold_grads) == set(named) and "lm_head.weight" in named
-    ratios = {n: mo.grad_ratio(gold_grads[n], named[n].grad.float().cpu()) for n in gold_grads}
-    print(f"{case}/{mode}: logprob err max {float(err.max()):.4f} mean {float(err.mean()):.4f}, loss rel "
-          f"{abs(loss - g['bwd_dense_loss']) / abs(loss):.2e}, ratio max {max(ratios.values()):.4f} median {float(np.median(list(ratios.values()))):.4f}")
-    assert float(err.max()) < 0.08 and float(err.mean()) < 0.015
-    assert abs(loss - g["bwd_dense_loss"]) < 1e-2 * abs(loss)
-    assert max(ratios.values()) <= REF_BF16_BOUND, max(ratios.items(), key=lambda kv: kv[1])
-    assert float(np.median(list(ratios.values()))) <= REF_BF16_MEDIAN
+    named = family.check_bf16_against_fixture(hf, _seqs(case), g, mode, bs, monkeypatch, label=case)
+    assert set(named) == set(fx.gold_grads(g)) and "lm_head.weight" in named
 
 
 @pytest.mark.parametrize("case", list(fx.CASES))
 def test_tree_equals_dense_on_the_device(case):
     """dense.backward (one pass per sequence, the stack form) against engine.backward (one packed pass) in fp32."""
     pytest.importorskip("transformers")
-    seqs = _seqs(case)
-    att = fx.att(len(seqs))
-    a = fx.hf_model(case).to(DEV)
-    loss_d = dense.backward(a, seqs, att, mo.default_loss)
-    b = fx.hf_model(case).to(DEV)
-    t = TokenTrie(seqs, att); t.backward_permute()
-    e = TreeTrainingEngine(b.config, DEV, torch.float32, max(map(len, seqs))); e.mode = "packed"
-    loss_t = e.backward(b, t, mo.default_loss, 2048)
-    assert abs(loss_t - loss_d) <= 1e-5 * abs(loss_d)
-    gd = dict(a.named_parameters())
-    ratios = {n: mo.grad_ratio(gd[n].grad, p.grad) for n, p in b.named_parameters()}
-    assert max(ratios.values()) <= 1e-4, max(ratios.items(), key=lambda kv: kv[1])
-    fwd = dense.forward(b, seqs)                                       # and the dense forward equals the packed forward
-    t = TokenTrie(seqs); t.forward_permute()
-    out = TreeTrainingEngine(b.config, DEV, torch.float32, max(map(len, seqs)), forward_only=True).forward(b, t)
-    assert max(float((x - y).abs().max()) for x, y in zip(fwd, out)) < 1e-4
+    family.check_tree_equals_dense(fx.hf_model(case).to(DEV), fx.hf_model(case).to(DEV), _seqs(case))
 
 
 @pytest.mark.parametrize("case", list(fx.CASES))
@@ -131,24 +81,7 @@ def test_recomputation_with_kept_attention_outputs_changes_nothing(case, monkeyp
     recomputation back-propagates through its one output); with kept attention outputs the recomputation replays them - loss and
     gradients are those of the plain packed pass, bit for bit."""
     pytest.importorskip("transformers")
-    hf = fx.hf_model(case).to(device=DEV, dtype=torch.bfloat16).train()
-    seqs = _seqs(case)
-    L = hf.config.num_hidden_layers
-    ref = None
-    for ckpt, frac, launches in ((None, 0.25, L), (True, 0.25, L), (True, 0.0, 2 * L)):
-        hf.zero_grad(set_to_none=True)
-        tm = ops.KernelTimer(); ops.KernelTimer.active = tm
-        try:
-            _, loss, e = _engine(hf, seqs, torch.bfloat16, "packed", 2048, monkeypatch, forward=False,
-                                 checkpoint_layers=ckpt if ckpt else False, attn_keep_fraction=frac)
-        finally:
-            ops.KernelTimer.active = None
-        assert tm.totals_ms()["fwd"][1] == launches, (ckpt, frac, tm.totals_ms()["fwd"][1])
-        g = {n: p.grad.clone() for n, p in hf.named_parameters()}
-        if ref is None:
-            ref = (loss, g)
-        else:
-            assert loss == ref[0] and all(torch.equal(g[n], ref[1][n]) for n in g), (ckpt, frac)
+    family.check_recompute_is_bitwise(fx.hf_model(case).to(device=DEV, dtype=torch.bfloat16).train(), _seqs(case), monkeypatch)
 
 
 @pytest.mark.parametrize("mode,bs", MODES)

@@ -8,10 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+import family
 import test_qwen2_swa_fixture as fx
 from dynamictreeattn_amd import ops, synth
-from dynamictreeattn_amd.token_trie import TokenTrie
-from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
 from oracle import model_oracle as mo
 from test_gpu_engine import REF_BF16_BOUND, REF_BF16_MEDIAN
 
@@ -34,21 +33,10 @@ def test_unmodified_qwen2_sliding_window_through_the_engine(mode, bs, recompute,
     g = fx.gold()
     gold_grads = fx.gold_grads(g)
     seqs = _seqs()
-    maxlen = max(map(len, seqs))
-    t = TokenTrie(seqs); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, DEV, torch.bfloat16, maxlen, forward_only=True).forward(hf, t)
+    out, loss, e = family.run_engine(hf, seqs, family.att(len(seqs)), torch.bfloat16, mode, bs, monkeypatch, recompute=recompute)
     for a, b in zip(out, g["fwd_dense"]):
         assert a.dtype == torch.float32 and a.shape == b.shape
-        assert (a.cpu() - b).abs().max() < 0.08 and (a.cpu() - b).abs().mean() < 0.015
-    t = TokenTrie(seqs, fx.att(len(seqs))); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, DEV, torch.bfloat16, maxlen); e.mode = mode
-    if recompute is not None:
-        e.attn_keep_fraction = recompute
-        monkeypatch.setattr(e, "_should_checkpoint", lambda model, T: True)
-        monkeypatch.setattr(e, "_full_layers", lambda model, T: 0)
-    if mode == "stack":
-        monkeypatch.setattr(e, "_stack_block_rows", lambda *a, b=bs: b)
-    loss = e.backward(hf, t, mo.default_loss, bs)
+        assert (a - b).abs().max() < 0.08 and (a - b).abs().mean() < 0.015
     assert e.last_mode.startswith(mode + ("+recompute" if recompute is not None else "")), e.last_mode
     assert abs(loss - g["bwd_dense_loss"]) < 1e-2 * abs(loss)
     named = dict(hf.named_parameters())
@@ -57,44 +45,12 @@ def test_unmodified_qwen2_sliding_window_through_the_engine(mode, bs, recompute,
     assert float(np.median(list(ratios.values()))) <= REF_BF16_MEDIAN
 
 
-def _hf_dense(model, seqs, att):
-    """HF's own eager forward / backward per sequence (the reference's dense.py arithmetic): logprobs, loss sum; grads in .grad."""
-    lps, total = [], 0.0
-    for s, a in zip(seqs, att):
-        ids = s.to(DEV)[None]
-        lp, ent = _lp_ent(model(input_ids=ids, use_cache=False).logits[0, :-1], ids[0, 1:])
-        loss = mo.default_loss(lp, ent, a)
-        loss.backward()
-        total += float(loss.detach())
-        lps.append(lp.detach().float().cpu())
-    return lps, total
-
-
-def _lp_ent(logits, labels):
-    lp = torch.log_softmax(logits if logits.dtype == torch.float64 else logits.float(), -1)
-    return lp.gather(-1, labels[:, None])[:, 0], -(lp.exp() * lp).sum(-1)
-
-
 def _qwen3_ratios(cfg, mode, monkeypatch):
-    """The engine in fp32 against HF eager in float64 on Qwen3ForCausalLM(cfg): logprob error, loss, reference loss, grad ratios."""
+    """family.fp32_against_hf64 on Qwen3ForCausalLM(cfg) at its seeded initialisation: logprob error, loss, reference loss, grad ratios."""
     import transformers as tr
     torch.manual_seed(3)
-    ref = tr.Qwen3ForCausalLM(cfg).double().to(DEV).train()
-    mine = tr.Qwen3ForCausalLM(cfg).float().to(DEV).train()
-    mine.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
     seqs = _seqs()
-    att = fx.att(len(seqs))
-    lps, loss_r = _hf_dense(ref, seqs, att)
-    t = TokenTrie(seqs); t.forward_permute()
-    out = TreeTrainingEngine(mine.config, DEV, torch.float32, max(map(len, seqs)), forward_only=True).forward(mine, t)
-    lp_err = max(float((a.cpu() - b).abs().max()) for a, b in zip(out, lps))
-    t = TokenTrie(seqs, att); t.backward_permute()
-    e = TreeTrainingEngine(mine.config, DEV, torch.float32, max(map(len, seqs))); e.mode = mode
-    if mode == "stack":
-        monkeypatch.setattr(e, "_stack_block_rows", lambda *a: 16)
-    loss = e.backward(mine, t, mo.default_loss, 16)
-    rg = dict(ref.named_parameters())
-    return lp_err, loss, loss_r, {n: mo.grad_ratio(rg[n].grad.float(), p.grad) for n, p in mine.named_parameters()}
+    return family.fp32_against_hf64(tr.Qwen3ForCausalLM(cfg).float().train(), seqs, family.att(len(seqs)), mode, monkeypatch)[:4]
 
 
 @pytest.mark.parametrize("mode", ["packed", "stack"])

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import logprob_ref64 as L
-import moe_ref64
+import ref64_common
 from dynamictreeattn_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -309,7 +309,7 @@ def test_public_logprob_entropy_gradient(dtype):
 def test_public_lm_head_rows_gradient():
     """ops.lm_head_rows with chunked rows (recomputed logits) and forks on both sides of the chunk edges: dh element-wise.  dh = dlogits W
     is a GEMM over V of the kernel's rounded dlogits: the bound carries each element's dlogits bound through |W|, and the GEMM term of
-    moe_ref64.bound."""
+    ref64_common.bound."""
     worst = {}
     g = torch.Generator().manual_seed(0)
     T_, H, V, chunk = 300, 64, 1000, 128
@@ -331,7 +331,7 @@ def test_public_lm_head_rows_gradient():
         gref, gbound = L.bwd_ref(logits, nxt, fork_ptr, fork_tok, lse, ent, go[0], go[1], go[2], 1.0)["dlogits"]
         W64 = W.double()
         dh, mag = gref @ W64, gref.abs() @ W64.abs()
-        _merge(worst, {"dh": L.check("head.dh", h.grad, dh, gbound @ W64.abs() + moe_ref64.bound(dh, mag, V, BF))})
+        _merge(worst, {"dh": L.check("head.dh", h.grad, dh, gbound @ W64.abs() + ref64_common.bound(dh, mag, V, BF))})
     _report("ops.lm_head_rows", BF, worst)
 
 

@@ -1,5 +1,5 @@
 """GPU: the LoRA entry points (dta_lora_down, dta_lora_wgrad; csrc/lora_kernels.hip) against float64 on the kernels' rounded inputs
-(tests/lora_ref64.py) with the project's per-element bound moe_ref64.bound - bf16 and f16, every row count (a single row, masked tails,
+(tests/lora_ref64.py) with the project's per-element bound ref64_common.bound - bf16 and f16, every row count (a single row, masked tails,
 the bench's 28 160), every rank class (1, not a multiple of 8, 16, 64, 200, 256) and K of one 16-step, 1024 and a non-multiple of the
 tiles - bit-identical results across two calls, and the status codes; and ops.lora_linear (the operator the model layer calls: base
 GEMM + adapters, each low-rank product in the form ops.py chooses for its shape - kernel or GEMM expression) against float64 with
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import lora_ref64 as ref64
-from moe_ref64 import U, bound
+from ref64_common import U, bound
 from dynamictreeattn_amd import ops
 from dynamictreeattn_amd._lib import lib
 
@@ -138,7 +138,7 @@ def test_lora_linear_against_float64(T, layout, dtype, adapter_dtype):
         o = n0 + nlen
     yr = torch.cat(cols + [yr[:, o:]], 1)
     yr.backward(dy.double())
-    lim = 4 * U[dtype] / 2                       # moe_ref64.U is the doubled half-spacing
+    lim = 4 * U[dtype] / 2                       # ref64_common.U is the doubled half-spacing
     rel = lambda a, r_: float((a.double() - r_).norm() / r_.norm())
     errs = {"y": rel(y, yr.detach())}
     for name, m_, r_ in zip(["x", "w", "b"] + [f"{ab_}{i}" for i in range(len(spec)) for ab_ in "AB"], mine, ref):

@@ -17,9 +17,11 @@ import os
 import pytest
 import torch
 
+import family
 from dynamictreeattn_amd import synth
 from dynamictreeattn_amd.model import _windows_of, check_supported, make_config
 from dynamictreeattn_amd.tree_training_engine import _mlp_elems_per_token
+from family import _m, att, gold_grads  # noqa: F401  (re-exported: the GPU tests and scripts/make_golden_llama.py read them here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 WINDOW = 24
@@ -92,28 +94,17 @@ def hf_model(case, off=False, attn="eager"):
     stem, seed = CASES[case][2], CASES[case][5]
     m = getattr(transformers, stem + "ForCausalLM")(hf_config(case, off, attn))
     w = weights(m, seed, CASE_STD.get(case, STD))
-    with torch.no_grad():
-        for n, p in m.named_parameters():
-            p.copy_(torch.zeros_like(p) if off and n.endswith(".bias") else w[n])
-    return m.float().train()
+    return family.load_weights(m, {n: torch.zeros_like(v) if off and n.endswith(".bias") else v for n, v in w.items()})
 
 
 def seqs_of(case):
     return synth.make_case(CASES[case][4])
 
 
-def att(n):
-    return [{"w_logprobs": -1.0 - 0.01 * i, "w_entropy": 0.1 + 0.003 * i} for i in range(n)]
-
-
 def gold(case):
     file, rec = CASES[case][:2]
     g = torch.load(os.path.join(GOLD, file), weights_only=True)
     return g[rec] if rec is not None else g
-
-
-def gold_grads(g):
-    return {n: q.float() * s_ for n, (q, s_) in g["bwd_dense_grads_fp16_scaled"].items()}
 
 
 # ---------------------------------------------------------------------------------------------------------------- fixtures
@@ -146,10 +137,6 @@ def test_fixture_files_are_small():
 
 
 # ---------------------------------------------------------------------------------------------------------------- configuration rules
-def _m(c):
-    return type("M", (), {"config": c})()
-
-
 def test_windows_of_mistral_and_mixtral_configs():
     tr = pytest.importorskip("transformers")
     for case, cls in (("mistral", tr.MistralConfig), ("mixtral", tr.MixtralConfig)):
@@ -226,25 +213,6 @@ def test_llama_engine_on_cpu_matches_the_reference_fixture(case, monkeypatch):
     """The product engine with its device steps replaced by the CPU stand-ins of tests/hostmirror.py (fp32) reproduces the reference's
     dense logprobs, loss and every gradient: the scaled RoPE table, the o_proj / MLP biases and the untied head are host-side plumbing."""
     pytest.importorskip("transformers")
-    import hostmirror
-    from dynamictreeattn_amd.token_trie import TokenTrie
-    from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
-    from oracle import model_oracle as mo
-    hostmirror.install(monkeypatch)
-    cpu = torch.device("cpu")
-    hf = hf_model(case)
     g = gold(case)
-    seqs = synth.as_tensors(seqs_of(case))
-    maxlen = max(map(len, seqs))
-    t = TokenTrie(seqs, device=cpu); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen, forward_only=True).forward(hf, t)
-    for a, b in zip(out, g["fwd_dense"]):
-        assert torch.allclose(a, b, atol=1e-4), float((a - b).abs().max())
-    t = TokenTrie(seqs, att(len(seqs)), device=cpu); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen); e.mode = "packed"
-    loss = e.backward(hf, t, mo.default_loss, 2048)
-    assert abs(loss - g["bwd_dense_loss"]) < 1e-4 * abs(loss)
-    named = dict(hf.named_parameters())
+    named = family.check_cpu_engine_matches_fixture(hf_model(case), synth.as_tensors(seqs_of(case)), g, monkeypatch)
     assert set(named) == set(gold_grads(g))
-    for n, gg in gold_grads(g).items():
-        assert mo.grad_ratio(gg, named[n].grad) <= 1e-3, n                   # fp16-packed golden: 5e-4 per element

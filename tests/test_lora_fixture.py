@@ -21,8 +21,10 @@ import pytest
 import torch
 import torch.nn as nn
 
+import family
 import test_llama_family_fixture as fx
 from dynamictreeattn_amd import lora, synth
+from family import gold_grads  # noqa: F401  (re-exported: the GPU tests and scripts/make_golden_lora.py read it here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FIXTURE = os.path.join(GOLD, "engine_lora.pt")
@@ -63,11 +65,7 @@ def base_model(case, attn="eager"):
     c = transformers.Qwen3Config(**QWEN3, max_position_embeddings=256, rope_parameters={"rope_type": "default", "rope_theta": 10000.0})
     c._attn_implementation = attn
     m = transformers.Qwen3ForCausalLM(c)
-    w = fx.weights(m, 26)
-    with torch.no_grad():
-        for n, p in m.named_parameters():
-            p.copy_(w[n])
-    return m.float().train()
+    return family.load_weights(m, fx.weights(m, 26))
 
 
 def seqs_of(case):
@@ -139,10 +137,6 @@ def attach_product(case, model, adapter_dtype=torch.float32):
 
 def gold(case):
     return torch.load(FIXTURE, weights_only=True)[case]
-
-
-def gold_grads(g):
-    return {n: q.float() * s_ for n, (q, s_) in g["bwd_dense_grads_fp16_scaled"].items()}
 
 
 # ---------------------------------------------------------------------------------------------------------------- the fixture
@@ -409,26 +403,6 @@ def test_lora_engine_on_cpu_matches_the_reference_fixture(case, monkeypatch):
     """The product engine with its device steps replaced by the CPU stand-ins of tests/hostmirror.py (fp32: the adapter terms are torch
     expressions there) reproduces the reference's logprobs, loss and every adapter gradient, and gives no frozen parameter a gradient."""
     pytest.importorskip("transformers")
-    import hostmirror
-    from dynamictreeattn_amd.token_trie import TokenTrie
-    from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
-    from oracle import model_oracle as mo
-    hostmirror.install(monkeypatch)
-    cpu = torch.device("cpu")
     hf = base_model(case)
     attach_product(case, hf)
-    g = gold(case)
-    seqs = synth.as_tensors(seqs_of(case))
-    maxlen = max(map(len, seqs))
-    t = TokenTrie(seqs, device=cpu); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen, forward_only=True).forward(hf, t)
-    for a, b in zip(out, g["fwd_dense"]):
-        assert torch.allclose(a, b, atol=1e-4), float((a - b).abs().max())
-    t = TokenTrie(seqs, fx.att(len(seqs)), device=cpu); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen); e.mode = "packed"
-    loss = e.backward(hf, t, mo.default_loss, 2048)
-    assert abs(loss - g["bwd_dense_loss"]) < 1e-4 * abs(loss)
-    named = dict(hf.named_parameters())
-    assert {n for n, p in named.items() if p.grad is not None} == set(gold_grads(g))
-    for n, gg in gold_grads(g).items():
-        assert mo.grad_ratio(gg, named[n].grad) <= 1e-3, n                   # fp16-packed golden: 5e-4 per element
+    family.check_cpu_engine_matches_fixture(hf, synth.as_tensors(seqs_of(case)), gold(case), monkeypatch)

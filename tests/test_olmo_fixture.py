@@ -23,11 +23,15 @@ import os
 import pytest
 import torch
 
+import family
+import hostmirror
 import olmo_ref64 as OR
 import rowops_ref64 as R
 from dynamictreeattn_amd import synth
 from dynamictreeattn_amd.model import _windows_of, check_supported, ensure_supported, is_olmo, make_config, rope_of
-from test_llama_family_fixture import LLAMA, MIN_GAP, att, gold_grads  # noqa: F401  (att / gold_grads: shared with the GPU tests)
+from family import _m, att, gold_grads  # noqa: F401  (re-exported: the GPU tests and scripts/make_golden_olmo.py read them here)
+from hostmirror import _cs, plain_wide  # noqa: F401  (HF's formula: the autograd reference here and the CPU stand-in there)
+from test_llama_family_fixture import LLAMA, MIN_GAP
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FILE = "engine_olmo.pt"
@@ -107,10 +111,7 @@ def hf_model(case, off=None, attn="eager", **change):
     modules replaced by PerHeadNorm over the same parameters."""
     import transformers
     m = getattr(transformers, CASES[case][1] + "ForCausalLM")(hf_config(case, off, attn, **change))
-    w = weights(m, CASES[case][4], CASE_STD.get(case, STD))
-    with torch.no_grad():
-        for n, p in m.named_parameters():
-            p.copy_(w[n])
+    family.load_weights(m, weights(m, CASES[case][4], CASE_STD.get(case, STD)))
     if off == "wide_norm":
         for layer in m.model.layers:
             a = layer.self_attn
@@ -126,11 +127,7 @@ def llama_control(case):
     c = transformers.LlamaConfig(**geo, rope_parameters=dict(DEFAULT_ROPE))
     c._attn_implementation = "eager"
     m = transformers.LlamaForCausalLM(c)
-    w = weights(m, CASES[case][4], CASE_STD.get(case, STD))
-    with torch.no_grad():
-        for n, p in m.named_parameters():
-            p.copy_(w[n])
-    return m.float().train()
+    return family.load_weights(m, weights(m, CASES[case][4], CASE_STD.get(case, STD)))
 
 
 def seqs_of(case):
@@ -139,10 +136,6 @@ def seqs_of(case):
 
 def gold(case):
     return torch.load(os.path.join(GOLD, FILE), weights_only=True)[CASES[case][0]]
-
-
-def _m(c):
-    return type("M", (), {"config": c})()
 
 
 # ---------------------------------------------------------------------------------------------------------------- fixture
@@ -335,11 +328,6 @@ def wide_case(T, NH, D, dtype, seed):
     return x, w, ops.rope_cos_sin(depth, D, 1e4), R.randn((T, NH, D), dtype, seed + 3)
 
 
-def _cs(cs, D):
-    c, s = cs[:, :D // 2], cs[:, D // 2:]
-    return torch.cat([c, c], -1)[:, None, :], torch.cat([s, s], -1)[:, None, :]
-
-
 def emu_wide_fwd(x, w, cs, eps, dtype):
     """The kernel's documented arithmetic in torch fp32: r over the whole row, a = cast(w x r) (one rounding), y = cast(a c + b s)."""
     xf = x.float()
@@ -368,15 +356,6 @@ def emu_norm_add(y, w, res, eps, dtype):
     r = torch.rsqrt((yf * yf).sum(-1) / yf.shape[1] + eps)
     yn = (w.float() * (yf * r[:, None])).to(dtype)
     return yn, (res.float() + yn.float()).to(dtype), r
-
-
-def plain_wide(x, w, cs, eps):
-    """HF's formula in the tensors' own dtype (float64 for autograd): Olmo2RMSNorm over the flattened row, then rotate-half RoPE."""
-    T, NH, D = x.shape
-    cos, sin = _cs(cs.to(x.dtype), D)
-    f = x.reshape(T, NH * D)
-    a = (w * (f * torch.rsqrt(f.pow(2).mean(-1, keepdim=True) + eps))).view(T, NH, D)
-    return a * cos + torch.cat([-a[..., D // 2:], a[..., :D // 2]], -1) * sin
 
 
 @pytest.mark.parametrize("T,NH,D", [(5, 3, 64), (4, 2, 128), (6, 1, 64)])
@@ -455,74 +434,15 @@ def test_norm_add_emulation_stays_inside_every_bound(R_, H, dtype):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the engine on the CPU
-def cpu_qkv_prep_wide(qkv, wq, wk, cos_sin, eps, Hq, Hkv):
-    """fp32 stand-in of ops.qkv_prep_wide: HF's formula (plain_wide) on q and k, v as it is."""
-    q, k, v = qkv.split([Hq, Hkv, Hkv], dim=1)
-    return plain_wide(q, wq, cos_sin, eps), plain_wide(k, wk, cos_sin, eps), v
-
-
-def cpu_rms_norm_add(res, y, w, eps):
-    yf = y.float()
-    return res + (w * (yf * torch.rsqrt(yf.pow(2).mean(-1, keepdim=True) + eps))).to(y.dtype)
-
-
-def install_cpu_olmo(monkeypatch):
-    """hostmirror's stand-ins plus the OLMo operators, a windowed tree attention and the host window meta (the Gemma-2 CPU test's)."""
-    import dataclasses
-    import hostmirror
-    import softcap_ref64 as SR
-    from dynamictreeattn_amd import ops, packing
-    hostmirror.install(monkeypatch)
-
-    def attention(q, k, v, meta, scale=None, softcap=0.0):
-        T = q.shape[0]
-        s = torch.arange(T)
-        if meta.subtree_end is None:
-            assert meta.q_offset == 0
-            vis = s[None, :] <= s[:, None]
-        else:
-            vis = (s[None, :] <= s[:, None]) & (s[:, None] < meta.subtree_end.long()[None, :])
-        if meta.window > 0:
-            vis = vis & (s[None, :] >= meta.win_lo.long()[:, None]) if meta.win_lo is not None else vis & (s[:, None] - s[None, :] < meta.window)
-        return SR.plain_capped_attention(q, k, v, vis, q.shape[-1] ** -0.5 if scale is None else scale, softcap)[0]
-
-    def window_meta(meta, plan, depth, window, Hkv=8, seg_tables=None):
-        if window <= 0 or window > packing.max_depth(plan):
-            return meta
-        return dataclasses.replace(meta, win_lo=torch.from_numpy(packing.window_lo_host(plan, window)), window=int(window))
-
-    for name, fn in (("tree_attention", attention), ("window_meta", window_meta), ("qkv_prep_wide", cpu_qkv_prep_wide),
-                     ("rms_norm_add", cpu_rms_norm_add)):
-        monkeypatch.setattr(ops, name, fn)
-
-
 @pytest.mark.parametrize("case", list(CASES))
 def test_olmo_engine_on_cpu_matches_the_reference_fixture(case, monkeypatch):
     """The product engine with its device steps replaced by CPU stand-ins (fp32) reproduces the reference's dense logprobs, loss and
     every gradient: the layer wiring (post-norm branches, projection-wide q/k norms, per-layer windows, one RoPE table per layer type)
     is host-side plumbing around the kernels."""
     pytest.importorskip("transformers")
-    from dynamictreeattn_amd.token_trie import TokenTrie
-    from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
-    from oracle import model_oracle as mo
-    install_cpu_olmo(monkeypatch)
-    cpu = torch.device("cpu")
-    hf = hf_model(case)
     g = gold(case)
-    seqs = synth.as_tensors(seqs_of(case))
-    maxlen = max(map(len, seqs))
-    t = TokenTrie(seqs, device=cpu); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen, forward_only=True).forward(hf, t)
-    for a, b in zip(out, g["fwd_dense"]):
-        assert torch.allclose(a, b, atol=1e-4), float((a - b).abs().max())
-    t = TokenTrie(seqs, att(len(seqs)), device=cpu); t.backward_permute()
-    e = TreeTrainingEngine(hf.config, cpu, torch.float32, maxlen); e.mode = "packed"
-    loss = e.backward(hf, t, mo.default_loss, 2048)
-    assert abs(loss - g["bwd_dense_loss"]) < 1e-4 * abs(loss)
-    named = dict(hf.named_parameters())
+    named = family.check_cpu_engine_matches_fixture(hf_model(case), synth.as_tensors(seqs_of(case)), g, monkeypatch)
     assert set(named) == set(gold_grads(g))
-    for n, gg in gold_grads(g).items():
-        assert mo.grad_ratio(gg, named[n].grad) <= 1e-3, n                   # fp16-packed golden: 5e-4 per element
 
 
 def test_olmo3_on_the_sliding_table_misses_the_fixture(monkeypatch):
@@ -532,7 +452,7 @@ def test_olmo3_on_the_sliding_table_misses_the_fixture(monkeypatch):
     from dynamictreeattn_amd import model as M
     from dynamictreeattn_amd.token_trie import TokenTrie
     from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
-    install_cpu_olmo(monkeypatch)
+    hostmirror.install(monkeypatch)
     real = M.rope_of
     monkeypatch.setattr(M, "rope_of", lambda c, layer_type=None: real(c, "sliding_attention" if layer_type else None))
     cpu = torch.device("cpu")

@@ -2,21 +2,19 @@
 norm, tied head): the tiny configuration behind tests/golden/engine_qwen2_d64.pt (scripts/make_golden.py qwen2_d64, the
 REFERENCE engine in fp32 on the CPU), its fixture checks, and the product engine on the CPU stand-ins against it.
 tests/test_gpu_engine_d64.py runs the same model on the HIP kernels."""
+import functools
 import os
 
 import pytest
 import torch
 
 import cases
-import hostmirror
+import family
 from dynamictreeattn_amd import synth
-from dynamictreeattn_amd.token_trie import TokenTrie
-from dynamictreeattn_amd.tree_training_engine import TreeTrainingEngine
-from oracle import model_oracle as mo
+from family import att  # noqa: F401  (re-exported: the GPU tests read it here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FIXTURE = os.path.join(GOLD, "engine_qwen2_d64.pt")
-CPU = torch.device("cpu")
 
 # head_dim 64 with the 0.5B head counts (q/o projections 896 wide); hidden 16 and intermediate 32 keep the fixture small (~170 KB of
 # fp16-packed gradients) - the attention geometry, not the hidden width, is what this configuration is for
@@ -43,16 +41,11 @@ def hf_qwen2_d64():
     return m.float().train()
 
 
-def att(n):
-    return [{"w_logprobs": -1.0 - 0.01 * i, "w_entropy": 0.1 + 0.003 * i} for i in range(n)]
-
-
 def gold():
     return torch.load(FIXTURE, weights_only=True)
 
 
-def gold_grads(g):
-    return {n: q.float() * s_ for n, (q, s_) in g["bwd_bs2048_grads_fp16_scaled"].items()}
+gold_grads = functools.partial(family.gold_grads, key="bwd_bs2048_grads_fp16_scaled")      # this fixture's gradients are the engine run's
 
 
 def test_qwen2_d64_fixture_names_and_shapes():
@@ -76,19 +69,6 @@ def test_qwen2_d64_engine_on_cpu_matches_the_reference_fixture(monkeypatch):
     """The product engine with its device steps replaced by the CPU stand-ins of tests/hostmirror.py (fp32) reproduces the reference
     engine's logprobs, loss and every gradient at head_dim 64 (the host logic sizes everything from D)."""
     pytest.importorskip("transformers")
-    hostmirror.install(monkeypatch)
-    hf = hf_qwen2_d64()
-    g = gold()
-    seqs = synth.as_tensors(synth.make_case(QWEN2_D64_DATA))
-    maxlen = max(map(len, seqs))
-    t = TokenTrie(seqs, device=CPU); t.forward_permute()
-    out = TreeTrainingEngine(hf.config, CPU, torch.float32, maxlen, forward_only=True).forward(hf, t)
-    for a, b in zip(out, g["fwd_forward"]):
-        assert torch.allclose(a, b, atol=2e-5)
-    t = TokenTrie(seqs, att(len(seqs)), device=CPU); t.backward_permute()
-    loss = TreeTrainingEngine(hf.config, CPU, torch.float32, maxlen).backward(hf, t, mo.default_loss, 2048)
-    assert abs(loss - g["bwd_bs2048_loss"]) < 2e-5 * abs(loss)
-    named = dict(hf.named_parameters())
-    for n, gg in gold_grads(g).items():
-        assert mo.grad_ratio(gg, named[n].grad) <= 1e-3, n                   # fp16-packed golden: 5e-4 per element
-        assert abs(float(named[n].grad.norm()) - g["grad_norms"][n]) <= 2e-5 * g["grad_norms"][n] + 1e-9, n
+    family.check_cpu_engine_matches_fixture(hf_qwen2_d64(), synth.as_tensors(synth.make_case(QWEN2_D64_DATA)), gold(), monkeypatch,
+                                            fwd_key="fwd_forward", loss_key="bwd_bs2048_loss", grads_key="bwd_bs2048_grads_fp16_scaled",
+                                            mode=None, atol=2e-5, loss_rtol=2e-5, norm_rtol=2e-5)

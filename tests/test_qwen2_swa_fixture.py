@@ -11,6 +11,7 @@ import torch
 import cases
 from dynamictreeattn_amd import synth
 from dynamictreeattn_amd.model import _windows_of
+from family import _m, att, gold_grads  # noqa: F401  (re-exported: the GPU tests and scripts/make_golden.py read them here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FIXTURE = os.path.join(GOLD, "engine_qwen2_swa.pt")
@@ -48,16 +49,8 @@ def hf_qwen2_swa(attn="eager"):
     return m.float().train()
 
 
-def att(n):
-    return [{"w_logprobs": -1.0 - 0.01 * i, "w_entropy": 0.1 + 0.003 * i} for i in range(n)]
-
-
 def gold():
     return torch.load(FIXTURE, weights_only=True)
-
-
-def gold_grads(g):
-    return {n: q.float() * s_ for n, (q, s_) in g["bwd_dense_grads_fp16_scaled"].items()}
 
 
 def test_qwen2_swa_fixture_names_and_shapes():
@@ -82,4 +75,4 @@ def test_qwen2_swa_fixture_config_windows():
     pytest.importorskip("transformers")
     for cls in ("Qwen2Config", "Qwen3Config"):
         c = hf_config(cls)
-        assert _windows_of(type("M", (), {"config": c})()) == [0, WINDOW, WINDOW], cls
+        assert _windows_of(_m(c)) == [0, WINDOW, WINDOW], cls

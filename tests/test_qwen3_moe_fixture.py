@@ -8,7 +8,9 @@ import os
 
 import torch
 
+import family
 from dynamictreeattn_amd import synth
+from family import att, gold_grads  # noqa: F401  (re-exported: the GPU tests and scripts/make_golden.py read them here)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FIXTURE = os.path.join(GOLD, "engine_qwen3_moe.pt")
@@ -57,23 +59,11 @@ def hf_qwen3_moe(cfg=QWEN3_MOE, seed=WEIGHT_SEED):
     """transformers.Qwen3MoeForCausalLM of `cfg` with the seeded weights (fp32, train mode)."""
     import transformers
     m = transformers.Qwen3MoeForCausalLM(hf_config(cfg))
-    w = moe_weights(m, seed)
-    with torch.no_grad():
-        for n, p in m.named_parameters():
-            p.copy_(w[n])
-    return m.float().train()
-
-
-def att(n):
-    return [{"w_logprobs": -1.0 - 0.01 * i, "w_entropy": 0.1 + 0.003 * i} for i in range(n)]
+    return family.load_weights(m, moe_weights(m, seed))
 
 
 def gold():
     return torch.load(FIXTURE, weights_only=True)
-
-
-def gold_grads(g):
-    return {n: q.float() * s_ for n, (q, s_) in g["bwd_dense_grads_fp16_scaled"].items()}
 
 
 def test_qwen3_moe_fixture_names_shapes_and_routing_margins():
