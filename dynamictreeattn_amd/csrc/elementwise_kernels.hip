@@ -336,6 +336,74 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(const void* __res
 }
 
 // ---------------------------------------------------------------------------------------------
+// RoPE over the first R of D elements of a head (Phi-3 / Phi-4-mini, GLM-4), no norm: elements R .. D-1 pass through bit for bit.
+// cs: [T, R] float = {cos[R/2], sin[R/2]}.  The lane layout is that of qk_norm_rope_*: LPH = D/8 lanes own one head, 8 elements each, and
+// HPL heads of one token share the lane group's table values.  A lane whose 8 elements lie at or past R (sub >= R/8) reads no table entry
+// and stores the vector it loaded.
+//   PAIR 0 (half-split, R % 16 == 0): element i <-> i + R/2, i.e. lane sub <-> sub +- R/16 of the same head.  R/16 is 3 for R = 48 and 6
+//     for R = 96 - no power of two - so the partner's value comes by an indexed shuffle.
+//   PAIR 1 (interleaved, R % 8 == 0): element 2i <-> 2i+1, both inside the lane's own 8 elements; the lane reads 4 cos and 4 sin.
+// One kernel serves both directions: sgn = +1 rotates by the token's angle (forward), -1 by its negative (the backward).  ONE_PASS (the
+// forward): the grid covers every unit and a lane group past the end leaves at once, as in qk_norm_rope_fwd_kernel; otherwise grid-stride
+// over (token, head group) units; out_ may be in_ with the same strides (in place): a lane writes exactly the bytes it read, partner
+// values travel through registers.  No LDS.
+// ---------------------------------------------------------------------------------------------
+template <int DT, int HPL, int D, int PAIR, bool ONE_PASS>
+__global__ __launch_bounds__(256) void rope_partial_kernel(const void* in_, const float* __restrict__ cs, void* out_, int64_t n_units, int NH, int R,
+                                                           int64_t in_st_t, int64_t in_st_h, int64_t out_st_t, float sgn) {
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
+  constexpr int LPH = D / 8, LSH = D == 128 ? 4 : 3, UPB = 4 * (64 / LPH);
+  const int lane = threadIdx.x & 63, sub = lane & (LPH - 1);
+  const int groups = NH / HPL;
+  const bool rot = 8 * sub < R;
+  const int half = R >> 4;                                 // PAIR 0: lanes per rotated half
+  const bool lo = sub < half;
+  const int src = PAIR == 0 && rot ? (lo ? lane + half : lane - half) : lane;
+  for (int64_t base = (int64_t)blockIdx.x * UPB; base < n_units; base += (int64_t)gridDim.x * UPB) {
+    const int64_t unit = base + (threadIdx.x >> 6) * (64 / LPH) + (lane >> LSH);
+    if (ONE_PASS && unit >= n_units) return;               // (a lane group is one unit: the partner lanes of a shuffle leave together)
+    const bool live = ONE_PASS || unit < n_units;          // grid-stride: a dead lane group runs along on the last unit, the shuffles stay uniform
+    const int64_t uc = live ? unit : n_units - 1;
+    const int64_t tok = uc / groups; const int head0 = (int)(uc - tok * groups) * HPL;
+    const e* in = reinterpret_cast<const e*>(in_) + tok * in_st_t + (int64_t)head0 * in_st_h + 8 * sub;
+    v8 v[HPL];
+#pragma unroll
+    for (int h = 0; h < HPL; ++h) v[h] = *reinterpret_cast<const v8*>(in + h * in_st_h);
+    float cj[8], sj[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { cj[j] = 0.f; sj[j] = 0.f; }
+    if (rot) {
+      if (PAIR == 0) {
+        const float* c = cs + tok * R + 8 * (lo ? sub : sub - half);
+        const float sg = lo ? -sgn : sgn;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { cj[j] = c[j]; sj[j] = sg * c[(R >> 1) + j]; }
+      } else {
+        const float* c = cs + tok * R + 4 * sub;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float s = sgn * c[(R >> 1) + i];
+          cj[2 * i] = cj[2 * i + 1] = c[i]; sj[2 * i] = -s; sj[2 * i + 1] = s;
+        }
+      }
+    }
+    e* out = reinterpret_cast<e*>(out_) + tok * out_st_t + (int64_t)head0 * D + 8 * sub;
+#pragma unroll
+    for (int h = 0; h < HPL; ++h) {
+      v8 o = v[h];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float a = (float)v[h][j];
+        const float other = PAIR == 0 ? __shfl(a, src) : (float)v[h][j ^ 1];
+        if (rot) o[j] = (e)(a * cj[j] + other * sj[j]);
+      }
+      if (live) *reinterpret_cast<v8*>(out + h * D) = o;
+    }
+    if (ONE_PASS) break;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // OLMo-2 / OLMo-3: q/k RMSNorm over the WHOLE projection row (NH*D <= 8192 elements, weight [NH*D]), then RoPE per head.
 // WPT = waves per token.  Rows of up to 2 048 elements: one wave per token, 4 tokens per workgroup (WPT 1); longer rows: the 4 waves of
 // a workgroup share one token (WPT 4) - at most 4 groups per lane either way, where one wave holding a row of 8 192 (16 groups per lane)
@@ -920,6 +988,44 @@ extern "C" int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* c
     });
   });
   return DTA_LAUNCH_STATUS();
+}
+
+namespace {
+// the checks both dta_rope_partial_* entries share, in the header's order, and the launch: `grid_cap` 0 = one pass over every unit
+int rope_partial(const void* in, const float* cos_sin, void* out, int32_t T, int32_t NH, int32_t head_dim, int32_t rotary_dim, int32_t pairing,
+                 int64_t in_st_t, int64_t in_st_h, int64_t out_st_t, float sgn, int grid_cap, int32_t dtype, void* stream) {
+  if (!in || !cos_sin || !out || T <= 0 || NH <= 0 || rotary_dim <= 0 || (pairing != 0 && pairing != 1)) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || (head_dim != 128 && head_dim != 64) || rotary_dim > head_dim || rotary_dim % (pairing == 0 ? 16 : 8)) return DTA_EUNSUPPORTED;
+  if (!aligned16(in) || !aligned16(out) || !aligned16(cos_sin) || in_st_t % 8 || in_st_h % 8 || out_st_t % 8) return DTA_EALIGN;
+  if (in_st_t < 0 || in_st_h < head_dim || out_st_t < (int64_t)NH * head_dim) return DTA_EINVAL;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  qk_form(NH, head_dim, [&](auto hpl, auto d) {
+    constexpr int HPL = decltype(hpl)::value, D = decltype(d)::value, UPB = 4 * (64 / (D / 8));
+    const int64_t n = (int64_t)T * (NH / HPL);
+    const dim3 grid(grid_cap ? (unsigned)row_blocks((int64_t)T * NH, 16, grid_cap) : ceil_blocks(n, UPB)), block(256);
+    auto launch = [&](auto dt, auto pair, auto one_pass) {
+      hipLaunchKernelGGL((rope_partial_kernel<decltype(dt)::value, HPL, D, decltype(pair)::value, decltype(one_pass)::value>), grid, block, 0, st_,
+                         in, cos_sin, out, n, NH, rotary_dim, in_st_t, in_st_h, out_st_t, sgn);
+    };
+    dta_storage_type(dtype, [&](auto dt) {
+      if (grid_cap) { if (pairing == 0) launch(dt, Int<0>{}, std::false_type{}); else launch(dt, Int<1>{}, std::false_type{}); }
+      else if (pairing == 0) launch(dt, Int<0>{}, std::true_type{}); else launch(dt, Int<1>{}, std::true_type{});
+    });
+  });
+  return DTA_LAUNCH_STATUS();
+}
+}  // namespace
+
+extern "C" int dta_rope_partial_fwd(const void* x, const float* cos_sin, void* y, int32_t T, int32_t NH, int32_t head_dim, int32_t rotary_dim,
+                                    int32_t pairing, int64_t x_stride_t, int32_t dtype, void* stream) {
+  return rope_partial(x, cos_sin, y, T, NH, head_dim, rotary_dim, pairing, x_stride_t, head_dim, (int64_t)NH * head_dim, 1.f, 0, dtype, stream);
+}
+
+// the rotation by the negative angle; the grid-stride form of dta_qk_norm_rope_bwd (the same workgroup count)
+extern "C" int dta_rope_partial_bwd(const float* cos_sin, const void* dy, void* dx, int32_t T, int32_t NH, int32_t head_dim, int32_t rotary_dim,
+                                    int32_t pairing, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t, int32_t dtype, void* stream) {
+  return rope_partial(dy, cos_sin, dx, T, NH, head_dim, rotary_dim, pairing, dy_stride_t, dy_stride_h, dx_stride_t, -1.f, 1024, dtype, stream);
 }
 
 extern "C" int dta_wide_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,

@@ -8,14 +8,16 @@ from typing import List
 import torch
 
 from . import ops
-from .model import ensure_supported, final_softcap_of, head_weight, packed_hidden_states
+from .model import ensure_supported, final_softcap_of, head_weight, is_longrope, longrope_boundary, packed_hidden_states
 from .tree_training_engine import packed_logprob_entropy
 
 
 def _one(model, ids: torch.Tensor, want_entropy: bool, checkpoint_layers: bool):
     n = ids.numel()
     depth = torch.arange(n, device=ids.device, dtype=torch.int32)
-    h = packed_hidden_states(model, ids, depth, ops.stack_meta(0), checkpoint_layers)
+    # a longrope model (Phi-3 / Phi-4-mini): the long factors for a sequence longer than original_max_position_embeddings, as HF decides
+    long = is_longrope(model.config) and n > longrope_boundary(model.config)
+    h = packed_hidden_states(model, ids, depth, ops.stack_meta(0), checkpoint_layers, longrope_long=long)
     parent = depth.to(torch.long) - 1
     return packed_logprob_entropy(h, head_weight(model), ids, parent, want_entropy, softcap=final_softcap_of(model))
 

@@ -7,7 +7,7 @@ torch.  `Qwen3TreeLM` mirrors the HF module/parameter tree (``model.embed_tokens
 ``model.layers.N.self_attn.q_proj.weight`` …, tied head) so that
 
 * gradients compare name by name with grad/Qwen3-0.6B-TB-vs-DB-bf16.txt (310 tensors), and
-* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral/Gemma-2/OLMo-2/OLMo-3 ``*ForCausalLM`` by duck typing —
+* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral/Gemma-2/OLMo-2/OLMo-3/Phi-3/Phi-4/GLM-4 ``*ForCausalLM`` by duck typing —
   its own ``nn.Parameter`` objects are used, so ``param.grad`` lands where the training loop expects.
 """
 from __future__ import annotations
@@ -148,6 +148,32 @@ def is_olmo(config) -> bool:
     return getattr(config, "model_type", None) in ("olmo2", "olmo3")
 
 
+def is_phi3(config) -> bool:
+    """Phi-3 / Phi-4 arithmetic (fused qkv_proj and gate_up_proj modules, half-split RoPE over the first rotary_dim elements of the
+    head, rope_type longrope, a sliding window on every layer) is keyed on config.model_type == "phi3" and on nothing else."""
+    return getattr(config, "model_type", None) == "phi3"
+
+
+def is_glm4(config) -> bool:
+    """GLM-4 arithmetic (interleaved RoPE pairs (2i, 2i+1) over the first rotary_dim elements of the head, four sandwich norms with
+    weight offset 0, a fused gate_up_proj) is keyed on config.model_type == "glm4" and on nothing else."""
+    return getattr(config, "model_type", None) == "glm4"
+
+
+def _head_dim(c) -> int:
+    return getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+
+
+def rotary_dim(config) -> int:
+    """int(head_dim * partial_rotary_factor), the factor from config.rope_parameters first, then from the configuration, as HF's
+    rotary-embedding initialisers take it (1.0 when neither has one)."""
+    rp = getattr(config, "rope_parameters", None) or getattr(config, "rope_scaling", None) or {}
+    prf = rp.get("partial_rotary_factor") if isinstance(rp, dict) else None
+    if prf is None:
+        prf = getattr(config, "partial_rotary_factor", None)
+    return int(_head_dim(config) * (1.0 if prf is None else float(prf)))
+
+
 def rope_layer_types(c):
     """The layer types that carry their own RoPE parameters: for model_type "olmo3" (HF's Olmo3RotaryEmbedding keeps one set of
     frequencies per layer type) the sorted set of config.layer_types; None for every other model type (one table per model)."""
@@ -191,18 +217,31 @@ def _rope_dict(c, layer_type=None) -> dict:
 _ROPE: dict = {}
 
 
-def rope_of(c, layer_type=None):
+def is_longrope(c) -> bool:
+    """A phi3 configuration with rope_type longrope: two sets of frequencies (short_factor / long_factor), one per call."""
+    return is_phi3(c) and _rope_dict(c)["rope_type"] == "longrope"
+
+
+def longrope_boundary(c) -> int:
+    """original_max_position_embeddings of a longrope configuration: a sequence longer than this takes the long factors."""
+    return int(_rope_dict(c)["original_max_position_embeddings"])
+
+
+def rope_of(c, layer_type=None, long=False):
     """(inv_freq [D/2] fp32 on the host, attention_factor) of a configuration (ops.rope_inv_freq), resolved once per distinct
     parameter set: every consumer of one model - the packed pass, the block-wise walk, dense.py, engine.forward, warm_gemm_shapes -
     reaches it through packed_hidden_states and so builds its table from the same frequencies.  `layer_type`: which of the nested
-    parameter sets of an olmo3 configuration (rope_layer_types); two layer types with equal parameters resolve to the same pair."""
+    parameter sets of an olmo3 configuration (rope_layer_types); two layer types with equal parameters resolve to the same pair.
+    For phi3 and glm4 the vector has rotary_dim(c) / 2 entries; `long` picks the long_factor set of a longrope configuration
+    (ops.longrope_inv_freq; one cached pair per set) and means nothing elsewhere."""
     rp = _rope_dict(c, layer_type)
-    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    D = rotary_dim(c) if is_phi3(c) or is_glm4(c) else _head_dim(c)
     max_pos = getattr(c, "max_position_embeddings", None)
-    key = (D, max_pos, tuple(sorted((k, repr(v)) for k, v in rp.items())))
+    longrope = is_phi3(c) and rp["rope_type"] == "longrope"
+    key = (D, max_pos, bool(long) and longrope, tuple(sorted((k, repr(v)) for k, v in rp.items())))
     hit = _ROPE.get(key)
     if hit is None:
-        hit = _ROPE[key] = ops.rope_inv_freq(D, rp, max_pos)
+        hit = _ROPE[key] = ops.longrope_inv_freq(D, rp, max_pos, bool(long)) if longrope else ops.rope_inv_freq(D, rp, max_pos)
     return hit
 
 
@@ -255,6 +294,30 @@ def _check_olmo(c) -> None:
                              f"one row of at most 8192 elements")
 
 
+def _check_partial_rope(c, training: bool) -> None:
+    """phi3 / glm4: the head_dim and rotary_dim the partial RoPE kernels take, longrope's lists (phi3 only), Phi-3's dropouts."""
+    mt, D = c.model_type, _head_dim(c)
+    if D not in (64, 128):
+        raise ValueError(f"config.head_dim = {D} is not supported for {mt}: the attention and RoPE kernels cover head_dim 64 and 128"
+                         + (" (Phi-3-mini and Phi-3.5-mini use 96)" if D == 96 else ""))
+    R, step = rotary_dim(c), 16 if is_phi3(c) else 8
+    if not 0 < R <= D or R % step:
+        raise ValueError(f"config partial_rotary_factor gives a rotary dimension of {R} of head_dim {D}, which is not supported for {mt}: "
+                         f"the {'half-split' if is_phi3(c) else 'interleaved'} RoPE kernel rotates a multiple of {step} elements, at most head_dim")
+    rp = _rope_dict(c)
+    if rp["rope_type"] == "longrope" and is_phi3(c):
+        if rp.get("original_max_position_embeddings") is None:
+            raise ValueError("config.original_max_position_embeddings is missing: longrope picks its factors by it")
+        for f in ("short_factor", "long_factor"):
+            v = rp.get(f)
+            if not isinstance(v, (list, tuple)) or len(v) != R // 2:
+                raise ValueError(f"config.rope_parameters[{f!r}] must be a list of {R // 2} numbers (rotary dimension {R}), got "
+                                 f"{len(v) if isinstance(v, (list, tuple)) else v!r}")
+    for f in ("resid_pdrop", "embd_pdrop"):
+        if training and float(getattr(c, f, 0.0) or 0.0) > 0:
+            raise ValueError(f"config.{f} = {getattr(c, f)} on a model in training mode is not supported (model.eval(), or set it to 0)")
+
+
 def check_supported(config, training: bool = True) -> None:
     """Refuses, with a ValueError that names the field, a configuration whose arithmetic the engine cannot honour - it would run,
     and compute something else: a rope_type other than default / linear / llama3 / yarn, rope_parameters nested per layer type,
@@ -264,9 +327,17 @@ def check_supported(config, training: bool = True) -> None:
     a head_dim other than 64 / 128 and a missing or non-positive query_pre_attn_scalar are refused.  An OLMo-2 / OLMo-3 configuration
     (is_olmo) needs head_dim 64 / 128 and num_attention_heads * head_dim, num_key_value_heads * head_dim <= 8192 (the projection-wide
     q/k norm kernels); for model_type "olmo3" alone rope_parameters nested per layer type is honoured - its keys must be exactly the
-    configuration's layer types, and every sub-dict passes the checks above.  OLMo-1 (model_type "olmo") is refused by name."""
+    configuration's layer types, and every sub-dict passes the checks above.  OLMo-1 (model_type "olmo") is refused by name.
+    A Phi-3 / Phi-4 or GLM-4 configuration (is_phi3, is_glm4) is the exception for partial rotary embedding: a partial_rotary_factor
+    whose rotary_dim is a multiple of 16 (phi3, half-split pairs) or 8 (glm4, interleaved pairs) and at most head_dim is honoured, and
+    on phi3 alone rope_type longrope with short_factor and long_factor of rotary_dim / 2 entries and original_max_position_embeddings.
+    Refused there: a head_dim other than 64 / 128 (Phi-3-mini's 96), any other rotary_dim, resid_pdrop or embd_pdrop above 0 on a model
+    in training mode, longrope on glm4."""
     c = config
     gemma = is_gemma2(c)
+    partial = is_phi3(c) or is_glm4(c)
+    if partial:
+        _check_partial_rope(c, training)
     if gemma:
         _check_gemma2(c)
     if getattr(c, "model_type", None) == "olmo":
@@ -275,10 +346,10 @@ def check_supported(config, training: bool = True) -> None:
         _check_olmo(c)
     for lt in rope_layer_types(c) or [None]:
         rp = _rope_dict(c, lt)
-        if rp["rope_type"] not in ops.ROPE_TYPES:
+        if rp["rope_type"] not in ops.ROPE_TYPES and not (is_phi3(c) and rp["rope_type"] == "longrope"):
             raise ValueError(f"config.rope_parameters['rope_type'] = {rp['rope_type']!r} is not supported ({' / '.join(ops.ROPE_TYPES)})")
         prf = rp.get("partial_rotary_factor", getattr(c, "partial_rotary_factor", None))
-        if prf is not None and float(prf) != 1.0:
+        if not partial and prf is not None and float(prf) != 1.0:
             raise ValueError(f"config partial_rotary_factor = {prf} is not supported: the rotary kernels rotate the whole head")
     act = getattr(c, "hidden_act", None)
     if not gemma and act is not None and act != "silu":         # (Gemma2Config keeps hidden_act as a legacy field; hidden_activation decides)
@@ -328,11 +399,11 @@ def ensure_supported(model) -> None:
         seen.add(training)
 
 
-def _cfg_of(model):
+def _cfg_of(model, longrope_long=False):
     c = model.config
-    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    D = _head_dim(c)
     types = rope_layer_types(c)                  # olmo3: one resolved pair per layer, by the layer's type
-    rope = rope_of(c) if types is None else [rope_of(c, t) for t in c.layer_types]
+    rope = (rope_of(c, long=True) if longrope_long else rope_of(c)) if types is None else [rope_of(c, t) for t in c.layer_types]
     return c.num_attention_heads, c.num_key_value_heads, D, float(getattr(c, "rms_norm_eps", 1e-6)), rope
 
 
@@ -340,11 +411,12 @@ def _windows_of(model):
     """Sliding window of every decoder layer (0 = full attention), as the HF Qwen2 / Qwen3 configurations define it:
     config.sliding_window where config.layer_types[l] == "sliding_attention"; without layer_types, the rule those config classes
     apply (use_sliding_window and l >= max_window_layers).  A sliding layer without a sliding_window attends in full, as in HF.
-    Mistral and Mixtral (config.model_type) have neither field: every layer slides whenever config.sliding_window is set."""
+    Mistral, Mixtral and Phi-3 (config.model_type) have neither field: every layer slides whenever config.sliding_window is set (HF
+    picks the sliding mask for the whole model)."""
     c = model.config
     n = c.num_hidden_layers
     W = getattr(c, "sliding_window", None) or 0
-    if getattr(c, "model_type", None) in ("mistral", "mixtral"):
+    if getattr(c, "model_type", None) in ("mistral", "mixtral", "phi3"):
         return [int(W)] * n
     types = getattr(c, "layer_types", None)
     if types is not None:
@@ -441,6 +513,40 @@ def _olmo_layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     return ops.rms_norm_add(h, _project(act, m.down_proj), layer.post_feedforward_layernorm.weight, eps), None
 
 
+def _phi3_layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
+    """One Phi-3 / Phi-4 decoder layer in the (residual stream, pending update) convention of _layer_forward: pre-norm, with the fused
+    modules HF keeps - qkv_proj's output is already q|k|v and gate_up_proj's gate|up, so nothing is stacked.  A table narrower than
+    the head (cos_sin [T, R], R < D: Phi-4-mini) rotates the first R elements (ops.qkv_prep_partial); a full one is ops.qkv_prep."""
+    T = res.shape[0]
+    a, m = layer.self_attn, layer.mlp
+    res, h = ops.add_rms_norm(res, delta, layer.input_layernorm.weight, eps)
+    qkv = _project(h, a.qkv_proj).view(T, Hq + 2 * Hkv, D)
+    if cos_sin.shape[1] < D:
+        q, k, v = ops.qkv_prep_partial(qkv, cos_sin, Hq, Hkv, False)
+    else:
+        q, k, v = ops.qkv_prep(qkv, None, None, cos_sin, eps, Hq, Hkv)
+    o = attn(q, k, v)
+    res, h = ops.add_rms_norm(res, _project(o.reshape(T, Hq * D), a.o_proj), layer.post_attention_layernorm.weight, eps)
+    act = ops.swiglu_fused(_project(h, m.gate_up_proj))
+    return res, _project(act, m.down_proj)
+
+
+def _glm4_layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
+    """One GLM-4 decoder layer in the (residual stream, pending update) convention of _layer_forward: Gemma-2's sandwich layout - both
+    branch outputs are normalised before they join the residual stream - with weight offset 0, biased q/k/v projections, interleaved
+    RoPE pairs over the first cos_sin.shape[1] elements of the head, a fused gate_up_proj and SwiGLU."""
+    T = res.shape[0]
+    a, m = layer.self_attn, layer.mlp
+    res, h = ops.add_rms_norm(res, delta, layer.input_layernorm.weight, eps)
+    qkv = _project(h, a.q_proj, a.k_proj, a.v_proj).view(T, Hq + 2 * Hkv, D)
+    q, k, v = ops.qkv_prep_partial(qkv, cos_sin, Hq, Hkv, True)
+    o = attn(q, k, v)
+    delta = ops.rms_norm(_project(o.reshape(T, Hq * D), a.o_proj), layer.post_self_attn_layernorm.weight, eps)
+    res, h = ops.add_rms_norm(res, delta, layer.post_attention_layernorm.weight, eps)
+    act = ops.swiglu_fused(_project(h, m.gate_up_proj))
+    return res, ops.rms_norm(_project(act, m.down_proj), layer.post_mlp_layernorm.weight, eps)
+
+
 def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     """One decoder layer over the packed rows.  The hidden state enters as (residual stream, pending update)
     so that each residual add is fused into the RMSNorm that follows it.  hipBLASLt GEMMs through torch;
@@ -533,7 +639,7 @@ class _LayerRecompute(torch.autograd.Function):
 
 def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta, checkpoint_layers: bool = False,
                          attn_keep_bytes: int = 0, attn_of_layer=None, full_layers=0, kept_out=None, embed=None,
-                         meta_for_window=None) -> torch.Tensor:
+                         meta_for_window=None, longrope_long: bool = False) -> torch.Tensor:
     """Final-norm hidden states [T, hidden] of the packed tokens.  `model` is a Qwen3TreeLM or an HF
     Qwen2/Qwen3/Llama/Mistral (and their MoE kin) *ForCausalLM (duck-typed).  `checkpoint_layers`: recompute each layer in the backward, except the first
     `full_layers`, which keep their activations like the plain pass — an int, or a plan `bytes kept by layer 0 -> number of
@@ -543,12 +649,14 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
     stack form bound to layer l's KV stack; `meta` is unused then); `embed(tokens)` replaces the plain embedding lookup (the
     block-wise engine routes the rows' gradients into its fp32 sink instead of a dense [vocab, hidden] gradient per block).
     Sliding-window layers (_windows_of) attend with `meta_for_window(W)` (layer_metas); the stack form gets its window from
-    `attn_of_layer`."""
-    Hq, Hkv, D, eps, rope = _cfg_of(model)
+    `attn_of_layer`.  `longrope_long`: a longrope model (is_longrope) rotates by its long_factor frequencies in this call."""
+    Hq, Hkv, D, eps, rope = _cfg_of(model, longrope_long)
     metas = layer_metas(meta, _windows_of(model), meta_for_window) if attn_of_layer is None else None
     body = model.model
     gemma = is_gemma2(model.config)
-    layer_fwd = _gemma2_layer_forward if gemma else _olmo_layer_forward if is_olmo(model.config) else _layer_forward
+    layer_fwd = (_gemma2_layer_forward if gemma else _olmo_layer_forward if is_olmo(model.config) else _phi3_layer_forward if is_phi3(model.config)
+                 else _glm4_layer_forward if is_glm4(model.config) else _layer_forward)
+    R = rotary_dim(model.config) if is_phi3(model.config) or is_glm4(model.config) else D          # the table's width: the rotary dimension
     akw = attn_args_of(model)
     res, delta = (embed(tokens) if embed is not None else F.embedding(tokens, body.embed_tokens.weight)), None
     if gemma:            # the normaliser, rounded to the model dtype as HF does; on the embed= path too, so the fp32 sink gets the scaled gradient
@@ -557,7 +665,7 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
         tables = {id(r_): ops.rope_cos_sin(depth, D, r_) for r_ in {id(r_): r_ for r_ in rope}.values()}
         cos_sins = [tables[id(r_)] for r_ in rope]
     else:
-        cos_sins = [ops.rope_cos_sin(depth, D, rope)] * len(body.layers)
+        cos_sins = [ops.rope_cos_sin(depth, R, rope)] * len(body.layers)
     per_layer = tokens.shape[0] * Hq * (D * res.element_size() + 4)             # out + lse of one layer
     n_full = full_layers if isinstance(full_layers, int) else 1
     for li, layer in enumerate(body.layers):

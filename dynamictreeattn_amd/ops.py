@@ -832,6 +832,95 @@ def qkv_prep_wide(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, cos_sin
     return _QKVPrep.apply(qkv, wq, wk, cos_sin, eps, Hq, Hkv, True)
 
 
+def _rope_partial_fwd(x, cos_sin, interleaved):
+    """One dta_rope_partial_fwd launch over x [T, NH, D] (rows of D contiguous, any token stride), cos_sin [T, R]: y contiguous."""
+    T, NH, D = x.shape
+    R = cos_sin.shape[1]
+    y = torch.empty((T, NH, D), dtype=x.dtype, device=x.device)
+    _launch("dta_rope_partial_fwd", (x, cos_sin), ptr(x), ptr(cos_sin), ptr(y), T, NH, D, R, int(bool(interleaved)), x.stride(0), _DT[x.dtype],
+            nbytes=2 * T * NH * D * x.element_size() + T * R * 4)
+    return y
+
+
+def _rope_partial_bwd(cos_sin, dy, dx, interleaved):
+    """One dta_rope_partial_bwd launch into dx [T, NH, D] (any token stride; may be dy)."""
+    T, NH, D = dx.shape
+    if dy.stride(2) != 1:
+        dy = dy.contiguous()
+    _launch("dta_rope_partial_bwd", (cos_sin, dy), ptr(cos_sin), ptr(dy), ptr(dx), T, NH, D, cos_sin.shape[1], int(bool(interleaved)),
+            dy.stride(0), dy.stride(1), dx.stride(0), _DT[dx.dtype], nbytes=2 * T * NH * D * dx.element_size() + T * cos_sin.shape[1] * 4)
+
+
+def _check_partial_table(x, cos_sin):
+    if cos_sin.dim() != 2 or cos_sin.shape[0] != x.shape[0] or cos_sin.dtype != torch.float32 or not cos_sin.is_contiguous():
+        raise ValueError(f"partial RoPE: cos_sin must be a contiguous fp32 [T, R] table for x {tuple(x.shape)}, got {cos_sin.dtype} {tuple(cos_sin.shape)}")
+
+
+class _RopePartial(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, cos_sin, interleaved):
+        _require_cuda(x, cos_sin)
+        _check_partial_table(x, cos_sin)
+        if x.stride(2) != 1 or x.stride(1) != x.shape[2]:
+            x = x.contiguous()
+        ctx.save_for_backward(cos_sin)
+        ctx.interleaved = bool(interleaved)
+        return _rope_partial_fwd(x, cos_sin, interleaved)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (cos_sin,) = ctx.saved_tensors
+        dx = torch.empty(dy.shape, dtype=dy.dtype, device=dy.device)
+        _rope_partial_bwd(cos_sin, dy, dx, ctx.interleaved)
+        return dx, None, None
+
+
+class _QKVPrepPartial(torch.autograd.Function):
+    """_QKVPrep for the models that rotate part of the head or pair neighbouring elements (dta_rope_partial_*; no norm, so nothing but
+    the table is saved): q and k are read in place from the fused buffer, v is a view of it, the three gradients land in ONE
+    [T, Hq+2Hkv, D] buffer, and the backward runs in place when _TreeAttention's backward laid them out that way."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos_sin, Hq, Hkv, interleaved):
+        _require_cuda(qkv, cos_sin)
+        T, H3, D = qkv.shape
+        assert H3 == Hq + 2 * Hkv and qkv.is_contiguous()
+        _check_partial_table(qkv, cos_sin)
+        ctx.save_for_backward(cos_sin)
+        ctx.geom = (T, Hq, Hkv, D, qkv.dtype, bool(interleaved))
+        return _rope_partial_fwd(qkv[:, :Hq], cos_sin, interleaved), _rope_partial_fwd(qkv[:, Hq:Hq + Hkv], cos_sin, interleaved), qkv[:, Hq + Hkv:]
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        (cos_sin,) = ctx.saved_tensors
+        T, Hq, Hkv, D, dtype, interleaved = ctx.geom
+        H3 = Hq + 2 * Hkv
+        base = dv._base
+        in_place = (base is not None and dq._base is base and dk._base is base and base.shape == (T, H3, D) and base.is_contiguous()
+                    and base.dtype == dtype and dq.shape == (T, Hq, D) and dk.shape == (T, Hkv, D) and dv.shape == (T, Hkv, D)
+                    and dq.stride() == dk.stride() == dv.stride() == (H3 * D, D, 1)
+                    and (dq.storage_offset(), dk.storage_offset(), dv.storage_offset()) == (0, Hq * D, (Hq + Hkv) * D))
+        d = base if in_place else torch.empty((T, H3, D), dtype=dtype, device=dv.device)
+        _rope_partial_bwd(cos_sin, dq, d[:, :Hq], interleaved)
+        _rope_partial_bwd(cos_sin, dk, d[:, Hq:Hq + Hkv], interleaved)
+        if not in_place:
+            d[:, Hq + Hkv:].copy_(dv)
+        return d, None, None, None, None
+
+
+def rope_partial(x: torch.Tensor, cos_sin: torch.Tensor, interleaved: bool) -> torch.Tensor:
+    """x [T, NH, D] (D = 64 or 128) -> RoPE over the first R = cos_sin.shape[1] elements of every head at the positions encoded in
+    cos_sin [T, R] (fp32, rope_cos_sin with R as its D); elements R.. pass through.  interleaved False: the half-split pairing
+    i <-> i + R/2 (Phi-3, R % 16 == 0); True: the pairs (2i, 2i+1) (GLM-4, R % 8 == 0)."""
+    return _RopePartial.apply(x, cos_sin, interleaved)
+
+
+def qkv_prep_partial(qkv: torch.Tensor, cos_sin: torch.Tensor, Hq: int, Hkv: int, interleaved: bool):
+    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D] of a model without q/k norms whose RoPE covers
+    the first R = cos_sin.shape[1] elements of the head (rope_partial)."""
+    return _QKVPrepPartial.apply(qkv, cos_sin, Hq, Hkv, interleaved)
+
+
 def qk_norm_rope(x: torch.Tensor, w: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float) -> torch.Tensor:
     """x [T, NH, D] (D = 64 or 128) -> RoPE(RMSNorm_D(x) * w) at the positions encoded in cos_sin [T,D] (fp32)."""
     return _QKNormRope.apply(x, w, cos_sin, eps)
@@ -895,6 +984,35 @@ def rope_inv_freq(D: int, rope_parameters: dict, max_position_embeddings: Option
     extrapolation, interpolation = 1.0 / pos_freqs, 1.0 / (factor * pos_freqs)
     keep = 1 - torch.clamp((torch.arange(D // 2, dtype=torch.float32) - low) / (high - low), 0, 1)
     return interpolation * (1 - keep) + extrapolation * keep, att
+
+
+def longrope_inv_freq(R: int, rope_parameters: dict, max_position_embeddings: Optional[int], long: bool):
+    """(inv_freq [R/2] fp32 on the host, attention_factor) of a `longrope` parameter dict (Phi-3 / Phi-4-mini) over the rotary dimension
+    R, with the `long_factor` (long) or the `short_factor` list: transformers' _compute_longrope_parameters restated with the same fp32
+    host operations in the same order - 1 / (ext_factors * base ** (arange(0, R, 2) / R)) - so that the frequencies come out bit for bit.
+    Which set a call uses is the caller's decision (HF: long when the sequence is longer than original_max_position_embeddings).
+    factor defaults to max_position_embeddings / original_max_position_embeddings; without an explicit attention_factor the table is
+    scaled by sqrt(1 + ln(factor) / ln(original_max_position_embeddings)) when factor > 1."""
+    rp = rope_parameters
+    orig = rp.get("original_max_position_embeddings")
+    if orig is None:
+        raise ValueError("rope_parameters: longrope needs original_max_position_embeddings")
+    name = "long_factor" if long else "short_factor"
+    ext = rp.get(name)
+    if ext is None or len(ext) != R // 2:
+        raise ValueError(f"rope_parameters: longrope needs {name} with {R // 2} entries (rotary dimension {R}), got "
+                         f"{'none' if ext is None else len(ext)}")
+    factor = rp.get("factor")
+    if factor is None:
+        if max_position_embeddings is None:
+            raise ValueError("rope_parameters: longrope needs factor (or max_position_embeddings)")
+        factor = max_position_embeddings / orig
+    att = rp.get("attention_factor")
+    if att is None:
+        att = 1.0 if factor <= 1.0 else math.sqrt(1 + math.log(factor) / math.log(orig))
+    base = rp["rope_theta"]
+    shape = torch.arange(0, R, 2, dtype=torch.int64).float() / R
+    return 1.0 / (torch.tensor(ext, dtype=torch.float32) * base ** shape), att
 
 
 _INV_FREQ: dict = {}

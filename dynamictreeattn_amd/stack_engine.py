@@ -125,8 +125,10 @@ class _EmbedRows(torch.autograd.Function):
 
 
 class StackWalk:
-    def __init__(self, model, token_trie, device, dtype, block_rows: int, head_chunk: int = 2048, tp_group=None, grad_budget_bytes: Optional[int] = None):
+    def __init__(self, model, token_trie, device, dtype, block_rows: int, head_chunk: int = 2048, tp_group=None, grad_budget_bytes: Optional[int] = None,
+                 longrope_long: bool = False):
         self.model, self.trie, self.dev, self.dtype = model, token_trie, device, dtype
+        self.longrope_long = longrope_long          # a longrope model: the frequency set of this walk (TreeTrainingEngine._longrope_long)
         self.block = max(int(block_rows), 1)
         self.head_chunk, self.tp_group = head_chunk, tp_group
         Hq, Hkv, D, _, _ = _cfg_of(model)
@@ -165,7 +167,7 @@ class StackWalk:
     def _hidden(self, s: int, e: int, with_grad: bool):
         pos = torch.arange(s, e, device=self.dev, dtype=torch.int32)
         return packed_hidden_states(self.model, self.tokens[s:e].clone(), pos, None, False, 0, self._attn_of_layer(s, with_grad),
-                                    embed=self.sink.embed)
+                                    embed=self.sink.embed, longrope_long=self.longrope_long)
 
     def _head(self, h, s: int, e: int, want_forks: bool, last_label: bool = True):
         """(lp_next [B], lp_fork [F], ent [B], g_fork [F]) of rows s..e-1: lp_next[r-s] = log p(tokens[r+1] | row r) with the label of

@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .model import ensure_supported, final_softcap_of, head_weight, is_gemma2, is_moe_layer, moe_geometry, packed_hidden_states
+from .model import (ensure_supported, final_softcap_of, head_weight, is_gemma2, is_glm4, is_longrope, is_moe_layer, moe_geometry, longrope_boundary,
+                    packed_hidden_states)
 from .trie import pop_block_starts
 
 __all__ = ["TreeTrainingEngine", "_get_forkpos", "packed_logprob_entropy"]
@@ -254,6 +255,7 @@ class TreeTrainingEngine:
         self.tp_group = None                             # set to a process group to split the LM-head vocabulary across it
         self._attn_keep_planned = 0
         self.stack_fp32_grads = True                     # block-wise walk: sum the blocks' parameter gradients in fp32 (False: model dtype, as the reference)
+        self.longrope_factors = "auto"                   # longrope models: "auto" (by the trie's sequence lengths) / "short" / "long"
 
     # ------------------------------------------------------------------------------------------
     def _pack(self, token_trie) -> _PackedTrie:
@@ -266,6 +268,28 @@ class TreeTrainingEngine:
         packed = _PackedTrie(token_trie, self.device, self.n_kv_heads)
         self.last_packed = packed
         return packed
+
+    def _longrope_long(self, model, token_trie) -> bool:
+        """Which frequency set of a longrope model (Phi-3 / Phi-4-mini) this call rotates by: True = long_factor.  HF decides per
+        sequence, by len > original_max_position_embeddings; the tokens of a trie share their prefix rows, so one call has one set.
+        "auto" takes it from the trie's sequence lengths on the host (no device synchronisation) and refuses a trie with sequences on
+        both sides of the boundary; "short" / "long" force one set for every call - what a sampler that fixes the set by its maximum
+        model length does.  False for every other model."""
+        if not is_longrope(model.config):
+            return False
+        how = self.longrope_factors
+        if how in ("short", "long"):
+            return how == "long"
+        if how != "auto":
+            raise ValueError(f"longrope_factors = {how!r}: 'auto', 'short' or 'long'")
+        orig = longrope_boundary(model.config)
+        lens = [int(ids.size(0)) for ids in token_trie.inputs]
+        n_long = sum(n > orig for n in lens)
+        if 0 < n_long < len(lens):
+            raise ValueError(f"this trie holds sequences on both sides of original_max_position_embeddings = {orig} ({len(lens) - n_long} up to "
+                             f"it, {n_long} longer): HF rotates the two groups by different longrope factors, and their shared prefix rows "
+                             f"cannot have both - set engine.longrope_factors to 'short' or 'long' (the set the sampler used)")
+        return n_long > 0
 
     def _should_checkpoint(self, model, T: int) -> bool:
         if self.checkpoint_layers is not None:
@@ -286,8 +310,8 @@ class TreeTrainingEngine:
     def _per_token_layer_bytes(self, model) -> int:
         """Activation bytes kept per token and layer (the mean over the layers: MoE and dense layers differ), 2-byte elements.
         Of the 10 hidden-size rows, four are what a pre-norm layer really keeps between its GEMMs: the residual stream in front of
-        each of its two norms and the two norm outputs (the projections' inputs); the rest is slack.  Gemma-2 keeps the outputs of its
-        two post-branch norms on top: 12.  An OLMo layer has no pre-branch norm outputs; it keeps the two branch outputs before their
+        each of its two norms and the two norm outputs (the projections' inputs); the rest is slack.  Gemma-2 and GLM-4 keep the outputs
+        of their two post-branch norms on top: 12.  An OLMo layer has no pre-branch norm outputs; it keeps the two branch outputs before their
         norms (ops.rms_norm_add's saved rows) and one materialised stream per branch (the projections' inputs): the same four, 10."""
         c = model.config
         D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
@@ -295,7 +319,7 @@ class TreeTrainingEngine:
         mlp = sum(_mlp_elems_per_token(c, l) for l in range(L)) / max(L, 1)
         from . import lora
         ranks = lora.rank_elems_per_token(model)        # LoRA: x·Aᵀ of every adapted projection is kept for the backward (Σr elements)
-        norms = 2 * c.hidden_size if is_gemma2(c) else 0          # Gemma-2: the outputs of the two post-branch norms are kept too
+        norms = 2 * c.hidden_size if is_gemma2(c) or is_glm4(c) else 0          # Gemma-2, GLM-4: the outputs of the two post-branch norms are kept too
         return int(2 * (10 * c.hidden_size + norms + mlp + ranks + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
 
     def _budget(self) -> Optional[int]:
@@ -338,7 +362,8 @@ class TreeTrainingEngine:
         # fp32 gradient buffers of the walk: a fifth of the budget at most (Qwen3-0.6B: 2.4 GB; 14B would need 59 GB and may not get it)
         budget = self._budget()
         walk = StackWalk(model, token_trie, self.device, self.dtype, block_rows, self.head_chunk, self.tp_group,
-                         grad_budget_bytes=0 if not self.stack_fp32_grads else (None if budget is None else budget // 5))
+                         grad_budget_bytes=0 if not self.stack_fp32_grads else (None if budget is None else budget // 5),
+                         longrope_long=self._longrope_long(model, token_trie))
         total = walk.run(loss_fn)
         self.last_mode = f"stack[{block_rows}]x{walk.n_blocks}"
         self.cur_len = 0
@@ -473,7 +498,8 @@ class TreeTrainingEngine:
 
     def _forward(self, model, token_trie):
         packed = self._pack(token_trie)
-        h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, False, meta_for_window=packed.for_window)
+        h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, False, meta_for_window=packed.for_window,
+                                 longrope_long=self._longrope_long(model, token_trie))
         lp, _ = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, False, self.head_chunk,
                                        packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model))
         for i, attach_list in enumerate(token_trie.attach_lists):
@@ -517,7 +543,7 @@ class TreeTrainingEngine:
         full = self._full_layers(model, packed.plan.T) if ckpt else 0
         kept = []
         h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, ckpt, attn_keep, None, full, kept,
-                                 meta_for_window=packed.for_window)
+                                 meta_for_window=packed.for_window, longrope_long=self._longrope_long(model, token_trie))
         if ckpt and kept:
             self.last_mode = "packed" if kept[0] >= self.n_layers else f"packed+recompute[{self.n_layers - kept[0]}/{self.n_layers}]"
         lp, ent = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, True, max(chunk, 1),

@@ -251,6 +251,21 @@ int dta_qk_norm_rope_bwd(const void* x, const void* w, const float* cos_sin, con
                          void* dx, float* dw_partial, int32_t T, int32_t NH, int32_t head_dim,
                          int64_t x_stride_t, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t,
                          int32_t dtype, void* stream);   /* dx: [T, NH, D] with dx_stride_t elements between tokens (>= NH*D); dx == dy (same strides) is allowed: in place */
+/* RoPE over the first R = rotary_dim elements of every head, no norm (Phi-3 / Phi-4-mini: partial_rotary_factor; GLM-4: interleaved
+ * pairs).  x: [T, NH, D], D = 128 or 64, rows of D contiguous, token stride x_stride_t; cos_sin: float [T, R] = {cos[R/2], sin[R/2]} of
+ * the token's depth; y: [T, NH, D] contiguous.  0 < R <= D.
+ *   pairing 0 (half-split, R % 16 == 0), i < R/2:  y[i] = x[i] c[i] - x[i+R/2] s[i],   y[i+R/2] = x[i+R/2] c[i] + x[i] s[i]
+ *   pairing 1 (interleaved, R % 8 == 0), i < R/2:  y[2i] = x[2i] c[i] - x[2i+1] s[i],  y[2i+1] = x[2i+1] c[i] + x[2i] s[i]
+ * in fp32 with one rounding to the storage type; elements R .. D-1 are copied bit for bit, and their lanes read no table entry.
+ * bwd: the rotation by the negative angle.  dy: token stride dy_stride_t, head stride dy_stride_h; dx: token stride dx_stride_t
+ * (>= NH*D); dx == dy (same strides) is allowed: a lane writes exactly the bytes it read.
+ * Refusals come in this order: DTA_EINVAL (a null pointer, T, NH or rotary_dim <= 0, pairing not 0 / 1), DTA_EUNSUPPORTED (dtype,
+ * head_dim, rotary_dim > head_dim, rotary_dim % 16 for pairing 0 / % 8 for pairing 1), DTA_EALIGN (a pointer off 16 bytes, a stride off 8
+ * elements), DTA_EINVAL (a negative token stride, dy_stride_h < head_dim, dx_stride_t < NH*D), DTA_EPRIOR. */
+int dta_rope_partial_fwd(const void* x, const float* cos_sin, void* y, int32_t T, int32_t NH, int32_t head_dim, int32_t rotary_dim,
+                         int32_t pairing, int64_t x_stride_t, int32_t dtype, void* stream);
+int dta_rope_partial_bwd(const float* cos_sin, const void* dy, void* dx, int32_t T, int32_t NH, int32_t head_dim, int32_t rotary_dim,
+                         int32_t pairing, int64_t dy_stride_t, int64_t dy_stride_h, int64_t dx_stride_t, int32_t dtype, void* stream);
 /* Projection-wide q/k RMSNorm + RoPE (OLMo-2 / OLMo-3: `q_norm(q_proj(x))` with a weight of [NH*D], then the reshape to heads and
  * rotate-half RoPE - transformers' Olmo2Attention.forward).  x: [T, NH, D] with token stride x_stride_t (q or k read in place from the
  * fused projection output); w: [NH*D]; cos_sin as above; y: [T, NH, D] contiguous; rstd: [T].  D = 64 or 128, any NH >= 1 with
