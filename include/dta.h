@@ -63,6 +63,7 @@ int dta_lcp_adjacent(const int64_t* tokens, const int64_t* starts, const int32_t
  * lcp[i] < min(len[i], len[i+1]).  Writes the kept positions (ascending) to out_leaf_pos, the
  * leaf's LCP with the next leaf to out_leaf_lcp, for every sequence the leaf it folds onto to
  * out_seq_leaf[S] (lens[S] = sequence lengths in sorted order), and the leaf count to *out_M.  One workgroup (S <= 2^20).
+ * The caller sizes out_leaf_pos for S and out_leaf_lcp for S-1 entries; M and M-1 of them are written, the rest is left untouched.
  * Replaces token_trie.py:32-49 (_leafization, second half).  */
 int dta_leafize(const int32_t* lens, const int32_t* lcp, int32_t S,
                 int32_t* out_leaf_pos, int32_t* out_leaf_lcp, int32_t* out_seq_leaf, int32_t* out_M,

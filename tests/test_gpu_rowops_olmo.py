@@ -3,8 +3,9 @@
 terms of tests/rowops_ref64.py, in bf16, f16 and fp32 storage, on rowops_ref64.rows (log-spaced row scales, an all-zero row, a
 single-element row).  Shapes: rows narrower than one wave's reach, NH no multiple of 4, 1536 (no power of two), 5120, both ways to the
 8192 limit; 1 / 3 / 5 / 37 tokens (a partial workgroup, several workgroups); the backward's second, ragged grid-stride pass; q and k in
-place from a fused [T, Hq+2Hkv, D] buffer with the gradients landing in one buffer; a frozen weight; a NaN-poisoned tail behind every
-output.  tests/test_olmo_fixture.py shows on the CPU that the bounds hold for an honest emulation and reject the per-head arithmetic.
+place from a fused [T, Hq+2Hkv, D] buffer with the gradients landing in one buffer; a frozen weight; every output a NaN-filled arena
+of tests/arena.py whose guard bands, in front and behind, must keep their bytes.  tests/test_olmo_fixture.py shows on the CPU that the
+bounds hold for an honest emulation and reject the per-head arithmetic.
 
 Each test prints its worst err / bound per output (pytest -s shows them)."""
 import json
@@ -12,6 +13,7 @@ import json
 import pytest
 import torch
 
+import arena as A
 import olmo_ref64 as OR
 import rowops_ref64 as R
 from dynamictreeattn_amd import ops
@@ -22,8 +24,7 @@ DEV = "cuda:0"
 BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 DTYPES = [BF, F16, F32]
 EPS = (1e-6, 1e-5)
-TAIL = 96                         # poisoned elements behind every output
-NAN = float("nan")
+TAIL = 96                         # guard elements in front of and behind every output
 
 
 def _merge(into, res):
@@ -35,12 +36,9 @@ def _report(name, dtype, worst):
     print(f"\nWORST {name} {str(dtype).split('.')[-1]} " + json.dumps({k: round(v, 3) for k, v in sorted(worst.items())}))
 
 
-def _poisoned(n, dtype):
-    return torch.full((n + TAIL,), NAN, dtype=dtype, device=DEV)
-
-
-def _tail_untouched(buf, n, label):
-    assert bool(torch.isnan(buf[n:]).all()), label + ": an element past the output was written"
+def _poisoned(name, n, dtype):
+    """An output arena of n elements, NaN in the payload and in the guard bands."""
+    return A.out_arena(name, (n,), dtype, "A", guard_rows=TAIL, device=DEV)
 
 
 def _inputs(T, NH, D, dtype, seed):
@@ -54,10 +52,10 @@ def _wide_fwd(x, w, cs, eps, label=""):
     """One forward entry call over x [T, NH, D] (any token stride) into poisoned buffers: (y, rstd)."""
     T, NH, D = x.shape
     n = T * NH * D
-    yb, rb = _poisoned(n, x.dtype), _poisoned(T, F32)
-    ops._launch("dta_wide_qk_norm_rope_fwd", (x, w, cs), ptr(x), ptr(w), ptr(cs), ptr(yb), ptr(rb), T, NH, D, x.stride(0), eps, ops._DT[x.dtype])
-    _tail_untouched(yb, n, label + " y"); _tail_untouched(rb, T, label + " rstd")
-    return yb[:n].view(T, NH, D), rb[:T]
+    yb, rb = _poisoned("y", n, x.dtype), _poisoned("rstd", T, F32)
+    ops._launch("dta_wide_qk_norm_rope_fwd", (x, w, cs), ptr(x), ptr(w), ptr(cs), yb.ptr(), rb.ptr(), T, NH, D, x.stride(0), eps, ops._DT[x.dtype])
+    yb.assert_guards_intact(label); rb.assert_guards_intact(label)
+    return yb.view.view(T, NH, D), rb.view
 
 
 def _wide_bwd(x, w, cs, dy, rstd, frozen=False, label=""):
@@ -65,17 +63,17 @@ def _wide_bwd(x, w, cs, dy, rstd, frozen=False, label=""):
     row the kernel owns is written in full, nothing behind it."""
     T, NH, D = x.shape
     n = NH * D
-    dxb = _poisoned(T * n, x.dtype)
-    dx = dxb[:T * n].view(T, NH, D)
+    dxb = _poisoned("dx", T * n, x.dtype)
+    dx = dxb.view.view(T, NH, D)
     blocks = lib().dta_wide_qk_norm_rope_bwd_blocks(T)
-    pb = None if frozen else _poisoned(blocks * n, F32)
-    ops._launch("dta_wide_qk_norm_rope_bwd", (x, w, cs, dy), ptr(x), ptr(w), ptr(cs), ptr(dy), ptr(rstd), ptr(dx), ptr(pb), T, NH, D,
-                x.stride(0), dy.stride(0), dy.stride(1), dx.stride(0), ops._DT[x.dtype])
-    _tail_untouched(dxb, T * n, label + " dx")
+    pb = None if frozen else _poisoned("dw_partial", blocks * n, F32)
+    ops._launch("dta_wide_qk_norm_rope_bwd", (x, w, cs, dy), ptr(x), ptr(w), ptr(cs), ptr(dy), ptr(rstd), ptr(dx), None if frozen else pb.ptr(),
+                T, NH, D, x.stride(0), dy.stride(0), dy.stride(1), dx.stride(0), ops._DT[x.dtype])
+    dxb.assert_guards_intact(label)
     if frozen:
         return dx, None
-    _tail_untouched(pb, blocks * n, label + " dw_partial")
-    part = pb[:blocks * n].view(blocks, n)
+    pb.assert_guards_intact(label)
+    part = pb.view.view(blocks, n)
     assert bool(torch.isfinite(part).all()), label + ": a row of dw_partial was left unwritten"
     return dx, ops.sum_slabs(part, w.dtype)
 
@@ -169,13 +167,14 @@ def test_qkv_prep_wide_with_the_gradients_in_one_fused_buffer(D, Hq, Hkv, dtype)
 # ------------------------------------------------------------------------------------------------ RMSNorm, then the residual add
 def _norm_add(y, w, res, eps, want_yn, label=""):
     R_, H = y.shape
-    ob, rb = _poisoned(R_ * H, y.dtype), _poisoned(R_, F32)
-    nb = _poisoned(R_ * H, y.dtype) if want_yn else None
-    ops._launch("dta_rmsnorm_add_fwd", (y, w, res), ptr(y), ptr(w), ptr(res), ptr(ob), ptr(nb), ptr(rb), R_, H, eps, ops._DT[y.dtype])
-    _tail_untouched(ob, R_ * H, label + " out"); _tail_untouched(rb, R_, label + " rstd")
+    ob, rb = _poisoned("out", R_ * H, y.dtype), _poisoned("rstd", R_, F32)
+    nb = _poisoned("yn", R_ * H, y.dtype) if want_yn else None
+    ops._launch("dta_rmsnorm_add_fwd", (y, w, res), ptr(y), ptr(w), ptr(res), ob.ptr(), nb.ptr() if want_yn else None, rb.ptr(), R_, H, eps,
+                ops._DT[y.dtype])
+    ob.assert_guards_intact(label); rb.assert_guards_intact(label)
     if want_yn:
-        _tail_untouched(nb, R_ * H, label + " yn")
-    return ob[:R_ * H].view(R_, H), (nb[:R_ * H].view(R_, H) if want_yn else None), rb[:R_]
+        nb.assert_guards_intact(label)
+    return ob.view.view(R_, H), (nb.view.view(R_, H) if want_yn else None), rb.view
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -4,7 +4,8 @@ R .. D-1 bit for bit, in bf16, f16 and fp32 storage, on rowops_ref64.rows (log-s
 row) at depths up to 131 072.  Shapes: both head dims; every rotary dimension whose partner distance is a power of two or not (48: 3
 lanes, 96: 6) and the edges R = 8 / 16 and R = D; NH 1 / 3 / 4 / 5 / 14 (one head per lane group, and four); 1 / 3 / 37 tokens (a
 partial workgroup, several); the backward's second, ragged grid-stride pass; q and k in place from a fused [T, Hq+2Hkv, D] buffer with
-the gradients in one buffer and the in-place backward; a NaN-poisoned tail behind every output.
+the gradients in one buffer and the in-place backward; every output a NaN-filled arena of tests/arena.py whose guard bands, in front and
+behind, must keep their bytes.
 tests/test_partial_rope_ref64.py shows on the CPU that the bounds hold for an honest emulation and reject four deliberate errors.
 
 Each test prints its worst err / bound per output (pytest -s shows them)."""
@@ -13,6 +14,7 @@ import json
 import pytest
 import torch
 
+import arena as A
 import partial_rope_ref64 as PR
 import rowops_ref64 as R
 from dynamictreeattn_amd import ops
@@ -22,8 +24,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 DTYPES = [BF, F16, F32]
-TAIL = 96                         # poisoned elements behind every output
-NAN = float("nan")
+TAIL = 96                         # guard elements in front of and behind every output
 HALF_SPLIT = [16, 32, 48, 64, 96, 112, 128]
 INTERLEAVED = [8, 32, 64, 120, 128]
 CASES = [(0, D, r) for D in (64, 128) for r in HALF_SPLIT if r <= D] + [(1, D, r) for D in (64, 128) for r in INTERLEAVED if r <= D]
@@ -39,12 +40,9 @@ def _report(name, dtype, worst):
     print(f"\nWORST {name} {str(dtype).split('.')[-1]} " + json.dumps({k: round(v, 3) for k, v in sorted(worst.items())}))
 
 
-def _poisoned(n, dtype):
-    return torch.full((n + TAIL,), NAN, dtype=dtype, device=DEV)
-
-
-def _tail_untouched(buf, n, label):
-    assert bool(torch.isnan(buf[n:]).all()), label + ": an element past the output was written"
+def _poisoned(name, n, dtype):
+    """An output arena of n elements, NaN in the payload and in the guard bands."""
+    return A.out_arena(name, (n,), dtype, "A", guard_rows=TAIL, device=DEV)
 
 
 def _inputs(T, NH, D, rot, dtype, seed):
@@ -57,21 +55,21 @@ def _fwd(x, cs, pairing, label=""):
     """One forward entry call over x [T, NH, D] (any token stride) into a poisoned buffer: y."""
     T, NH, D = x.shape
     n = T * NH * D
-    yb = _poisoned(n, x.dtype)
-    ops._launch("dta_rope_partial_fwd", (x, cs), ptr(x), ptr(cs), ptr(yb), T, NH, D, cs.shape[1], pairing, x.stride(0), ops._DT[x.dtype])
-    _tail_untouched(yb, n, label + " y")
-    return yb[:n].view(T, NH, D)
+    yb = _poisoned("y", n, x.dtype)
+    ops._launch("dta_rope_partial_fwd", (x, cs), ptr(x), ptr(cs), yb.ptr(), T, NH, D, cs.shape[1], pairing, x.stride(0), ops._DT[x.dtype])
+    yb.assert_guards_intact(label)
+    return yb.view.view(T, NH, D)
 
 
 def _bwd(cs, dy, pairing, label=""):
     """One backward entry call, out of place, into a poisoned buffer: dx."""
     T, NH, D = dy.shape
     n = T * NH * D
-    dxb = _poisoned(n, dy.dtype)
-    dx = dxb[:n].view(T, NH, D)
+    dxb = _poisoned("dx", n, dy.dtype)
+    dx = dxb.view.view(T, NH, D)
     ops._launch("dta_rope_partial_bwd", (cs, dy), ptr(cs), ptr(dy), ptr(dx), T, NH, D, cs.shape[1], pairing, dy.stride(0), dy.stride(1),
                 dx.stride(0), ops._DT[dy.dtype])
-    _tail_untouched(dxb, n, label + " dx")
+    dxb.assert_guards_intact(label)
     return dx
 
 
