@@ -30,6 +30,9 @@ _PROTOS = {
     "dta_rmsnorm_fwd": ([_vp] * 6 + [_i32, _i32, _f32, _f32, _i32, _vp], C.c_int),
     "dta_rmsnorm_bwd_blocks": ([_i32], C.c_int),
     "dta_rmsnorm_bwd": ([_vp] * 7 + [_i32, _i32, _f32, _i32, _vp], C.c_int),
+    "dta_layernorm_fwd": ([_vp] * 8 + [_i32, _i32, _f32, _i32, _vp], C.c_int),
+    "dta_layernorm_bwd_blocks": ([_i32], C.c_int),
+    "dta_layernorm_bwd": ([_vp] * 8 + [_i32, _i32, _i32, _vp], C.c_int),
     "dta_qk_norm_rope_fwd": ([_vp] * 5 + [_i32, _i32, _i32, _i64, _f32, _i32, _vp], C.c_int),
     "dta_qk_norm_rope_bwd_blocks": ([_i64], C.c_int),
     "dta_qk_norm_rope_bwd": ([_vp] * 7 + [_i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp], C.c_int),

@@ -1,5 +1,6 @@
 // Fused row kernels of the decoder layer for gfx950 — HBM-bound, 16-byte accesses, fp32 math.
 //   dta_rmsnorm_fwd/bwd        y = w · cast(x · rsqrt(mean(x²)+eps))                 (Qwen3RMSNorm arithmetic)
+//   dta_layernorm_fwd/bwd      y = cast(w · (x − mean(x)) · rsqrt(var(x)+eps)), x = x + delta_a + delta_b fused in   (CohereLayerNorm arithmetic)
 //   dta_qk_norm_rope_fwd/bwd   per (token, head) of 128 or 64: optional RMSNorm, then RoPE at position = trie depth
 //   dta_wide_qk_norm_rope_fwd/bwd  per token: RMSNorm over the whole [NH·D] projection row (OLMo), then RoPE per head
 //   dta_rmsnorm_add_fwd        out = res + cast(w · y · rsqrt(mean(y²)+eps)): OLMo's post-norm branch end
@@ -187,6 +188,161 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const void* __restrict
   float* out = dw_part + (int64_t)blockIdx.x * H;
 #pragma unroll
   for (int a = 0; a < NA; ++a) {                              // static register index; `a < per_lane` is block-uniform
+    if (a < per_lane) {
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[(wave * 64 + lane) * 8 + j] = acc[a][j];
+      __syncthreads();
+      if (wave == 0) {
+        const int i = lane + 64 * a;
+        if (i < nv) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) out[8 * i + j] = red[lane * 8 + j] + red[(64 + lane) * 8 + j] + red[(128 + lane) * 8 + j] + red[(192 + lane) * 8 + j];
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// LayerNorm without bias over rows of H (CohereLayerNorm; H % 8 == 0, H <= 8192 = 512·NA).  One wave per row, 4 rows per workgroup,
+// grid-stride.  The row stays in registers for three passes: Σx -> m, Σ(x-m)² -> r (the centred form: E[x²]-m² in fp32 loses rstd to
+// cancellation on rows with a common offset), then y = cast(w·((x-m)·r)) with ONE rounding.  x is read once, y written once.
+// da / db: the pending branch outputs of the parallel block, x_out = cast((x + da) + db) summed in fp32 and rounded once; db may be null.
+// ---------------------------------------------------------------------------------------------
+template <int DT, int NA>
+__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const void* __restrict__ x_, const void* __restrict__ da_, const void* __restrict__ db_,
+                                                            const void* __restrict__ w_, void* __restrict__ xout_, void* __restrict__ y_,
+                                                            float* __restrict__ mean, float* __restrict__ rstd, int R, int H, float eps) {
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const e* w = reinterpret_cast<const e*>(w_);
+  const int nv = H >> 3;
+  const float inv_h = 1.f / (float)H;
+  for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
+    const e* x = reinterpret_cast<const e*>(x_) + (int64_t)row * H;
+    const e* da = da_ ? reinterpret_cast<const e*>(da_) + (int64_t)row * H : nullptr;
+    const e* db = db_ ? reinterpret_cast<const e*>(db_) + (int64_t)row * H : nullptr;
+    e* xo = da_ ? reinterpret_cast<e*>(xout_) + (int64_t)row * H : nullptr;
+    e* y = reinterpret_cast<e*>(y_) + (int64_t)row * H;
+    v8 keep[NA];
+    float s = 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int i = lane + 64 * a;
+      if (i < nv) {
+        v8 v = *reinterpret_cast<const v8*>(x + 8 * i);
+        if (da) {
+          const v8 d = *reinterpret_cast<const v8*>(da + 8 * i);
+          if (db) {
+            const v8 d2 = *reinterpret_cast<const v8*>(db + 8 * i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (e)(((float)v[j] + (float)d[j]) + (float)d2[j]);
+          } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (e)((float)v[j] + (float)d[j]);
+          }
+          *reinterpret_cast<v8*>(xo + 8 * i) = v;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += (float)v[j];
+        keep[a] = v;
+      }
+    }
+    const float m = wave_sum(s) * inv_h;
+    float q = 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      if (lane + 64 * a < nv) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float c = (float)keep[a][j] - m; q = __builtin_fmaf(c, c, q); }
+      }
+    }
+    const float r = __builtin_amdgcn_rsqf(wave_sum(q) * inv_h + eps);
+    if (lane == 0) { mean[row] = m; rstd[row] = r; }
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int i = lane + 64 * a;
+      if (i < nv) {
+        const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
+        v8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (e)((float)wv[j] * (((float)keep[a][j] - m) * r));
+        *reinterpret_cast<v8*>(y + 8 * i) = o;
+      }
+    }
+  }
+}
+
+// t = (x-m)·r, g = dy·w:  dx = r·(g − mean(g) − t·mean(g·t)) + dres ;  dw partial per workgroup: Σ_rows dy·t.  NA and KEEP as
+// rmsnorm_bwd_kernel; the dw partials leave through the same LDS reduction, so the workspace has dta_layernorm_bwd_blocks(R) rows.
+template <int DT, int NA>
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restrict__ x_, const void* __restrict__ w_, const void* __restrict__ dy_,
+                                                            const void* __restrict__ dres_, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, void* __restrict__ dx_, float* __restrict__ dw_part,
+                                                            int R, int H) {
+  using e = typename Ty<DT>::e; using v8 = typename Ty<DT>::v8;
+  __shared__ float red[4 * 64 * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const e* w = reinterpret_cast<const e*>(w_);
+  const int nv = H >> 3;
+  const int per_lane = (nv + 63) >> 6;                      // <= NA
+  const float inv_h = 1.f / (float)H;
+  constexpr bool KEEP = NA * sizeof(v8) <= 128;
+  float acc[NA][8];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[a][j] = 0.f;
+  for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
+    const e* x = reinterpret_cast<const e*>(x_) + (int64_t)row * H;
+    const e* dy = reinterpret_cast<const e*>(dy_) + (int64_t)row * H;
+    e* dx = reinterpret_cast<e*>(dx_) + (int64_t)row * H;
+    const float m = mean[row], r = rstd[row];
+    float sg = 0.f, sgt = 0.f;
+    v8 kx[KEEP ? NA : 1], kg[KEEP ? NA : 1];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int i = lane + 64 * a;
+      if (a < per_lane && i < nv) {
+        const v8 v = DTA_SAVED_LOAD(reinterpret_cast<const v8*>(x + 8 * i)); const v8 g = *reinterpret_cast<const v8*>(dy + 8 * i);
+        const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float t = ((float)v[j] - m) * r; const float gg = (float)g[j]; const float gw = gg * (float)wv[j];
+          sg += gw; sgt = __builtin_fmaf(gw, t, sgt); acc[a][j] = __builtin_fmaf(gg, t, acc[a][j]);
+        }
+        if constexpr (KEEP) { kx[a] = v; kg[a] = g; }
+      }
+    }
+    sg = wave_sum(sg) * inv_h; sgt = wave_sum(sgt) * inv_h;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int i = lane + 64 * a;
+      if (a < per_lane && i < nv) {
+        v8 v, g;
+        if constexpr (KEEP) { v = kx[a]; g = kg[a]; }
+        else { v = *reinterpret_cast<const v8*>(x + 8 * i); g = *reinterpret_cast<const v8*>(dy + 8 * i); }
+        const v8 wv = *reinterpret_cast<const v8*>(w + 8 * i);
+        // the gradient on the residual stream joins here; both deltas share this dx.  ONE expression for both forms (dres NULL adds a
+        // zero), so that a NULL dres and a dres of zeros give the same bits whatever the compiler fuses
+        v8 dr;
+        if (dres_) dr = *reinterpret_cast<const v8*>(reinterpret_cast<const e*>(dres_) + (int64_t)row * H + 8 * i);
+        else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dr[j] = (e)0.f;
+        }
+        v8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float t = ((float)v[j] - m) * r; o[j] = (e)(r * (((float)g[j] * (float)wv[j] - sg) - t * sgt) + (float)dr[j]); }
+        *reinterpret_cast<v8*>(dx + 8 * i) = o;
+      }
+    }
+  }
+  if (!dw_part) return;                                       // frozen weight: no partials wanted (block-uniform)
+  float* out = dw_part + (int64_t)blockIdx.x * H;
+#pragma unroll
+  for (int a = 0; a < NA; ++a) {
     if (a < per_lane) {
       __syncthreads();
 #pragma unroll
@@ -942,6 +1098,52 @@ extern "C" int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, con
     dta_storage_type(dtype, [&](auto dt) {
       hipLaunchKernelGGL((rmsnorm_bwd_kernel<decltype(dt)::value, decltype(na)::value, decltype(off)::value>), grid, block, 0, st_,
                          x, w, dy, dres, rstd, dx, dw_partial, R, H, w_offset);
+    });
+  });
+  return DTA_LAUNCH_STATUS();
+}
+
+namespace {
+// The kernel form of a LayerNorm call, the same in both directions: f(NA) with NA 16-byte groups per lane for rows of up to 1 024 / 2 048 /
+// 4 096 / 8 192 elements
+template <class F> inline void ln_form(int H, F&& f) {
+  if (H <= 1024) f(Int<2>{}); else if (H <= 2048) f(Int<4>{}); else if (H <= 4096) f(Int<8>{}); else f(Int<16>{});
+}
+}  // namespace
+
+extern "C" int dta_layernorm_fwd(const void* x, const void* delta_a, const void* delta_b, const void* w, void* x_out, void* y,
+                                 float* mean, float* rstd, int32_t R, int32_t H, float eps, int32_t dtype, void* stream) {
+  if (!x || !w || !y || !mean || !rstd || R <= 0 || H <= 0 || (delta_b && !delta_a) || ((delta_a != nullptr) != (x_out != nullptr)) || eps != eps)
+    return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || H % 8 || H > 8192) return DTA_EUNSUPPORTED;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (delta_a && (!aligned16(delta_a) || !aligned16(x_out))) || (delta_b && !aligned16(delta_b)))
+    return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const dim3 grid(row_blocks(R, 4, 8192)), block(256);
+  ln_form(H, [&](auto na) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((layernorm_fwd_kernel<decltype(dt)::value, decltype(na)::value>), grid, block, 0, st_,
+                         x, delta_a, delta_b, w, x_out, y, mean, rstd, R, H, eps);
+    });
+  });
+  return DTA_LAUNCH_STATUS();
+}
+
+/* dw_partial: float [dta_layernorm_bwd_blocks(R), H]; the caller sums it over dim 0.  NULL: the weight needs no gradient, dx only. */
+extern "C" int dta_layernorm_bwd_blocks(int32_t R) { return row_blocks(R, 4, 2048); }
+extern "C" int dta_layernorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* mean, const float* rstd,
+                                 void* dx, float* dw_partial, int32_t R, int32_t H, int32_t dtype, void* stream) {
+  if (!x || !w || !dy || !mean || !rstd || !dx || R <= 0 || H <= 0) return DTA_EINVAL;
+  if (!row_dtype_ok(dtype) || H % 8 || H > 8192) return DTA_EUNSUPPORTED;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(dy) || !aligned16(dx) || (dres && !aligned16(dres))) return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const dim3 grid(row_blocks(R, 4, 2048)), block(256);
+  ln_form(H, [&](auto na) {
+    dta_storage_type(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(dt)::value, decltype(na)::value>), grid, block, 0, st_,
+                         x, w, dy, dres, mean, rstd, dx, dw_partial, R, H);
     });
   });
   return DTA_LAUNCH_STATUS();

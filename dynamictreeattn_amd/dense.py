@@ -8,7 +8,7 @@ from typing import List
 import torch
 
 from . import ops
-from .model import ensure_supported, final_softcap_of, head_weight, is_longrope, longrope_boundary, packed_hidden_states
+from .model import ensure_supported, final_softcap_of, head_weight, is_longrope, logit_scale_of, longrope_boundary, packed_hidden_states
 from .tree_training_engine import packed_logprob_entropy
 
 
@@ -19,7 +19,7 @@ def _one(model, ids: torch.Tensor, want_entropy: bool, checkpoint_layers: bool):
     long = is_longrope(model.config) and n > longrope_boundary(model.config)
     h = packed_hidden_states(model, ids, depth, ops.stack_meta(0), checkpoint_layers, longrope_long=long)
     parent = depth.to(torch.long) - 1
-    return packed_logprob_entropy(h, head_weight(model), ids, parent, want_entropy, softcap=final_softcap_of(model))
+    return packed_logprob_entropy(h, head_weight(model), ids, parent, want_entropy, softcap=final_softcap_of(model), logit_scale=logit_scale_of(model))
 
 
 @torch.no_grad()

@@ -7,7 +7,7 @@ torch.  `Qwen3TreeLM` mirrors the HF module/parameter tree (``model.embed_tokens
 ``model.layers.N.self_attn.q_proj.weight`` …, tied head) so that
 
 * gradients compare name by name with grad/Qwen3-0.6B-TB-vs-DB-bf16.txt (310 tensors), and
-* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral/Gemma-2/OLMo-2/OLMo-3/Phi-3/Phi-4/GLM-4 ``*ForCausalLM`` by duck typing —
+* `packed_hidden_states` also accepts a HuggingFace Qwen2/Qwen3/Qwen3-MoE/Llama/Mistral/Mixtral/Gemma-2/OLMo-2/OLMo-3/Phi-3/Phi-4/GLM-4/Cohere/Cohere2 ``*ForCausalLM`` by duck typing —
   its own ``nn.Parameter`` objects are used, so ``param.grad`` lands where the training loop expects.
 """
 from __future__ import annotations
@@ -39,7 +39,8 @@ class _Attn(nn.Module):
         super().__init__()
         H, Hq, Hkv, D = c.hidden_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim
         self.q_proj, self.k_proj, self.v_proj, self.o_proj = _Lin(H, Hq * D), _Lin(H, Hkv * D), _Lin(H, Hkv * D), _Lin(Hq * D, H)
-        self.q_norm, self.k_norm = _Norm(D), _Norm(D)
+        if not is_cohere(c):                                  # (the supported Cohere models have no q/k norm)
+            self.q_norm, self.k_norm = _Norm(D), _Norm(D)
 
 
 class _MLP(nn.Module):
@@ -94,7 +95,9 @@ class _Layer(nn.Module):
     def __init__(self, c, l=0):
         super().__init__()
         self.self_attn, self.mlp = _Attn(c), (_MoE(c) if is_moe_layer(c, l) else _MLP(c))
-        self.input_layernorm, self.post_attention_layernorm = _Norm(c.hidden_size), _Norm(c.hidden_size)
+        self.input_layernorm = _Norm(c.hidden_size)
+        if not is_cohere(c):                                  # Cohere's parallel block has one norm per layer
+            self.post_attention_layernorm = _Norm(c.hidden_size)
 
 
 class _Body(nn.Module):
@@ -107,7 +110,8 @@ class _Body(nn.Module):
 
 def make_config(d: dict) -> SimpleNamespace:
     """Configuration of a Qwen3TreeLM from a dict of HF field names.  `rope_parameters` is the dict HF configurations keep
-    (rope_type default / linear / llama3 / yarn with the type's fields; its rope_theta goes before the top-level one)."""
+    (rope_type default / linear / llama3 / yarn with the type's fields; its rope_theta goes before the top-level one).
+    model_type "cohere" / "cohere2" builds the Cohere parameter tree: one LayerNorm weight per layer, no q/k norms."""
     c = SimpleNamespace(**d)
     if not hasattr(c, "head_dim"):
         c.head_dim = c.hidden_size // c.num_attention_heads
@@ -146,6 +150,19 @@ def is_olmo(config) -> bool:
     """OLMo-2 / OLMo-3 arithmetic (q/k RMSNorm over the whole projection row before RoPE, and the post-norm layer
     h = x + norm(attn(x)), y = h + norm(mlp(h))) is keyed on config.model_type in ("olmo2", "olmo3") and on nothing else."""
     return getattr(config, "model_type", None) in ("olmo2", "olmo3")
+
+
+def is_cohere(config) -> bool:
+    """Cohere / Cohere2 arithmetic (mean-centred LayerNorm without bias, the parallel block x + attn(h) + mlp(h) behind ONE norm,
+    interleaved RoPE pairs over the whole head, a scale on the final logits and, for cohere2, full-attention layers without RoPE) is
+    keyed on config.model_type in ("cohere", "cohere2") and on nothing else."""
+    return getattr(config, "model_type", None) in ("cohere", "cohere2")
+
+
+def logit_scale_of(model) -> float:
+    """The factor on the final logits the LM-head kernels apply for `model` as their temperature 1 / scale: config.logit_scale of a
+    Cohere model, 1.0 for every other (their head runs bit for bit as without it)."""
+    return float(model.config.logit_scale) if is_cohere(model.config) else 1.0
 
 
 def is_phi3(config) -> bool:
@@ -294,6 +311,35 @@ def _check_olmo(c) -> None:
                              f"one row of at most 8192 elements")
 
 
+def _check_cohere(c) -> None:
+    """cohere / cohere2: what the LayerNorm kernel, the attention kernels and the head's temperature take."""
+    mt, D, H = c.model_type, _head_dim(c), c.hidden_size
+    if D not in (64, 128):
+        raise ValueError(f"config.head_dim = {D} is not supported for {mt}: the attention and RoPE kernels cover head_dim 64 and 128")
+    if H % 8 or H > 8192:
+        raise ValueError(f"config.hidden_size = {H} is not supported for {mt}: the LayerNorm kernel holds one row of a multiple of 8 and at "
+                         f"most 8192 elements (Command-R+ and Command-A are wider)")
+    if getattr(c, "use_qk_norm", False):
+        raise ValueError(f"config.use_qk_norm = True is not supported for {mt} (Command-R+): there is no per-head LayerNorm kernel")
+    ls = getattr(c, "logit_scale", None)
+    if isinstance(ls, bool) or not isinstance(ls, (int, float)) or not 0.0 < float(ls) < float("inf"):
+        raise ValueError(f"config.logit_scale = {ls!r} is not supported for {mt}: the head scales its logits by a finite number > 0")
+    act = getattr(c, "hidden_act", None)
+    if act != "silu":
+        raise ValueError(f"config.hidden_act = {act!r} is not supported for {mt}: the MLP kernels compute silu(gate) * up")
+    if mt == "cohere2":
+        types = getattr(c, "layer_types", None)
+        if not types or len(types) != c.num_hidden_layers:
+            raise ValueError(f"config.layer_types has {len(types or [])} entries for {c.num_hidden_layers} layers: a cohere2 layer rotates "
+                             f"(sliding_attention) or not (full_attention) by its type")
+        for t in types:
+            if t not in ("full_attention", "sliding_attention"):
+                raise ValueError(f"config.layer_types entry {t!r} is not supported for cohere2 (full_attention / sliding_attention)")
+        W = getattr(c, "sliding_window", None)
+        if "sliding_attention" in types and not (isinstance(W, int) and not isinstance(W, bool) and W > 0):
+            raise ValueError(f"config.sliding_window = {W!r} is not supported for cohere2: a sliding_attention layer needs its window")
+
+
 def _check_partial_rope(c, training: bool) -> None:
     """phi3 / glm4: the head_dim and rotary_dim the partial RoPE kernels take, longrope's lists (phi3 only), Phi-3's dropouts."""
     mt, D = c.model_type, _head_dim(c)
@@ -332,7 +378,10 @@ def check_supported(config, training: bool = True) -> None:
     whose rotary_dim is a multiple of 16 (phi3, half-split pairs) or 8 (glm4, interleaved pairs) and at most head_dim is honoured, and
     on phi3 alone rope_type longrope with short_factor and long_factor of rotary_dim / 2 entries and original_max_position_embeddings.
     Refused there: a head_dim other than 64 / 128 (Phi-3-mini's 96), any other rotary_dim, resid_pdrop or embd_pdrop above 0 on a model
-    in training mode, longrope on glm4."""
+    in training mode, longrope on glm4.
+    A Cohere / Cohere2 configuration (is_cohere) needs head_dim 64 / 128, hidden_size a multiple of 8 and at most 8192, use_qk_norm off,
+    a finite logit_scale > 0 and hidden_act silu; for cohere2, layer_types of full_attention / sliding_attention, one per layer, and a
+    sliding_window wherever a layer slides.  attention_bias is honoured."""
     c = config
     gemma = is_gemma2(c)
     partial = is_phi3(c) or is_glm4(c)
@@ -344,6 +393,8 @@ def check_supported(config, training: bool = True) -> None:
         raise ValueError("config.model_type = 'olmo' (OLMo-1: LayerNorm without weights, clip_qkv) is not supported; olmo2 and olmo3 are")
     if is_olmo(c):
         _check_olmo(c)
+    if is_cohere(c):
+        _check_cohere(c)
     for lt in rope_layer_types(c) or [None]:
         rp = _rope_dict(c, lt)
         if rp["rope_type"] not in ops.ROPE_TYPES and not (is_phi3(c) and rp["rope_type"] == "longrope"):
@@ -404,7 +455,8 @@ def _cfg_of(model, longrope_long=False):
     D = _head_dim(c)
     types = rope_layer_types(c)                  # olmo3: one resolved pair per layer, by the layer's type
     rope = (rope_of(c, long=True) if longrope_long else rope_of(c)) if types is None else [rope_of(c, t) for t in c.layer_types]
-    return c.num_attention_heads, c.num_key_value_heads, D, float(getattr(c, "rms_norm_eps", 1e-6)), rope
+    eps = getattr(c, "layer_norm_eps", 1e-5) if is_cohere(c) else getattr(c, "rms_norm_eps", 1e-6)      # Cohere's norm keeps its own field
+    return c.num_attention_heads, c.num_key_value_heads, D, float(eps), rope
 
 
 def _windows_of(model):
@@ -547,6 +599,22 @@ def _glm4_layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     return res, ops.rms_norm(_project(act, m.down_proj), layer.post_mlp_layernorm.weight, eps)
 
 
+def _cohere_layer_forward(layer, res, delta_a, delta_b, cos_sin, attn, Hq, Hkv, D, eps):
+    """One Cohere / Cohere2 decoder layer: the parallel block out = x + attn(h) + mlp(h) behind ONE LayerNorm h = LN(x).  The stream
+    travels with TWO pending updates - the previous layer's branch outputs - which ops.add_layer_norm joins to it inside the norm's
+    pass (x + delta_a + delta_b in fp32, one rounding), so no stand-alone add runs; the layer hands on (x, attn(h), mlp(h)).
+    cos_sin [T, D]: interleaved RoPE pairs over the whole head; None: a cohere2 full-attention layer, which does not rotate - q and k
+    are the projection's values bit for bit."""
+    T = res.shape[0]
+    a, m = layer.self_attn, layer.mlp
+    res, h = ops.add_layer_norm(res, delta_a, delta_b, layer.input_layernorm.weight, eps)
+    qkv = _project(h, a.q_proj, a.k_proj, a.v_proj).view(T, Hq + 2 * Hkv, D)
+    q, k, v = ops.qkv_prep_nope(qkv, Hq, Hkv) if cos_sin is None else ops.qkv_prep_partial(qkv, cos_sin, Hq, Hkv, True)
+    o = attn(q, k, v)
+    act = ops.swiglu_fused(_project(h, m.gate_proj, m.up_proj))
+    return res, _project(o.reshape(T, Hq * D), a.o_proj), _project(act, m.down_proj)
+
+
 def _layer_forward(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps):
     """One decoder layer over the packed rows.  The hidden state enters as (residual stream, pending update)
     so that each residual add is fused into the RMSNorm that follows it.  hipBLASLt GEMMs through torch;
@@ -605,36 +673,37 @@ class _LayerRecompute(torch.autograd.Function):
     `.grad` directly (nested autograd), input gradients are returned."""
 
     @staticmethod
-    def forward(ctx, fn, keep_attn, res, delta):
-        ctx.fn, ctx.has_delta = fn, delta is not None
+    def forward(ctx, fn, keep_attn, res, *deltas):
+        # deltas: the pending update of the stream (None behind the embedding or an OLMo layer), or the two of a Cohere layer; the
+        # layer returns the stream and as many
+        ctx.fn, ctx.has_delta = fn, tuple(d is not None for d in deltas)
         items = []
         with torch.no_grad():
             if keep_attn:
                 with ops.AttentionTape("record", items):
-                    out = fn(res, delta)
+                    out = fn(res, *deltas)
             else:
-                out = fn(res, delta)
+                out = fn(res, *deltas)
         ctx.items = items
-        ctx.save_for_backward(res, delta if delta is not None else res)
+        ctx.save_for_backward(res, *(d for d in deltas if d is not None))
         return out
 
     @staticmethod
-    def backward(ctx, g_res, g_delta):
-        res, delta = ctx.saved_tensors
+    def backward(ctx, g_res, *g_deltas):
+        res, *kept = ctx.saved_tensors
         r = res.detach().requires_grad_(True)
-        d = delta.detach().requires_grad_(True) if ctx.has_delta else None
+        kept = iter(kept)
+        ds = [next(kept).detach().requires_grad_(True) if has else None for has in ctx.has_delta]
         with torch.enable_grad():
             if ctx.items:
                 with ops.AttentionTape("replay", ctx.items):
-                    o_res, o_delta = ctx.fn(r, d)
+                    outs = ctx.fn(r, *ds)
             else:
-                o_res, o_delta = ctx.fn(r, d)
+                outs = ctx.fn(r, *ds)
         ctx.items = None
-        if o_delta is None:                  # a layer that leaves no pending update (OLMo)
-            torch.autograd.backward((o_res,), (g_res,))
-        else:
-            torch.autograd.backward((o_res, o_delta), (g_res, g_delta))
-        return None, None, r.grad, (d.grad if d is not None else None)
+        live = [(o, g) for o, g in zip(outs, (g_res, *g_deltas)) if o is not None]      # (a layer that leaves no pending update: OLMo)
+        torch.autograd.backward(tuple(o for o, _ in live), tuple(g for _, g in live))
+        return (None, None, r.grad, *(d.grad if d is not None else None for d in ds))
 
 
 def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta, checkpoint_layers: bool = False,
@@ -654,11 +723,13 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
     metas = layer_metas(meta, _windows_of(model), meta_for_window) if attn_of_layer is None else None
     body = model.model
     gemma = is_gemma2(model.config)
+    cohere = is_cohere(model.config)
     layer_fwd = (_gemma2_layer_forward if gemma else _olmo_layer_forward if is_olmo(model.config) else _phi3_layer_forward if is_phi3(model.config)
-                 else _glm4_layer_forward if is_glm4(model.config) else _layer_forward)
+                 else _glm4_layer_forward if is_glm4(model.config) else _cohere_layer_forward if cohere else _layer_forward)
     R = rotary_dim(model.config) if is_phi3(model.config) or is_glm4(model.config) else D          # the table's width: the rotary dimension
     akw = attn_args_of(model)
-    res, delta = (embed(tokens) if embed is not None else F.embedding(tokens, body.embed_tokens.weight)), None
+    res = embed(tokens) if embed is not None else F.embedding(tokens, body.embed_tokens.weight)
+    deltas = (None, None) if cohere else (None,)         # the pending update(s) of the stream: a Cohere layer leaves its two branch outputs
     if gemma:            # the normaliser, rounded to the model dtype as HF does; on the embed= path too, so the fp32 sink gets the scaled gradient
         res = _ScaleRows.apply(res, float(model.config.hidden_size) ** 0.5)
     if isinstance(rope, list):           # olmo3: one table per distinct parameter set (rope_of returns one pair object per set)
@@ -666,6 +737,8 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
         cos_sins = [tables[id(r_)] for r_ in rope]
     else:
         cos_sins = [ops.rope_cos_sin(depth, R, rope)] * len(body.layers)
+    if cohere and model.config.model_type == "cohere2":                   # NoPE: a full-attention layer gets no table
+        cos_sins = [cs if t == "sliding_attention" else None for cs, t in zip(cos_sins, model.config.layer_types)]
     per_layer = tokens.shape[0] * Hq * (D * res.element_size() + 4)             # out + lse of one layer
     n_full = full_layers if isinstance(full_layers, int) else 1
     for li, layer in enumerate(body.layers):
@@ -673,22 +746,24 @@ def packed_hidden_states(model, tokens: torch.Tensor, depth: torch.Tensor, meta,
         attn = attn_of_layer(li) if attn_of_layer is not None else (lambda m_: lambda q, k, v: ops.tree_attention(q, k, v, m_, **akw))(metas[li])
         if li == 0 and callable(full_layers) and checkpoint_layers and torch.is_grad_enabled() and res.is_cuda:
             m0 = torch.cuda.memory_allocated(res.device)
-            res, delta = layer_fwd(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)
+            res, *deltas = layer_fwd(layer, res, *deltas, cos_sin, attn, Hq, Hkv, D, eps)
             n_full = int(full_layers(torch.cuda.memory_allocated(res.device) - m0))
             continue
         # (a layer whose input carries no gradient - the first one behind a frozen embedding, LoRA - runs in full: a recomputed layer
         # whose inputs need no gradient would be cut out of the graph, and its adapters with it)
-        if checkpoint_layers and li >= n_full and torch.is_grad_enabled() and (res.requires_grad or (delta is not None and delta.requires_grad)):
+        if checkpoint_layers and li >= n_full and torch.is_grad_enabled() and (res.requires_grad or any(d is not None and d.requires_grad for d in deltas)):
             keep = attn_of_layer is None and attn_keep_bytes >= per_layer
             if keep:
                 attn_keep_bytes -= per_layer
-            fn = (lambda layer_, attn_, cs_: lambda r_, d_: layer_fwd(layer_, r_, d_, cs_, attn_, Hq, Hkv, D, eps))(layer, attn, cos_sin)
-            res, delta = _LayerRecompute.apply(fn, keep, res, delta)
+            fn = (lambda layer_, attn_, cs_: lambda r_, *d_: layer_fwd(layer_, r_, *d_, cs_, attn_, Hq, Hkv, D, eps))(layer, attn, cos_sin)
+            res, *deltas = _LayerRecompute.apply(fn, keep, res, *deltas)
         else:
-            res, delta = layer_fwd(layer, res, delta, cos_sin, attn, Hq, Hkv, D, eps)
+            res, *deltas = layer_fwd(layer, res, *deltas, cos_sin, attn, Hq, Hkv, D, eps)
     if kept_out is not None:
         kept_out.append(n_full if checkpoint_layers else len(body.layers))
-    return ops.add_rms_norm(res, delta, body.norm.weight, eps, *((1.0,) if gemma else ()))[1]
+    if cohere:                           # the last layer's two branch outputs join the stream inside the final norm
+        return ops.add_layer_norm(res, *deltas, body.norm.weight, eps)[1]
+    return ops.add_rms_norm(res, deltas[0], body.norm.weight, eps, *((1.0,) if gemma else ()))[1]
 
 
 def head_weight(model) -> torch.Tensor:

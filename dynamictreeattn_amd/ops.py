@@ -440,7 +440,8 @@ class _HeadRows(torch.autograd.Function):
     chunk and the hidden-state gradient is summed across the group while the weight-gradient GEMM runs."""
 
     @staticmethod
-    def forward(ctx, h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes, tp_group, vocab_offset, softcap=0.0):
+    def forward(ctx, h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes, tp_group, vocab_offset, softcap=0.0,
+                temperature=1.0):
         T = h.shape[0]
         dev = h.device
         V = W.shape[0]
@@ -461,11 +462,11 @@ class _HeadRows(torch.autograd.Function):
             b = min(a + step, T)
             logits = torch.mm(h[a:b], W.t())
             if tp_group is None:
-                l, e, p = logprob_entropy_fwd_raw(logits, next_loc[a:b], want_entropy, 1.0,
+                l, e, p = logprob_entropy_fwd_raw(logits, next_loc[a:b], want_entropy, temperature,
                                                   xp[a:b + 1] if F_ else None, fork_loc if F_ else None, lp_fork if F_ else None, softcap)
             else:
                 f0, f1 = (0, F_) if keep else (fork_bounds[ci], fork_bounds[ci + 1])
-                stats = logprob_entropy_shard_stats_raw(logits, next_loc[a:b], 1.0, xp[a:b + 1] if F_ else None, fork_loc if F_ else None,
+                stats = logprob_entropy_shard_stats_raw(logits, next_loc[a:b], temperature, xp[a:b + 1] if F_ else None, fork_loc if F_ else None,
                                                         lp_fork if F_ else None, softcap)
                 l, e, picked, raw = combine_shard_stats(stats, lp_fork[f0:f1], tp_group)
                 p = picked - l
@@ -478,6 +479,7 @@ class _HeadRows(torch.autograd.Function):
                 kept = logits
         ctx.save_for_backward(h, W, next_loc, fork_loc, lse, ent if ent is not None else lse, xp if F_ else lse)
         ctx.kept, ctx.chunk, ctx.want_entropy, ctx.tp_group, ctx.has_forks, ctx.softcap = kept, chunk, want_entropy, tp_group, bool(F_), softcap
+        ctx.temperature = temperature
         return lp_next, lp_fork, (ent if want_entropy else lse.new_zeros(0))
 
     @staticmethod
@@ -497,7 +499,7 @@ class _HeadRows(torch.autograd.Function):
             b = min(a + step, T)
             logits = kept if kept is not None else torch.mm(h[a:b], W.t())
             logprob_entropy_bwd_raw(logits, next_loc[a:b], lse[a:b], ent[a:b] if ctx.want_entropy else None, g_next[a:b],
-                                    g_ent[a:b] if ctx.want_entropy else None, 1.0,
+                                    g_ent[a:b] if ctx.want_entropy else None, ctx.temperature,
                                     xp[a:b + 1] if ctx.has_forks else None, fork_loc if ctx.has_forks else None, g_fork, softcap=ctx.softcap)
             if W.dtype in (torch.bfloat16, torch.float16) and (b - a) >= 4096 and W.shape[0] % 8 == 0 and W.shape[1] % 8 == 0:
                 torch.mm(logits, _TransposedWeights.get(W).t(), out=dh[a:b])        # contraction index contiguous in both operands (see _dgrad)
@@ -517,20 +519,25 @@ class _HeadRows(torch.autograd.Function):
         ctx.kept = None
         for w in pending:
             w.wait()
-        return dh, (dW.to(W.dtype) if need_w else None), None, None, None, None, None, None, None, None, None, None, None
+        return dh, (dW.to(W.dtype) if need_w else None), None, None, None, None, None, None, None, None, None, None, None, None
 
 
 MAX_CAPPED_PICKS_PER_ROW = 2048     # dta.h: extra picks of one row in the in-place backward of the capped log-prob kernel
 
 
 def lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes=None, tp_group=None, vocab_offset=0,
-                 softcap: float = 0.0, max_picks_per_row: Optional[int] = None):
+                 softcap: float = 0.0, max_picks_per_row: Optional[int] = None, temperature: float = 1.0):
     """See _HeadRows.  `fork_ptr` int32 [T+1]: CSR of the forks over the rows; `fork_rows` int64 [F] their rows (ascending);
     `fork_bounds[c] .. fork_bounds[c+1]` = the forks whose row lies in chunk c (host list; used by the vocabulary-split path).
     softcap > 0: final-logit soft-capping - every statistic is taken on softcap * tanh(logit / softcap), inside the kernels (the
     [chunk, V] logits get no extra pass).  `max_picks_per_row`: the largest number of forks on one row, from the caller's host tables;
-    it is checked against the capped kernel's limit (None: unknown - beyond the limit the kernel writes NaN for the pick, dta.h)."""
+    it is checked against the capped kernel's limit (None: unknown - beyond the limit the kernel writes NaN for the pick, dta.h).
+    `temperature`: every statistic is taken on logit / temperature, inside the kernels (a model with a logit scale s passes 1 / s:
+    model.logit_scale_of); 1.0 is the plain head."""
     _require_cuda(h, W)
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError(f"temperature must be a finite number > 0 (got {temperature!r})")
     softcap = _cap_of(softcap)
     if softcap > 0 and max_picks_per_row is not None and max_picks_per_row > MAX_CAPPED_PICKS_PER_ROW:
         raise ValueError(f"a row with {max_picks_per_row} fork picks exceeds the capped log-prob kernel's {MAX_CAPPED_PICKS_PER_ROW} per row")
@@ -544,7 +551,7 @@ def lm_head_rows(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, wan
         dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=tp_group)
         keep_bytes = (1 << 62) if int(ok.item()) else 0
     lp_next, lp_fork, ent = _HeadRows.apply(h, W, next_tok, fork_ptr, fork_tok, fork_rows, fork_bounds, want_entropy, chunk, keep_bytes,
-                                            tp_group, vocab_offset, softcap)
+                                            tp_group, vocab_offset, softcap, temperature)
     return lp_next, lp_fork, (ent if want_entropy else None)
 
 
@@ -669,6 +676,91 @@ def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float, w_offset: float = 0.0
 def add_rms_norm(x: torch.Tensor, delta: Optional[torch.Tensor], w: torch.Tensor, eps: float, w_offset: float = 0.0):
     """Residual-stream update fused with the following RMSNorm: returns (x + delta, rmsnorm(x + delta) * (w_offset + w))."""
     return _RMSNorm.apply(x, delta, w, eps, float(w_offset))
+
+
+class _LayerNorm(torch.autograd.Function):
+    """(x_out, y) = (x + delta_a + delta_b, LN(x_out) * w) without bias (CohereLayerNorm): mean-centred, the weight multiplied in fp32
+    and one rounding.  delta_b needs delta_a; without deltas x_out is x itself.  Both deltas and x share the one input gradient."""
+
+    @staticmethod
+    def forward(ctx, x, delta_a, delta_b, w, eps):
+        _require_cuda(x, w)
+        if delta_b is not None and delta_a is None:
+            raise ValueError("layer norm: delta_b without delta_a")
+        x2 = x.contiguous().view(-1, x.shape[-1])
+        R, H = x2.shape
+        y = torch.empty_like(x2)
+        mean = torch.empty(R, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(R, dtype=torch.float32, device=x.device)
+        a2 = delta_a.contiguous().view(R, H) if delta_a is not None else None
+        b2 = delta_b.contiguous().view(R, H) if delta_b is not None else None
+        xo = torch.empty_like(x2) if a2 is not None else None
+        n_in = 1 + (a2 is not None) + (b2 is not None)
+        _launch("dta_layernorm_fwd", (x2, a2, b2, w), ptr(x2), ptr(a2), ptr(b2), ptr(w), ptr(xo), ptr(y), ptr(mean), ptr(rstd), R, H, float(eps),
+                _DT[x.dtype], nbytes=R * H * x2.element_size() * (n_in + 1 + (xo is not None)))
+        xin = xo if xo is not None else x2
+        ctx.save_for_backward(xin, w, mean, rstd)
+        ctx.deltas = (delta_a is not None, delta_b is not None)
+        return xin.view(x.shape), y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, g_res, dy):
+        x2, w, mean, rstd = ctx.saved_tensors
+        R, H = x2.shape
+        dy2 = dy.contiguous().view(R, H)
+        gr = g_res.contiguous().view(R, H) if g_res is not None else None
+        dx = torch.empty_like(x2)
+        need_w = ctx.needs_input_grad[3]
+        part = torch.empty(lib().dta_layernorm_bwd_blocks(R), H, dtype=torch.float32, device=x2.device) if need_w else None
+        _launch("dta_layernorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(mean), ptr(rstd), ptr(dx), ptr(part), R, H,
+                _DT[x2.dtype], nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
+        dx = dx.view(dy.shape)
+        return dx, (dx if ctx.deltas[0] else None), (dx if ctx.deltas[1] else None), (sum_slabs(part, w.dtype) if need_w else None), None
+
+
+def layer_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
+    """CohereLayerNorm: w * (x - mean) * rsqrt(var + eps) in fp32 with one rounding; no bias."""
+    return _LayerNorm.apply(x, None, None, w, eps)[1]
+
+
+def add_layer_norm(x: torch.Tensor, delta_a: Optional[torch.Tensor], delta_b: Optional[torch.Tensor], w: torch.Tensor, eps: float):
+    """The residual join of the parallel attention || MLP block fused with the next LayerNorm: returns (x + delta_a + delta_b summed
+    in fp32 and rounded once, LN of that).  Either delta may be None (delta_b only with delta_a)."""
+    return _LayerNorm.apply(x, delta_a, delta_b, w, eps)
+
+
+class _QKVSplit(torch.autograd.Function):
+    """The q|k|v prep of a layer without rotation (Cohere2's full-attention layers): q, k and v are views of the fused projection
+    output [T, Hq+2Hkv, D] - the projection's values bit for bit - and the backward hands back ONE [T, Hq+2Hkv, D] buffer: the one
+    _TreeAttention's backward laid the three gradients out in, when it did, else a copy."""
+
+    @staticmethod
+    def forward(ctx, qkv, Hq, Hkv):
+        T, H3, D = qkv.shape
+        assert H3 == Hq + 2 * Hkv and qkv.is_contiguous()
+        ctx.geom = (T, Hq, Hkv, D, qkv.dtype)
+        return qkv[:, :Hq], qkv[:, Hq:Hq + Hkv], qkv[:, Hq + Hkv:]
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        T, Hq, Hkv, D, dtype = ctx.geom
+        H3 = Hq + 2 * Hkv
+        base = dv._base
+        in_place = (base is not None and dq._base is base and dk._base is base and base.shape == (T, H3, D) and base.is_contiguous()
+                    and base.dtype == dtype and dq.shape == (T, Hq, D) and dk.shape == (T, Hkv, D) and dv.shape == (T, Hkv, D)
+                    and dq.stride() == dk.stride() == dv.stride() == (H3 * D, D, 1)
+                    and (dq.storage_offset(), dk.storage_offset(), dv.storage_offset()) == (0, Hq * D, (Hq + Hkv) * D))
+        if in_place:
+            return base, None, None
+        d = torch.empty((T, H3, D), dtype=dtype, device=dv.device)
+        d[:, :Hq].copy_(dq); d[:, Hq:Hq + Hkv].copy_(dk); d[:, Hq + Hkv:].copy_(dv)
+        return d, None, None
+
+
+def qkv_prep_nope(qkv: torch.Tensor, Hq: int, Hkv: int):
+    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D] of a layer that applies no RoPE: strided views,
+    no kernel."""
+    return _QKVSplit.apply(qkv, Hq, Hkv)
 
 
 class _RMSNormAdd(torch.autograd.Function):

@@ -31,7 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .model import _cfg_of, _windows_of, attn_args_of, final_softcap_of, head_weight, packed_hidden_states
+from .model import _cfg_of, _windows_of, attn_args_of, final_softcap_of, head_weight, logit_scale_of, packed_hidden_states
 from .tree_training_engine import sum_loss_terms
 from .trie import pop_block_starts
 
@@ -204,6 +204,9 @@ class StackWalk:
         cap = final_softcap_of(self.model)
         if cap:
             kw.update(softcap=cap, max_picks_per_row=int(np.bincount(rows_np).max()) if F_ else 0)
+        scale = logit_scale_of(self.model)
+        if scale != 1.0:                                                    # Cohere: the statistics of logit_scale * logits
+            kw.update(temperature=1.0 / scale)
         lp_next, lp_fork, ent = ops.lm_head_rows(h, W, labels, fork_ptr, fork_tok, fork_rows, bounds, True, self.head_chunk, **kw)
         return lp_next, lp_fork, ent, g_fork
 

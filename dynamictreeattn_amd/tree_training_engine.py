@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .model import (ensure_supported, final_softcap_of, head_weight, is_gemma2, is_glm4, is_longrope, is_moe_layer, moe_geometry, longrope_boundary,
+from .model import (ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry, longrope_boundary,
                     packed_hidden_states)
 from .trie import pop_block_starts
 
@@ -64,7 +64,8 @@ def fork_tables_host(fork_child, fork_parent, T: int):
 
 def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tensor, parent: torch.Tensor,
                            want_entropy: bool, chunk: int = 2048, fork_child: Optional[np.ndarray] = None,
-                           fork_parent: Optional[np.ndarray] = None, tp_group=None, fork_dev=None, softcap: float = 0.0):
+                           fork_parent: Optional[np.ndarray] = None, tp_group=None, fork_dev=None, softcap: float = 0.0,
+                           logit_scale: float = 1.0):
     """lp[t] = log softmax(h[parent[t]] Wᵀ)[tokens[t]] (0 for roots), ent[t] = H(softmax(h[t] Wᵀ)); fp32.
     The arithmetic (vocab_parallel.py:13-27; call sites tte:190-193, 256-261, 361-372) runs in
     `ops.lm_head_rows`: hipBLASLt logits GEMM per row chunk + the HIP statistics kernels; at most one
@@ -72,7 +73,9 @@ def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tenso
     `fork_child`/`fork_parent`: host lists of the tokens whose parent is not the preceding packed token (sorted by parent);
     `fork_dev` = their device copies (child int64, parent int64, CSR ptr int32 [T+1]) when the caller uploaded them with the
     plan tables — otherwise they are uploaded here (a blocking copy in the middle of the step).
-    `softcap` > 0: final-logit soft-capping (config.final_logit_softcapping of a Gemma-2 model), applied inside the statistics kernels."""
+    `softcap` > 0: final-logit soft-capping (config.final_logit_softcapping of a Gemma-2 model), applied inside the statistics kernels.
+    `logit_scale`: the statistics are those of logit_scale * logits (config.logit_scale of a Cohere model, model.logit_scale_of): it
+    reaches the statistics kernels as their temperature 1 / logit_scale, so no pass over the logits is added; 1.0 is the plain head."""
     T = h.shape[0]
     dev = h.device
     if fork_child is None:
@@ -92,6 +95,8 @@ def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tenso
     cap_kw = {}
     if softcap:
         cap_kw = dict(softcap=softcap, max_picks_per_row=int(np.bincount(np.asarray(fork_parent, np.int64)).max()) if nF else 0)
+    if logit_scale != 1.0:
+        cap_kw["temperature"] = 1.0 / float(logit_scale)
     if tp_group is not None:
         # vocabulary split across the group (BASELINE config 4; vocab_parallel.py:128-130): this rank multiplies by
         # its contiguous slice of the (tied) head weight only; labels stay global
@@ -312,7 +317,9 @@ class TreeTrainingEngine:
         Of the 10 hidden-size rows, four are what a pre-norm layer really keeps between its GEMMs: the residual stream in front of
         each of its two norms and the two norm outputs (the projections' inputs); the rest is slack.  Gemma-2 and GLM-4 keep the outputs
         of their two post-branch norms on top: 12.  An OLMo layer has no pre-branch norm outputs; it keeps the two branch outputs before their
-        norms (ops.rms_norm_add's saved rows) and one materialised stream per branch (the projections' inputs): the same four, 10."""
+        norms (ops.rms_norm_add's saved rows) and one materialised stream per branch (the projections' inputs): the same four, 10.
+        A Cohere layer has ONE norm: it keeps the joined stream in front of it and its one output, which both branches read - two
+        rows fewer, 8."""
         c = model.config
         D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
         L = c.num_hidden_layers
@@ -320,7 +327,8 @@ class TreeTrainingEngine:
         from . import lora
         ranks = lora.rank_elems_per_token(model)        # LoRA: x·Aᵀ of every adapted projection is kept for the backward (Σr elements)
         norms = 2 * c.hidden_size if is_gemma2(c) or is_glm4(c) else 0          # Gemma-2, GLM-4: the outputs of the two post-branch norms are kept too
-        return int(2 * (10 * c.hidden_size + norms + mlp + ranks + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
+        rows = 8 if is_cohere(c) else 10
+        return int(2 * (rows * c.hidden_size + norms + mlp + ranks + 4 * (c.num_attention_heads + c.num_key_value_heads) * D))
 
     def _budget(self) -> Optional[int]:
         if self.memory_budget_bytes is not None:
@@ -393,7 +401,8 @@ class TreeTrainingEngine:
             parent = torch.arange(-1, T - 1, device=self.device, dtype=torch.int32)
             with torch.enable_grad():
                 h = packed_hidden_states(one, tokens, depth, None, False, 0, ident)
-                lp, ent = packed_logprob_entropy(h, head_weight(model), tokens, parent, True, self.head_chunk, softcap=final_softcap_of(model))
+                lp, ent = packed_logprob_entropy(h, head_weight(model), tokens, parent, True, self.head_chunk, softcap=final_softcap_of(model),
+                                                 logit_scale=logit_scale_of(model))
                 (lp.sum() + ent.sum()).backward()
         for p in model.parameters():
             p.grad = None
@@ -501,7 +510,8 @@ class TreeTrainingEngine:
         h = packed_hidden_states(model, packed.tokens, packed.depth, packed.meta, False, meta_for_window=packed.for_window,
                                  longrope_long=self._longrope_long(model, token_trie))
         lp, _ = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, False, self.head_chunk,
-                                       packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model))
+                                       packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model),
+                                       logit_scale_of(model))
         for i, attach_list in enumerate(token_trie.attach_lists):
             lp_path = lp[packed.paths[i][1:]]
             for attachment, length in attach_list:
@@ -547,7 +557,8 @@ class TreeTrainingEngine:
         if ckpt and kept:
             self.last_mode = "packed" if kept[0] >= self.n_layers else f"packed+recompute[{self.n_layers - kept[0]}/{self.n_layers}]"
         lp, ent = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, True, max(chunk, 1),
-                                         packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model))
+                                         packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model),
+                                       logit_scale_of(model))
         total, leaves = self._path_losses(packed, token_trie, lp, ent, loss_fn)
         if total is None:
             return 0.0

@@ -243,6 +243,25 @@ int dta_rmsnorm_bwd_blocks(int32_t R);   /* rows of the dw_partial workspace [bl
                                           * dw_partial NULL (here and in dta_qk_norm_rope_bwd): a frozen weight - dx only, no partials written */
 int dta_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* rstd, void* dx, float* dw_partial,
                     int32_t R, int32_t H, float w_offset, int32_t dtype, void* stream);
+/* LayerNorm without bias (CohereLayerNorm, transformers' modeling_cohere.py) with the residual join of the parallel attention || MLP
+ * block.  Rows of H, H % 8 == 0 and H <= 8192 in both directions; bf16 / f16 / fp32 storage, fp32 arithmetic; mean, rstd: float [R].
+ *   m = mean(x),  r = rsqrt(mean((x - m)^2) + eps),  y = cast(w ((x - m) r)):  the weight multiplies in fp32 and the result is rounded
+ *   ONCE.  The statistics are two passes over the row held in registers (the centred form, never E[x^2] - m^2), so a row with a large
+ *   common offset keeps its rstd.
+ * delta_a, delta_b, x_out all NULL: y = LN(x).  x_out with delta_a, or with delta_a and delta_b: x_out = cast((x + delta_a) + delta_b),
+ * summed in fp32 and rounded once, and y = LN(x_out), in one pass over the row (the two branch outputs of the previous layer join the
+ * stream here).  No operand may alias an output.
+ * bwd: `x` is the normalised input (the forward's x_out).  With t = (x - m) r and g = dy w:
+ *   dx = r (g - mean(g) - t mean(g t)) + dres  (dres may be NULL: the gradient arriving on the residual stream); x, delta_a and delta_b
+ *   all take this one dx.  dw_partial: float [dta_layernorm_bwd_blocks(R), H] = per-workgroup sums over rows of dy t, summed over dim 0
+ *   by dta_sum_slabs; NULL: a frozen weight, dx only.  No float atomics: identical calls give identical bits.
+ * Refusals come in this order: DTA_EINVAL (a null pointer, a size <= 0, delta_b without delta_a, a delta without x_out or the reverse,
+ * a NaN eps), DTA_EUNSUPPORTED (dtype, H % 8, H > 8192), DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR. */
+int dta_layernorm_fwd(const void* x, const void* delta_a, const void* delta_b, const void* w, void* x_out, void* y,
+                      float* mean, float* rstd, int32_t R, int32_t H, float eps, int32_t dtype, void* stream);
+int dta_layernorm_bwd_blocks(int32_t R);   /* rows of the dw_partial workspace [blocks, H] (float) */
+int dta_layernorm_bwd(const void* x, const void* w, const void* dy, const void* dres, const float* mean, const float* rstd,
+                      void* dx, float* dw_partial, int32_t R, int32_t H, int32_t dtype, void* stream);
 /* head_dim D = 128 or 64.  x: [T, NH, D] with token stride x_stride_t; cos_sin: float [T, D] = {cos[D/2], sin[D/2]} of the token's
  * depth (rotate-half pairs element i with i + D/2); y: [T, NH, D] contiguous; w (head-norm weight [D]) may be NULL = RoPE only. */
 int dta_qk_norm_rope_fwd(const void* x, const void* w, const float* cos_sin, void* y, float* rstd,
