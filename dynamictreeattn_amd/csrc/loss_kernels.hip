@@ -1,0 +1,209 @@
+// Policy objective over the packed trie (include/dta.h, dta_policy_loss): the clipped PPO / GRPO surrogate, KL penalty, entropy bonus
+// and loss mask of losses.PolicyLoss evaluated where the data lives - every packed row once, dlp[T] and dent[T] written directly.
+//
+// Row-major work.  Row t at depth d is on the path of the sequences s of ONE contiguous range [row_seq_lo[t], row_seq_hi[t]) (callback
+// order) with n_s = len_s - 1 >= d.  For each of them it owns the log-prob term (s, j = d - 1) when d >= 1 and the entropy term
+// (s, j = d) when d < n_s: every (s, j) is owned by exactly one row in each role, so nothing is scattered and nothing is atomic.
+// A thread takes a row; a row whose range is longer than PL_SERIAL sequences is summed by its whole wave, lane-strided over s and
+// joined by the xor butterfly - a fixed order either way, so equal inputs give equal bits.
+#include "dta_common.h"
+#include "dta_device.h"
+#include <math.h>
+
+namespace {
+
+constexpr int PL_BLOCK = 256;       // rows per workgroup step
+constexpr int PL_SERIAL = 16;       // longest sequence range a single thread sums
+constexpr int PL_MAX_BLOCKS = 1024; // grid cap: the rest is grid-strided, the partial-sum workspace has at most this many rows
+constexpr int PL_NSTAT = 8;         // {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0}
+
+struct PolicyParams {
+  const float *lp, *ent;
+  const int32_t *depth, *row_lo, *row_hi, *seq_ptr;
+  const float *old_lp, *ref_lp, *mask, *adv, *w;
+  float *dlp, *dent, *partial;
+  int32_t T, S, adv_per_seq;
+  float lo, hi, dual, kl_coef, ent_coef;     // lo = 1 - clip_low, hi = 1 + clip_high, dual = 0: none
+};
+
+struct Acc { float glp, gent, st[6]; };
+
+// the terms row (depth d, log-prob lp_t, entropy ent_t) owns for sequence s
+template <int KL>
+__device__ __forceinline__ void seq_terms(const PolicyParams& p, int s, int d, float lp_t, float ent_t, Acc& a) {
+  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+  if (n < d) return;                                       // the sequence ends above this row
+  const float w = p.w[s];
+  if (d >= 1) {
+    const int i = b + d - 1;
+    const float m = p.mask[i];
+    const float A = p.adv[p.adv_per_seq ? s : i];
+    const float r = p.old_lp ? expf(lp_t - p.old_lp[i]) : 1.f;
+    const float s1 = -r * A, s2 = -fminf(fmaxf(r, p.lo), p.hi) * A;
+    float pg = fmaxf(s1, s2);
+    bool clipped = s2 > s1;                                // the clamp is the active branch: d pg / d lp = 0
+    if (p.dual > 0.f && A < 0.f) {
+      const float cap = -p.dual * A;
+      if (cap < pg) { pg = cap; clipped = true; }
+    }
+    float g = clipped ? 0.f : s1;                          // d(-r A)/d lp = -r A
+    float kl = 0.f;
+    if (KL >= 0) {
+      const float dd = p.ref_lp[i] - lp_t;
+      float dk;
+      if (KL == 0) { kl = -dd; dk = 1.f; }
+      else if (KL == 1) { kl = 0.5f * dd * dd; dk = -dd; }
+      else { const float e = expf(dd); kl = e - dd - 1.f; dk = 1.f - e; }
+      g += p.kl_coef * dk;
+      a.st[2] += m * kl;
+    }
+    const float wm = w * m;
+    a.glp += wm * g;
+    a.st[0] += wm * (pg + p.kl_coef * kl);
+    a.st[1] += m * pg;
+    a.st[4] += clipped ? m : 0.f;
+    a.st[5] += m;
+  }
+  if (d < n) {
+    const float m = p.mask[b + d];
+    const float wm = w * m;
+    a.gent -= wm * p.ent_coef;
+    a.st[0] -= wm * p.ent_coef * ent_t;
+    a.st[3] += m * ent_t;
+  }
+}
+
+template <int KL>
+__global__ __launch_bounds__(PL_BLOCK) void policy_loss_kernel(const PolicyParams p) {
+  __shared__ float red[PL_BLOCK / 64][PL_NSTAT];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Acc a;
+  for (int i = 0; i < 6; ++i) a.st[i] = 0.f;
+  for (int base = blockIdx.x * PL_BLOCK; base < p.T; base += gridDim.x * PL_BLOCK) {   // `base` is the same in every lane of the workgroup
+    const int t = base + threadIdx.x;
+    const bool live = t < p.T;
+    int d = 0, s0 = 0, s1 = 0;
+    float lp_t = 0.f, ent_t = 0.f;
+    if (live) {
+      d = p.depth[t]; lp_t = p.lp[t]; ent_t = p.ent[t];
+      s0 = max(p.row_lo[t], 0); s1 = min(p.row_hi[t], p.S);
+    }
+    a.glp = 0.f; a.gent = 0.f;
+    const bool wide = s1 - s0 > PL_SERIAL;
+    if (!wide)
+      for (int s = s0; s < s1; ++s) seq_terms<KL>(p, s, d, lp_t, ent_t, a);
+    // rows with a long range: the wave takes them one after the other, in lane order
+    unsigned long long todo = __ballot(wide);
+    float glp_w = 0.f, gent_w = 0.f;
+    while (todo) {
+      const int k = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int dk = __shfl(d, k), b0 = __shfl(s0, k), b1 = __shfl(s1, k);
+      const float lpk = __shfl(lp_t, k), entk = __shfl(ent_t, k);
+      Acc r = a;
+      r.glp = 0.f; r.gent = 0.f;
+      for (int s = b0 + lane; s < b1; s += 64) seq_terms<KL>(p, s, dk, lpk, entk, r);
+      for (int i = 0; i < 6; ++i) a.st[i] = r.st[i];
+      const float gl = wave_sum(r.glp), ge = wave_sum(r.gent);
+      if (lane == k) { glp_w = gl; gent_w = ge; }
+    }
+    if (live) {
+      p.dlp[t] = wide ? glp_w : a.glp;
+      p.dent[t] = wide ? gent_w : a.gent;
+    }
+  }
+  // the workgroup's partial sums: lanes by butterfly, then the four waves in order
+  for (int i = 0; i < 6; ++i) {
+    const float v = wave_sum(a.st[i]);
+    if (lane == 0) red[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < PL_NSTAT) {
+    float v = 0.f;
+    if (threadIdx.x < 6)
+      for (int wv = 0; wv < PL_BLOCK / 64; ++wv) v += red[wv][threadIdx.x];
+    p.partial[blockIdx.x * PL_NSTAT + threadIdx.x] = v;
+  }
+}
+
+// stats[c] = sum over the workgroups' partials, in a fixed order: 32 strided chains per column, then the 32 in order
+__global__ __launch_bounds__(256) void policy_loss_reduce_kernel(const float* __restrict__ partial, int nb, float* __restrict__ stats) {
+  __shared__ float red[32][PL_NSTAT];
+  const int c = threadIdx.x & 7, g = threadIdx.x >> 3;
+  float v = 0.f;
+  for (int b = g; b < nb; b += 32) v += partial[b * PL_NSTAT + c];
+  red[g][c] = v;
+  __syncthreads();
+  if (threadIdx.x < PL_NSTAT) {
+    float s = 0.f;
+    for (int i = 0; i < 32; ++i) s += red[i][threadIdx.x];
+    stats[threadIdx.x] = s;
+  }
+}
+
+// w[s] = scale / max(sum of the sequence's mask, 1): one workgroup per sequence, lanes strided, butterfly, the four waves in order
+__global__ __launch_bounds__(256) void policy_seq_weight_kernel(const float* __restrict__ mask, const int32_t* __restrict__ seq_ptr, int S,
+                                                               float scale, float* __restrict__ w) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int s = blockIdx.x; s < S; s += gridDim.x) {
+    const int b = seq_ptr[s], e = seq_ptr[s + 1];
+    float v = 0.f;
+    for (int i = b + (int)threadIdx.x; i < e; i += 256) v += mask[i];
+    v = wave_sum(v);
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) w[s] = scale / fmaxf(((red[0] + red[1]) + red[2]) + red[3], 1.f);
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void policy_fill_weight_kernel(int S, float scale, float* __restrict__ w) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s < S) w[s] = scale;
+}
+
+inline bool finite_f(float v) { return v == v && v - v == 0.f; }
+
+}  // namespace
+
+extern "C" int dta_policy_loss_blocks(int32_t T) { return T <= 0 ? DTA_EINVAL : row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS); }
+
+extern "C" int dta_policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                               const int32_t* seq_ptr, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
+                               int32_t adv_per_seq, float* w, float* dlp, float* dent, float* partial, float* stats, int32_t T, int32_t S,
+                               float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef,
+                               int32_t agg, float scale, void* stream) {
+  if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !mask || !adv || !w || !dlp || !dent || !partial || !stats ||
+      T <= 0 || S <= 0)
+    return DTA_EINVAL;
+  if (!finite_f(clip_low) || !finite_f(clip_high) || clip_low < 0.f || clip_high < 0.f) return DTA_EINVAL;
+  if (dual_clip != 0.f && !(finite_f(dual_clip) && dual_clip > 1.f)) return DTA_EINVAL;
+  if (kl_estimator < 0 || kl_estimator > 2 || agg < 0 || agg > 1) return DTA_EINVAL;
+  if (!finite_f(kl_coef) || !finite_f(entropy_coef) || !finite_f(scale)) return DTA_EINVAL;
+  if (kl_coef != 0.f && !ref_lp) return DTA_EINVAL;
+  if (!aligned16(lp) || !aligned16(ent) || !aligned16(depth) || !aligned16(row_seq_lo) || !aligned16(row_seq_hi) || !aligned16(seq_ptr) ||
+      !aligned16(mask) || !aligned16(adv) || !aligned16(w) || !aligned16(dlp) || !aligned16(dent) || !aligned16(partial) || !aligned16(stats) ||
+      (old_lp && !aligned16(old_lp)) || (ref_lp && !aligned16(ref_lp)))
+    return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  if (agg == 0)
+    hipLaunchKernelGGL(policy_seq_weight_kernel, dim3(S < 2048 ? S : 2048), dim3(256), 0, st_, mask, seq_ptr, S, scale, w);
+  else
+    hipLaunchKernelGGL(policy_fill_weight_kernel, dim3(ceil_blocks(S, 256)), dim3(256), 0, st_, S, scale, w);
+  PolicyParams p;
+  p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
+  p.old_lp = old_lp; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w;
+  p.dlp = dlp; p.dent = dent; p.partial = partial;
+  p.T = T; p.S = S; p.adv_per_seq = adv_per_seq != 0;
+  p.lo = 1.f - clip_low; p.hi = 1.f + clip_high; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
+  const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS);
+  const dim3 grid(nb), block(PL_BLOCK);
+  if (kl_coef == 0.f) hipLaunchKernelGGL(policy_loss_kernel<-1>, grid, block, 0, st_, p);
+  else if (kl_estimator == 0) hipLaunchKernelGGL(policy_loss_kernel<0>, grid, block, 0, st_, p);
+  else if (kl_estimator == 1) hipLaunchKernelGGL(policy_loss_kernel<1>, grid, block, 0, st_, p);
+  else hipLaunchKernelGGL(policy_loss_kernel<2>, grid, block, 0, st_, p);
+  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb, stats);
+  return DTA_LAUNCH_STATUS();
+}

@@ -1705,3 +1705,84 @@ def lora_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], ada
     if o < y.shape[1]:
         cols.append(y[:, o:])
     return cols[0] if len(cols) == 1 else torch.cat(cols, dim=1)
+
+
+# --------------------------------------------------------------------------------------------------
+# Policy objective over packed rows (losses.PolicyLoss, dta_policy_loss)
+# --------------------------------------------------------------------------------------------------
+def policy_token_inputs(loss, attach_lists, seq_ptr, device):
+    """The per-token inputs of the fused objective, concatenated in callback order behind seq_ptr: (old, ref, mask, adv, adv_per_seq), fp32
+    device vectors of N = seq_ptr[-1] elements (old / ref None: on-policy / no KL; adv one value per sequence when every attachment gives
+    a float).  Each key is checked as PolicyLoss.__call__ checks it.  A key whose tensors all live on the host is concatenated there and
+    uploaded once out of page-locked staging; tensors already on the device are concatenated there."""
+    from ._staging import upload
+    cols = {"adv": [], "old": [], "ref": [], "mask": []}
+    s = 0
+    for attach_list in attach_lists:
+        for attachment, length in attach_list:
+            n = int(length) - 1
+            if n != int(seq_ptr[s + 1]) - int(seq_ptr[s]):
+                raise ValueError("attach lists and seq_ptr disagree")
+            adv, old, ref, mask = loss.fields(attachment, n)
+            cols["adv"].append(adv); cols["old"].append(old); cols["ref"].append(ref); cols["mask"].append(mask)
+            s += 1
+    S, N = s, int(seq_ptr[-1])
+    lens = np.diff(np.asarray(seq_ptr, np.int64))
+
+    def cat(vals, fill):
+        """fp32 [N] on the device; a None / float entry stands for `fill` / that float on every token of its sequence"""
+        if all(not isinstance(v, torch.Tensor) or not v.is_cuda for v in vals):
+            host = np.empty(N, np.float32)
+            for v, b, n in zip(vals, seq_ptr[:-1], lens):
+                host[b:b + n] = fill if v is None else v if isinstance(v, float) else v.detach().to(torch.float32).numpy()
+            return upload([host], device, np.float32)[0]
+        if all(isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == vals[0].dtype for v in vals):
+            return torch.cat([v.detach().to(device) for v in vals]).to(torch.float32)       # one concatenation, one cast (bool masks)
+        parts = [torch.full((int(n),), fill if v is None else v, dtype=torch.float32, device=device) if not isinstance(v, torch.Tensor)
+                 else v.detach().to(device=device, dtype=torch.float32) for v, n in zip(vals, lens)]
+        return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=device)
+
+    if any(v is None for v in cols["old"]) and not all(v is None for v in cols["old"]):
+        raise ValueError("old_logprobs: given for some sequences of the trie and absent for others")
+    old = None if all(v is None for v in cols["old"]) else cat(cols["old"], 0.0)
+    ref = None if loss.kl_coef == 0 else cat(cols["ref"], 0.0)
+    mask = cat(cols["mask"], 1.0)
+    adv_per_seq = all(isinstance(v, float) for v in cols["adv"])
+    adv = upload([np.asarray(cols["adv"], np.float32)], device, np.float32)[0] if adv_per_seq else cat(cols["adv"], 0.0)
+    return old, ref, mask, adv, adv_per_seq
+
+
+def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, row_seq_lo: torch.Tensor, row_seq_hi: torch.Tensor,
+                seq_ptr: torch.Tensor, old: Optional[torch.Tensor], ref: Optional[torch.Tensor], mask: torch.Tensor, adv: torch.Tensor,
+                adv_per_seq: bool):
+    """The objective `loss` (losses.PolicyLoss) over T packed rows in one C-ABI call: returns (dlp [T], dent [T], stats [8], w [S]), fp32.
+    lp / ent: the fp32 row statistics of packed_logprob_entropy (no graph is followed: the caller back-propagates dlp / dent);
+    row_seq_lo / row_seq_hi / seq_ptr: packing.policy_row_tables; old / ref / mask / adv: policy_token_inputs.
+    stats = {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0} (losses.STATS); w: the per-sequence weights."""
+    from .losses import AGGREGATIONS, KL_ESTIMATORS
+    T, S = int(lp.shape[0]), int(seq_ptr.shape[0]) - 1
+    def f32(t):                 # fp32, contiguous and on a 16-byte boundary (a view into a larger buffer may start anywhere)
+        if t is None:
+            return None
+        t = t.detach().to(torch.float32).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    lp, ent, old, ref, mask, adv = f32(lp), f32(ent), f32(old), f32(ref), f32(mask), f32(adv)
+    _require_cuda(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv)
+    N = int(mask.shape[0])
+    assert ent.shape[0] == T and depth.shape[0] == T and row_seq_lo.shape[0] == T and row_seq_hi.shape[0] == T
+    assert depth.dtype == row_seq_lo.dtype == row_seq_hi.dtype == seq_ptr.dtype == torch.int32
+    assert adv.shape[0] == (S if adv_per_seq else N) and (old is None or old.shape[0] == N) and (ref is None or ref.shape[0] == N)
+    nb = lib().dta_policy_loss_blocks(T)
+    # one fp32 buffer: dlp | dent | w | partial | stats, each part a multiple of 4 floats
+    r4 = lambda n: (n + 3) // 4 * 4
+    buf = torch.empty(2 * r4(T) + r4(S) + 8 * nb + 8, dtype=torch.float32, device=lp.device)
+    dlp, dent = buf[:T], buf[r4(T):r4(T) + T]
+    o = 2 * r4(T)
+    w, partial, stats = buf[o:o + S], buf[o + r4(S):o + r4(S) + 8 * nb], buf[o + r4(S) + 8 * nb:]
+    _launch("dta_policy_loss", (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, buf),
+            ptr(lp), ptr(ent), ptr(depth), ptr(row_seq_lo), ptr(row_seq_hi), ptr(seq_ptr), ptr(old), ptr(ref), ptr(mask), ptr(adv),
+            int(bool(adv_per_seq)), ptr(w), ptr(dlp), ptr(dent), ptr(partial), ptr(stats), T, S,
+            float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
+            KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
+            nbytes=4 * (4 * T + (3 + (old is not None) + (ref is not None)) * N))
+    return dlp, dent, stats, w

@@ -377,3 +377,54 @@ def ktile_qend_window(ktile_qend: np.ndarray, win_lo: np.ndarray, tile: int = KT
     kmax = np.minimum((np.arange(nkt, dtype=np.int64) + 1) * tile, T) - 1
     qe = np.searchsorted(sufmin, kmax, side="right")                       # one past the last row whose window reaches the tile
     return np.minimum(ktile_qend.astype(np.int64), qe).astype(np.int32)
+
+
+# ---- policy objective over packed rows -------------------------------------------------------------------------------------
+# The loss callbacks see the sequences leaf by leaf in packed order and, within a leaf, in attach-list order: "callback order".  The
+# leaves below a packed row are consecutive, so the sequences that pass through it are the members of ONE range of that order whose
+# length exceeds the row's depth - what lets dta_policy_loss sum a row's terms without a gather.
+
+def policy_row_tables(plan: SegmentPlan, attach_lists):
+    """Tables of the fused policy objective, from the plan and the per-leaf [(attachment, length), ...] lists alone (host, no GPU):
+    (row_seq_lo int32 [T], row_seq_hi int32 [T], seq_ptr int32 [S+1], seq_lens int64 [S]).  Sequence s (callback order) passes through
+    packed row t iff row_seq_lo[t] <= s < row_seq_hi[t] and seq_lens[s] > depth[t]; seq_ptr is the prefix sum of seq_lens - 1, the
+    offsets of the per-token inputs.  The range of a row in segment i runs from leaf i's first sequence to the first sequence of the
+    leaf that closes the row's subtree.  That leaf comes from the walk below and not from the VALUE of subtree_end: an empty segment
+    shares its offset with its successor, and the sequences of such a leaf still pass through the rows above their end.  Filler rows
+    (pad_plan) get the empty range (0, 0)."""
+    M = int(getattr(plan, "n_real", plan.M))
+    if len(attach_lists) != M:
+        raise ValueError(f"{len(attach_lists)} attach lists for {M} leaves")
+    T = int(plan.T)
+    leaf_ptr = np.zeros(M + 1, np.int64)
+    np.cumsum([len(a) for a in attach_lists], out=leaf_ptr[1:])
+    seq_lens = np.asarray([int(n) for a in attach_lists for _, n in a], np.int64)
+    if seq_lens.size and int(seq_lens.min()) < 1:
+        raise ValueError("a sequence of length 0")
+    seq_ptr = np.zeros(seq_lens.size + 1, np.int64)
+    np.cumsum(seq_lens - 1, out=seq_ptr[1:])
+    if int(seq_ptr[-1]) >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 predictions in one call")
+    seg_off, d0 = plan.seg_off.astype(np.int64), plan.seg_depth0.astype(np.int64)
+    seg_len = np.diff(seg_off)
+    lo, hi = np.zeros(T, np.int32), np.zeros(T, np.int32)
+    real_T = int(seg_off[M])
+    lo[:real_T] = np.repeat(leaf_ptr[:M], seg_len[:M])
+
+    def close(j, a, b, leaf):                       # the rows of segment j at depths [a, b) have no descendant from `leaf` on
+        hi[seg_off[j] + a - d0[j]:seg_off[j] + b - d0[j]] = leaf_ptr[leaf]
+
+    live: List[List[int]] = []                      # [segment, depth_lo, depth_hi) on the current root->leaf path (as plan_segments)
+    for i in range(M):
+        cut = int(d0[i])
+        while live and live[-1][1] >= cut:
+            j, a, b = live.pop()
+            close(j, a, b, i)
+        if live and live[-1][2] > cut:
+            close(live[-1][0], cut, live[-1][2], i)
+            live[-1][2] = cut
+        if seg_len[i] > 0:
+            live.append([i, cut, cut + int(seg_len[i])])
+    for j, a, b in live:
+        close(j, a, b, M)
+    return lo, hi, seq_ptr.astype(np.int32), seq_lens

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
+from .losses import STATS as LOSS_STATS, PolicyLoss
 from .model import (ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry, longrope_boundary,
                     packed_hidden_states)
 from .trie import pop_block_starts
@@ -261,6 +262,8 @@ class TreeTrainingEngine:
         self._attn_keep_planned = 0
         self.stack_fp32_grads = True                     # block-wise walk: sum the blocks' parameter gradients in fp32 (False: model dtype, as the reference)
         self.longrope_factors = "auto"                   # longrope models: "auto" (by the trie's sequence lengths) / "short" / "long"
+        self.last_loss_path: Optional[str] = None        # how the last backward() evaluated the loss: "fused" (a losses.PolicyLoss on the packed rows) / "callback"
+        self.loss_stats: Optional[torch.Tensor] = None   # fused path: device vector in the order of losses.STATS, not synchronised; None on the callback path
 
     # ------------------------------------------------------------------------------------------
     def _pack(self, token_trie) -> _PackedTrie:
@@ -492,6 +495,19 @@ class TreeTrainingEngine:
         if roots:
             torch.autograd.backward(roots, grads)
 
+    @staticmethod
+    def _policy_rows(packed, token_trie, lp, ent, loss):
+        """The built-in objective on the packed rows: (dlp [T], dent [T], stats [8]) of ops.policy_loss.  The row -> sequence-range
+        tables come from the packing plan on the host and travel in one staged upload; the attachments' per-token tensors are
+        concatenated in callback order (ops.policy_token_inputs)."""
+        from ._staging import upload
+        row_lo, row_hi, seq_ptr, _ = packing.policy_row_tables(packed.plan, token_trie.attach_lists)
+        dev = packed.tokens.device
+        row_lo_d, row_hi_d, seq_ptr_d = upload([row_lo, row_hi, seq_ptr], dev, np.int32)
+        old, ref, mask, adv, adv_per_seq = ops.policy_token_inputs(loss, token_trie.attach_lists, seq_ptr, dev)
+        dlp, dent, stats, _ = ops.policy_loss(loss, lp, ent, packed.depth, row_lo_d, row_hi_d, seq_ptr_d, old, ref, mask, adv, adv_per_seq)
+        return dlp, dent, stats
+
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, model, token_trie) -> List[torch.Tensor]:
@@ -526,6 +542,7 @@ class TreeTrainingEngine:
         ensure_supported(model)
         lens = [int(ids.size(0)) for ids in token_trie.inputs]
         self.forkpos_list = _get_forkpos(lens, token_trie.lcp_lens, block_size)
+        self.last_loss_path, self.loss_stats = "callback", None      # the packed pass switches to "fused" for a losses.PolicyLoss
         if token_trie.n_sequences == 0:          # an empty bin of a data-parallel step: no loss, no gradient (the caller still reduces)
             return 0.0
         with ops.weight_cache():                 # per-weight copies (stacked rows, transposes) are shared inside this call and dropped after it
@@ -559,7 +576,16 @@ class TreeTrainingEngine:
         lp, ent = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, True, max(chunk, 1),
                                          packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model),
                                        logit_scale_of(model))
-        total, leaves = self._path_losses(packed, token_trie, lp, ent, loss_fn)
+        fused = isinstance(loss_fn, PolicyLoss)
+        if fused:
+            # the built-in objective runs over the packed rows themselves (one C-ABI call): no gather along the paths, no per-sequence
+            # callback, no scatter of per-sequence gradients - dlp / dent come out per row
+            self.last_loss_path = "fused"
+            dlp, dent, stats = self._policy_rows(packed, token_trie, lp, ent, loss_fn)
+            self.loss_stats = stats[:len(LOSS_STATS)]
+            total = stats[0]
+        else:
+            total, leaves = self._path_losses(packed, token_trie, lp, ent, loss_fn)
         if total is None:
             return 0.0
         # the loss value leaves the device as soon as the forward has produced it (an asynchronous copy into page-locked memory) and the
@@ -572,7 +598,12 @@ class TreeTrainingEngine:
                 self._loss_host = torch.empty(1, dtype=torch.float32).pin_memory()
             self._loss_host.copy_(total.detach().reshape(1).float(), non_blocking=True)
             landed = torch.cuda.Event(); landed.record()
-        if total.requires_grad:                     # (a callback that returns constants only leaves nothing to back-propagate)
+        if fused:
+            roots = [(lp, dlp)] + ([(ent, dent)] if loss_fn.entropy_coef != 0 else [])      # no entropy bonus: entropy is not differentiated
+            roots = [(t, g) for t, g in roots if t.requires_grad]
+            if roots and torch.is_grad_enabled():
+                torch.autograd.backward([t for t, _ in roots], [g for _, g in roots])
+        elif total.requires_grad:                   # (a callback that returns constants only leaves nothing to back-propagate)
             self._backprop_paths(packed, token_trie, lp, ent, total, leaves)
         self.cur_len = 0
         if landed is None:

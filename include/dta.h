@@ -412,6 +412,41 @@ int dta_lora_wgrad_slabs(int32_t T, int32_t K);
 int dta_lora_wgrad(const void* l, int64_t ldl, const void* x, int64_t ldx, float* part, const float* rscale_host,
                    int32_t T, int32_t R, int32_t K, int32_t dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Policy objective over the packed trie (HBM-bound; fp32 throughout): the clipped PPO / GRPO surrogate with an optional dual clip, a KL
+ * penalty to a reference policy, an entropy bonus and a loss mask, evaluated per packed ROW.  Stands where the reference calls the
+ * user's loss_fn once per sequence on gathered slices and sums the per-sequence gradients back (tree_training_engine.py:379-440).
+ *
+ * Sequences are numbered in callback order: leaf by leaf in packed order, within a leaf in attach-list order.  Sequence s has
+ * n_s = len_s - 1 predictions; its per-token inputs are elements [seq_ptr[s], seq_ptr[s+1]) of old_lp / ref_lp / mask / adv (fp32,
+ * N = seq_ptr[S] elements each; element j belongs to the prediction of token j + 1).  adv_per_seq != 0: adv is [S], one value per
+ * sequence.  old_lp NULL: on-policy (ratio 1, gradient as if old_lp == lp).  ref_lp may be NULL when kl_coef == 0 (it is not read then).
+ *
+ * Row t (depth[t] = d, log-prob lp[t] of its token given its parent, entropy ent[t] of the distribution at it) lies on the path of the
+ * sequences s in [row_seq_lo[t], row_seq_hi[t]) with n_s >= d - one contiguous range, because the sequences through a subtree are
+ * contiguous in callback order; an empty range (filler rows) is legal.  For each such s the row owns
+ *   the log-prob term (s, j = d - 1) when d >= 1:   x = lp[t] - old_lp[.],  r = exp(x),  A = adv,  m = mask
+ *       pg = max(-r A, -clamp(r, 1 - clip_low, 1 + clip_high) A);  dual_clip = c > 1 and A < 0:  pg = min(pg, -c A)
+ *       dd = ref_lp[.] - lp[t];  kl = -dd (estimator 0, "k1") | dd^2 / 2 (1, "k2") | exp(dd) - dd - 1 (2, "k3")
+ *       loss += w_s m (pg + kl_coef kl);   dlp[t] += w_s m (dpg + kl_coef dkl),  dpg = -r A where -r A is the active branch
+ *       (ties included), 0 where the clamp or the dual clip is;  dkl = 1 | -dd | 1 - exp(dd)
+ *   the entropy term (s, j = d) when d < n_s:       loss -= w_s m entropy_coef ent[t];   dent[t] -= w_s m entropy_coef
+ * w_s = scale / max(sum_j m, 1) (agg 0, "seq_mean") or scale (agg 1, "token_sum"); the entry writes it to w[S] first (a workspace the
+ * caller may read afterwards).  exp is the accurate expf.  Every (s, j) is owned by exactly one row in each role: no scatter, no
+ * atomics; dlp[T] and dent[T] are written for EVERY row (0 where nothing contributes), and identical calls give identical bits.
+ * stats[8] = {loss, sum m pg, sum m kl, sum m ent, sum m [clamp or dual clip active], sum m, 0, 0}: per-workgroup partials in
+ * partial[dta_policy_loss_blocks(T)][8], then one workgroup sums them in a fixed order.  Three launches on `stream` (weights, rows,
+ * reduction); the launch geometry depends on T and S alone.
+ * Refusals come in this order: DTA_EINVAL (a null pointer other than old_lp / ref_lp, T <= 0, S <= 0, a negative or non-finite clip,
+ * dual_clip neither 0 (= none) nor a finite value > 1, kl_estimator not 0..2, agg not 0 / 1, a non-finite coefficient or scale,
+ * kl_coef != 0 with ref_lp NULL), DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR. */
+int dta_policy_loss_blocks(int32_t T);   /* rows of the partial workspace [blocks, 8] (float); T <= 0: DTA_EINVAL */
+int dta_policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                    const int32_t* seq_ptr, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
+                    int32_t adv_per_seq, float* w, float* dlp, float* dent, float* partial, float* stats, int32_t T, int32_t S,
+                    float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef,
+                    int32_t agg, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
