@@ -6,6 +6,11 @@
 // (s, j = d) when d < n_s: every (s, j) is owned by exactly one row in each role, so nothing is scattered and nothing is atomic.
 // A thread takes a row; a row whose range is longer than PL_SERIAL sequences is summed by its whole wave, lane-strided over s and
 // joined by the xor butterfly - a fixed order either way, so equal inputs give equal bits.
+//
+// Sequence-level ratios (dta_policy_loss_seq, GSPO): every token of sequence s is clipped on r_s = exp(sum_j m_j x_j / n^), so the
+// surrogate's gradient at token t of s is c_s m_t with one scalar c_s per sequence.  A sequence pass (one workgroup per sequence)
+// walks the sequence's root path - a few contiguous row runs - for r_s, w_s, c_s and the surrogate's share of the statistics; the row
+// pass is the one above with c_s m in place of the token's own surrogate gradient; one reduction joins the partials of both.
 #include "dta_common.h"
 #include "dta_device.h"
 #include <math.h>
@@ -16,11 +21,13 @@ constexpr int PL_BLOCK = 256;       // rows per workgroup step
 constexpr int PL_SERIAL = 16;       // longest sequence range a single thread sums
 constexpr int PL_MAX_BLOCKS = 1024; // grid cap: the rest is grid-strided, the partial-sum workspace has at most this many rows
 constexpr int PL_NSTAT = 8;         // {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0}
+constexpr int PL_SEQ_BLOCKS = 2048; // grid cap of the sequence pass: one workgroup per sequence, the rest grid-strided
 
 struct PolicyParams {
   const float *lp, *ent;
   const int32_t *depth, *row_lo, *row_hi, *seq_ptr;
   const float *old_lp, *ref_lp, *mask, *adv, *w;
+  const float* c = nullptr;                  // sequence-level ratios only: the surrogate's gradient scalar per sequence
   float *dlp, *dent, *partial;
   int32_t T, S, adv_per_seq;
   float lo, hi, dual, kl_coef, ent_coef;     // lo = 1 - clip_low, hi = 1 + clip_high, dual = 0: none
@@ -73,7 +80,46 @@ __device__ __forceinline__ void seq_terms(const PolicyParams& p, int s, int d, f
   }
 }
 
+// the same for sequence-level ratios: the surrogate's value and statistics are the sequence pass's, its gradient here is c_s m
 template <int KL>
+__device__ __forceinline__ void seq_terms_sl(const PolicyParams& p, int s, int d, float lp_t, float ent_t, Acc& a) {
+  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+  if (n < d) return;
+  const float w = p.w[s];
+  if (d >= 1) {
+    const int i = b + d - 1;
+    const float m = p.mask[i];
+    float g = p.c[s] * m;
+    if (KL >= 0) {
+      const float dd = p.ref_lp[i] - lp_t;
+      float kl, dk;
+      if (KL == 0) { kl = -dd; dk = 1.f; }
+      else if (KL == 1) { kl = 0.5f * dd * dd; dk = -dd; }
+      else { const float e = expf(dd); kl = e - dd - 1.f; dk = 1.f - e; }
+      const float wm = w * m;
+      g += wm * (p.kl_coef * dk);
+      a.st[0] += wm * (p.kl_coef * kl);
+      a.st[2] += m * kl;
+    }
+    a.glp += g;
+    a.st[5] += m;
+  }
+  if (d < n) {
+    const float m = p.mask[b + d];
+    const float wm = w * m;
+    a.gent -= wm * p.ent_coef;
+    a.st[0] -= wm * p.ent_coef * ent_t;
+    a.st[3] += m * ent_t;
+  }
+}
+
+template <int KL, bool SEQ>
+__device__ __forceinline__ void row_terms(const PolicyParams& p, int s, int d, float lp_t, float ent_t, Acc& a) {
+  if (SEQ) seq_terms_sl<KL>(p, s, d, lp_t, ent_t, a);
+  else seq_terms<KL>(p, s, d, lp_t, ent_t, a);
+}
+
+template <int KL, bool SEQ = false>
 __global__ __launch_bounds__(PL_BLOCK) void policy_loss_kernel(const PolicyParams p) {
   __shared__ float red[PL_BLOCK / 64][PL_NSTAT];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -91,7 +137,7 @@ __global__ __launch_bounds__(PL_BLOCK) void policy_loss_kernel(const PolicyParam
     a.glp = 0.f; a.gent = 0.f;
     const bool wide = s1 - s0 > PL_SERIAL;
     if (!wide)
-      for (int s = s0; s < s1; ++s) seq_terms<KL>(p, s, d, lp_t, ent_t, a);
+      for (int s = s0; s < s1; ++s) row_terms<KL, SEQ>(p, s, d, lp_t, ent_t, a);
     // rows with a long range: the wave takes them one after the other, in lane order
     unsigned long long todo = __ballot(wide);
     float glp_w = 0.f, gent_w = 0.f;
@@ -102,7 +148,7 @@ __global__ __launch_bounds__(PL_BLOCK) void policy_loss_kernel(const PolicyParam
       const float lpk = __shfl(lp_t, k), entk = __shfl(ent_t, k);
       Acc r = a;
       r.glp = 0.f; r.gent = 0.f;
-      for (int s = b0 + lane; s < b1; s += 64) seq_terms<KL>(p, s, dk, lpk, entk, r);
+      for (int s = b0 + lane; s < b1; s += 64) row_terms<KL, SEQ>(p, s, dk, lpk, entk, r);
       for (int i = 0; i < 6; ++i) a.st[i] = r.st[i];
       const float gl = wave_sum(r.glp), ge = wave_sum(r.gent);
       if (lane == k) { glp_w = gl; gent_w = ge; }
@@ -163,6 +209,83 @@ __global__ __launch_bounds__(256) void policy_fill_weight_kernel(int S, float sc
   if (s < S) w[s] = scale;
 }
 
+// The sequence pass of the sequence-level objective.  Sequence s follows the root path of leaf seq_leaf[s]: runs
+// [leaf_run_ptr[leaf], leaf_run_ptr[leaf + 1]) of contiguous packed rows, run k starting at row run_row0[k] with depth run_depth0[k].
+// Prediction j of s (element seq_ptr[s] + j of the per-token inputs) is the row of depth j + 1.
+struct SeqPassParams {
+  const float* lp;
+  const int32_t *seq_ptr, *leaf_run_ptr, *run_row0, *run_depth0, *seq_leaf;
+  const float *old_lp, *mask, *adv;
+  float *w, *c, *partial;
+  int32_t T, S, M, R, adv_per_seq, seq_mean;
+  float lo, hi, dual, scale;
+};
+
+// the workgroup's sum of v in a fixed order (lanes by butterfly, the four waves in order), in every thread
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();                                         // the previous use of red is over
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParams p) {
+  __shared__ float red[4];
+  float st_loss = 0.f, st_pg = 0.f, st_clip = 0.f;         // thread 0: this workgroup's sequences, in order
+  for (int s = blockIdx.x; s < p.S; s += gridDim.x) {      // `s` is the same in every thread of the workgroup
+    const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+    float sm = 0.f, sx = 0.f;
+    if (p.old_lp) {
+      const int leaf = min(max(p.seq_leaf[s], 0), p.M - 1);
+      const int k0 = max(p.leaf_run_ptr[leaf], 0), k1 = min(p.leaf_run_ptr[leaf + 1], p.R);
+      for (int k = k0; k < k1; ++k) {
+        const int row0 = p.run_row0[k], d0 = p.run_depth0[k];
+        const int da = max(d0, 1), db = min(k + 1 < k1 ? p.run_depth0[k + 1] : n + 1, n + 1);     // depths [da, db) of this run
+        for (int d = da + (int)threadIdx.x; d < db; d += 256) {
+          const int t = row0 + (d - d0), i = b + d - 1;
+          if (t < 0 || t >= p.T) continue;
+          const float m = p.mask[i];
+          sm += m;
+          sx += m * (p.lp[t] - p.old_lp[i]);
+        }
+      }
+    } else {
+      for (int j = threadIdx.x; j < n; j += 256) sm += p.mask[b + j];
+    }
+    const float nh = fmaxf(block_sum(sm, red), 1.f);
+    const float r = p.old_lp ? expf(block_sum(sx, red) / nh) : 1.f;
+    const float w = p.seq_mean ? p.scale / nh : p.scale;
+    // every token of the sequence sees the same r: its branch depends on the sign of its advantage alone
+    const float rc = fminf(fmaxf(r, p.lo), p.hi);
+    float spg = 0.f, sg = 0.f, sc = 0.f;
+    for (int j = threadIdx.x; j < n; j += 256) {
+      const float m = p.mask[b + j];
+      const float A = p.adv[p.adv_per_seq ? s : b + j];
+      const float s1 = -r * A, s2 = -rc * A;
+      float pg = fmaxf(s1, s2);
+      bool clipped = s2 > s1;
+      if (p.dual > 0.f && A < 0.f) {
+        const float cap = -p.dual * A;
+        if (cap < pg) { pg = cap; clipped = true; }
+      }
+      spg += m * pg;
+      sg += clipped ? 0.f : m * -A;
+      sc += clipped ? m : 0.f;
+    }
+    spg = block_sum(spg, red); sg = block_sum(sg, red); sc = block_sum(sc, red);
+    if (threadIdx.x == 0) {
+      p.w[s] = w;
+      p.c[s] = w * r / nh * sg;
+      st_loss += w * spg; st_pg += spg; st_clip += sc;
+    }
+  }
+  if (threadIdx.x == 0) {                                  // this workgroup's row of the partial sums: the surrogate's columns
+    float* out = p.partial + (size_t)blockIdx.x * PL_NSTAT;
+    out[0] = st_loss; out[1] = st_pg; out[2] = 0.f; out[3] = 0.f; out[4] = st_clip; out[5] = 0.f; out[6] = 0.f; out[7] = 0.f;
+  }
+}
+
 inline bool finite_f(float v) { return v == v && v - v == 0.f; }
 
 }  // namespace
@@ -205,5 +328,52 @@ extern "C" int dta_policy_loss(const float* lp, const float* ent, const int32_t*
   else if (kl_estimator == 1) hipLaunchKernelGGL(policy_loss_kernel<1>, grid, block, 0, st_, p);
   else hipLaunchKernelGGL(policy_loss_kernel<2>, grid, block, 0, st_, p);
   hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb, stats);
+  return DTA_LAUNCH_STATUS();
+}
+
+extern "C" int dta_policy_loss_seq_blocks(int32_t T, int32_t S) {
+  return T <= 0 || S <= 0 ? DTA_EINVAL : row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS) + (S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS);
+}
+
+extern "C" int dta_policy_loss_seq(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                                   const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                                   const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
+                                   int32_t adv_per_seq, float* w, float* c, float* dlp, float* dent, float* partial, float* stats, int32_t T,
+                                   int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip, float kl_coef,
+                                   int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, void* stream) {
+  if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !leaf_run_ptr || !run_row0 || !run_depth0 || !seq_leaf || !mask ||
+      !adv || !w || !c || !dlp || !dent || !partial || !stats || T <= 0 || S <= 0 || M <= 0 || R <= 0)
+    return DTA_EINVAL;
+  if (!finite_f(clip_low) || !finite_f(clip_high) || clip_low < 0.f || clip_high < 0.f) return DTA_EINVAL;
+  if (dual_clip != 0.f && !(finite_f(dual_clip) && dual_clip > 1.f)) return DTA_EINVAL;
+  if (kl_estimator < 0 || kl_estimator > 2 || agg < 0 || agg > 1) return DTA_EINVAL;
+  if (!finite_f(kl_coef) || !finite_f(entropy_coef) || !finite_f(scale)) return DTA_EINVAL;
+  if (kl_coef != 0.f && !ref_lp) return DTA_EINVAL;
+  if (!aligned16(lp) || !aligned16(ent) || !aligned16(depth) || !aligned16(row_seq_lo) || !aligned16(row_seq_hi) || !aligned16(seq_ptr) ||
+      !aligned16(leaf_run_ptr) || !aligned16(run_row0) || !aligned16(run_depth0) || !aligned16(seq_leaf) || !aligned16(mask) ||
+      !aligned16(adv) || !aligned16(w) || !aligned16(c) || !aligned16(dlp) || !aligned16(dent) || !aligned16(partial) || !aligned16(stats) ||
+      (old_lp && !aligned16(old_lp)) || (ref_lp && !aligned16(ref_lp)))
+    return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS), nsb = S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS;
+  SeqPassParams q;
+  q.lp = lp; q.seq_ptr = seq_ptr; q.leaf_run_ptr = leaf_run_ptr; q.run_row0 = run_row0; q.run_depth0 = run_depth0; q.seq_leaf = seq_leaf;
+  q.old_lp = old_lp; q.mask = mask; q.adv = adv; q.w = w; q.c = c; q.partial = partial + (size_t)nb * PL_NSTAT;
+  q.T = T; q.S = S; q.M = M; q.R = R; q.adv_per_seq = adv_per_seq != 0; q.seq_mean = agg == 0;
+  q.lo = 1.f - clip_low; q.hi = 1.f + clip_high; q.dual = dual_clip; q.scale = scale;
+  hipLaunchKernelGGL(policy_seq_pass_kernel, dim3(nsb), dim3(256), 0, st_, q);
+  PolicyParams p;
+  p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
+  p.old_lp = nullptr; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w; p.c = c;
+  p.dlp = dlp; p.dent = dent; p.partial = partial;
+  p.T = T; p.S = S; p.adv_per_seq = adv_per_seq != 0;
+  p.lo = q.lo; p.hi = q.hi; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
+  const dim3 grid(nb), block(PL_BLOCK);
+  if (kl_coef == 0.f) hipLaunchKernelGGL((policy_loss_kernel<-1, true>), grid, block, 0, st_, p);
+  else if (kl_estimator == 0) hipLaunchKernelGGL((policy_loss_kernel<0, true>), grid, block, 0, st_, p);
+  else if (kl_estimator == 1) hipLaunchKernelGGL((policy_loss_kernel<1, true>), grid, block, 0, st_, p);
+  else hipLaunchKernelGGL((policy_loss_kernel<2, true>), grid, block, 0, st_, p);
+  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb + nsb, stats);
   return DTA_LAUNCH_STATUS();
 }

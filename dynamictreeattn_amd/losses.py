@@ -23,6 +23,16 @@ Per token, with lp = logprob[j], A = advantages[j], m = loss_mask[j]:
 
 and the sequence loss is w_s * sum_j term, w_s = scale / max(sum_j m, 1) ("seq_mean") or scale ("token_sum": put 1 / (global
 masked-token count) into ``scale``, which stays correct under data parallelism).  ``entropy[len - 1]`` is not used.
+
+``ratio="sequence"`` is GSPO (the objective Qwen3 and Qwen3-MoE were trained with; ``importance_sampling_level="sequence"`` in TRL and
+verl): every token of a sequence is clipped on ONE ratio, the geometric mean of the masked tokens' ratios,
+
+    r_s  = exp( sum_j m_j (lp_j - old_j) / max(sum_j m_j, 1) )    length-normalised under "token_sum" too; on-policy: r_s == 1
+    pg_j = max(-r_s A_j, -clamp(r_s, 1 - clip_low, 1 + clip_high) A_j);   the dual clip with r_s in place of r
+
+with KL, entropy, mask and w_s as above.  The gradient flows through r_s to every masked token of the sequence (GSPO itself, not the
+stop-gradient "GSPO-token" variant):  d loss_s / d lp_t = c_s m_t + the token-level KL gradient, with the per-sequence scalar
+c_s = w_s r_s / max(sum m, 1) * sum_j m_j (-A_j) [pg_j not clipped].  The fused path evaluates it with ``dta_policy_loss_seq``.
 """
 from __future__ import annotations
 
@@ -31,10 +41,11 @@ from typing import Optional
 
 import torch
 
-__all__ = ["PolicyLoss", "KL_ESTIMATORS", "AGGREGATIONS", "STATS"]
+__all__ = ["PolicyLoss", "KL_ESTIMATORS", "AGGREGATIONS", "RATIOS", "STATS"]
 
 KL_ESTIMATORS = ("k1", "k2", "k3")           # position = the estimator id of dta_policy_loss
 AGGREGATIONS = ("seq_mean", "token_sum")     # position = the aggregation id of dta_policy_loss
+RATIOS = ("token", "sequence")               # importance ratio per prediction (PPO / GRPO) or one per sequence (GSPO: dta_policy_loss_seq)
 # entries of the statistics vector of the fused path (engine.loss_stats), in order
 STATS = ("loss", "sum_pg", "sum_kl", "sum_entropy", "clipped_tokens", "masked_tokens")
 
@@ -48,7 +59,8 @@ def _finite(name: str, v) -> float:
 
 class PolicyLoss:
     def __init__(self, clip_low: float = 0.2, clip_high: float = 0.2, dual_clip: Optional[float] = None, kl_coef: float = 0.0,
-                 kl_estimator: str = "k3", entropy_coef: float = 0.0, agg: str = "seq_mean", scale: float = 1.0):
+                 kl_estimator: str = "k3", entropy_coef: float = 0.0, agg: str = "seq_mean", scale: float = 1.0,
+                 ratio: str = "token"):
         self.clip_low, self.clip_high = _finite("clip_low", clip_low), _finite("clip_high", clip_high)
         if self.clip_low < 0:
             raise ValueError(f"clip_low = {clip_low!r} is negative")
@@ -63,11 +75,14 @@ class PolicyLoss:
             raise ValueError(f"kl_estimator = {kl_estimator!r}: one of {KL_ESTIMATORS}")
         if agg not in AGGREGATIONS:
             raise ValueError(f"agg = {agg!r}: one of {AGGREGATIONS}")
-        self.kl_estimator, self.agg = kl_estimator, agg
+        if ratio not in RATIOS:
+            raise ValueError(f"ratio = {ratio!r}: one of {RATIOS}")
+        self.kl_estimator, self.agg, self.ratio = kl_estimator, agg, ratio
 
     def __repr__(self):
         return (f"PolicyLoss(clip_low={self.clip_low}, clip_high={self.clip_high}, dual_clip={self.dual_clip}, kl_coef={self.kl_coef}, "
-                f"kl_estimator={self.kl_estimator!r}, entropy_coef={self.entropy_coef}, agg={self.agg!r}, scale={self.scale})")
+                f"kl_estimator={self.kl_estimator!r}, entropy_coef={self.entropy_coef}, agg={self.agg!r}, scale={self.scale}, "
+                f"ratio={self.ratio!r})")
 
     # ------------------------------------------------------------------------------------------
     def fields(self, attachment: dict, n: int):
@@ -101,7 +116,16 @@ class PolicyLoss:
         to = lambda v: v.detach().to(device=logprob.device, dtype=logprob.dtype)
         A = torch.full_like(logprob, adv) if isinstance(adv, float) else to(adv)
         old = logprob.detach() if old is None else to(old)
-        r = torch.exp(logprob - old)
+        if self.ratio == "sequence":          # one ratio per sequence: the geometric mean of the masked tokens' ratios, differentiated
+            x = logprob - old
+            if mask is not None:
+                x = to(mask) * x
+                r = torch.exp(x.sum() / torch.clamp(to(mask).sum(), min=1.0))
+            else:
+                r = torch.exp(x.sum() / max(n, 1))
+            r = r.expand(n)
+        else:
+            r = torch.exp(logprob - old)
         pg = torch.maximum(-r * A, -torch.clamp(r, 1.0 - self.clip_low, 1.0 + self.clip_high) * A)
         if self.dual_clip is not None:
             pg = torch.where(A < 0, torch.minimum(pg, -self.dual_clip * A), pg)

@@ -1754,12 +1754,17 @@ def policy_token_inputs(loss, attach_lists, seq_ptr, device):
 
 def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, row_seq_lo: torch.Tensor, row_seq_hi: torch.Tensor,
                 seq_ptr: torch.Tensor, old: Optional[torch.Tensor], ref: Optional[torch.Tensor], mask: torch.Tensor, adv: torch.Tensor,
-                adv_per_seq: bool):
+                adv_per_seq: bool, path_tables=None):
     """The objective `loss` (losses.PolicyLoss) over T packed rows in one C-ABI call: returns (dlp [T], dent [T], stats [8], w [S]), fp32.
     lp / ent: the fp32 row statistics of packed_logprob_entropy (no graph is followed: the caller back-propagates dlp / dent);
     row_seq_lo / row_seq_hi / seq_ptr: packing.policy_row_tables; old / ref / mask / adv: policy_token_inputs.
-    stats = {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0} (losses.STATS); w: the per-sequence weights."""
+    stats = {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0} (losses.STATS); w: the per-sequence weights.
+    loss.ratio == "sequence" (dta_policy_loss_seq) needs path_tables = (leaf_run_ptr, run_row0, run_depth0, seq_leaf), the int32 device
+    tables of packing.policy_path_tables; "token" (dta_policy_loss) takes none."""
     from .losses import AGGREGATIONS, KL_ESTIMATORS
+    seq_level = loss.ratio == "sequence"
+    if seq_level != (path_tables is not None):
+        raise ValueError(f"ratio = {loss.ratio!r}: path_tables (packing.policy_path_tables) go with the sequence-level ratio, and only with it")
     T, S = int(lp.shape[0]), int(seq_ptr.shape[0]) - 1
     def f32(t):                 # fp32, contiguous and on a 16-byte boundary (a view into a larger buffer may start anywhere)
         if t is None:
@@ -1772,13 +1777,29 @@ def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, 
     assert ent.shape[0] == T and depth.shape[0] == T and row_seq_lo.shape[0] == T and row_seq_hi.shape[0] == T
     assert depth.dtype == row_seq_lo.dtype == row_seq_hi.dtype == seq_ptr.dtype == torch.int32
     assert adv.shape[0] == (S if adv_per_seq else N) and (old is None or old.shape[0] == N) and (ref is None or ref.shape[0] == N)
-    nb = lib().dta_policy_loss_blocks(T)
-    # one fp32 buffer: dlp | dent | w | partial | stats, each part a multiple of 4 floats
+    nb = lib().dta_policy_loss_seq_blocks(T, S) if seq_level else lib().dta_policy_loss_blocks(T)
+    # one fp32 buffer: dlp | dent | w | partial | stats (| c), each part a multiple of 4 floats
     r4 = lambda n: (n + 3) // 4 * 4
-    buf = torch.empty(2 * r4(T) + r4(S) + 8 * nb + 8, dtype=torch.float32, device=lp.device)
+    buf = torch.empty(2 * r4(T) + r4(S) + 8 * nb + 8 + (r4(S) if seq_level else 0), dtype=torch.float32, device=lp.device)
     dlp, dent = buf[:T], buf[r4(T):r4(T) + T]
     o = 2 * r4(T)
-    w, partial, stats = buf[o:o + S], buf[o + r4(S):o + r4(S) + 8 * nb], buf[o + r4(S) + 8 * nb:]
+    w, partial, stats = buf[o:o + S], buf[o + r4(S):o + r4(S) + 8 * nb], buf[o + r4(S) + 8 * nb:o + r4(S) + 8 * nb + 8]
+    if seq_level:
+        run_ptr, run_row0, run_depth0, seq_leaf = path_tables
+        _require_cuda(run_ptr, run_row0, run_depth0, seq_leaf)
+        assert run_ptr.dtype == run_row0.dtype == run_depth0.dtype == seq_leaf.dtype == torch.int32
+        M, R = int(run_ptr.shape[0]) - 1, int(run_row0.shape[0])
+        assert seq_leaf.shape[0] == S and run_depth0.shape[0] == R
+        c = buf[o + r4(S) + 8 * nb + 8:][:S]
+        _launch("dta_policy_loss_seq", (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, old, ref,
+                                        mask, adv, buf),
+                ptr(lp), ptr(ent), ptr(depth), ptr(row_seq_lo), ptr(row_seq_hi), ptr(seq_ptr), ptr(run_ptr), ptr(run_row0), ptr(run_depth0),
+                ptr(seq_leaf), ptr(old), ptr(ref), ptr(mask), ptr(adv), int(bool(adv_per_seq)), ptr(w), ptr(c), ptr(dlp), ptr(dent),
+                ptr(partial), ptr(stats), T, S, M, R,
+                float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
+                KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
+                nbytes=4 * (4 * T + (5 + 2 * (old is not None) + (ref is not None)) * N))
+        return dlp, dent, stats, w
     _launch("dta_policy_loss", (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, buf),
             ptr(lp), ptr(ent), ptr(depth), ptr(row_seq_lo), ptr(row_seq_hi), ptr(seq_ptr), ptr(old), ptr(ref), ptr(mask), ptr(adv),
             int(bool(adv_per_seq)), ptr(w), ptr(dlp), ptr(dent), ptr(partial), ptr(stats), T, S,

@@ -428,3 +428,27 @@ def policy_row_tables(plan: SegmentPlan, attach_lists):
     for j, a, b in live:
         close(j, a, b, M)
     return lo, hi, seq_ptr.astype(np.int32), seq_lens
+
+
+def policy_path_tables(plan: SegmentPlan, attach_lists):
+    """Tables of the sequence-level objective (dta_policy_loss_seq), the row <- sequence direction policy_row_tables does not need, from
+    the plan and the attach lists alone (host, no GPU): (leaf_run_ptr int32 [M+1], run_row0 int32 [R], run_depth0 int32 [R],
+    seq_leaf int32 [S]).  The root path of leaf i is a short list of contiguous packed-row runs - plan.path_runs[i], then the leaf's own
+    segment when it is not empty: run k of leaf i, leaf_run_ptr[i] <= k < leaf_run_ptr[i+1], starts at packed row run_row0[k] with the
+    token of depth run_depth0[k] and reaches to the depth the next run of the leaf starts at (the last run: to the leaf's end).  Sequence
+    s (callback order) follows the path of leaf seq_leaf[s] down to depth len_s - 1.  Nothing here is sized by the sum of the lengths."""
+    M = int(getattr(plan, "n_real", plan.M))
+    if len(attach_lists) != M:
+        raise ValueError(f"{len(attach_lists)} attach lists for {M} leaves")
+    ptr, row0, depth0 = np.zeros(M + 1, np.int64), [], []
+    for i in range(M):
+        d = 0
+        for b, e in list(plan.path_runs[i]) + [(int(plan.seg_off[i]), int(plan.seg_off[i + 1]))]:
+            if e > b:
+                row0.append(int(b)); depth0.append(d)
+                d += int(e) - int(b)
+        if any(int(n) > d for _, n in attach_lists[i]):
+            raise ValueError(f"leaf {i}: a sequence longer than the leaf's root path ({d} tokens)")
+        ptr[i + 1] = len(row0)
+    seq_leaf = np.repeat(np.arange(M, dtype=np.int32), [len(a) for a in attach_lists])
+    return ptr.astype(np.int32), np.asarray(row0, np.int32), np.asarray(depth0, np.int32), seq_leaf.astype(np.int32)

@@ -499,13 +499,18 @@ class TreeTrainingEngine:
     def _policy_rows(packed, token_trie, lp, ent, loss):
         """The built-in objective on the packed rows: (dlp [T], dent [T], stats [8]) of ops.policy_loss.  The row -> sequence-range
         tables come from the packing plan on the host and travel in one staged upload; the attachments' per-token tensors are
-        concatenated in callback order (ops.policy_token_inputs)."""
+        concatenated in callback order (ops.policy_token_inputs).  A sequence-level ratio adds the sequence -> row-run tables of
+        packing.policy_path_tables to the same upload."""
         from ._staging import upload
         row_lo, row_hi, seq_ptr, _ = packing.policy_row_tables(packed.plan, token_trie.attach_lists)
+        tables = [row_lo, row_hi, seq_ptr]
+        if loss.ratio == "sequence":
+            tables += packing.policy_path_tables(packed.plan, token_trie.attach_lists)
         dev = packed.tokens.device
-        row_lo_d, row_hi_d, seq_ptr_d = upload([row_lo, row_hi, seq_ptr], dev, np.int32)
+        row_lo_d, row_hi_d, seq_ptr_d, *path_d = upload(tables, dev, np.int32)
         old, ref, mask, adv, adv_per_seq = ops.policy_token_inputs(loss, token_trie.attach_lists, seq_ptr, dev)
-        dlp, dent, stats, _ = ops.policy_loss(loss, lp, ent, packed.depth, row_lo_d, row_hi_d, seq_ptr_d, old, ref, mask, adv, adv_per_seq)
+        dlp, dent, stats, _ = ops.policy_loss(loss, lp, ent, packed.depth, row_lo_d, row_hi_d, seq_ptr_d, old, ref, mask, adv, adv_per_seq,
+                                              tuple(path_d) or None)
         return dlp, dent, stats
 
     # ------------------------------------------------------------------------------------------

@@ -447,6 +447,35 @@ int dta_policy_loss(const float* lp, const float* ent, const int32_t* depth, con
                     float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef,
                     int32_t agg, float scale, void* stream);
 
+/* The same objective with ONE importance ratio per sequence (GSPO; losses.PolicyLoss(ratio="sequence")).  Everything not said here is
+ * as for dta_policy_loss: the numbering of the sequences, the per-token inputs, the row tables, w_s, the KL and entropy terms, dlp / dent
+ * written for every row, no atomics, identical bits for identical calls.  With n^ = max(sum_j m_j, 1) over the predictions of s
+ *       r_s  = exp( sum_j m_j (lp[row(s, j)] - old_lp[.]) / n^ )        (old_lp NULL: r_s = 1; length-normalised under agg 1 too)
+ *       pg_j = max(-r_s A_j, -clamp(r_s, 1 - clip_low, 1 + clip_high) A_j);  dual_clip = c > 1 and A_j < 0:  pg_j = min(pg_j, -c A_j)
+ *       loss += w_s m_j (pg_j + kl_coef kl_j);    d loss / d lp[row(s, t)] = c_s m_t + w_s m_t kl_coef dkl_t,
+ *       c_s  = w_s r_s / n^ * sum_j m_j (-A_j) [-r_s A_j is the active branch of pg_j (ties included)]
+ * (the gradient flows through r_s to every masked token of the sequence).  row(s, j), the packed row of depth j + 1 on the root path
+ * of s, comes from a path table over the M leaves: the path of leaf i is runs [leaf_run_ptr[i], leaf_run_ptr[i+1]) of contiguous packed
+ * rows, root first; run k starts at row run_row0[k] with depth run_depth0[k] and ends where the leaf's next run starts (the last run:
+ * at the leaf's end, which no sequence of the leaf passes); seq_leaf[s] is the leaf of sequence s.  R = leaf_run_ptr[M] runs in all.
+ * Table entries that point outside [0, M), [0, R) or [0, T) are clamped or skipped, never followed.
+ * Three launches on `stream`; their geometry depends on T and S alone:
+ *   sequence pass  one workgroup per sequence (grid-strided past 2048): the runs of its path with the threads strided over each run's
+ *                  rows for sum m and sum m x, the accurate expf for r_s, w[s]; one more sweep of adv / mask for c[s] (a workspace the
+ *                  caller may read afterwards) and the sequence's share of loss, sum m pg and the clipped tokens;
+ *   row pass       the row kernel of dta_policy_loss with c_s m in place of the token's own surrogate gradient;
+ *   reduction      both passes' partials, partial[dta_policy_loss_seq_blocks(T, S)][8], summed in a fixed order into stats[8] (same
+ *                  entries as dta_policy_loss; "clipped" counts the masked tokens whose branch is the clamp or the dual clip).
+ * Refusals come in this order: DTA_EINVAL (a null pointer other than old_lp / ref_lp, T, S, M or R <= 0, then the hyper-parameters
+ * exactly as dta_policy_loss refuses them), DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR. */
+int dta_policy_loss_seq_blocks(int32_t T, int32_t S);   /* rows of the partial workspace [blocks, 8] (float); T <= 0 or S <= 0: DTA_EINVAL */
+int dta_policy_loss_seq(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                        const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                        const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
+                        int32_t adv_per_seq, float* w, float* c, float* dlp, float* dent, float* partial, float* stats, int32_t T,
+                        int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip, float kl_coef,
+                        int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

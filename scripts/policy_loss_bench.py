@@ -10,14 +10,16 @@ Variants (one per process run: --variant)
   lambda   : the same object behind a lambda                          - the per-sequence callback path
   closure  : a hand-written closure of the same objective that uses nothing but torch - runs on any revision of the package; the
              baseline
+--ratio sequence runs every variant with one importance ratio per sequence (GSPO, PolicyLoss(ratio="sequence")); the closure is then
+the hand-written sequence-level objective.
 Old and reference log-probs come from one engine.forward per workload (outside the timed window) and stay on the device.
 
 Per workload and variant: tokens/s over the timed calls (host clock around calls that end in a device synchronise), host milliseconds
 per call (until backward() returns: the loss has landed, the backward is queued), and - from one more call under torch.profiler - the
 number of device launches (kernels and copies) between the last forward kernel of the LM head and the first kernel of its backward:
 the loss stage.  `null` there means the profiler gave no device events, not zero.  One JSON object per run is appended to --out.
-Usage: python scripts/policy_loss_bench.py --variant fused|lambda|closure [--workloads tau2,short] [--steps 4] [--warmup 2]
-       [--out profiles/policy_loss_bench.json]"""
+Usage: python scripts/policy_loss_bench.py --variant fused|lambda|closure [--ratio token|sequence] [--workloads tau2,short] [--steps 4]
+       [--warmup 2] [--out profiles/policy_loss_bench.json]"""
 import argparse
 import json
 import os
@@ -46,11 +48,23 @@ def closure_loss(logprob, entropy, att):
     return (m * term).sum() / torch.clamp(m.sum(), min=1.0)
 
 
-def loss_of(variant):
+def closure_loss_seq(logprob, entropy, att):
+    """The same with ratio="sequence": every token of the sequence is clipped on the geometric mean of the masked tokens' ratios."""
+    A, m = att["advantages"], att["loss_mask"].to(logprob.dtype)
+    n = torch.clamp(m.sum(), min=1.0)
+    r = torch.exp((m * (logprob - att["old_logprobs"])).sum() / n)
+    pg = torch.maximum(-r * A, -torch.clamp(r, 1.0 - CLIP_LOW, 1.0 + CLIP_HIGH) * A)
+    d = att["ref_logprobs"] - logprob
+    term = pg + KL_COEF * (torch.exp(d) - d - 1.0) - ENT_COEF * entropy[:-1]
+    return (m * term).sum() / n
+
+
+def loss_of(variant, ratio="token"):
     if variant == "closure":
-        return closure_loss
+        return closure_loss_seq if ratio == "sequence" else closure_loss
     from dynamictreeattn_amd.losses import PolicyLoss
-    loss = PolicyLoss(clip_low=CLIP_LOW, clip_high=CLIP_HIGH, kl_coef=KL_COEF, kl_estimator="k3", entropy_coef=ENT_COEF)
+    kw = {"ratio": ratio} if ratio != "token" else {}
+    loss = PolicyLoss(clip_low=CLIP_LOW, clip_high=CLIP_HIGH, kl_coef=KL_COEF, kl_estimator="k3", entropy_coef=ENT_COEF, **kw)
     return loss if variant == "fused" else (lambda a, e, att: loss(a, e, att))
 
 
@@ -130,6 +144,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--variant", choices=["fused", "lambda", "closure"], default="fused")
     ap.add_argument("--closure", action="store_true", help="same as --variant closure")
+    ap.add_argument("--ratio", choices=["token", "sequence"], default="token")
     ap.add_argument("--workloads", default="tau2,short")
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)
@@ -141,8 +156,9 @@ if __name__ == "__main__":
     a = ap.parse_args()
     variant = "closure" if a.closure else a.variant
     model = build_model()
-    fn = loss_of(variant)
-    rec = {"metric": "policy_loss_engine_call", "model": "Qwen3-0.6B geometry (random init), bf16", "variant": variant, "label": a.label,
+    fn = loss_of(variant, a.ratio)
+    rec = {"metric": "policy_loss_engine_call", "model": "Qwen3-0.6B geometry (random init), bf16", "variant": variant, "ratio": a.ratio,
+           "label": a.label,
            "steps": a.steps, "warmup": a.warmup, "runs": [run(w, a, model, fn) for w in a.workloads.split(",")]}
     print(json.dumps(rec), flush=True)
     prior = json.load(open(a.out)) if os.path.exists(a.out) else []
