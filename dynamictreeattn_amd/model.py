@@ -289,7 +289,7 @@ def _check_gemma2(c) -> None:
     act = getattr(c, "hidden_activation", None)
     if act != "gelu_pytorch_tanh":
         raise ValueError(f"config.hidden_activation = {act!r} is not supported for gemma2: the MLP kernel computes gelu_pytorch_tanh(gate) * up")
-    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    D = _head_dim(c)
     if D not in (64, 128):
         raise ValueError(f"config.head_dim = {D} is not supported: the attention kernels cover head_dim 64 and 128 (Gemma-2-27B; the 2B / 9B use 256)")
     qs = getattr(c, "query_pre_attn_scalar", None)
@@ -302,7 +302,7 @@ def _check_gemma2(c) -> None:
 
 
 def _check_olmo(c) -> None:
-    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    D = _head_dim(c)
     if D not in (64, 128):
         raise ValueError(f"config.head_dim = {D} is not supported for {c.model_type}: the projection-wide q/k norm kernels cover head_dim 64 and 128")
     for f in ("num_attention_heads", "num_key_value_heads"):
@@ -423,7 +423,7 @@ def _check_olmo_norms(model) -> None:
     """The q_norm / k_norm weights of an OLMo model span the whole projection row: Hq*D and Hkv*D elements (a per-head [D] weight
     is another model's arithmetic)."""
     c = model.config
-    D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+    D = _head_dim(c)
     for l, layer in enumerate(model.model.layers):
         for name, heads in (("q_norm", c.num_attention_heads), ("k_norm", c.num_key_value_heads)):
             w = getattr(getattr(layer.self_attn, name, None), "weight", None)

@@ -246,8 +246,9 @@ class _TreeAttention(torch.autograd.Function):
         q, k, v, out, lse = ctx.saved_tensors
         Hq, Hkv = q.shape[1], k.shape[1]
         if q.shape[0] == k.shape[0]:
-            # the three gradients side by side in ONE [T, Hq+2Hkv, D] buffer, the layout of the fused projection's gradient: _QKVPrep's
-            # backward then transforms dq and dk in place and hands the buffer on - no gather of dv (0.65 ms per step at tau2 size)
+            # the three gradients side by side in ONE [T, Hq+2Hkv, D] buffer, the layout of the fused projection's gradient: the q|k|v
+            # prep's backward recognises it (_fused_grad_buffer: what is built here must satisfy it), transforms dq and dk in place and
+            # hands the buffer on - no gather of dv (0.65 ms per step at tau2 size)
             fused = torch.empty((q.shape[0], Hq + 2 * Hkv, q.shape[2]), dtype=q.dtype, device=q.device)
             dq, dk, dv = fused[:, :Hq], fused[:, Hq:Hq + Hkv], fused[:, Hq + Hkv:]
             attn_bwd_raw(q, k, v, out, dout, lse, ctx.meta, ctx.scale, dk=dk, dv=dv, dq=dq, softcap=ctx.softcap)
@@ -630,6 +631,21 @@ def logprob_entropy(logits2d, labels1d, temperature=1.0, want_entropy=True, tp_g
 # --------------------------------------------------------------------------------------------------
 # Fused decoder-layer row kernels (RMSNorm, head-norm + RoPE, SwiGLU)
 # --------------------------------------------------------------------------------------------------
+def _norm_bwd(entry, x2, w, dy, g_res, stats, tail, need_w):
+    """The backward of the row norms, one `entry` launch (dta_rmsnorm_bwd / dta_layernorm_bwd): (dx shaped as dy, dw | None) of the
+    saved input rows x2 [R, H], the output gradient dy and the residual stream's g_res (or None), `stats` the forward's per-row
+    statistics and `tail` the entry's scalars between H and the dtype.  A frozen norm weight (need_w False) is still read - dx depends
+    on it - but gets no partial slab and no dta_sum_slabs."""
+    R, H = x2.shape
+    dy2 = dy.contiguous().view(R, H)
+    gr = g_res.contiguous().view(R, H) if g_res is not None else None
+    dx = torch.empty_like(x2)
+    part = torch.empty(getattr(lib(), entry + "_blocks")(R), H, dtype=torch.float32, device=x2.device) if need_w else None
+    _launch(entry, (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), *map(ptr, stats), ptr(dx), ptr(part), R, H, *tail, _DT[x2.dtype],
+            nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
+    return dx.view(dy.shape), (sum_slabs(part, w.dtype) if need_w else None)
+
+
 class _RMSNorm(torch.autograd.Function):
     """(x_out, y) = (x + delta, rmsnorm(x + delta) * w); delta may be None (then x_out is x itself).  w_offset != 0 (Gemma: 1):
     y = rmsnorm(x + delta) * (w_offset + w) with the sum formed in fp32 inside the kernel and one rounding."""
@@ -657,16 +673,8 @@ class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_res, dy):
         x2, w, rstd = ctx.saved_tensors
-        R, H = x2.shape
-        dy2 = dy.contiguous().view(R, H)
-        gr = g_res.contiguous().view(R, H) if g_res is not None else None
-        dx = torch.empty_like(x2)
-        need_w = ctx.needs_input_grad[2]          # a frozen norm weight is still read (dx depends on it) but gets no partials and no sum
-        part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, dtype=torch.float32, device=x2.device) if need_w else None
-        _launch("dta_rmsnorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(rstd), ptr(dx), ptr(part), R, H, ctx.off, _DT[x2.dtype],
-                nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
-        dx = dx.view(dy.shape)
-        return dx, (dx if ctx.has_delta else None), (sum_slabs(part, w.dtype) if need_w else None), None, None
+        dx, dw = _norm_bwd("dta_rmsnorm_bwd", x2, w, dy, g_res, (rstd,), (ctx.off,), ctx.needs_input_grad[2])
+        return dx, (dx if ctx.has_delta else None), dw, None, None
 
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float, w_offset: float = 0.0) -> torch.Tensor:
@@ -706,16 +714,8 @@ class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_res, dy):
         x2, w, mean, rstd = ctx.saved_tensors
-        R, H = x2.shape
-        dy2 = dy.contiguous().view(R, H)
-        gr = g_res.contiguous().view(R, H) if g_res is not None else None
-        dx = torch.empty_like(x2)
-        need_w = ctx.needs_input_grad[3]
-        part = torch.empty(lib().dta_layernorm_bwd_blocks(R), H, dtype=torch.float32, device=x2.device) if need_w else None
-        _launch("dta_layernorm_bwd", (x2, w, dy2, gr), ptr(x2), ptr(w), ptr(dy2), ptr(gr), ptr(mean), ptr(rstd), ptr(dx), ptr(part), R, H,
-                _DT[x2.dtype], nbytes=R * H * x2.element_size() * (4 if gr is not None else 3))
-        dx = dx.view(dy.shape)
-        return dx, (dx if ctx.deltas[0] else None), (dx if ctx.deltas[1] else None), (sum_slabs(part, w.dtype) if need_w else None), None
+        dx, dw = _norm_bwd("dta_layernorm_bwd", x2, w, dy, g_res, (mean, rstd), (), ctx.needs_input_grad[3])
+        return dx, (dx if ctx.deltas[0] else None), (dx if ctx.deltas[1] else None), dw, None
 
 
 def layer_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
@@ -727,40 +727,6 @@ def add_layer_norm(x: torch.Tensor, delta_a: Optional[torch.Tensor], delta_b: Op
     """The residual join of the parallel attention || MLP block fused with the next LayerNorm: returns (x + delta_a + delta_b summed
     in fp32 and rounded once, LN of that).  Either delta may be None (delta_b only with delta_a)."""
     return _LayerNorm.apply(x, delta_a, delta_b, w, eps)
-
-
-class _QKVSplit(torch.autograd.Function):
-    """The q|k|v prep of a layer without rotation (Cohere2's full-attention layers): q, k and v are views of the fused projection
-    output [T, Hq+2Hkv, D] - the projection's values bit for bit - and the backward hands back ONE [T, Hq+2Hkv, D] buffer: the one
-    _TreeAttention's backward laid the three gradients out in, when it did, else a copy."""
-
-    @staticmethod
-    def forward(ctx, qkv, Hq, Hkv):
-        T, H3, D = qkv.shape
-        assert H3 == Hq + 2 * Hkv and qkv.is_contiguous()
-        ctx.geom = (T, Hq, Hkv, D, qkv.dtype)
-        return qkv[:, :Hq], qkv[:, Hq:Hq + Hkv], qkv[:, Hq + Hkv:]
-
-    @staticmethod
-    def backward(ctx, dq, dk, dv):
-        T, Hq, Hkv, D, dtype = ctx.geom
-        H3 = Hq + 2 * Hkv
-        base = dv._base
-        in_place = (base is not None and dq._base is base and dk._base is base and base.shape == (T, H3, D) and base.is_contiguous()
-                    and base.dtype == dtype and dq.shape == (T, Hq, D) and dk.shape == (T, Hkv, D) and dv.shape == (T, Hkv, D)
-                    and dq.stride() == dk.stride() == dv.stride() == (H3 * D, D, 1)
-                    and (dq.storage_offset(), dk.storage_offset(), dv.storage_offset()) == (0, Hq * D, (Hq + Hkv) * D))
-        if in_place:
-            return base, None, None
-        d = torch.empty((T, H3, D), dtype=dtype, device=dv.device)
-        d[:, :Hq].copy_(dq); d[:, Hq:Hq + Hkv].copy_(dk); d[:, Hq + Hkv:].copy_(dv)
-        return d, None, None
-
-
-def qkv_prep_nope(qkv: torch.Tensor, Hq: int, Hkv: int):
-    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D] of a layer that applies no RoPE: strided views,
-    no kernel."""
-    return _QKVSplit.apply(qkv, Hq, Hkv)
 
 
 class _RMSNormAdd(torch.autograd.Function):
@@ -783,14 +749,8 @@ class _RMSNormAdd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         y2, w, rstd = ctx.saved_tensors
-        R, H = y2.shape
-        d2 = dout.contiguous().view(R, H)
-        dy = torch.empty_like(y2)
-        need_w = ctx.needs_input_grad[2]
-        part = torch.empty(lib().dta_rmsnorm_bwd_blocks(R), H, dtype=torch.float32, device=y2.device) if need_w else None
-        _launch("dta_rmsnorm_bwd", (y2, w, d2), ptr(y2), ptr(w), ptr(d2), None, ptr(rstd), ptr(dy), ptr(part), R, H, 0.0, _DT[y2.dtype],
-                nbytes=3 * R * H * y2.element_size())
-        return dout, dy.view(dout.shape), (sum_slabs(part, w.dtype) if need_w else None), None
+        dy, dw = _norm_bwd("dta_rmsnorm_bwd", y2, w, dout, None, (rstd,), (0.0,), ctx.needs_input_grad[2])
+        return dout, dy, dw, None
 
 
 def rms_norm_add(res: torch.Tensor, y: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
@@ -799,6 +759,10 @@ def rms_norm_add(res: torch.Tensor, y: torch.Tensor, w: torch.Tensor, eps: float
     return _RMSNormAdd.apply(res, y, w, eps)
 
 
+# A q / k member form is a pair of launch functions over one member x [T, NH, D] of the fused projection output (rows of D contiguous, any
+# token stride): fwd(x, w, cos_sin, arg) -> (y contiguous, the statistic the backward needs | None) and
+# bwd(x, w, cos_sin, dy, stat, dx, need_w, arg) -> dw | None, which writes dx [T, NH, D] (any token stride; may be dy: a lane reads and
+# writes the same 16 bytes, partner values travel through registers).  arg: eps of the norm forms, the pairing of the partial form.
 def _wide_qk_norm_rope_fwd(x, w, cos_sin, eps):
     """One dta_wide_qk_norm_rope_fwd launch over x [T, NH, D] (any token stride), w [NH*D]: (y contiguous, rstd [T])."""
     T, NH, D = x.shape
@@ -811,7 +775,7 @@ def _wide_qk_norm_rope_fwd(x, w, cos_sin, eps):
     return y, rstd
 
 
-def _wide_qk_norm_rope_bwd(x, w, cos_sin, dy, rstd, dx, need_w):
+def _wide_qk_norm_rope_bwd(x, w, cos_sin, dy, rstd, dx, need_w, eps=None):
     """One dta_wide_qk_norm_rope_bwd launch into dx [T, NH, D] (any token stride; may be dy).  Returns dw (None unless need_w)."""
     T, NH, D = x.shape
     if dy.stride(2) != 1:
@@ -832,7 +796,7 @@ def _qk_norm_rope_fwd(x, w, cos_sin, eps):
     return y, rstd
 
 
-def _qk_norm_rope_bwd(x, w, cos_sin, dy, rstd, dx, need_w):
+def _qk_norm_rope_bwd(x, w, cos_sin, dy, rstd, dx, need_w, eps=None):
     """One dta_qk_norm_rope_bwd launch into dx [T, NH, D] (any token stride; may be dy); w None: RoPE only.  Returns dw (None unless
     w is given and need_w)."""
     T, NH, D = x.shape
@@ -845,101 +809,24 @@ def _qk_norm_rope_bwd(x, w, cos_sin, dy, rstd, dx, need_w):
     return sum_slabs(part, w.dtype) if part is not None else None
 
 
-class _QKNormRope(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, cos_sin, eps):
-        _require_cuda(x, cos_sin)
-        T, NH, D = x.shape
-        if x.stride(2) != 1 or x.stride(1) != D:
-            x = x.contiguous()
-        y, rstd = _qk_norm_rope_fwd(x, w, cos_sin, eps)
-        ctx.save_for_backward(x, w if w is not None else cos_sin, cos_sin, rstd if rstd is not None else cos_sin)
-        ctx.has_w = w is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, cos_sin, rstd = ctx.saved_tensors
-        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        dw = _qk_norm_rope_bwd(x, w if ctx.has_w else None, cos_sin, dy, rstd, dx, ctx.needs_input_grad[1])
-        return dx, dw, None, None
-
-
-class _QKVPrep(torch.autograd.Function):
-    """Fused projection output qkv [T, Hq+2Hkv, D] -> (RoPE(norm(q)), RoPE(norm(k)), v).  q and k are read in place
-    from the fused buffer (token stride) and v is returned as a view of it; the backward writes the three
-    gradients straight into ONE [T, Hq+2Hkv, D] buffer (the rope kernels take an output token stride), so
-    the 200 MB concatenation that `split`'s backward would do per layer disappears."""
-
-    @staticmethod
-    def forward(ctx, qkv, wq, wk, cos_sin, eps, Hq, Hkv, wide=False):
-        _require_cuda(qkv, cos_sin)
-        T, H3, D = qkv.shape
-        assert H3 == Hq + 2 * Hkv and qkv.is_contiguous()
-        assert not wide or (wq is not None and wk is not None)
-        ctx.wide = bool(wide)
-        fwd = _wide_qk_norm_rope_fwd if wide else _qk_norm_rope_fwd
-        outs, rstds = [], []
-        for x, w in ((qkv[:, :Hq], wq), (qkv[:, Hq:Hq + Hkv], wk)):
-            y, rstd = fwd(x, w, cos_sin, eps)
-            outs.append(y); rstds.append(rstd if rstd is not None else cos_sin)
-        ctx.save_for_backward(qkv, wq if wq is not None else cos_sin, wk if wk is not None else cos_sin, cos_sin, rstds[0], rstds[1])
-        ctx.has_w = (wq is not None, wk is not None)
-        ctx.heads = (Hq, Hkv)
-        return outs[0], outs[1], qkv[:, Hq + Hkv:]
-
-    @staticmethod
-    def backward(ctx, dq, dk, dv):
-        qkv, wq, wk, cos_sin, rq, rk = ctx.saved_tensors
-        Hq, Hkv = ctx.heads
-        T, H3, D = qkv.shape
-        base = dv._base
-        in_place = (base is not None and dq._base is base and dk._base is base and base.shape == qkv.shape and base.is_contiguous()
-                    and base.dtype == qkv.dtype and dq.shape == (T, Hq, D) and dk.shape == (T, Hkv, D) and dv.shape == (T, Hkv, D)
-                    and dq.stride() == dk.stride() == dv.stride() == (H3 * D, D, 1)
-                    and (dq.storage_offset(), dk.storage_offset(), dv.storage_offset()) == (0, Hq * D, (Hq + Hkv) * D))
-        # in_place: _TreeAttention's backward laid the three gradients out as this function's result; the kernel reads and writes the same
-        # 16 bytes per lane (partner values travel through registers), so dx may be dy
-        d = base if in_place else torch.empty_like(qkv)
-        dws = []
-        for lo, NH, w, rstd, has_w, need_w, dy in ((0, Hq, wq, rq, ctx.has_w[0], ctx.needs_input_grad[1], dq),
-                                                   (Hq, Hkv, wk, rk, ctx.has_w[1], ctx.needs_input_grad[2], dk)):
-            bwd = _wide_qk_norm_rope_bwd if ctx.wide else _qk_norm_rope_bwd
-            dws.append(bwd(qkv[:, lo:lo + NH], w if has_w else None, cos_sin, dy, rstd, d[:, lo:lo + NH], need_w))
-        if not in_place:
-            d[:, Hq + Hkv:].copy_(dv)
-        return d, dws[0], dws[1], None, None, None, None, None
-
-
-def qkv_prep(qkv: torch.Tensor, wq: Optional[torch.Tensor], wk: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float,
-             Hq: int, Hkv: int):
-    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D]."""
-    return _QKVPrep.apply(qkv, wq, wk, cos_sin, eps, Hq, Hkv)
-
-
-def qkv_prep_wide(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, cos_sin: torch.Tensor, eps: float, Hq: int, Hkv: int):
-    """qkv_prep with the projection-wide norms of OLMo-2 / OLMo-3: wq [Hq*D] and wk [Hkv*D] normalise the whole q / k row of a token
-    before the heads are rotated (dta_wide_qk_norm_rope_*).  q and k are read in place, v is a view, the three gradients land in one
-    [T, Hq+2Hkv, D] buffer and a frozen weight gets no partials - as qkv_prep."""
-    return _QKVPrep.apply(qkv, wq, wk, cos_sin, eps, Hq, Hkv, True)
-
-
-def _rope_partial_fwd(x, cos_sin, interleaved):
-    """One dta_rope_partial_fwd launch over x [T, NH, D] (rows of D contiguous, any token stride), cos_sin [T, R]: y contiguous."""
+def _rope_partial_fwd(x, w, cos_sin, interleaved):
+    """One dta_rope_partial_fwd launch over x [T, NH, D] (rows of D contiguous, any token stride), cos_sin [T, R]: (y contiguous, None).
+    The form has no norm: w is None."""
     T, NH, D = x.shape
     R = cos_sin.shape[1]
     y = torch.empty((T, NH, D), dtype=x.dtype, device=x.device)
-    _launch("dta_rope_partial_fwd", (x, cos_sin), ptr(x), ptr(cos_sin), ptr(y), T, NH, D, R, int(bool(interleaved)), x.stride(0), _DT[x.dtype],
+    _launch("dta_rope_partial_fwd", (x, cos_sin), ptr(x), ptr(cos_sin), ptr(y), T, NH, D, R, int(interleaved), x.stride(0), _DT[x.dtype],
             nbytes=2 * T * NH * D * x.element_size() + T * R * 4)
-    return y
+    return y, None
 
 
-def _rope_partial_bwd(cos_sin, dy, dx, interleaved):
-    """One dta_rope_partial_bwd launch into dx [T, NH, D] (any token stride; may be dy)."""
+def _rope_partial_bwd(x, w, cos_sin, dy, stat, dx, need_w, interleaved):
+    """One dta_rope_partial_bwd launch into dx [T, NH, D] (any token stride; may be dy).  The rotation by the negative angle needs
+    neither the input nor a statistic: x, w and stat are None."""
     T, NH, D = dx.shape
     if dy.stride(2) != 1:
         dy = dy.contiguous()
-    _launch("dta_rope_partial_bwd", (cos_sin, dy), ptr(cos_sin), ptr(dy), ptr(dx), T, NH, D, cos_sin.shape[1], int(bool(interleaved)),
+    _launch("dta_rope_partial_bwd", (cos_sin, dy), ptr(cos_sin), ptr(dy), ptr(dx), T, NH, D, cos_sin.shape[1], int(interleaved),
             dy.stride(0), dy.stride(1), dx.stride(0), _DT[dx.dtype], nbytes=2 * T * NH * D * dx.element_size() + T * cos_sin.shape[1] * 4)
 
 
@@ -948,74 +835,123 @@ def _check_partial_table(x, cos_sin):
         raise ValueError(f"partial RoPE: cos_sin must be a contiguous fp32 [T, R] table for x {tuple(x.shape)}, got {cos_sin.dtype} {tuple(cos_sin.shape)}")
 
 
-class _RopePartial(torch.autograd.Function):
+_HEAD_NORM = (_qk_norm_rope_fwd, _qk_norm_rope_bwd)                 # per-head norm + RoPE; w None: RoPE alone
+_WIDE_NORM = (_wide_qk_norm_rope_fwd, _wide_qk_norm_rope_bwd)       # OLMo's projection-wide norm + RoPE
+_PARTIAL = (_rope_partial_fwd, _rope_partial_bwd)                   # partial / interleaved RoPE: keeps nothing but the table for its backward
+
+
+class _Rotate(torch.autograd.Function):
+    """One member form over a single tensor x [T, NH, D] (made contiguous first): what _QKVPrep does to q and to k."""
+
     @staticmethod
-    def forward(ctx, x, cos_sin, interleaved):
+    def forward(ctx, x, w, cos_sin, form, arg):
         _require_cuda(x, cos_sin)
-        _check_partial_table(x, cos_sin)
+        if form is _PARTIAL:
+            _check_partial_table(x, cos_sin)
         if x.stride(2) != 1 or x.stride(1) != x.shape[2]:
             x = x.contiguous()
-        ctx.save_for_backward(cos_sin)
-        ctx.interleaved = bool(interleaved)
-        return _rope_partial_fwd(x, cos_sin, interleaved)
+        y, stat = form[0](x, w, cos_sin, arg)
+        ctx.save_for_backward(None if form is _PARTIAL else x, w, cos_sin, stat)
+        ctx.form, ctx.arg = form, arg
+        return y
 
     @staticmethod
     def backward(ctx, dy):
-        (cos_sin,) = ctx.saved_tensors
+        x, w, cos_sin, stat = ctx.saved_tensors
         dx = torch.empty(dy.shape, dtype=dy.dtype, device=dy.device)
-        _rope_partial_bwd(cos_sin, dy, dx, ctx.interleaved)
-        return dx, None, None
+        return dx, ctx.form[1](x, w, cos_sin, dy, stat, dx, ctx.needs_input_grad[1], ctx.arg), None, None, None
 
 
-class _QKVPrepPartial(torch.autograd.Function):
-    """_QKVPrep for the models that rotate part of the head or pair neighbouring elements (dta_rope_partial_*; no norm, so nothing but
-    the table is saved): q and k are read in place from the fused buffer, v is a view of it, the three gradients land in ONE
-    [T, Hq+2Hkv, D] buffer, and the backward runs in place when _TreeAttention's backward laid them out that way."""
+def _fused_grad_buffer(dq, dk, dv, T, Hq, Hkv, D, dtype):
+    """The fused-gradient-buffer contract: the ONE contiguous [T, Hq+2Hkv, D] buffer of `dtype` whose q | k | v head slices
+    dq, dk and dv are - the layout _TreeAttention.backward writes them in, which is that of the fused projection's gradient - or None
+    when they are anything else (then the caller gathers them into a fresh buffer)."""
+    H3 = Hq + 2 * Hkv
+    base = dv._base
+    in_place = (base is not None and dq._base is base and dk._base is base and base.shape == (T, H3, D) and base.is_contiguous()
+                and base.dtype == dtype and dq.shape == (T, Hq, D) and dk.shape == (T, Hkv, D) and dv.shape == (T, Hkv, D)
+                and dq.stride() == dk.stride() == dv.stride() == (H3 * D, D, 1)
+                and (dq.storage_offset(), dk.storage_offset(), dv.storage_offset()) == (0, Hq * D, (Hq + Hkv) * D))
+    return base if in_place else None
+
+
+class _QKVPrep(torch.autograd.Function):
+    """Fused projection output qkv [T, Hq+2Hkv, D] -> (form(q), form(k), v).  q and k are read in place from the fused buffer (token
+    stride) and v is returned as a view of it; form None (Cohere2's NoPE layers): q and k are views too, no kernel, nothing saved.
+    The backward hands back ONE [T, Hq+2Hkv, D] buffer: the one _TreeAttention's backward laid the three gradients out in
+    (_fused_grad_buffer), transformed in place, else a fresh one the members' backwards write into (the kernels take an output token
+    stride) and dv is copied to - either way without the 200 MB concatenation that `split`'s backward would do per layer."""
 
     @staticmethod
-    def forward(ctx, qkv, cos_sin, Hq, Hkv, interleaved):
-        _require_cuda(qkv, cos_sin)
+    def forward(ctx, qkv, wq, wk, cos_sin, Hq, Hkv, form, arg):
         T, H3, D = qkv.shape
+        ctx.geom, ctx.form, ctx.arg = (T, Hq, Hkv, D, qkv.dtype), form, arg
+        xq, xk, v = qkv[:, :Hq], qkv[:, Hq:Hq + Hkv], qkv[:, Hq + Hkv:]
+        if form is not None:
+            _require_cuda(qkv, cos_sin)
         assert H3 == Hq + 2 * Hkv and qkv.is_contiguous()
-        _check_partial_table(qkv, cos_sin)
-        ctx.save_for_backward(cos_sin)
-        ctx.geom = (T, Hq, Hkv, D, qkv.dtype, bool(interleaved))
-        return _rope_partial_fwd(qkv[:, :Hq], cos_sin, interleaved), _rope_partial_fwd(qkv[:, Hq:Hq + Hkv], cos_sin, interleaved), qkv[:, Hq + Hkv:]
+        if form is None:
+            return xq, xk, v
+        if form is _PARTIAL:
+            _check_partial_table(qkv, cos_sin)
+        (q, sq), (k, sk) = form[0](xq, wq, cos_sin, arg), form[0](xk, wk, cos_sin, arg)
+        ctx.save_for_backward(None if form is _PARTIAL else qkv, wq, wk, cos_sin, sq, sk)
+        return q, k, v
 
     @staticmethod
     def backward(ctx, dq, dk, dv):
-        (cos_sin,) = ctx.saved_tensors
-        T, Hq, Hkv, D, dtype, interleaved = ctx.geom
-        H3 = Hq + 2 * Hkv
-        base = dv._base
-        in_place = (base is not None and dq._base is base and dk._base is base and base.shape == (T, H3, D) and base.is_contiguous()
-                    and base.dtype == dtype and dq.shape == (T, Hq, D) and dk.shape == (T, Hkv, D) and dv.shape == (T, Hkv, D)
-                    and dq.stride() == dk.stride() == dv.stride() == (H3 * D, D, 1)
-                    and (dq.storage_offset(), dk.storage_offset(), dv.storage_offset()) == (0, Hq * D, (Hq + Hkv) * D))
-        d = base if in_place else torch.empty((T, H3, D), dtype=dtype, device=dv.device)
-        _rope_partial_bwd(cos_sin, dq, d[:, :Hq], interleaved)
-        _rope_partial_bwd(cos_sin, dk, d[:, Hq:Hq + Hkv], interleaved)
-        if not in_place:
+        T, Hq, Hkv, D, dtype = ctx.geom
+        fused = _fused_grad_buffer(dq, dk, dv, T, Hq, Hkv, D, dtype)
+        d = fused if fused is not None else torch.empty((T, Hq + 2 * Hkv, D), dtype=dtype, device=dv.device)
+        dwq = dwk = None
+        if ctx.form is not None:
+            qkv, wq, wk, cos_sin, sq, sk = ctx.saved_tensors
+            xq, xk = (qkv[:, :Hq], qkv[:, Hq:Hq + Hkv]) if qkv is not None else (None, None)
+            dwq = ctx.form[1](xq, wq, cos_sin, dq, sq, d[:, :Hq], ctx.needs_input_grad[1], ctx.arg)
+            dwk = ctx.form[1](xk, wk, cos_sin, dk, sk, d[:, Hq:Hq + Hkv], ctx.needs_input_grad[2], ctx.arg)
+        elif fused is None:
+            d[:, :Hq].copy_(dq); d[:, Hq:Hq + Hkv].copy_(dk)
+        if fused is None:
             d[:, Hq + Hkv:].copy_(dv)
-        return d, None, None, None, None
+        return d, dwq, dwk, None, None, None, None, None
+
+
+def qkv_prep(qkv: torch.Tensor, wq: Optional[torch.Tensor], wk: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float,
+             Hq: int, Hkv: int):
+    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D]."""
+    return _QKVPrep.apply(qkv, wq, wk, cos_sin, Hq, Hkv, _HEAD_NORM, eps)
+
+
+def qkv_prep_wide(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, cos_sin: torch.Tensor, eps: float, Hq: int, Hkv: int):
+    """qkv_prep with the projection-wide norms of OLMo-2 / OLMo-3: wq [Hq*D] and wk [Hkv*D] normalise the whole q / k row of a token
+    before the heads are rotated (dta_wide_qk_norm_rope_*).  q and k are read in place, v is a view, the three gradients land in one
+    [T, Hq+2Hkv, D] buffer and a frozen weight gets no partials - as qkv_prep."""
+    assert wq is not None and wk is not None
+    return _QKVPrep.apply(qkv, wq, wk, cos_sin, Hq, Hkv, _WIDE_NORM, eps)
+
+
+def qkv_prep_partial(qkv: torch.Tensor, cos_sin: torch.Tensor, Hq: int, Hkv: int, interleaved: bool):
+    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D] of a model without q/k norms whose RoPE covers
+    the first R = cos_sin.shape[1] elements of the head (rope_partial)."""
+    return _QKVPrep.apply(qkv, None, None, cos_sin, Hq, Hkv, _PARTIAL, bool(interleaved))
+
+
+def qkv_prep_nope(qkv: torch.Tensor, Hq: int, Hkv: int):
+    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D] of a layer that applies no RoPE (Cohere2's
+    full-attention layers): strided views - the projection's values bit for bit - no kernel."""
+    return _QKVPrep.apply(qkv, None, None, None, Hq, Hkv, None, None)
 
 
 def rope_partial(x: torch.Tensor, cos_sin: torch.Tensor, interleaved: bool) -> torch.Tensor:
     """x [T, NH, D] (D = 64 or 128) -> RoPE over the first R = cos_sin.shape[1] elements of every head at the positions encoded in
     cos_sin [T, R] (fp32, rope_cos_sin with R as its D); elements R.. pass through.  interleaved False: the half-split pairing
     i <-> i + R/2 (Phi-3, R % 16 == 0); True: the pairs (2i, 2i+1) (GLM-4, R % 8 == 0)."""
-    return _RopePartial.apply(x, cos_sin, interleaved)
-
-
-def qkv_prep_partial(qkv: torch.Tensor, cos_sin: torch.Tensor, Hq: int, Hkv: int, interleaved: bool):
-    """(q, k, v) for `tree_attention` from the fused projection output [T, Hq+2Hkv, D] of a model without q/k norms whose RoPE covers
-    the first R = cos_sin.shape[1] elements of the head (rope_partial)."""
-    return _QKVPrepPartial.apply(qkv, cos_sin, Hq, Hkv, interleaved)
+    return _Rotate.apply(x, None, cos_sin, _PARTIAL, bool(interleaved))
 
 
 def qk_norm_rope(x: torch.Tensor, w: Optional[torch.Tensor], cos_sin: torch.Tensor, eps: float) -> torch.Tensor:
     """x [T, NH, D] (D = 64 or 128) -> RoPE(RMSNorm_D(x) * w) at the positions encoded in cos_sin [T,D] (fp32)."""
-    return _QKNormRope.apply(x, w, cos_sin, eps)
+    return _Rotate.apply(x, w, cos_sin, _HEAD_NORM, eps)
 
 
 ROPE_TYPES = ("default", "linear", "llama3", "yarn")

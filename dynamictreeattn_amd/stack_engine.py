@@ -32,7 +32,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .model import _cfg_of, _windows_of, attn_args_of, final_softcap_of, head_weight, logit_scale_of, packed_hidden_states
-from .tree_training_engine import sum_loss_terms
+from .tree_training_engine import head_call_args, sum_loss_terms
 from .trie import pop_block_starts
 
 
@@ -194,19 +194,7 @@ class StackWalk:
         else:
             fork_tok = self.tokens.new_zeros(0); g_fork = None; fork_ptr = None; fork_rows = self.tokens.new_zeros(0)
             bounds = [0] * (B // self.head_chunk + 2)
-        kw = {}
-        if self.tp_group is not None:
-            import torch.distributed as dist
-            tp, rk = dist.get_world_size(self.tp_group), dist.get_rank(self.tp_group)
-            Vp = W.shape[0] // tp
-            W = W[rk * Vp:(rk + 1) * Vp]
-            kw = dict(tp_group=self.tp_group, vocab_offset=rk * Vp)
-        cap = final_softcap_of(self.model)
-        if cap:
-            kw.update(softcap=cap, max_picks_per_row=int(np.bincount(rows_np).max()) if F_ else 0)
-        scale = logit_scale_of(self.model)
-        if scale != 1.0:                                                    # Cohere: the statistics of logit_scale * logits
-            kw.update(temperature=1.0 / scale)
+        W, kw = head_call_args(W, self.tp_group, final_softcap_of(self.model), logit_scale_of(self.model), rows)
         lp_next, lp_fork, ent = ops.lm_head_rows(h, W, labels, fork_ptr, fork_tok, fork_rows, bounds, True, self.head_chunk, **kw)
         return lp_next, lp_fork, ent, g_fork
 

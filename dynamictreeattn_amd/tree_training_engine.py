@@ -30,8 +30,8 @@ import torch
 
 from . import ops, packing
 from .losses import STATS as LOSS_STATS, PolicyLoss
-from .model import (ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry, longrope_boundary,
-                    packed_hidden_states)
+from .model import (_head_dim, ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry,
+                    longrope_boundary, packed_hidden_states)
 from .trie import pop_block_starts
 
 __all__ = ["TreeTrainingEngine", "_get_forkpos", "packed_logprob_entropy"]
@@ -61,6 +61,27 @@ def fork_tables_host(fork_child, fork_parent, T: int):
     if fp.size:
         np.cumsum(np.bincount(fp, minlength=T), out=ptr[1:])
     return fc, fp, ptr
+
+
+def head_call_args(W: torch.Tensor, tp_group, softcap: float, logit_scale: float, pick_rows):
+    """(W of this rank, keyword arguments) of an `ops.lm_head_rows` call, from what a model and an engine say about the head - the one
+    place both engines take them from.  With `tp_group` the vocabulary is split across the group (BASELINE config 4;
+    vocab_parallel.py:128-130): this rank multiplies by its contiguous slice of the (tied) head weight only and labels stay global.
+    `softcap` > 0 (model.final_softcap_of): the cap and, for the capped kernel's limit, the largest pick count of one row of `pick_rows`
+    (host, the row of every fork pick of the call).  `logit_scale` != 1 (model.logit_scale_of): the statistics of logit_scale * logits."""
+    kw = {}
+    if tp_group is not None:
+        import torch.distributed as dist
+        tp, rk = dist.get_world_size(tp_group), dist.get_rank(tp_group)
+        Vp = W.shape[0] // tp
+        assert Vp * tp == W.shape[0], "vocabulary must divide by the tensor-parallel size"
+        W = W[rk * Vp:(rk + 1) * Vp]
+        kw.update(tp_group=tp_group, vocab_offset=rk * Vp)
+    if softcap:
+        kw.update(softcap=softcap, max_picks_per_row=int(np.bincount(pick_rows).max()) if len(pick_rows) else 0)
+    if logit_scale != 1.0:
+        kw.update(temperature=1.0 / float(logit_scale))
+    return W, kw
 
 
 def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tensor, parent: torch.Tensor,
@@ -93,22 +114,8 @@ def packed_logprob_entropy(h: torch.Tensor, W: torch.Tensor, tokens: torch.Tenso
         fork_ptr = None
     nxt = torch.cat([tokens[1:], tokens.new_zeros(1)])
     bounds = np.searchsorted(np.asarray(fork_parent), np.arange(0, T + chunk, chunk)).tolist()
-    cap_kw = {}
-    if softcap:
-        cap_kw = dict(softcap=softcap, max_picks_per_row=int(np.bincount(np.asarray(fork_parent, np.int64)).max()) if nF else 0)
-    if logit_scale != 1.0:
-        cap_kw["temperature"] = 1.0 / float(logit_scale)
-    if tp_group is not None:
-        # vocabulary split across the group (BASELINE config 4; vocab_parallel.py:128-130): this rank multiplies by
-        # its contiguous slice of the (tied) head weight only; labels stay global
-        import torch.distributed as dist
-        tp, rk = dist.get_world_size(tp_group), dist.get_rank(tp_group)
-        Vp = W.shape[0] // tp
-        assert Vp * tp == W.shape[0], "vocabulary must divide by the tensor-parallel size"
-        lp_next, lp_fork, ent = ops.lm_head_rows(h, W[rk * Vp:(rk + 1) * Vp], nxt, fork_ptr, ftok, fp_dev, bounds, want_entropy, chunk,
-                                                 tp_group=tp_group, vocab_offset=rk * Vp, **cap_kw)
-    else:
-        lp_next, lp_fork, ent = ops.lm_head_rows(h, W, nxt, fork_ptr, ftok, fp_dev, bounds, want_entropy, chunk, **cap_kw)
+    W, kw = head_call_args(W, tp_group, softcap, logit_scale, np.asarray(fork_parent, np.int64))
+    lp_next, lp_fork, ent = ops.lm_head_rows(h, W, nxt, fork_ptr, ftok, fp_dev, bounds, want_entropy, chunk, **kw)
     chain = torch.zeros(T, dtype=torch.bool, device=dev)           # lp_next[r] = log p(tokens[r+1] | node r)
     chain[1:] = parent[1:] == torch.arange(0, T - 1, device=dev, dtype=parent.dtype)
     lp = torch.cat([lp_next.new_zeros(1), lp_next[:-1]]) * chain
@@ -324,7 +331,7 @@ class TreeTrainingEngine:
         A Cohere layer has ONE norm: it keeps the joined stream in front of it and its one output, which both branches read - two
         rows fewer, 8."""
         c = model.config
-        D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+        D = _head_dim(c)
         L = c.num_hidden_layers
         mlp = sum(_mlp_elems_per_token(c, l) for l in range(L)) / max(L, 1)
         from . import lora
@@ -423,7 +430,7 @@ class TreeTrainingEngine:
         c = model.config
         head = int(2.0 * T * c.vocab_size * 2 + 2 * 4 * c.vocab_size * c.hidden_size)      # logits (+ slack) and the fp32 head gradient
         esz = torch.empty(0, dtype=self.dtype).element_size()
-        D = getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads
+        D = _head_dim(c)
         stash_l = 2 * T * c.hidden_size * esz                                                # (res, delta) kept per RECOMPUTED layer
         attn_l = T * c.num_attention_heads * (D * esz + 4)                                   # (out, lse) kept per recomputed layer ...
         attn_keep = self._attn_keep_planned                                                  # ... within the budget already promised to them

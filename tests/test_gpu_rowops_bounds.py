@@ -214,6 +214,52 @@ def test_qkv_prep_with_the_gradients_in_one_fused_buffer(D, Hq, Hkv, dtype):
     _report(f"qkv_prep D={D} Hq={Hq} Hkv={Hkv}", dtype, worst)
 
 
+def _prep_form(form, qkv, depth, D, Hq, Hkv, dtype):
+    """(q, k, v, the norm weights that take a gradient) of one q|k|v member form over the leaf qkv."""
+    wn = {"head_norm": (D, D), "wide_norm": (Hq * D, Hkv * D)}.get(form, ())
+    ws = [R.norm_weight(n, dtype, 5 + j, False).to(DEV).requires_grad_(True) for j, n in enumerate(wn)]
+    if form == "none":
+        return (*ops.qkv_prep_nope(qkv, Hq, Hkv), ws)
+    if form in ("half_split", "interleaved"):
+        rot = D // 2 if form == "half_split" else D
+        return (*ops.qkv_prep_partial(qkv, ops.rope_cos_sin(depth, rot, 1e6), Hq, Hkv, form == "interleaved"), ws)
+    prep = ops.qkv_prep_wide if form == "wide_norm" else ops.qkv_prep
+    return (*prep(qkv, *(ws or (None, None)), ops.rope_cos_sin(depth, D, 1e6), 1e-6, Hq, Hkv), ws)
+
+
+@pytest.mark.parametrize("dtype", [BF, F32])
+@pytest.mark.parametrize("form", ["none", "rope", "head_norm", "wide_norm", "half_split", "interleaved"])
+@pytest.mark.parametrize("Hq,Hkv", [(4, 4), (3, 1)])
+@pytest.mark.parametrize("D", [64, 128])
+def test_qkv_prep_backward_paths_agree_in_every_form(D, Hq, Hkv, form, dtype):
+    """The two backward paths of every q|k|v member form - no rotation, RoPE alone, per-head norm + RoPE, projection-wide norm + RoPE,
+    half-split partial RoPE over R = D/2, interleaved over R = D - at T = 5 (dead lane groups in the last workgroup), 4 heads per lane
+    group and 1: with dq, dk, dv the slices of ONE [T, Hq+2Hkv, D] buffer the backward returns that buffer; with three tensors of
+    their own it gathers into a fresh one.  The same kernels on the same grid over the same values: both results and both dw pairs are
+    equal bit for bit."""
+    T, H3 = 5, Hq + 2 * Hkv
+    label = f"form={form} Hq={Hq} Hkv={Hkv} D={D}"
+    qkv, _, _, grads = _qk_inputs(T, H3, D, dtype, False, T + H3 + D)
+    depth = torch.randint(0, 131072, (T,), generator=torch.Generator().manual_seed(T + D)).to(DEV)
+    a = qkv.clone().requires_grad_(True)
+    q, k, v, ws = _prep_form(form, a, depth, D, Hq, Hkv, dtype)
+    assert torch.equal(v, qkv[:, Hq + Hkv:])
+    buf = grads.clone()
+    inp = torch.autograd.grad([q, k, v], [a] + ws, [buf[:, :Hq], buf[:, Hq:Hq + Hkv], buf[:, Hq + Hkv:]], retain_graph=True)
+    assert inp[0].data_ptr() == buf.data_ptr(), label + ": the backward did not hand the gradient buffer on"
+    sep = [grads[:, :Hq].clone(), grads[:, Hq:Hq + Hkv].clone(), grads[:, Hq + Hkv:].clone()]         # three tensors of their own
+    out = torch.autograd.grad([q, k, v], [a] + ws, sep)
+    assert out[0].shape == (T, H3, D) and out[0].data_ptr() not in [buf.data_ptr()] + [s.data_ptr() for s in sep]
+    assert len(inp) == len(out) == 1 + len(ws)
+    for x, y in zip(inp, out):
+        assert torch.equal(x, y), label + ": the in-place backward differs from the gathered one"
+    assert torch.equal(inp[0][:, Hq + Hkv:], grads[:, Hq + Hkv:]), label + ": v's gradient slice changed"
+    if form == "none":
+        assert torch.equal(inp[0], grads), label + ": a layer without rotation changed a gradient"
+    else:
+        assert not torch.equal(inp[0][:, :Hq + Hkv], grads[:, :Hq + Hkv]), label + ": the q / k gradients came back untransformed"
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("T,NH,D", [(5462, 3, 128), (16390, 4, 128), (10923, 3, 64), (32771, 4, 64)])
 def test_qk_norm_rope_grid_stride_backward(T, NH, D, dtype):
