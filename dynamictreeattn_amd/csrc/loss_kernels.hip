@@ -11,6 +11,10 @@
 // surrogate's gradient at token t of s is c_s m_t with one scalar c_s per sequence.  A sequence pass (one workgroup per sequence)
 // walks the sequence's root path - a few contiguous row runs - for r_s, w_s, c_s and the surrogate's share of the statistics; the row
 // pass is the one above with c_s m in place of the token's own surrogate gradient; one reduction joins the partials of both.
+//
+// Preference objectives (dta_preference_loss: DPO / cDPO / SimPO, SLiC, IPO): a pair couples two sequences, so a pair pass stands
+// between the sequence pass (u_s, one number per sequence, over the same path walk) and a row pass that sums g_s m with the pair's
+// coefficient g_s; the statistics are per pair and come from the pair pass alone.
 #include "dta_common.h"
 #include "dta_device.h"
 #include <math.h>
@@ -286,6 +290,154 @@ __global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParam
   }
 }
 
+// ---- preference objectives (dta_preference_loss): DPO / cDPO / SimPO, SLiC, IPO --------------------------------------------------
+// A pair couples two sequences, so there is a pair stage between a sequence pass and a row pass: the sequence pass leaves one
+// number u_s per sequence, the pair pass turns the two numbers of a pair into one coefficient g_s per member, and the row pass sums
+// g_s m over the sequences through a row - the same row-major ownership as above, with nothing but the mask to read per term.
+
+constexpr int PF_MAX_BLOCKS = 1024; // grid cap of the pair pass: one thread per pair, the rest grid-strided; one partial row per workgroup
+
+struct PrefSeqParams {
+  const float* lp;
+  const int32_t *seq_ptr, *leaf_run_ptr, *run_row0, *run_depth0, *seq_leaf;
+  const float *ref_lp, *ref_sum, *mask;
+  float *nhat, *u, *sft, *g;
+  int32_t T, S, M, R, length_normalize;
+};
+
+// n^_s, u_s and P_s / n^_s of every sequence, and g_s = 0 (the pair pass overwrites the members of a pair)
+__global__ __launch_bounds__(256) void preference_seq_pass_kernel(const PrefSeqParams p) {
+  __shared__ float red[4];
+  for (int s = blockIdx.x; s < p.S; s += gridDim.x) {      // `s` is the same in every thread of the workgroup
+    const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+    const int leaf = min(max(p.seq_leaf[s], 0), p.M - 1);
+    const int k0 = max(p.leaf_run_ptr[leaf], 0), k1 = min(p.leaf_run_ptr[leaf + 1], p.R);
+    float sm = 0.f, sp = 0.f, sf = 0.f;
+    for (int k = k0; k < k1; ++k) {
+      const int row0 = p.run_row0[k], d0 = p.run_depth0[k];
+      const int da = max(d0, 1), db = min(k + 1 < k1 ? p.run_depth0[k + 1] : n + 1, n + 1);       // depths [da, db) of this run
+      for (int d = da + (int)threadIdx.x; d < db; d += 256) {
+        const int t = row0 + (d - d0), i = b + d - 1;
+        if (t < 0 || t >= p.T) continue;
+        const float m = p.mask[i];
+        sm += m;
+        sp += m * p.lp[t];
+        if (p.ref_lp) sf += m * p.ref_lp[i];
+      }
+    }
+    const float nh = fmaxf(block_sum(sm, red), 1.f);
+    const float P = block_sum(sp, red);
+    const float F = p.ref_lp ? block_sum(sf, red) : p.ref_sum ? p.ref_sum[s] : 0.f;
+    if (threadIdx.x == 0) {
+      p.nhat[s] = nh;
+      p.u[s] = p.length_normalize ? (P - F) / nh : P - F;
+      p.sft[s] = P / nh;
+      p.g[s] = 0.f;
+    }
+  }
+}
+
+struct PrefPairParams {
+  const int32_t *pair_c, *pair_r;
+  const float *nhat, *u, *sft;
+  float *g, *partial;
+  int32_t S, P, kind, length_normalize;
+  float beta, eps, gamma, half_inv_beta, sft_coef, scale;   // half_inv_beta = 1 / (2 beta): the target of "ipo"
+};
+
+__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+// one thread per pair: z, L, the two coefficients and the pair's share of the statistics
+__global__ __launch_bounds__(PL_BLOCK) void preference_pair_kernel(const PrefPairParams p) {
+  __shared__ float red[PL_BLOCK / 64][PL_NSTAT];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float st[PL_NSTAT];
+  for (int i = 0; i < PL_NSTAT; ++i) st[i] = 0.f;
+  for (int q = blockIdx.x * PL_BLOCK + threadIdx.x; q < p.P; q += gridDim.x * PL_BLOCK) {
+    const int c = p.pair_c[q], r = p.pair_r[q];
+    if (c < 0 || c >= p.S || r < 0 || r >= p.S) continue;
+    const float uc = p.u[c], ur = p.u[r], du = uc - ur;
+    float L, dLdu;                                         // the pair's loss and its derivative by u_c (by u_r: the negative)
+    if (p.kind == 2) {
+      const float h = du - p.half_inv_beta;
+      L = h * h; dLdu = 2.f * h;
+    } else {
+      const float z = p.beta * du - p.gamma;
+      float dz;
+      if (p.kind == 0) {
+        const float e = expf(-fabsf(z));                   // in (0, 1]: neither branch can overflow
+        const float sig = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+        L = (1.f - p.eps) * softplus_f(-z) + p.eps * softplus_f(z);
+        dz = sig - (1.f - p.eps);
+      } else {
+        L = fmaxf(0.f, 1.f - z);
+        dz = z < 1.f ? -1.f : 0.f;
+      }
+      dLdu = p.beta * dz;
+    }
+    const float nc = p.nhat[c], sc = p.sft[c];
+    const float a = p.scale * dLdu;
+    p.g[c] = (p.length_normalize ? a / nc : a) - p.scale * p.sft_coef / nc;
+    p.g[r] = -(p.length_normalize ? a / p.nhat[r] : a);
+    st[0] += p.scale * L - p.scale * p.sft_coef * sc;
+    st[1] += L; st[2] += sc;
+    st[3] += p.beta * du; st[4] += p.beta * uc; st[5] += p.beta * ur;
+    st[6] += uc > ur ? 1.f : 0.f; st[7] += 1.f;
+  }
+  for (int i = 0; i < PL_NSTAT; ++i) {
+    const float v = wave_sum(st[i]);
+    if (lane == 0) red[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < PL_NSTAT) {
+    float v = 0.f;
+    for (int wv = 0; wv < PL_BLOCK / 64; ++wv) v += red[wv][threadIdx.x];
+    p.partial[blockIdx.x * PL_NSTAT + threadIdx.x] = v;
+  }
+}
+
+struct PrefRowParams {
+  const int32_t *depth, *row_lo, *row_hi, *seq_ptr;
+  const float *mask, *g;
+  float* dlp;
+  int32_t T, S;
+};
+
+// the term row (depth d >= 1) owns for sequence s: g_s m at prediction d - 1
+__device__ __forceinline__ float pref_term(const PrefRowParams& p, int s, int d) {
+  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+  return n < d ? 0.f : p.g[s] * p.mask[b + d - 1];
+}
+
+// dlp for every row: the row kernel of the policy objective with g_s m as the only term
+__global__ __launch_bounds__(PL_BLOCK) void preference_row_kernel(const PrefRowParams p) {
+  const int lane = threadIdx.x & 63;
+  for (int base = blockIdx.x * PL_BLOCK; base < p.T; base += gridDim.x * PL_BLOCK) {   // `base` is the same in every lane of the workgroup
+    const int t = base + threadIdx.x;
+    const bool live = t < p.T;
+    int d = 0, s0 = 0, s1 = 0;
+    if (live) {
+      d = p.depth[t];
+      if (d >= 1) { s0 = max(p.row_lo[t], 0); s1 = min(p.row_hi[t], p.S); }
+    }
+    const bool wide = s1 - s0 > PL_SERIAL;
+    float v = 0.f;
+    if (!wide)
+      for (int s = s0; s < s1; ++s) v += pref_term(p, s, d);
+    unsigned long long todo = __ballot(wide);
+    while (todo) {                                         // rows with a long range: the wave takes them one after the other
+      const int k = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int dk = __shfl(d, k), b0 = __shfl(s0, k), b1 = __shfl(s1, k);
+      float r = 0.f;
+      for (int s = b0 + lane; s < b1; s += 64) r += pref_term(p, s, dk);
+      r = wave_sum(r);
+      if (lane == k) v = r;
+    }
+    if (live) p.dlp[t] = v;
+  }
+}
+
 inline bool finite_f(float v) { return v == v && v - v == 0.f; }
 
 }  // namespace
@@ -375,5 +527,50 @@ extern "C" int dta_policy_loss_seq(const float* lp, const float* ent, const int3
   else if (kl_estimator == 1) hipLaunchKernelGGL((policy_loss_kernel<1, true>), grid, block, 0, st_, p);
   else hipLaunchKernelGGL((policy_loss_kernel<2, true>), grid, block, 0, st_, p);
   hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb + nsb, stats);
+  return DTA_LAUNCH_STATUS();
+}
+
+extern "C" int dta_preference_loss_blocks(int32_t T, int32_t S, int32_t P) {
+  return T <= 0 || S <= 0 || P <= 0 ? DTA_EINVAL : row_blocks(P, PL_BLOCK, PF_MAX_BLOCKS);
+}
+
+extern "C" int dta_preference_loss(const float* lp, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                                   const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                                   const int32_t* seq_leaf, const int32_t* pair_c, const int32_t* pair_r, const float* ref_lp,
+                                   const float* ref_sum, const float* mask, float* nhat, float* u, float* sft, float* g, float* dlp,
+                                   float* partial, float* stats, int32_t T, int32_t S, int32_t M, int32_t R, int32_t P, int32_t kind,
+                                   float beta, float label_smoothing, float gamma, int32_t length_normalize, int32_t reference_free,
+                                   float sft_coef, float scale, void* stream) {
+  if (!lp || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !leaf_run_ptr || !run_row0 || !run_depth0 || !seq_leaf || !pair_c ||
+      !pair_r || !mask || !nhat || !u || !sft || !g || !dlp || !partial || !stats || T <= 0 || S <= 0 || M <= 0 || R <= 0 || P <= 0)
+    return DTA_EINVAL;
+  if (kind < 0 || kind > 2) return DTA_EINVAL;
+  if (!finite_f(beta) || !finite_f(label_smoothing) || !finite_f(gamma) || !finite_f(sft_coef) || !finite_f(scale)) return DTA_EINVAL;
+  if (!(beta > 0.f) || label_smoothing < 0.f || !(label_smoothing < 0.5f) || (label_smoothing != 0.f && kind != 0)) return DTA_EINVAL;
+  if ((kind == 2 && gamma != 0.f) || sft_coef < 0.f) return DTA_EINVAL;
+  if (!reference_free && (ref_lp != nullptr) == (ref_sum != nullptr)) return DTA_EINVAL;      // exactly one form of the reference
+  if (reference_free) ref_lp = ref_sum = nullptr;                                             // neither is read
+  if (!aligned16(lp) || !aligned16(depth) || !aligned16(row_seq_lo) || !aligned16(row_seq_hi) || !aligned16(seq_ptr) ||
+      !aligned16(leaf_run_ptr) || !aligned16(run_row0) || !aligned16(run_depth0) || !aligned16(seq_leaf) || !aligned16(pair_c) ||
+      !aligned16(pair_r) || !aligned16(mask) || !aligned16(nhat) || !aligned16(u) || !aligned16(sft) || !aligned16(g) || !aligned16(dlp) ||
+      !aligned16(partial) || !aligned16(stats) || (ref_lp && !aligned16(ref_lp)) || (ref_sum && !aligned16(ref_sum)))
+    return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  PrefSeqParams q;
+  q.lp = lp; q.seq_ptr = seq_ptr; q.leaf_run_ptr = leaf_run_ptr; q.run_row0 = run_row0; q.run_depth0 = run_depth0; q.seq_leaf = seq_leaf;
+  q.ref_lp = ref_lp; q.ref_sum = ref_sum; q.mask = mask; q.nhat = nhat; q.u = u; q.sft = sft; q.g = g;
+  q.T = T; q.S = S; q.M = M; q.R = R; q.length_normalize = length_normalize != 0;
+  hipLaunchKernelGGL(preference_seq_pass_kernel, dim3(S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS), dim3(256), 0, st_, q);
+  PrefPairParams c;
+  c.pair_c = pair_c; c.pair_r = pair_r; c.nhat = nhat; c.u = u; c.sft = sft; c.g = g; c.partial = partial;
+  c.S = S; c.P = P; c.kind = kind; c.length_normalize = q.length_normalize;
+  c.beta = beta; c.eps = label_smoothing; c.gamma = gamma; c.half_inv_beta = 1.f / (2.f * beta); c.sft_coef = sft_coef; c.scale = scale;
+  const int npb = row_blocks(P, PL_BLOCK, PF_MAX_BLOCKS);
+  hipLaunchKernelGGL(preference_pair_kernel, dim3(npb), dim3(PL_BLOCK), 0, st_, c);
+  PrefRowParams r;
+  r.depth = depth; r.row_lo = row_seq_lo; r.row_hi = row_seq_hi; r.seq_ptr = seq_ptr; r.mask = mask; r.g = g; r.dlp = dlp; r.T = T; r.S = S;
+  hipLaunchKernelGGL(preference_row_kernel, dim3(row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS)), dim3(PL_BLOCK), 0, st_, r);
+  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, npb, stats);
   return DTA_LAUNCH_STATUS();
 }

@@ -164,3 +164,22 @@ class GradReducer:
 
 
 OverlappedGradAllReduce = GradReducer      # round-1 name
+
+
+def rejoin_pairs(bins: Sequence[Sequence[int]], pair_ids: Sequence, chosen: Optional[Sequence[bool]] = None) -> List[List[int]]:
+    """New bins in which every (chosen, rejected) pair of a preference objective sits in one bin.  The LB_by_* balancers bin single
+    sequences and may split a pair; a trie that holds half a pair is refused (packing.preference_pair_tables).  `pair_ids[i]` is the
+    pair id of original sequence i (None: not in a pair), `chosen[i]` whether it is the chosen member.  The rejected member moves into
+    its chosen member's bin, behind what that bin held before it in bin order (without `chosen`: the member met second in bin order
+    moves to the first), so every sequence is kept exactly once and bins that hold whole pairs are unchanged.  Host only, deterministic."""
+    home, out = {}, [[] for _ in bins]
+    for k, b in enumerate(bins):
+        for i in b:
+            pid = pair_ids[i]
+            if pid is not None and (pid not in home or (chosen is not None and chosen[i])):
+                home[pid] = k
+    for k, b in enumerate(bins):
+        for i in b:
+            pid = pair_ids[i]
+            out[k if pid is None else home[pid]].append(int(i))
+    return out

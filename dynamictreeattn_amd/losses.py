@@ -33,6 +33,9 @@ verl): every token of a sequence is clipped on ONE ratio, the geometric mean of 
 with KL, entropy, mask and w_s as above.  The gradient flows through r_s to every masked token of the sequence (GSPO itself, not the
 stop-gradient "GSPO-token" variant):  d loss_s / d lp_t = c_s m_t + the token-level KL gradient, with the per-sequence scalar
 c_s = w_s r_s / max(sum m, 1) * sum_j m_j (-A_j) [pg_j not clipped].  The fused path evaluates it with ``dta_policy_loss_seq``.
+
+``PreferenceLoss`` (DPO / cDPO / SimPO, SLiC, IPO) couples a chosen and a rejected sequence and is therefore no per-sequence callback:
+see the class.  ``two_pass_backward`` runs it through any engine with a ``forward`` / ``backward`` surface.
 """
 from __future__ import annotations
 
@@ -41,13 +44,17 @@ from typing import Optional
 
 import torch
 
-__all__ = ["PolicyLoss", "KL_ESTIMATORS", "AGGREGATIONS", "RATIOS", "STATS"]
+__all__ = ["PolicyLoss", "KL_ESTIMATORS", "AGGREGATIONS", "RATIOS", "STATS", "PreferenceLoss", "PREFERENCE_KINDS", "PREFERENCE_STATS",
+           "two_pass_backward"]
 
 KL_ESTIMATORS = ("k1", "k2", "k3")           # position = the estimator id of dta_policy_loss
 AGGREGATIONS = ("seq_mean", "token_sum")     # position = the aggregation id of dta_policy_loss
 RATIOS = ("token", "sequence")               # importance ratio per prediction (PPO / GRPO) or one per sequence (GSPO: dta_policy_loss_seq)
 # entries of the statistics vector of the fused path (engine.loss_stats), in order
 STATS = ("loss", "sum_pg", "sum_kl", "sum_entropy", "clipped_tokens", "masked_tokens")
+PREFERENCE_KINDS = ("sigmoid", "hinge", "ipo")   # position = the kind id of dta_preference_loss
+# entries of the statistics vector of a PreferenceLoss (engine.loss_stats), in order
+PREFERENCE_STATS = ("loss", "sum_pair_loss", "sum_sft", "reward_margin", "chosen_reward", "rejected_reward", "correct_pairs", "pairs")
 
 
 def _finite(name: str, v) -> float:
@@ -143,3 +150,171 @@ class PolicyLoss:
         else:
             w = self.scale / max(n, 1) if self.agg == "seq_mean" else self.scale
         return w * term.sum()
+
+
+# --------------------------------------------------------------------------------------------------
+# Preference objectives: DPO / cDPO / SimPO ("sigmoid"), SLiC ("hinge"), IPO ("ipo")
+# --------------------------------------------------------------------------------------------------
+def _softplus(x: torch.Tensor) -> torch.Tensor:
+    return torch.clamp(x, min=0.0) + torch.log1p(torch.exp(-x.abs()))      # exact in every range (F.softplus switches form at 20)
+
+
+class PreferenceLoss:
+    """A pair objective over (chosen, rejected) completions.  It couples two sequences - the loss of a pair needs the summed
+    log-probability of both members before either gradient is known - so it is NOT a per-sequence ``loss_fn``: ``__call__`` raises.
+    Hand the object itself to ``TreeTrainingEngine.backward``: the packed pass evaluates it in one C-ABI call over the packed rows
+    (``ops.preference_loss``, ``dta_preference_loss``); the block-wise walk and ``two_pass_backward`` use the two-pass form.
+
+    Attachment keys, per sequence of ``len`` tokens (n = len - 1, index j the prediction of token j + 1, as for PolicyLoss):
+
+        pair_id          hashable                                    required; each id exactly twice in a trie
+        chosen           bool                                        required; once True and once False per pair_id
+        loss_mask        bool or float tensor [n]; absent = all ones (normally zero over the prompt)
+        ref_logprobs     tensor [n]                                  per-token reference log-probs, or
+        ref_logprob_sum  float                                       their already masked sum
+
+    exactly one form of the reference in a call and for every sequence of it; with ``reference_free`` neither is read.  Per sequence s
+
+        n^ = max(sum m, 1),  P = sum_j m_j lp_j,  F = sum_j m_j ref_j | ref_logprob_sum | 0,  u = (P - F) / (n^ if length_normalize else 1)
+
+    and per pair (c, r), z = beta (u_c - u_r) - gamma:
+
+        "sigmoid"  L = (1 - eps) softplus(-z) + eps softplus(z)      DPO; eps = label_smoothing > 0: cDPO; reference_free +
+                                                                     length_normalize + gamma: SimPO
+        "hinge"    L = max(0, 1 - z)                                 SLiC; a tie z = 1 takes gradient 0
+        "ipo"      L = (u_c - u_r - 1 / (2 beta))^2                  IPO
+
+    total = scale sum_pairs L - scale sft_coef sum_pairs P_c / n^_c  (the NLL term on the chosen completion of RPO / the Llama-3
+    recipe).  Under data parallelism put 1 / (global pair count) into ``scale``.  The gradient is linear in the rows once one
+    coefficient per sequence is known: d total / d lp[row(s, j)] = g_s m_j (``coefficients``).  Entropy is not used."""
+
+    def __init__(self, beta: float = 0.1, kind: str = "sigmoid", label_smoothing: float = 0.0, gamma: float = 0.0,
+                 length_normalize: bool = False, reference_free: bool = False, sft_coef: float = 0.0, scale: float = 1.0):
+        self.beta, self.label_smoothing = _finite("beta", beta), _finite("label_smoothing", label_smoothing)
+        self.gamma, self.sft_coef, self.scale = _finite("gamma", gamma), _finite("sft_coef", sft_coef), _finite("scale", scale)
+        if kind not in PREFERENCE_KINDS:
+            raise ValueError(f"kind = {kind!r}: one of {PREFERENCE_KINDS}")
+        if self.beta <= 0:
+            raise ValueError(f"beta = {beta!r} must be > 0")
+        if not 0 <= self.label_smoothing < 0.5:
+            raise ValueError(f"label_smoothing = {label_smoothing!r} must be in [0, 0.5)")
+        if self.label_smoothing != 0 and kind != "sigmoid":
+            raise ValueError(f"label_smoothing = {label_smoothing!r} goes with kind 'sigmoid' only, not {kind!r}")
+        if self.gamma != 0 and kind == "ipo":
+            raise ValueError(f"gamma = {gamma!r} must be 0 with kind 'ipo'")
+        if self.sft_coef < 0:
+            raise ValueError(f"sft_coef = {sft_coef!r} is negative")
+        self.kind, self.length_normalize, self.reference_free = kind, bool(length_normalize), bool(reference_free)
+
+    def __repr__(self):
+        return (f"PreferenceLoss(beta={self.beta}, kind={self.kind!r}, label_smoothing={self.label_smoothing}, gamma={self.gamma}, "
+                f"length_normalize={self.length_normalize}, reference_free={self.reference_free}, sft_coef={self.sft_coef}, scale={self.scale})")
+
+    def __call__(self, logprob, entropy, attachment):
+        raise TypeError("a PreferenceLoss couples two sequences (chosen and rejected) and cannot be evaluated one sequence at a time: "
+                        "pass the object itself to engine.backward (or to losses.two_pass_backward), not a callback that calls it")
+
+    # ------------------------------------------------------------------------------------------
+    def fields(self, attachment: dict, n: int):
+        """(loss_mask, ref_logprobs, ref_logprob_sum) of one attachment for a sequence with n = len - 1 predictions, checked: the
+        tensors [n] or None, the sum a float or None; with reference_free both reference forms are None (not looked at), otherwise
+        exactly one is given.  pair_id and chosen must be present.  KeyError / ValueError name the key."""
+        for key in ("pair_id", "chosen"):
+            if key not in attachment or attachment[key] is None:
+                raise KeyError(key)
+        mask = attachment.get("loss_mask")
+        ref, ref_sum = (None, None) if self.reference_free else (attachment.get("ref_logprobs"), attachment.get("ref_logprob_sum"))
+        if not self.reference_free and (ref is None) == (ref_sum is None):
+            raise (KeyError("ref_logprobs or ref_logprob_sum (required unless reference_free)") if ref is None else
+                   ValueError("ref_logprobs and ref_logprob_sum are both given: exactly one form of the reference is used"))
+        for key, v in (("ref_logprobs", ref), ("loss_mask", mask)):
+            if v is None:
+                continue
+            if not isinstance(v, torch.Tensor):
+                raise ValueError(f"{key}: a tensor of {n} elements is expected, got {type(v).__name__}")
+            if v.dim() != 1 or v.shape[0] != n:
+                raise ValueError(f"{key}: shape {tuple(v.shape)} where [{n}] (len - 1) is expected")
+        if ref_sum is not None:
+            ref_sum = _finite("ref_logprob_sum", ref_sum)
+        return mask, ref, ref_sum
+
+    def _sequence_sums(self, logprobs, attachments):
+        """(n^ [S], P [S] - differentiable -, F [S], pair_c, pair_r) over the whole list"""
+        from . import packing
+        if len(logprobs) != len(attachments):
+            raise ValueError(f"{len(logprobs)} log-prob tensors for {len(attachments)} attachments")
+        pair_c, pair_r = packing.preference_pair_tables([[(a, int(lp.shape[0]) + 1) for lp, a in zip(logprobs, attachments)]])
+        nh, P, F, forms = [], [], [], set()
+        for lp, att in zip(logprobs, attachments):
+            mask, ref, ref_sum = self.fields(att, int(lp.shape[0]))
+            to = lambda v: v.detach().to(device=lp.device, dtype=lp.dtype)
+            m = torch.ones_like(lp) if mask is None else to(mask)
+            forms.add("ref_logprobs" if ref is not None else "ref_logprob_sum" if ref_sum is not None else None)
+            nh.append(torch.clamp(m.detach().sum(), min=1.0))
+            P.append((m * lp).sum())
+            F.append((m * to(ref)).sum() if ref is not None else torch.as_tensor(0.0 if ref_sum is None else ref_sum, device=lp.device, dtype=lp.dtype))
+        if len(forms) > 1:
+            raise ValueError("ref_logprobs for some sequences and ref_logprob_sum for others: one form of the reference per call")
+        idx = lambda a: torch.as_tensor(a, dtype=torch.long, device=P[0].device)
+        return torch.stack(nh), torch.stack(P), torch.stack(F), idx(pair_c), idx(pair_r)
+
+    def _pair_loss(self, du):
+        """(L, dL/d(u_c - u_r)) per pair"""
+        if self.kind == "ipo":
+            h = du - 1.0 / (2.0 * self.beta)
+            return h * h, 2.0 * h
+        z = self.beta * du - self.gamma
+        if self.kind == "sigmoid":
+            eps = self.label_smoothing
+            return (1.0 - eps) * _softplus(-z) + eps * _softplus(z), self.beta * (torch.sigmoid(z) - (1.0 - eps))
+        return torch.where(z < 1, 1.0 - z, torch.zeros_like(z)), self.beta * torch.where(z < 1, -torch.ones_like(z), torch.zeros_like(z))
+
+    def total(self, logprobs, attachments) -> torch.Tensor:
+        """The DEFINITION: the objective over the whole list of per-sequence log-prob tensors ([len_s - 1] each, lined up with
+        `attachments`), in differentiable torch on any device."""
+        nh, P, F, c, r = self._sequence_sums(logprobs, attachments)
+        u = (P - F) / nh if self.length_normalize else P - F
+        L, _ = self._pair_loss(u[c] - u[r])
+        return self.scale * L.sum() - self.scale * self.sft_coef * (P[c] / nh[c]).sum()
+
+    @torch.no_grad()
+    def coefficients(self, logprobs, attachments):
+        """(total, g [S], stats [8]) from detached log-probs: d total / d logprobs[s][j] = g[s] loss_mask_s[j]; stats in the order of
+        PREFERENCE_STATS.  The first pass of the two-pass form."""
+        nh, P, F, c, r = self._sequence_sums([lp.detach() for lp in logprobs], attachments)
+        N = nh if self.length_normalize else torch.ones_like(nh)
+        u = (P - F) / N
+        du = u[c] - u[r]
+        L, dL = self._pair_loss(du)
+        sft = P[c] / nh[c]
+        g = torch.zeros_like(u)
+        g[c] = self.scale * dL / N[c] - self.scale * self.sft_coef / nh[c]
+        g[r] = -self.scale * dL / N[r]
+        total = self.scale * L.sum() - self.scale * self.sft_coef * sft.sum()
+        stats = torch.stack([total, L.sum(), sft.sum(), (self.beta * du).sum(), (self.beta * u[c]).sum(), (self.beta * u[r]).sum(),
+                             (u[c] > u[r]).to(u.dtype).sum(), torch.as_tensor(float(c.shape[0]), device=u.device, dtype=u.dtype)])
+        return total, g, stats
+
+    def surrogate(self, g):
+        """The linear closure of the second pass: loss_fn(logprob, entropy, attachment) = g[s] (m logprob).sum(), s the attachment's
+        `_sequence_batch_id` - its gradient is the objective's, its value is not."""
+        def loss_fn(logprob, entropy, attachment):
+            mask = attachment.get("loss_mask")
+            x = logprob if mask is None else mask.detach().to(device=logprob.device, dtype=logprob.dtype) * logprob
+            return g[attachment["_sequence_batch_id"]].to(device=logprob.device, dtype=logprob.dtype) * x.sum()
+        return loss_fn
+
+
+def two_pass_backward(engine, model, trie, loss: PreferenceLoss, block_size: int):
+    """A PreferenceLoss through any engine with the `forward(model, trie)` / `backward(model, trie, loss_fn, block_size)` surface,
+    at the cost of one more (no-grad) model forward: `forward` for the sequence log-probs, `loss.coefficients` on them, `backward`
+    with the linear closure g_s (m logprob).sum().  Accumulates the gradient of the true objective and returns
+    (its value as a float, stats [8] in the order of PREFERENCE_STATS)."""
+    logprobs = engine.forward(model, trie)
+    atts = [None] * len(logprobs)
+    for attach_list in trie.attach_lists:
+        for att, _ in attach_list:
+            atts[att["_sequence_batch_id"]] = att
+    total, g, stats = loss.coefficients(logprobs, atts)
+    engine.backward(model, trie, loss.surrogate(g), block_size)
+    return float(total.item()), stats

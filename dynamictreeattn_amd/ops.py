@@ -1646,6 +1646,25 @@ def lora_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], ada
 # --------------------------------------------------------------------------------------------------
 # Policy objective over packed rows (losses.PolicyLoss, dta_policy_loss)
 # --------------------------------------------------------------------------------------------------
+def _cat_per_token(vals, fill, seq_ptr, device):
+    """One fp32 device vector of N = seq_ptr[-1] elements from one entry per sequence (callback order): a tensor [n_s], or None / a float,
+    which stand for `fill` / that float on every token of the sequence.  Entries that all live on the host are concatenated there and
+    uploaded once out of page-locked staging; tensors already on the device are concatenated there."""
+    from ._staging import upload
+    N = int(seq_ptr[-1])
+    lens = np.diff(np.asarray(seq_ptr, np.int64))
+    if all(not isinstance(v, torch.Tensor) or not v.is_cuda for v in vals):
+        host = np.empty(N, np.float32)
+        for v, b, n in zip(vals, seq_ptr[:-1], lens):
+            host[b:b + n] = fill if v is None else v if isinstance(v, float) else v.detach().to(torch.float32).numpy()
+        return upload([host], device, np.float32)[0]
+    if all(isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == vals[0].dtype for v in vals):
+        return torch.cat([v.detach().to(device) for v in vals]).to(torch.float32)       # one concatenation, one cast (bool masks)
+    parts = [torch.full((int(n),), fill if v is None else v, dtype=torch.float32, device=device) if not isinstance(v, torch.Tensor)
+             else v.detach().to(device=device, dtype=torch.float32) for v, n in zip(vals, lens)]
+    return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=device)
+
+
 def policy_token_inputs(loss, attach_lists, seq_ptr, device):
     """The per-token inputs of the fused objective, concatenated in callback order behind seq_ptr: (old, ref, mask, adv, adv_per_seq), fp32
     device vectors of N = seq_ptr[-1] elements (old / ref None: on-policy / no KL; adv one value per sequence when every attachment gives
@@ -1662,22 +1681,7 @@ def policy_token_inputs(loss, attach_lists, seq_ptr, device):
             adv, old, ref, mask = loss.fields(attachment, n)
             cols["adv"].append(adv); cols["old"].append(old); cols["ref"].append(ref); cols["mask"].append(mask)
             s += 1
-    S, N = s, int(seq_ptr[-1])
-    lens = np.diff(np.asarray(seq_ptr, np.int64))
-
-    def cat(vals, fill):
-        """fp32 [N] on the device; a None / float entry stands for `fill` / that float on every token of its sequence"""
-        if all(not isinstance(v, torch.Tensor) or not v.is_cuda for v in vals):
-            host = np.empty(N, np.float32)
-            for v, b, n in zip(vals, seq_ptr[:-1], lens):
-                host[b:b + n] = fill if v is None else v if isinstance(v, float) else v.detach().to(torch.float32).numpy()
-            return upload([host], device, np.float32)[0]
-        if all(isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == vals[0].dtype for v in vals):
-            return torch.cat([v.detach().to(device) for v in vals]).to(torch.float32)       # one concatenation, one cast (bool masks)
-        parts = [torch.full((int(n),), fill if v is None else v, dtype=torch.float32, device=device) if not isinstance(v, torch.Tensor)
-                 else v.detach().to(device=device, dtype=torch.float32) for v, n in zip(vals, lens)]
-        return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=device)
-
+    cat = lambda vals, fill: _cat_per_token(vals, fill, seq_ptr, device)
     if any(v is None for v in cols["old"]) and not all(v is None for v in cols["old"]):
         raise ValueError("old_logprobs: given for some sequences of the trie and absent for others")
     old = None if all(v is None for v in cols["old"]) else cat(cols["old"], 0.0)
@@ -1743,3 +1747,83 @@ def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, 
             KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
             nbytes=4 * (4 * T + (3 + (old is not None) + (ref is not None)) * N))
     return dlp, dent, stats, w
+
+
+# --------------------------------------------------------------------------------------------------
+# Preference objectives over packed rows (losses.PreferenceLoss, dta_preference_loss)
+# --------------------------------------------------------------------------------------------------
+def preference_token_inputs(loss, attach_lists, seq_ptr, device):
+    """The per-token and per-sequence inputs of the fused preference objective in callback order: (ref_lp, ref_sum, mask) - mask fp32 [N]
+    (N = seq_ptr[-1]); the reference as per-token log-probs ref_lp fp32 [N] or as masked sums ref_sum fp32 [S], the other None; both None
+    with loss.reference_free.  Each key is checked as PreferenceLoss.fields checks it, and one form of the reference must serve every
+    sequence.  Staging as policy_token_inputs (_cat_per_token)."""
+    from ._staging import upload
+    masks, refs, sums = [], [], []
+    s = 0
+    for attach_list in attach_lists:
+        for attachment, length in attach_list:
+            n = int(length) - 1
+            if n != int(seq_ptr[s + 1]) - int(seq_ptr[s]):
+                raise ValueError("attach lists and seq_ptr disagree")
+            mask, ref, ref_sum = loss.fields(attachment, n)
+            masks.append(mask); refs.append(ref); sums.append(ref_sum)
+            s += 1
+    if not loss.reference_free and any(v is None for v in refs) and any(v is None for v in sums):
+        raise ValueError("ref_logprobs for some sequences of the trie and ref_logprob_sum for others: one form of the reference per call")
+
+    cat = lambda vals, fill: _cat_per_token(vals, fill, seq_ptr, device)
+    mask = cat(masks, 1.0)
+    per_token = not loss.reference_free and all(v is not None for v in refs)
+    ref_lp = cat(refs, 0.0) if per_token else None
+    ref_sum = None if loss.reference_free or per_token else upload([np.asarray(sums, np.float32)], device, np.float32)[0]
+    return ref_lp, ref_sum, mask
+
+
+def preference_loss(loss, lp: torch.Tensor, depth: torch.Tensor, row_seq_lo: torch.Tensor, row_seq_hi: torch.Tensor, seq_ptr: torch.Tensor,
+                    path_tables, pair_tables, ref_lp: Optional[torch.Tensor], ref_sum: Optional[torch.Tensor], mask: torch.Tensor):
+    """The objective `loss` (losses.PreferenceLoss) over T packed rows in one C-ABI call (dta_preference_loss): returns
+    (dlp [T], stats [8], g [S], u [S]), fp32.  lp: the fp32 row log-probs of packed_logprob_entropy (no graph is followed: the caller
+    back-propagates dlp); row_seq_lo / row_seq_hi / seq_ptr: packing.policy_row_tables; path_tables = (leaf_run_ptr, run_row0,
+    run_depth0, seq_leaf): packing.policy_path_tables; pair_tables = (pair_c, pair_r): packing.preference_pair_tables - all int32 on the
+    device; ref_lp / ref_sum / mask: preference_token_inputs.  stats in the order of losses.PREFERENCE_STATS; g: the per-sequence
+    gradient coefficients (d loss / d lp[row(s, j)] = g[s] mask[j]); u: the per-sequence (length-normalised) log-ratio sums."""
+    from .losses import PREFERENCE_KINDS
+    T, S = int(lp.shape[0]), int(seq_ptr.shape[0]) - 1
+    def f32(t):                 # fp32, contiguous and on a 16-byte boundary (a view into a larger buffer may start anywhere)
+        if t is None:
+            return None
+        t = t.detach().to(torch.float32).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    lp, ref_lp, ref_sum, mask = f32(lp), f32(ref_lp), f32(ref_sum), f32(mask)
+    run_ptr, run_row0, run_depth0, seq_leaf = path_tables
+    pair_c, pair_r = pair_tables
+    _require_cuda(lp, depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r, ref_lp, ref_sum, mask)
+    N, P = int(mask.shape[0]), int(pair_c.shape[0])
+    M, R = int(run_ptr.shape[0]) - 1, int(run_row0.shape[0])
+    if loss.reference_free:
+        ref_lp = ref_sum = None
+    elif (ref_lp is None) == (ref_sum is None):
+        raise ValueError("exactly one of ref_lp and ref_sum is needed (neither with reference_free)")
+    if 2 * P != S:
+        raise ValueError(f"{P} pairs for {S} sequences: every sequence of the trie is a member of exactly one pair")
+    assert depth.shape[0] == T and row_seq_lo.shape[0] == T and row_seq_hi.shape[0] == T and seq_leaf.shape[0] == S
+    assert run_depth0.shape[0] == R and pair_r.shape[0] == P
+    assert all(t.dtype == torch.int32 for t in (depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r))
+    assert (ref_lp is None or ref_lp.shape[0] == N) and (ref_sum is None or ref_sum.shape[0] == S)
+    nb = lib().dta_preference_loss_blocks(T, S, P)
+    # one fp32 buffer: dlp | nhat | u | sft | g | partial | stats, each part a multiple of 4 floats
+    r4 = lambda n: (n + 3) // 4 * 4
+    buf = torch.empty(r4(T) + 4 * r4(S) + 8 * nb + 8, dtype=torch.float32, device=lp.device)
+    o = r4(T)
+    dlp = buf[:T]
+    nhat, u, sft, g = (buf[o + k * r4(S):o + k * r4(S) + S] for k in range(4))
+    o += 4 * r4(S)
+    partial, stats = buf[o:o + 8 * nb], buf[o + 8 * nb:o + 8 * nb + 8]
+    _launch("dta_preference_loss", (lp, depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r, ref_lp,
+                                    ref_sum, mask, buf),
+            ptr(lp), ptr(depth), ptr(row_seq_lo), ptr(row_seq_hi), ptr(seq_ptr), ptr(run_ptr), ptr(run_row0), ptr(run_depth0), ptr(seq_leaf),
+            ptr(pair_c), ptr(pair_r), ptr(ref_lp), ptr(ref_sum), ptr(mask), ptr(nhat), ptr(u), ptr(sft), ptr(g), ptr(dlp), ptr(partial),
+            ptr(stats), T, S, M, R, P, PREFERENCE_KINDS.index(loss.kind), float(loss.beta), float(loss.label_smoothing), float(loss.gamma),
+            int(loss.length_normalize), int(loss.reference_free), float(loss.sft_coef), float(loss.scale),
+            nbytes=4 * (5 * T + (2 + (ref_lp is not None)) * N))
+    return dlp, stats, g, u

@@ -452,3 +452,33 @@ def policy_path_tables(plan: SegmentPlan, attach_lists):
         ptr[i + 1] = len(row0)
     seq_leaf = np.repeat(np.arange(M, dtype=np.int32), [len(a) for a in attach_lists])
     return ptr.astype(np.int32), np.asarray(row0, np.int32), np.asarray(depth0, np.int32), seq_leaf.astype(np.int32)
+
+
+def preference_pair_tables(attach_lists):
+    """The pairs of a preference objective (losses.PreferenceLoss, dta_preference_loss), from the attach lists alone (host, no GPU):
+    (pair_c int32 [P], pair_r int32 [P]), the chosen and the rejected member of every pair as sequence indices in callback order, the
+    pairs sorted by their chosen member's index.  Every attachment carries `pair_id` (hashable) and `chosen` (bool); each pair_id must
+    occur exactly twice in the trie, once chosen and once not - anything else is a ValueError that names the pair_id.  The two members
+    may be the same token string: they then share a leaf and are two entries of its attach list."""
+    members = {}                                    # pair_id -> [chosen index or None, rejected index or None]
+    s = 0
+    for attach_list in attach_lists:
+        for attachment, _ in attach_list:
+            for key in ("pair_id", "chosen"):
+                if key not in attachment or attachment[key] is None:
+                    raise KeyError(f"{key} (sequence {s} in callback order)")
+            pid, k = attachment["pair_id"], 0 if bool(attachment["chosen"]) else 1
+            slot = members.setdefault(pid, [None, None, 0])
+            slot[2] += 1
+            if slot[2] > 2:
+                raise ValueError(f"pair_id {pid!r} occurs more than twice in the trie: a pair is one chosen and one rejected sequence")
+            if slot[k] is not None:
+                raise ValueError(f"pair_id {pid!r} has two {'chosen' if k == 0 else 'rejected'} members: a pair is one chosen and one rejected sequence")
+            slot[k] = s
+            s += 1
+    for pid, (c, r, _) in members.items():
+        if c is None or r is None:
+            raise ValueError(f"pair_id {pid!r} has no {'chosen' if c is None else 'rejected'} member in this trie: both members of a pair "
+                             f"must be in the same trie (dp.rejoin_pairs keeps them in one bin)")
+    pairs = sorted((c, r) for c, r, _ in members.values())
+    return np.asarray([c for c, _ in pairs], np.int32), np.asarray([r for _, r in pairs], np.int32)

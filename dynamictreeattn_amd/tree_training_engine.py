@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .losses import STATS as LOSS_STATS, PolicyLoss
+from .losses import PREFERENCE_STATS, STATS as LOSS_STATS, PolicyLoss, PreferenceLoss
 from .model import (_head_dim, ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry,
                     longrope_boundary, packed_hidden_states)
 from .trie import pop_block_starts
@@ -269,8 +269,8 @@ class TreeTrainingEngine:
         self._attn_keep_planned = 0
         self.stack_fp32_grads = True                     # block-wise walk: sum the blocks' parameter gradients in fp32 (False: model dtype, as the reference)
         self.longrope_factors = "auto"                   # longrope models: "auto" (by the trie's sequence lengths) / "short" / "long"
-        self.last_loss_path: Optional[str] = None        # how the last backward() evaluated the loss: "fused" (a losses.PolicyLoss on the packed rows) / "callback"
-        self.loss_stats: Optional[torch.Tensor] = None   # fused path: device vector in the order of losses.STATS, not synchronised; None on the callback path
+        self.last_loss_path: Optional[str] = None        # how the last backward() evaluated the loss: "fused" (a losses.PolicyLoss / PreferenceLoss on the packed rows) / "two_pass" (a PreferenceLoss on the block-wise walk) / "callback"
+        self.loss_stats: Optional[torch.Tensor] = None   # fused / two_pass: device vector in the order of losses.STATS (PREFERENCE_STATS for a PreferenceLoss), not synchronised; None on the callback path
 
     # ------------------------------------------------------------------------------------------
     def _pack(self, token_trie) -> _PackedTrie:
@@ -520,6 +520,38 @@ class TreeTrainingEngine:
                                               tuple(path_d) or None)
         return dlp, dent, stats
 
+    @staticmethod
+    def _preference_rows(packed, token_trie, lp, loss):
+        """A preference objective on the packed rows: (dlp [T], stats [8]) of ops.preference_loss.  The row tables, the path tables and the
+        pair tables come from the packing plan and the attach lists on the host and travel in one staged upload."""
+        from ._staging import upload
+        row_lo, row_hi, seq_ptr, _ = packing.policy_row_tables(packed.plan, token_trie.attach_lists)
+        tables = [row_lo, row_hi, seq_ptr, *packing.policy_path_tables(packed.plan, token_trie.attach_lists),
+                  *packing.preference_pair_tables(token_trie.attach_lists)]
+        dev = packed.tokens.device
+        row_lo_d, row_hi_d, seq_ptr_d, *rest = upload(tables, dev, np.int32)
+        ref_lp, ref_sum, mask = ops.preference_token_inputs(loss, token_trie.attach_lists, seq_ptr, dev)
+        dlp, stats, _, _ = ops.preference_loss(loss, lp, packed.depth, row_lo_d, row_hi_d, seq_ptr_d, tuple(rest[:4]), tuple(rest[4:]),
+                                               ref_lp, ref_sum, mask)
+        return dlp, stats
+
+    def _backward_stack_two_pass(self, model, token_trie, loss, block_rows: int) -> float:
+        """A preference objective on the block-wise walk, in two passes: the sequence log-probs from a no-grad forward, the per-sequence
+        coefficients g_s from them (PreferenceLoss.coefficients), then the walk with the linear closure g_s (m logprob).sum(), whose
+        gradient is the objective's.  Returns the objective itself, not the closure's sum.  Costs one more model forward."""
+        forkpos = self.forkpos_list
+        logprobs = self.forward(model, token_trie)          # resets the fork positions of this call: put them back
+        self.forkpos_list = forkpos
+        atts = [None] * len(logprobs)
+        for attach_list in token_trie.attach_lists:
+            for att, _ in attach_list:
+                atts[att["_sequence_batch_id"]] = att
+        total, g, stats = loss.coefficients(logprobs, atts)
+        del logprobs
+        self._backward_stack(model, token_trie, loss.surrogate(g), block_rows)
+        self.last_loss_path, self.loss_stats = "two_pass", stats
+        return float(total.item())
+
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, model, token_trie) -> List[torch.Tensor]:
@@ -573,6 +605,8 @@ class TreeTrainingEngine:
         if rows is not None:
             longest = max(token_trie.lens)
             assert longest <= self.max_seq_len, f"Exceeds max_seq_len: cur_len=0, new_tokens={longest}, max={self.max_seq_len}"
+            if isinstance(loss_fn, PreferenceLoss):
+                return self._backward_stack_two_pass(model, token_trie, loss_fn, rows)
             return self._backward_stack(model, token_trie, loss_fn, rows)
         packed = self._pack(token_trie)
         chunk = min(self.head_chunk, block_size) if block_size else self.head_chunk
@@ -588,8 +622,15 @@ class TreeTrainingEngine:
         lp, ent = packed_logprob_entropy(h, head_weight(model), packed.tokens, packed.parent, True, max(chunk, 1),
                                          packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model),
                                        logit_scale_of(model))
-        fused = isinstance(loss_fn, PolicyLoss)
-        if fused:
+        fused = isinstance(loss_fn, (PolicyLoss, PreferenceLoss))
+        if isinstance(loss_fn, PreferenceLoss):
+            # a pair objective couples sequences: sequence pass, pair pass and row pass in one C-ABI call; entropy takes no part
+            self.last_loss_path = "fused"
+            dlp, stats = self._preference_rows(packed, token_trie, lp, loss_fn)
+            dent = None
+            self.loss_stats = stats[:len(PREFERENCE_STATS)]
+            total = stats[0]
+        elif fused:
             # the built-in objective runs over the packed rows themselves (one C-ABI call): no gather along the paths, no per-sequence
             # callback, no scatter of per-sequence gradients - dlp / dent come out per row
             self.last_loss_path = "fused"
@@ -611,7 +652,7 @@ class TreeTrainingEngine:
             self._loss_host.copy_(total.detach().reshape(1).float(), non_blocking=True)
             landed = torch.cuda.Event(); landed.record()
         if fused:
-            roots = [(lp, dlp)] + ([(ent, dent)] if loss_fn.entropy_coef != 0 else [])      # no entropy bonus: entropy is not differentiated
+            roots = [(lp, dlp)] + ([(ent, dent)] if dent is not None and loss_fn.entropy_coef != 0 else [])      # no entropy bonus: entropy is not differentiated
             roots = [(t, g) for t, g in roots if t.requires_grad]
             if roots and torch.is_grad_enabled():
                 torch.autograd.backward([t for t, _ in roots], [g for _, g in roots])

@@ -476,6 +476,52 @@ int dta_policy_loss_seq(const float* lp, const float* ent, const int32_t* depth,
                         int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip, float kl_coef,
                         int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Preference objectives over the packed trie (losses.PreferenceLoss; HBM-bound, fp32 throughout): DPO / cDPO / SimPO (kind 0,
+ * "sigmoid"), SLiC (1, "hinge") and IPO (2, "ipo") over P (chosen, rejected) pairs of the trie's sequences, with an optional NLL term on
+ * the chosen member.  A pair couples two sequences, so no per-sequence callback can state it; here the pairs are one stage between a
+ * sequence pass and a row pass.  The numbering of the sequences, seq_ptr, mask, the row tables (depth, row_seq_lo, row_seq_hi) and the
+ * path tables (leaf_run_ptr, run_row0, run_depth0, seq_leaf over M leaves and R runs) are those of dta_policy_loss_seq; table entries
+ * that point outside [0, M), [0, R) or [0, T) are clamped or skipped, never followed.  mask [N] is required (all ones: no mask).
+ *
+ * The reference policy comes in exactly one of two forms: ref_lp [N], per-token reference log-probs (summed here under the mask), or
+ * ref_sum [S], the already masked sum per sequence; the other pointer is NULL.  reference_free != 0: neither is read (both may be NULL).
+ * For sequence s, with row(s, j) the packed row of depth j + 1 on its root path:
+ *       n^_s = max(sum_j m_j, 1),   P_s = sum_j m_j lp[row(s, j)],   F_s = sum_j m_j ref_lp[.] | ref_sum[s] | 0
+ *       u_s  = (P_s - F_s) / N_s,   N_s = n^_s when length_normalize != 0, else 1
+ * For pair q, c = pair_c[q] the chosen and r = pair_r[q] the rejected sequence, z = beta (u_c - u_r) - gamma, e = label_smoothing:
+ *       kind 0:  L = (1 - e) softplus(-z) + e softplus(z),   dL/dz = sigmoid(z) - (1 - e)
+ *       kind 1:  L = max(0, 1 - z),                          dL/dz = -[z < 1]            (a tie z == 1: gradient 0)
+ *       kind 2:  L = (u_c - u_r - 1 / (2 beta))^2,           dL/d(u_c - u_r) = 2 (u_c - u_r - 1 / (2 beta))
+ *       loss = scale sum_q L_q - scale sft_coef sum_q P_c / n^_c
+ *       g[c] = scale (dL/du_c) / N_c - scale sft_coef / n^_c,    g[r] = -scale (dL/du_c) / N_r,    dL/du_c = beta dL/dz (kinds 0, 1)
+ * and d loss / d lp[row(s, j)] = g[s] m_j.  softplus(x) = max(x, 0) + log1pf(expf(-|x|)); the sigmoid is formed from expf(-|z|) and
+ * cannot overflow; expf and log1pf are the accurate functions.  Every sequence should be a member of exactly one pair.  A sequence in
+ * no pair gets g = 0; a pair with an index outside [0, S) is skipped; a sequence named by several pairs gets the coefficient of one of
+ * them (which one is not defined: the Python side refuses such a trie).  Entropy takes no part and there is no dent.
+ * Four launches on `stream`; their geometry depends on T, S and P alone; no atomics, identical bits for identical calls:
+ *   sequence pass  one workgroup per sequence (grid-strided past 2048): the runs of its path with the threads strided over each run's
+ *                  rows, workgroup sums in a fixed order; writes nhat[s] = n^_s, u[s], sft[s] = P_s / n^_s and g[s] = 0 - workspaces [S]
+ *                  the caller may read afterwards;
+ *   pair pass      one thread per pair (grid-strided past 1024 workgroups of 256): z, L, g[c], g[r] and per-workgroup partial
+ *                  statistics, partial[dta_preference_loss_blocks(T, S, P)][8];
+ *   row pass       dlp[t] = sum over s in [row_seq_lo[t], row_seq_hi[t]) with n_s >= depth[t] >= 1 of g[s] mask[seq_ptr[s] + depth[t] - 1],
+ *                  written for EVERY row of dlp[T], 0 where nothing contributes (rows of depth 0, filler rows);
+ *   reduction      the partials in a fixed order into stats[8] = {loss, sum L, sum P_c / n^_c, sum beta (u_c - u_r), sum beta u_c,
+ *                  sum beta u_r, pairs with u_c > u_r (a tie is not counted), pairs} (losses.PREFERENCE_STATS).
+ * Refusals come in this order: DTA_EINVAL (a null pointer other than ref_lp / ref_sum; T, S, M, R or P <= 0; kind not 0..2; a
+ * non-finite beta, label_smoothing, gamma, sft_coef or scale; beta <= 0; label_smoothing outside [0, 0.5) or non-zero with kind != 0;
+ * gamma != 0 with kind 2; sft_coef < 0; reference_free == 0 with ref_lp and ref_sum both NULL or both given), DTA_EALIGN (a pointer off
+ * 16 bytes), DTA_EPRIOR. */
+int dta_preference_loss_blocks(int32_t T, int32_t S, int32_t P);   /* rows of the partial workspace [blocks, 8] (float); T, S or P <= 0: DTA_EINVAL */
+int dta_preference_loss(const float* lp, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                        const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                        const int32_t* seq_leaf, const int32_t* pair_c, const int32_t* pair_r, const float* ref_lp,
+                        const float* ref_sum, const float* mask, float* nhat, float* u, float* sft, float* g, float* dlp,
+                        float* partial, float* stats, int32_t T, int32_t S, int32_t M, int32_t R, int32_t P, int32_t kind,
+                        float beta, float label_smoothing, float gamma, int32_t length_normalize, int32_t reference_free,
+                        float sft_coef, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
