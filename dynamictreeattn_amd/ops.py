@@ -426,6 +426,16 @@ def local_labels(t, vocab_offset, V):
     return torch.where((t >= vocab_offset) & (t < vocab_offset + V), t - vocab_offset, torch.full_like(t, -1))
 
 
+def _head_logits(h, W):
+    """h Wᵀ [R, V] as the log-prob kernels read it: rows on a pitch of a multiple of 8 elements (16-byte vector loads).  A vocabulary
+    (or a rank's slice of one) that is no multiple of 8 gets rows with padding behind them, which nothing reads."""
+    V = W.shape[0]
+    if V % 8 == 0:
+        return torch.mm(h, W.t())
+    buf = torch.empty((h.shape[0], (V + 7) // 8 * 8), dtype=h.dtype, device=h.device)
+    return torch.mm(h, W.t(), out=buf[:, :V])
+
+
 HEAD_WGRAD_FUSED_ACCUMULATE = False      # chunked head only: accumulate the weight gradient inside the GEMM (scripts/head_stage_probe.py measures both)
 
 
@@ -461,7 +471,7 @@ class _HeadRows(torch.autograd.Function):
         kept = None
         for ci, a in enumerate(range(0, T, step)):
             b = min(a + step, T)
-            logits = torch.mm(h[a:b], W.t())
+            logits = _head_logits(h[a:b], W)
             if tp_group is None:
                 l, e, p = logprob_entropy_fwd_raw(logits, next_loc[a:b], want_entropy, temperature,
                                                   xp[a:b + 1] if F_ else None, fork_loc if F_ else None, lp_fork if F_ else None, softcap)
@@ -498,7 +508,7 @@ class _HeadRows(torch.autograd.Function):
         pending = []
         for a in range(0, T, step):
             b = min(a + step, T)
-            logits = kept if kept is not None else torch.mm(h[a:b], W.t())
+            logits = kept if kept is not None else _head_logits(h[a:b], W)
             logprob_entropy_bwd_raw(logits, next_loc[a:b], lse[a:b], ent[a:b] if ctx.want_entropy else None, g_next[a:b],
                                     g_ent[a:b] if ctx.want_entropy else None, ctx.temperature,
                                     xp[a:b + 1] if ctx.has_forks else None, fork_loc if ctx.has_forks else None, g_fork, softcap=ctx.softcap)
@@ -1232,7 +1242,9 @@ class _TransposedWeights:
     def get(w: torch.Tensor) -> torch.Tensor:
         if weight_cache.depth == 0:
             return transpose_2d(w)
-        key = (w.data_ptr(), tuple(w.shape), w.dtype, w._version)
+        # strides too: two views of one storage (a column slice of a fused buffer, a contiguous matrix at the same address) share the
+        # pointer, the shape and the version counter and are different matrices
+        key = (w.data_ptr(), tuple(w.shape), tuple(w.stride()), w.dtype, w._version)
         hit = _TransposedWeights.cache.get(key)
         if hit is not None:
             return hit

@@ -1,4 +1,4 @@
-"""The rounding-model constants every float64 reference (moe_ref64, rowops_ref64, logprob_ref64, olmo_ref64, lora_ref64) shares.
+"""The rounding-model constants every float64 reference (moe_ref64, rowops_ref64, logprob_ref64, olmo_ref64, lora_ref64, linear_ref64) shares.
 
     GEMM / reduction element:  |out - ref| <= u |ref| + C32 sqrt(n) u32 (|A| |B|)  (+ tiny)
         u = 2^-8 bf16, 2^-11 f16, 2^-24 fp32 (output rounding, a relative half-ulp doubled for margin; f16 adds its subnormal

@@ -91,7 +91,9 @@ def test_transpose_kernel_on_random_shapes(rb, cb, dtype, seed):
 @settings(max_examples=10, **COMMON)
 @given(st.integers(33, 80), st.sampled_from([(1024, 512), (256, 768), (512, 1024)]), st.booleans(), st.integers(0, 3))
 def test_split_k_weight_gradient_equals_the_single_gemm(t256, shape, transposed, seed):
-    """ops._wgrad: the 4-slice batched GEMM with fp32 partials (+ the remainder rows) against the plain product in fp32."""
+    """ops._wgrad: the 4-slice batched GEMM with fp32 partials against the plain product in fp32.  The row counts are 256 * t, so T // 4 is
+    always a multiple of 64 and NO rows are left over here: the left-over rows, the threshold at 8192 rows and the per-element bound (which
+    this whole-tensor norm cannot replace: tests/test_linear_ref64.py) are in tests/test_gpu_linear_bounds.py."""
     from dynamictreeattn_amd import ops
     T, (out_f, in_f) = 256 * t256, shape
     g = torch.Generator().manual_seed(seed)

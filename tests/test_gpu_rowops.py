@@ -157,7 +157,8 @@ def test_sum_slabs_is_the_float64_sum_rounded_once(shape, extra, dtype):
 
 def test_weight_copies_are_shared_inside_one_engine_call_only():
     """ops.weight_cache: inside the scope one transposed / stacked copy per weight (re-made when the weight's version moves); when the scope
-    ends the copies are gone, and outside it nothing is cached - no entry can outlive the tensors it was keyed on."""
+    ends the copies are gone, and outside it nothing is cached - no entry can outlive the tensors it was keyed on.
+    (ops._dgrad element by element at both of its forms, across an update and for two views of one storage: tests/test_gpu_linear_bounds.py.)"""
     w = torch.nn.Parameter(torch.randn(512, 256, device=DEV).bfloat16()); v = torch.nn.Parameter(torch.randn(256, 256, device=DEV).bfloat16())
     with ops.weight_cache():
         a = ops._TransposedWeights.get(w); b = ops._TransposedWeights.get(w)
