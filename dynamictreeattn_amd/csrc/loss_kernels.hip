@@ -15,6 +15,9 @@
 // Preference objectives (dta_preference_loss: DPO / cDPO / SimPO, SLiC, IPO): a pair couples two sequences, so a pair pass stands
 // between the sequence pass (u_s, one number per sequence, over the same path walk) and a row pass that sums g_s m with the pair's
 // coefficient g_s; the statistics are per pair and come from the pair pass alone.
+//
+// The three algorithms the objectives share are written once, with the objective's own terms handed in as functors: the row sweep
+// (row_sweep), the root-path walk (path_walk) and the workgroup's row of statistic partials (stat_partials).
 #include "dta_common.h"
 #include "dta_device.h"
 #include <math.h>
@@ -27,67 +30,190 @@ constexpr int PL_MAX_BLOCKS = 1024; // grid cap: the rest is grid-strided, the p
 constexpr int PL_NSTAT = 8;         // {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0}
 constexpr int PL_SEQ_BLOCKS = 2048; // grid cap of the sequence pass: one workgroup per sequence, the rest grid-strided
 
+// ---- the shared algorithms -----------------------------------------------------------------------------------------------------
+
+// Row sweep: every row t < T once, a thread per row, the grid striding over steps of PL_BLOCK rows.  load(t) gives the row's own
+// values (a Row, its depth d first), term(s, row, sum) adds what the row owns for sequence s to a Sum, store(t, sum) takes the row's
+// total over its sequence range [row_lo[t], row_hi[t]), clamped to [0, S).  Row::from_lane(k) is lane k's Row and Sum::wave_total()
+// the butterfly sum, for the rows with a range longer than PL_SERIAL: their wave takes them over one after the other, in lane order,
+// with every lane - also one whose own row is short or past T - running along, so no lane may leave before the ballot.
+// ROOT: the rows of depth 0 own terms too.
+template <class Row, class Sum, bool ROOT, class Load, class Term, class Store>
+__device__ __forceinline__ void row_sweep(int T, int S, const int32_t* row_lo, const int32_t* row_hi, Load load, Term term, Store store) {
+  const int lane = threadIdx.x & 63;
+  for (int base = blockIdx.x * PL_BLOCK; base < T; base += gridDim.x * PL_BLOCK) {   // `base` is the same in every lane of the workgroup
+    const int t = base + threadIdx.x;
+    const bool live = t < T;
+    Row row{};
+    int s0 = 0, s1 = 0;
+    if (live) {
+      row = load(t);
+      if (ROOT || row.d >= 1) { s0 = max(row_lo[t], 0); s1 = min(row_hi[t], S); }
+    }
+    const bool wide = s1 - s0 > PL_SERIAL;
+    Sum sum{};
+    if (!wide)
+      for (int s = s0; s < s1; ++s) term(s, row, sum);
+    unsigned long long todo = __ballot(wide);
+    Sum wsum{};                                            // lane k: the total of its wide row
+    while (todo) {
+      const int k = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const Row rk = row.from_lane(k);
+      const int b0 = __shfl(s0, k), b1 = __shfl(s1, k);
+      Sum r{};
+      for (int s = b0 + lane; s < b1; s += 64) term(s, rk, r);
+      r = r.wave_total();
+      if (lane == k) wsum = r;
+    }
+    if (live) store(t, wide ? wsum : sum);
+  }
+}
+
+// the workgroup's sum of v in a fixed order (lanes by butterfly, the four waves in order), in every thread
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();                                         // the previous use of red is over
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Root-path walk.  Sequence s (predictions [b, b + n) of the per-token inputs) follows the root path of leaf seq_leaf[s]: runs
+// [leaf_run_ptr[leaf], leaf_run_ptr[leaf + 1]) of contiguous packed rows, run k starting at row run_row0[k] with depth run_depth0[k].
+// Prediction j of s is the row of depth j + 1: f(t, i) is called for every row t < T of depth >= 1 on the path, with i = b + depth - 1,
+// the workgroup's threads striding over each run.
+struct PathParams {
+  const float* lp;
+  const int32_t *seq_ptr, *leaf_run_ptr, *run_row0, *run_depth0, *seq_leaf;
+  int32_t T, S, M, R;
+};
+
+template <class F>
+__device__ __forceinline__ void path_walk(const PathParams& p, int s, int b, int n, F f) {
+  const int leaf = min(max(p.seq_leaf[s], 0), p.M - 1);
+  const int k0 = max(p.leaf_run_ptr[leaf], 0), k1 = min(p.leaf_run_ptr[leaf + 1], p.R);
+  for (int k = k0; k < k1; ++k) {
+    const int row0 = p.run_row0[k], d0 = p.run_depth0[k];
+    const int da = max(d0, 1), db = min(k + 1 < k1 ? p.run_depth0[k + 1] : n + 1, n + 1);         // depths [da, db) of this run
+    for (int d = da + (int)threadIdx.x; d < db; d += 256) {
+      const int t = row0 + (d - d0);
+      if (t < 0 || t >= p.T) continue;
+      f(t, b + d - 1);
+    }
+  }
+}
+
+// The workgroup's row of statistic partials from every thread's st[N]: lanes by butterfly, then the four waves in order from 0.f;
+// all PL_NSTAT columns of the row are written, the ones from N on with 0.
+template <int N>
+__device__ __forceinline__ void stat_partials(const float (&st)[N], float* partial) {
+  __shared__ float red[PL_BLOCK / 64][PL_NSTAT];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = 0; i < N; ++i) {
+    const float v = wave_sum(st[i]);
+    if (lane == 0) red[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < PL_NSTAT) {
+    float v = 0.f;
+    if (threadIdx.x < N)
+      for (int wv = 0; wv < PL_BLOCK / 64; ++wv) v += red[wv][threadIdx.x];
+    partial[blockIdx.x * PL_NSTAT + threadIdx.x] = v;
+  }
+}
+
+// ---- policy objective ------------------------------------------------------------------------------------------------------------
+
 struct PolicyParams {
   const float *lp, *ent;
   const int32_t *depth, *row_lo, *row_hi, *seq_ptr;
   const float *old_lp, *ref_lp, *mask, *adv, *w;
-  const float* c = nullptr;                  // sequence-level ratios only: the surrogate's gradient scalar per sequence
+  const float* c;                            // sequence-level ratios only: the surrogate's gradient scalar per sequence
   float *dlp, *dent, *partial;
   int32_t T, S, adv_per_seq;
   float lo, hi, dual, kl_coef, ent_coef;     // lo = 1 - clip_low, hi = 1 + clip_high, dual = 0: none
 };
 
-struct Acc { float glp, gent, st[6]; };
+// a row's own values, and what it receives: dlp and dent
+struct PolicyRow {
+  int d; float lp, ent;
+  __device__ PolicyRow from_lane(int k) const { return {__shfl(d, k), __shfl(lp, k), __shfl(ent, k)}; }
+};
+// the first six columns of the statistics.  (A struct: a bare private array that loops index becomes one vector value before the loops
+// are unrolled, and the columns an instantiation never touches then no longer fold to constants.)
+struct PolicyStats { float v[6]; };
+struct PolicySum {
+  float glp, gent;
+  __device__ PolicySum wave_total() const { return {wave_sum(glp), wave_sum(gent)}; }
+};
 
-// the terms row (depth d, log-prob lp_t, entropy ent_t) owns for sequence s
+// the clipped surrogate of one token from its ratio r and advantage A; `clipped`: a clamp is the active branch, d pg / d lp = 0
+struct Pg { float pg; bool clipped; };
+__device__ __forceinline__ Pg clipped_pg(float r, float lo, float hi, float A, float dual) {
+  const float s1 = -r * A, s2 = -fminf(fmaxf(r, lo), hi) * A;
+  float pg = fmaxf(s1, s2);
+  bool clipped = s2 > s1;
+  if (dual > 0.f && A < 0.f) {
+    const float cap = -dual * A;
+    if (cap < pg) { pg = cap; clipped = true; }
+  }
+  return {pg, clipped};
+}
+
+// the KL estimate from dd = ref - lp, and dk = d kl / d lp
 template <int KL>
-__device__ __forceinline__ void seq_terms(const PolicyParams& p, int s, int d, float lp_t, float ent_t, Acc& a) {
-  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+__device__ __forceinline__ float kl_term(float dd, float& dk) {
+  if (KL == 0) { dk = 1.f; return -dd; }
+  if (KL == 1) { dk = -dd; return 0.5f * dd * dd; }
+  const float e = expf(dd);
+  dk = 1.f - e;
+  return e - dd - 1.f;
+}
+
+// the entropy term (s, j = d) of a row with entropy ent_t, for a sequence with predictions from b and weight w
+__device__ __forceinline__ void entropy_term(const PolicyParams& p, int b, int d, float w, float ent_t, PolicySum& a, PolicyStats& st) {
+  const float m = p.mask[b + d];
+  const float wm = w * m;
+  a.gent -= wm * p.ent_coef;
+  st.v[0] -= wm * p.ent_coef * ent_t;
+  st.v[3] += m * ent_t;
+}
+
+// the terms a row owns for sequence s
+template <int KL>
+__device__ __forceinline__ void seq_terms(const PolicyParams& p, int s, const PolicyRow& row, PolicySum& a, PolicyStats& st) {
+  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b, d = row.d;
   if (n < d) return;                                       // the sequence ends above this row
   const float w = p.w[s];
   if (d >= 1) {
     const int i = b + d - 1;
     const float m = p.mask[i];
     const float A = p.adv[p.adv_per_seq ? s : i];
-    const float r = p.old_lp ? expf(lp_t - p.old_lp[i]) : 1.f;
-    const float s1 = -r * A, s2 = -fminf(fmaxf(r, p.lo), p.hi) * A;
-    float pg = fmaxf(s1, s2);
-    bool clipped = s2 > s1;                                // the clamp is the active branch: d pg / d lp = 0
-    if (p.dual > 0.f && A < 0.f) {
-      const float cap = -p.dual * A;
-      if (cap < pg) { pg = cap; clipped = true; }
-    }
-    float g = clipped ? 0.f : s1;                          // d(-r A)/d lp = -r A
+    const float r = p.old_lp ? expf(row.lp - p.old_lp[i]) : 1.f;
+    const auto [pg, clipped] = clipped_pg(r, p.lo, p.hi, A, p.dual);
+    float g = clipped ? 0.f : -r * A;                      // d(-r A)/d lp = -r A
     float kl = 0.f;
     if (KL >= 0) {
-      const float dd = p.ref_lp[i] - lp_t;
       float dk;
-      if (KL == 0) { kl = -dd; dk = 1.f; }
-      else if (KL == 1) { kl = 0.5f * dd * dd; dk = -dd; }
-      else { const float e = expf(dd); kl = e - dd - 1.f; dk = 1.f - e; }
+      kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
       g += p.kl_coef * dk;
-      a.st[2] += m * kl;
+      st.v[2] += m * kl;
     }
     const float wm = w * m;
     a.glp += wm * g;
-    a.st[0] += wm * (pg + p.kl_coef * kl);
-    a.st[1] += m * pg;
-    a.st[4] += clipped ? m : 0.f;
-    a.st[5] += m;
+    st.v[0] += wm * (pg + p.kl_coef * kl);
+    st.v[1] += m * pg;
+    st.v[4] += clipped ? m : 0.f;
+    st.v[5] += m;
   }
-  if (d < n) {
-    const float m = p.mask[b + d];
-    const float wm = w * m;
-    a.gent -= wm * p.ent_coef;
-    a.st[0] -= wm * p.ent_coef * ent_t;
-    a.st[3] += m * ent_t;
-  }
+  if (d < n) entropy_term(p, b, d, w, row.ent, a, st);
 }
 
 // the same for sequence-level ratios: the surrogate's value and statistics are the sequence pass's, its gradient here is c_s m
 template <int KL>
-__device__ __forceinline__ void seq_terms_sl(const PolicyParams& p, int s, int d, float lp_t, float ent_t, Acc& a) {
-  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+__device__ __forceinline__ void seq_terms_sl(const PolicyParams& p, int s, const PolicyRow& row, PolicySum& a, PolicyStats& st) {
+  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b, d = row.d;
   if (n < d) return;
   const float w = p.w[s];
   if (d >= 1) {
@@ -95,85 +221,30 @@ __device__ __forceinline__ void seq_terms_sl(const PolicyParams& p, int s, int d
     const float m = p.mask[i];
     float g = p.c[s] * m;
     if (KL >= 0) {
-      const float dd = p.ref_lp[i] - lp_t;
-      float kl, dk;
-      if (KL == 0) { kl = -dd; dk = 1.f; }
-      else if (KL == 1) { kl = 0.5f * dd * dd; dk = -dd; }
-      else { const float e = expf(dd); kl = e - dd - 1.f; dk = 1.f - e; }
+      float dk;
+      const float kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
       const float wm = w * m;
       g += wm * (p.kl_coef * dk);
-      a.st[0] += wm * (p.kl_coef * kl);
-      a.st[2] += m * kl;
+      st.v[0] += wm * (p.kl_coef * kl);
+      st.v[2] += m * kl;
     }
     a.glp += g;
-    a.st[5] += m;
+    st.v[5] += m;
   }
-  if (d < n) {
-    const float m = p.mask[b + d];
-    const float wm = w * m;
-    a.gent -= wm * p.ent_coef;
-    a.st[0] -= wm * p.ent_coef * ent_t;
-    a.st[3] += m * ent_t;
-  }
+  if (d < n) entropy_term(p, b, d, w, row.ent, a, st);
 }
 
 template <int KL, bool SEQ>
-__device__ __forceinline__ void row_terms(const PolicyParams& p, int s, int d, float lp_t, float ent_t, Acc& a) {
-  if (SEQ) seq_terms_sl<KL>(p, s, d, lp_t, ent_t, a);
-  else seq_terms<KL>(p, s, d, lp_t, ent_t, a);
-}
-
-template <int KL, bool SEQ = false>
 __global__ __launch_bounds__(PL_BLOCK) void policy_loss_kernel(const PolicyParams p) {
-  __shared__ float red[PL_BLOCK / 64][PL_NSTAT];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  Acc a;
-  for (int i = 0; i < 6; ++i) a.st[i] = 0.f;
-  for (int base = blockIdx.x * PL_BLOCK; base < p.T; base += gridDim.x * PL_BLOCK) {   // `base` is the same in every lane of the workgroup
-    const int t = base + threadIdx.x;
-    const bool live = t < p.T;
-    int d = 0, s0 = 0, s1 = 0;
-    float lp_t = 0.f, ent_t = 0.f;
-    if (live) {
-      d = p.depth[t]; lp_t = p.lp[t]; ent_t = p.ent[t];
-      s0 = max(p.row_lo[t], 0); s1 = min(p.row_hi[t], p.S);
-    }
-    a.glp = 0.f; a.gent = 0.f;
-    const bool wide = s1 - s0 > PL_SERIAL;
-    if (!wide)
-      for (int s = s0; s < s1; ++s) row_terms<KL, SEQ>(p, s, d, lp_t, ent_t, a);
-    // rows with a long range: the wave takes them one after the other, in lane order
-    unsigned long long todo = __ballot(wide);
-    float glp_w = 0.f, gent_w = 0.f;
-    while (todo) {
-      const int k = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int dk = __shfl(d, k), b0 = __shfl(s0, k), b1 = __shfl(s1, k);
-      const float lpk = __shfl(lp_t, k), entk = __shfl(ent_t, k);
-      Acc r = a;
-      r.glp = 0.f; r.gent = 0.f;
-      for (int s = b0 + lane; s < b1; s += 64) row_terms<KL, SEQ>(p, s, dk, lpk, entk, r);
-      for (int i = 0; i < 6; ++i) a.st[i] = r.st[i];
-      const float gl = wave_sum(r.glp), ge = wave_sum(r.gent);
-      if (lane == k) { glp_w = gl; gent_w = ge; }
-    }
-    if (live) {
-      p.dlp[t] = wide ? glp_w : a.glp;
-      p.dent[t] = wide ? gent_w : a.gent;
-    }
-  }
-  // the workgroup's partial sums: lanes by butterfly, then the four waves in order
-  for (int i = 0; i < 6; ++i) {
-    const float v = wave_sum(a.st[i]);
-    if (lane == 0) red[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < PL_NSTAT) {
-    float v = 0.f;
-    if (threadIdx.x < 6)
-      for (int wv = 0; wv < PL_BLOCK / 64; ++wv) v += red[wv][threadIdx.x];
-    p.partial[blockIdx.x * PL_NSTAT + threadIdx.x] = v;
-  }
+  PolicyStats st = {};                                     // this thread's share of the statistics, over all its rows
+  row_sweep<PolicyRow, PolicySum, true>(
+      p.T, p.S, p.row_lo, p.row_hi, [&](int t) { return PolicyRow{p.depth[t], p.lp[t], p.ent[t]}; },
+      [&](int s, const PolicyRow& row, PolicySum& a) {
+        if (SEQ) seq_terms_sl<KL>(p, s, row, a, st);
+        else seq_terms<KL>(p, s, row, a, st);
+      },
+      [&](int t, const PolicySum& a) { p.dlp[t] = a.glp; p.dent[t] = a.gent; });
+  stat_partials(st.v, p.partial);
 }
 
 // stats[c] = sum over the workgroups' partials, in a fixed order: 32 strided chains per column, then the 32 in order
@@ -191,20 +262,16 @@ __global__ __launch_bounds__(256) void policy_loss_reduce_kernel(const float* __
   }
 }
 
-// w[s] = scale / max(sum of the sequence's mask, 1): one workgroup per sequence, lanes strided, butterfly, the four waves in order
+// w[s] = scale / max(sum of the sequence's mask, 1): one workgroup per sequence, lanes strided
 __global__ __launch_bounds__(256) void policy_seq_weight_kernel(const float* __restrict__ mask, const int32_t* __restrict__ seq_ptr, int S,
                                                                float scale, float* __restrict__ w) {
   __shared__ float red[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int s = blockIdx.x; s < S; s += gridDim.x) {
     const int b = seq_ptr[s], e = seq_ptr[s + 1];
     float v = 0.f;
     for (int i = b + (int)threadIdx.x; i < e; i += 256) v += mask[i];
-    v = wave_sum(v);
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) w[s] = scale / fmaxf(((red[0] + red[1]) + red[2]) + red[3], 1.f);
-    __syncthreads();
+    v = block_sum(v, red);
+    if (threadIdx.x == 0) w[s] = scale / fmaxf(v, 1.f);
   }
 }
 
@@ -213,26 +280,13 @@ __global__ __launch_bounds__(256) void policy_fill_weight_kernel(int S, float sc
   if (s < S) w[s] = scale;
 }
 
-// The sequence pass of the sequence-level objective.  Sequence s follows the root path of leaf seq_leaf[s]: runs
-// [leaf_run_ptr[leaf], leaf_run_ptr[leaf + 1]) of contiguous packed rows, run k starting at row run_row0[k] with depth run_depth0[k].
-// Prediction j of s (element seq_ptr[s] + j of the per-token inputs) is the row of depth j + 1.
-struct SeqPassParams {
-  const float* lp;
-  const int32_t *seq_ptr, *leaf_run_ptr, *run_row0, *run_depth0, *seq_leaf;
+// The sequence pass of the sequence-level objective.
+struct SeqPassParams : PathParams {
   const float *old_lp, *mask, *adv;
   float *w, *c, *partial;
-  int32_t T, S, M, R, adv_per_seq, seq_mean;
+  int32_t adv_per_seq, seq_mean;
   float lo, hi, dual, scale;
 };
-
-// the workgroup's sum of v in a fixed order (lanes by butterfly, the four waves in order), in every thread
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();                                         // the previous use of red is over
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 __global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParams p) {
   __shared__ float red[4];
@@ -241,19 +295,11 @@ __global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParam
     const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
     float sm = 0.f, sx = 0.f;
     if (p.old_lp) {
-      const int leaf = min(max(p.seq_leaf[s], 0), p.M - 1);
-      const int k0 = max(p.leaf_run_ptr[leaf], 0), k1 = min(p.leaf_run_ptr[leaf + 1], p.R);
-      for (int k = k0; k < k1; ++k) {
-        const int row0 = p.run_row0[k], d0 = p.run_depth0[k];
-        const int da = max(d0, 1), db = min(k + 1 < k1 ? p.run_depth0[k + 1] : n + 1, n + 1);     // depths [da, db) of this run
-        for (int d = da + (int)threadIdx.x; d < db; d += 256) {
-          const int t = row0 + (d - d0), i = b + d - 1;
-          if (t < 0 || t >= p.T) continue;
-          const float m = p.mask[i];
-          sm += m;
-          sx += m * (p.lp[t] - p.old_lp[i]);
-        }
-      }
+      path_walk(p, s, b, n, [&](int t, int i) {
+        const float m = p.mask[i];
+        sm += m;
+        sx += m * (p.lp[t] - p.old_lp[i]);
+      });
     } else {
       for (int j = threadIdx.x; j < n; j += 256) sm += p.mask[b + j];
     }
@@ -261,18 +307,11 @@ __global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParam
     const float r = p.old_lp ? expf(block_sum(sx, red) / nh) : 1.f;
     const float w = p.seq_mean ? p.scale / nh : p.scale;
     // every token of the sequence sees the same r: its branch depends on the sign of its advantage alone
-    const float rc = fminf(fmaxf(r, p.lo), p.hi);
     float spg = 0.f, sg = 0.f, sc = 0.f;
     for (int j = threadIdx.x; j < n; j += 256) {
       const float m = p.mask[b + j];
       const float A = p.adv[p.adv_per_seq ? s : b + j];
-      const float s1 = -r * A, s2 = -rc * A;
-      float pg = fmaxf(s1, s2);
-      bool clipped = s2 > s1;
-      if (p.dual > 0.f && A < 0.f) {
-        const float cap = -p.dual * A;
-        if (cap < pg) { pg = cap; clipped = true; }
-      }
+      const auto [pg, clipped] = clipped_pg(r, p.lo, p.hi, A, p.dual);
       spg += m * pg;
       sg += clipped ? 0.f : m * -A;
       sc += clipped ? m : 0.f;
@@ -297,12 +336,10 @@ __global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParam
 
 constexpr int PF_MAX_BLOCKS = 1024; // grid cap of the pair pass: one thread per pair, the rest grid-strided; one partial row per workgroup
 
-struct PrefSeqParams {
-  const float* lp;
-  const int32_t *seq_ptr, *leaf_run_ptr, *run_row0, *run_depth0, *seq_leaf;
+struct PrefSeqParams : PathParams {
   const float *ref_lp, *ref_sum, *mask;
   float *nhat, *u, *sft, *g;
-  int32_t T, S, M, R, length_normalize;
+  int32_t length_normalize;
 };
 
 // n^_s, u_s and P_s / n^_s of every sequence, and g_s = 0 (the pair pass overwrites the members of a pair)
@@ -310,21 +347,13 @@ __global__ __launch_bounds__(256) void preference_seq_pass_kernel(const PrefSeqP
   __shared__ float red[4];
   for (int s = blockIdx.x; s < p.S; s += gridDim.x) {      // `s` is the same in every thread of the workgroup
     const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
-    const int leaf = min(max(p.seq_leaf[s], 0), p.M - 1);
-    const int k0 = max(p.leaf_run_ptr[leaf], 0), k1 = min(p.leaf_run_ptr[leaf + 1], p.R);
     float sm = 0.f, sp = 0.f, sf = 0.f;
-    for (int k = k0; k < k1; ++k) {
-      const int row0 = p.run_row0[k], d0 = p.run_depth0[k];
-      const int da = max(d0, 1), db = min(k + 1 < k1 ? p.run_depth0[k + 1] : n + 1, n + 1);       // depths [da, db) of this run
-      for (int d = da + (int)threadIdx.x; d < db; d += 256) {
-        const int t = row0 + (d - d0), i = b + d - 1;
-        if (t < 0 || t >= p.T) continue;
-        const float m = p.mask[i];
-        sm += m;
-        sp += m * p.lp[t];
-        if (p.ref_lp) sf += m * p.ref_lp[i];
-      }
-    }
+    path_walk(p, s, b, n, [&](int t, int i) {
+      const float m = p.mask[i];
+      sm += m;
+      sp += m * p.lp[t];
+      if (p.ref_lp) sf += m * p.ref_lp[i];
+    });
     const float nh = fmaxf(block_sum(sm, red), 1.f);
     const float P = block_sum(sp, red);
     const float F = p.ref_lp ? block_sum(sf, red) : p.ref_sum ? p.ref_sum[s] : 0.f;
@@ -349,10 +378,7 @@ __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + lo
 
 // one thread per pair: z, L, the two coefficients and the pair's share of the statistics
 __global__ __launch_bounds__(PL_BLOCK) void preference_pair_kernel(const PrefPairParams p) {
-  __shared__ float red[PL_BLOCK / 64][PL_NSTAT];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float st[PL_NSTAT];
-  for (int i = 0; i < PL_NSTAT; ++i) st[i] = 0.f;
+  float st[PL_NSTAT] = {};
   for (int q = blockIdx.x * PL_BLOCK + threadIdx.x; q < p.P; q += gridDim.x * PL_BLOCK) {
     const int c = p.pair_c[q], r = p.pair_r[q];
     if (c < 0 || c >= p.S || r < 0 || r >= p.S) continue;
@@ -384,16 +410,7 @@ __global__ __launch_bounds__(PL_BLOCK) void preference_pair_kernel(const PrefPai
     st[3] += p.beta * du; st[4] += p.beta * uc; st[5] += p.beta * ur;
     st[6] += uc > ur ? 1.f : 0.f; st[7] += 1.f;
   }
-  for (int i = 0; i < PL_NSTAT; ++i) {
-    const float v = wave_sum(st[i]);
-    if (lane == 0) red[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < PL_NSTAT) {
-    float v = 0.f;
-    for (int wv = 0; wv < PL_BLOCK / 64; ++wv) v += red[wv][threadIdx.x];
-    p.partial[blockIdx.x * PL_NSTAT + threadIdx.x] = v;
-  }
+  stat_partials(st, p.partial);
 }
 
 struct PrefRowParams {
@@ -403,42 +420,78 @@ struct PrefRowParams {
   int32_t T, S;
 };
 
-// the term row (depth d >= 1) owns for sequence s: g_s m at prediction d - 1
-__device__ __forceinline__ float pref_term(const PrefRowParams& p, int s, int d) {
-  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
-  return n < d ? 0.f : p.g[s] * p.mask[b + d - 1];
-}
+struct PrefRow {
+  int d;
+  __device__ PrefRow from_lane(int k) const { return {__shfl(d, k)}; }
+};
+struct PrefSum {
+  float v;
+  __device__ PrefSum wave_total() const { return {wave_sum(v)}; }
+};
 
-// dlp for every row: the row kernel of the policy objective with g_s m as the only term
+// dlp for every row: the term a row of depth d >= 1 owns for sequence s is g_s m at prediction d - 1; a row of depth 0 owns none
 __global__ __launch_bounds__(PL_BLOCK) void preference_row_kernel(const PrefRowParams p) {
-  const int lane = threadIdx.x & 63;
-  for (int base = blockIdx.x * PL_BLOCK; base < p.T; base += gridDim.x * PL_BLOCK) {   // `base` is the same in every lane of the workgroup
-    const int t = base + threadIdx.x;
-    const bool live = t < p.T;
-    int d = 0, s0 = 0, s1 = 0;
-    if (live) {
-      d = p.depth[t];
-      if (d >= 1) { s0 = max(p.row_lo[t], 0); s1 = min(p.row_hi[t], p.S); }
-    }
-    const bool wide = s1 - s0 > PL_SERIAL;
-    float v = 0.f;
-    if (!wide)
-      for (int s = s0; s < s1; ++s) v += pref_term(p, s, d);
-    unsigned long long todo = __ballot(wide);
-    while (todo) {                                         // rows with a long range: the wave takes them one after the other
-      const int k = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int dk = __shfl(d, k), b0 = __shfl(s0, k), b1 = __shfl(s1, k);
-      float r = 0.f;
-      for (int s = b0 + lane; s < b1; s += 64) r += pref_term(p, s, dk);
-      r = wave_sum(r);
-      if (lane == k) v = r;
-    }
-    if (live) p.dlp[t] = v;
-  }
+  row_sweep<PrefRow, PrefSum, false>(
+      p.T, p.S, p.row_lo, p.row_hi, [&](int t) { return PrefRow{p.depth[t]}; },
+      [&](int s, const PrefRow& row, PrefSum& a) {
+        const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+        a.v += n < row.d ? 0.f : p.g[s] * p.mask[b + row.d - 1];
+      },
+      [&](int t, const PrefSum& a) { p.dlp[t] = a.v; });
 }
 
 inline bool finite_f(float v) { return v == v && v - v == 0.f; }
+template <class... P> inline bool all_aligned16(const P*... p) { return (aligned16(p) && ...); }    // a null pointer counts as aligned
+
+// dta_policy_loss (SEQ = false: no path tables, no c, M and R unused) and dta_policy_loss_seq
+template <bool SEQ>
+int policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* mask, const float* adv, int32_t adv_per_seq,
+                float* w, float* c, float* dlp, float* dent, float* partial, float* stats, int32_t T, int32_t S, int32_t M, int32_t R,
+                float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg,
+                float scale, void* stream) {
+  if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !mask || !adv || !w || !dlp || !dent || !partial || !stats ||
+      T <= 0 || S <= 0)
+    return DTA_EINVAL;
+  if (SEQ && (!leaf_run_ptr || !run_row0 || !run_depth0 || !seq_leaf || !c || M <= 0 || R <= 0)) return DTA_EINVAL;
+  if (!finite_f(clip_low) || !finite_f(clip_high) || clip_low < 0.f || clip_high < 0.f) return DTA_EINVAL;
+  if (dual_clip != 0.f && !(finite_f(dual_clip) && dual_clip > 1.f)) return DTA_EINVAL;
+  if (kl_estimator < 0 || kl_estimator > 2 || agg < 0 || agg > 1) return DTA_EINVAL;
+  if (!finite_f(kl_coef) || !finite_f(entropy_coef) || !finite_f(scale)) return DTA_EINVAL;
+  if (kl_coef != 0.f && !ref_lp) return DTA_EINVAL;
+  if (!all_aligned16(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, old_lp, ref_lp, mask,
+                     adv, w, c, dlp, dent, partial, stats))
+    return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS), nsb = SEQ ? (S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS) : 0;
+  PolicyParams p;
+  p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
+  p.old_lp = SEQ ? nullptr : old_lp; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w; p.c = c;
+  p.dlp = dlp; p.dent = dent; p.partial = partial;
+  p.T = T; p.S = S; p.adv_per_seq = adv_per_seq != 0;
+  p.lo = 1.f - clip_low; p.hi = 1.f + clip_high; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
+  if (SEQ) {                                 // the sequence pass leaves w and c; its partial rows stand behind the row pass's
+    SeqPassParams q;
+    static_cast<PathParams&>(q) = {lp, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, T, S, M, R};
+    q.old_lp = old_lp; q.mask = mask; q.adv = adv; q.w = w; q.c = c; q.partial = partial + (size_t)nb * PL_NSTAT;
+    q.adv_per_seq = p.adv_per_seq; q.seq_mean = agg == 0;
+    q.lo = p.lo; q.hi = p.hi; q.dual = dual_clip; q.scale = scale;
+    hipLaunchKernelGGL(policy_seq_pass_kernel, dim3(nsb), dim3(256), 0, st_, q);
+  } else if (agg == 0) {
+    hipLaunchKernelGGL(policy_seq_weight_kernel, dim3(S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS), dim3(256), 0, st_, mask, seq_ptr, S, scale, w);
+  } else {
+    hipLaunchKernelGGL(policy_fill_weight_kernel, dim3(ceil_blocks(S, 256)), dim3(256), 0, st_, S, scale, w);
+  }
+  const dim3 grid(nb), block(PL_BLOCK);
+  if (kl_coef == 0.f) hipLaunchKernelGGL((policy_loss_kernel<-1, SEQ>), grid, block, 0, st_, p);
+  else if (kl_estimator == 0) hipLaunchKernelGGL((policy_loss_kernel<0, SEQ>), grid, block, 0, st_, p);
+  else if (kl_estimator == 1) hipLaunchKernelGGL((policy_loss_kernel<1, SEQ>), grid, block, 0, st_, p);
+  else hipLaunchKernelGGL((policy_loss_kernel<2, SEQ>), grid, block, 0, st_, p);
+  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb + nsb, stats);
+  return DTA_LAUNCH_STATUS();
+}
 
 }  // namespace
 
@@ -449,38 +502,9 @@ extern "C" int dta_policy_loss(const float* lp, const float* ent, const int32_t*
                                int32_t adv_per_seq, float* w, float* dlp, float* dent, float* partial, float* stats, int32_t T, int32_t S,
                                float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef,
                                int32_t agg, float scale, void* stream) {
-  if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !mask || !adv || !w || !dlp || !dent || !partial || !stats ||
-      T <= 0 || S <= 0)
-    return DTA_EINVAL;
-  if (!finite_f(clip_low) || !finite_f(clip_high) || clip_low < 0.f || clip_high < 0.f) return DTA_EINVAL;
-  if (dual_clip != 0.f && !(finite_f(dual_clip) && dual_clip > 1.f)) return DTA_EINVAL;
-  if (kl_estimator < 0 || kl_estimator > 2 || agg < 0 || agg > 1) return DTA_EINVAL;
-  if (!finite_f(kl_coef) || !finite_f(entropy_coef) || !finite_f(scale)) return DTA_EINVAL;
-  if (kl_coef != 0.f && !ref_lp) return DTA_EINVAL;
-  if (!aligned16(lp) || !aligned16(ent) || !aligned16(depth) || !aligned16(row_seq_lo) || !aligned16(row_seq_hi) || !aligned16(seq_ptr) ||
-      !aligned16(mask) || !aligned16(adv) || !aligned16(w) || !aligned16(dlp) || !aligned16(dent) || !aligned16(partial) || !aligned16(stats) ||
-      (old_lp && !aligned16(old_lp)) || (ref_lp && !aligned16(ref_lp)))
-    return DTA_EALIGN;
-  hipStream_t st_ = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
-  if (agg == 0)
-    hipLaunchKernelGGL(policy_seq_weight_kernel, dim3(S < 2048 ? S : 2048), dim3(256), 0, st_, mask, seq_ptr, S, scale, w);
-  else
-    hipLaunchKernelGGL(policy_fill_weight_kernel, dim3(ceil_blocks(S, 256)), dim3(256), 0, st_, S, scale, w);
-  PolicyParams p;
-  p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
-  p.old_lp = old_lp; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w;
-  p.dlp = dlp; p.dent = dent; p.partial = partial;
-  p.T = T; p.S = S; p.adv_per_seq = adv_per_seq != 0;
-  p.lo = 1.f - clip_low; p.hi = 1.f + clip_high; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
-  const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS);
-  const dim3 grid(nb), block(PL_BLOCK);
-  if (kl_coef == 0.f) hipLaunchKernelGGL(policy_loss_kernel<-1>, grid, block, 0, st_, p);
-  else if (kl_estimator == 0) hipLaunchKernelGGL(policy_loss_kernel<0>, grid, block, 0, st_, p);
-  else if (kl_estimator == 1) hipLaunchKernelGGL(policy_loss_kernel<1>, grid, block, 0, st_, p);
-  else hipLaunchKernelGGL(policy_loss_kernel<2>, grid, block, 0, st_, p);
-  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb, stats);
-  return DTA_LAUNCH_STATUS();
+  return policy_loss<false>(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, nullptr, nullptr, nullptr, nullptr, old_lp, ref_lp, mask, adv,
+                            adv_per_seq, w, nullptr, dlp, dent, partial, stats, T, S, 0, 0, clip_low, clip_high, dual_clip, kl_coef,
+                            kl_estimator, entropy_coef, agg, scale, stream);
 }
 
 extern "C" int dta_policy_loss_seq_blocks(int32_t T, int32_t S) {
@@ -493,41 +517,9 @@ extern "C" int dta_policy_loss_seq(const float* lp, const float* ent, const int3
                                    int32_t adv_per_seq, float* w, float* c, float* dlp, float* dent, float* partial, float* stats, int32_t T,
                                    int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip, float kl_coef,
                                    int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, void* stream) {
-  if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !leaf_run_ptr || !run_row0 || !run_depth0 || !seq_leaf || !mask ||
-      !adv || !w || !c || !dlp || !dent || !partial || !stats || T <= 0 || S <= 0 || M <= 0 || R <= 0)
-    return DTA_EINVAL;
-  if (!finite_f(clip_low) || !finite_f(clip_high) || clip_low < 0.f || clip_high < 0.f) return DTA_EINVAL;
-  if (dual_clip != 0.f && !(finite_f(dual_clip) && dual_clip > 1.f)) return DTA_EINVAL;
-  if (kl_estimator < 0 || kl_estimator > 2 || agg < 0 || agg > 1) return DTA_EINVAL;
-  if (!finite_f(kl_coef) || !finite_f(entropy_coef) || !finite_f(scale)) return DTA_EINVAL;
-  if (kl_coef != 0.f && !ref_lp) return DTA_EINVAL;
-  if (!aligned16(lp) || !aligned16(ent) || !aligned16(depth) || !aligned16(row_seq_lo) || !aligned16(row_seq_hi) || !aligned16(seq_ptr) ||
-      !aligned16(leaf_run_ptr) || !aligned16(run_row0) || !aligned16(run_depth0) || !aligned16(seq_leaf) || !aligned16(mask) ||
-      !aligned16(adv) || !aligned16(w) || !aligned16(c) || !aligned16(dlp) || !aligned16(dent) || !aligned16(partial) || !aligned16(stats) ||
-      (old_lp && !aligned16(old_lp)) || (ref_lp && !aligned16(ref_lp)))
-    return DTA_EALIGN;
-  hipStream_t st_ = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
-  const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS), nsb = S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS;
-  SeqPassParams q;
-  q.lp = lp; q.seq_ptr = seq_ptr; q.leaf_run_ptr = leaf_run_ptr; q.run_row0 = run_row0; q.run_depth0 = run_depth0; q.seq_leaf = seq_leaf;
-  q.old_lp = old_lp; q.mask = mask; q.adv = adv; q.w = w; q.c = c; q.partial = partial + (size_t)nb * PL_NSTAT;
-  q.T = T; q.S = S; q.M = M; q.R = R; q.adv_per_seq = adv_per_seq != 0; q.seq_mean = agg == 0;
-  q.lo = 1.f - clip_low; q.hi = 1.f + clip_high; q.dual = dual_clip; q.scale = scale;
-  hipLaunchKernelGGL(policy_seq_pass_kernel, dim3(nsb), dim3(256), 0, st_, q);
-  PolicyParams p;
-  p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
-  p.old_lp = nullptr; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w; p.c = c;
-  p.dlp = dlp; p.dent = dent; p.partial = partial;
-  p.T = T; p.S = S; p.adv_per_seq = adv_per_seq != 0;
-  p.lo = q.lo; p.hi = q.hi; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
-  const dim3 grid(nb), block(PL_BLOCK);
-  if (kl_coef == 0.f) hipLaunchKernelGGL((policy_loss_kernel<-1, true>), grid, block, 0, st_, p);
-  else if (kl_estimator == 0) hipLaunchKernelGGL((policy_loss_kernel<0, true>), grid, block, 0, st_, p);
-  else if (kl_estimator == 1) hipLaunchKernelGGL((policy_loss_kernel<1, true>), grid, block, 0, st_, p);
-  else hipLaunchKernelGGL((policy_loss_kernel<2, true>), grid, block, 0, st_, p);
-  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb + nsb, stats);
-  return DTA_LAUNCH_STATUS();
+  return policy_loss<true>(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, old_lp, ref_lp, mask,
+                           adv, adv_per_seq, w, c, dlp, dent, partial, stats, T, S, M, R, clip_low, clip_high, dual_clip, kl_coef,
+                           kl_estimator, entropy_coef, agg, scale, stream);
 }
 
 extern "C" int dta_preference_loss_blocks(int32_t T, int32_t S, int32_t P) {
@@ -550,17 +542,15 @@ extern "C" int dta_preference_loss(const float* lp, const int32_t* depth, const 
   if ((kind == 2 && gamma != 0.f) || sft_coef < 0.f) return DTA_EINVAL;
   if (!reference_free && (ref_lp != nullptr) == (ref_sum != nullptr)) return DTA_EINVAL;      // exactly one form of the reference
   if (reference_free) ref_lp = ref_sum = nullptr;                                             // neither is read
-  if (!aligned16(lp) || !aligned16(depth) || !aligned16(row_seq_lo) || !aligned16(row_seq_hi) || !aligned16(seq_ptr) ||
-      !aligned16(leaf_run_ptr) || !aligned16(run_row0) || !aligned16(run_depth0) || !aligned16(seq_leaf) || !aligned16(pair_c) ||
-      !aligned16(pair_r) || !aligned16(mask) || !aligned16(nhat) || !aligned16(u) || !aligned16(sft) || !aligned16(g) || !aligned16(dlp) ||
-      !aligned16(partial) || !aligned16(stats) || (ref_lp && !aligned16(ref_lp)) || (ref_sum && !aligned16(ref_sum)))
+  if (!all_aligned16(lp, depth, row_seq_lo, row_seq_hi, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r, mask, nhat, u,
+                     sft, g, dlp, partial, stats, ref_lp, ref_sum))
     return DTA_EALIGN;
   hipStream_t st_ = static_cast<hipStream_t>(stream);
   DTA_REFUSE_IF_PRIOR_ERROR();
   PrefSeqParams q;
-  q.lp = lp; q.seq_ptr = seq_ptr; q.leaf_run_ptr = leaf_run_ptr; q.run_row0 = run_row0; q.run_depth0 = run_depth0; q.seq_leaf = seq_leaf;
+  static_cast<PathParams&>(q) = {lp, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, T, S, M, R};
   q.ref_lp = ref_lp; q.ref_sum = ref_sum; q.mask = mask; q.nhat = nhat; q.u = u; q.sft = sft; q.g = g;
-  q.T = T; q.S = S; q.M = M; q.R = R; q.length_normalize = length_normalize != 0;
+  q.length_normalize = length_normalize != 0;
   hipLaunchKernelGGL(preference_seq_pass_kernel, dim3(S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS), dim3(256), 0, st_, q);
   PrefPairParams c;
   c.pair_c = pair_c; c.pair_r = pair_r; c.nhat = nhat; c.u = u; c.sft = sft; c.g = g; c.partial = partial;

@@ -64,6 +64,22 @@ def _finite(name: str, v) -> float:
     return v
 
 
+def _per_token(key: str, v, n: int):
+    """An attachment entry per prediction is a tensor [n], or absent (None)."""
+    if v is None:
+        return
+    if not isinstance(v, torch.Tensor):
+        raise ValueError(f"{key}: a tensor of {n} elements is expected, got {type(v).__name__}")
+    if v.dim() != 1 or v.shape[0] != n:
+        raise ValueError(f"{key}: shape {tuple(v.shape)} where [{n}] (len - 1) is expected")
+
+
+def attachments_by_sequence(trie) -> list:
+    """The attachments of a trie's sequences in sequence order (`_sequence_batch_id`), as `forward` orders the log-probs."""
+    atts = {att["_sequence_batch_id"]: att for attach_list in trie.attach_lists for att, _ in attach_list}
+    return [atts[s] for s in range(len(atts))]
+
+
 class PolicyLoss:
     def __init__(self, clip_low: float = 0.2, clip_high: float = 0.2, dual_clip: Optional[float] = None, kl_coef: float = 0.0,
                  kl_estimator: str = "k3", entropy_coef: float = 0.0, agg: str = "seq_mean", scale: float = 1.0,
@@ -109,12 +125,8 @@ class PolicyLoss:
                 raise KeyError("ref_logprobs (required because kl_coef != 0)")
         mask = attachment.get("loss_mask")
         for key, v in (("advantages", adv), ("old_logprobs", old), ("ref_logprobs", ref), ("loss_mask", mask)):
-            if v is None or isinstance(v, float):
-                continue
-            if not isinstance(v, torch.Tensor):
-                raise ValueError(f"{key}: a tensor of {n} elements is expected, got {type(v).__name__}")
-            if v.dim() != 1 or v.shape[0] != n:
-                raise ValueError(f"{key}: shape {tuple(v.shape)} where [{n}] (len - 1) is expected")
+            if not isinstance(v, float):
+                _per_token(key, v, n)
         return adv, old, ref, mask
 
     def __call__(self, logprob: torch.Tensor, entropy: torch.Tensor, attachment: dict) -> torch.Tensor:
@@ -227,13 +239,8 @@ class PreferenceLoss:
         if not self.reference_free and (ref is None) == (ref_sum is None):
             raise (KeyError("ref_logprobs or ref_logprob_sum (required unless reference_free)") if ref is None else
                    ValueError("ref_logprobs and ref_logprob_sum are both given: exactly one form of the reference is used"))
-        for key, v in (("ref_logprobs", ref), ("loss_mask", mask)):
-            if v is None:
-                continue
-            if not isinstance(v, torch.Tensor):
-                raise ValueError(f"{key}: a tensor of {n} elements is expected, got {type(v).__name__}")
-            if v.dim() != 1 or v.shape[0] != n:
-                raise ValueError(f"{key}: shape {tuple(v.shape)} where [{n}] (len - 1) is expected")
+        _per_token("ref_logprobs", ref, n)
+        _per_token("loss_mask", mask, n)
         if ref_sum is not None:
             ref_sum = _finite("ref_logprob_sum", ref_sum)
         return mask, ref, ref_sum
@@ -310,11 +317,6 @@ def two_pass_backward(engine, model, trie, loss: PreferenceLoss, block_size: int
     at the cost of one more (no-grad) model forward: `forward` for the sequence log-probs, `loss.coefficients` on them, `backward`
     with the linear closure g_s (m logprob).sum().  Accumulates the gradient of the true objective and returns
     (its value as a float, stats [8] in the order of PREFERENCE_STATS)."""
-    logprobs = engine.forward(model, trie)
-    atts = [None] * len(logprobs)
-    for attach_list in trie.attach_lists:
-        for att, _ in attach_list:
-            atts[att["_sequence_batch_id"]] = att
-    total, g, stats = loss.coefficients(logprobs, atts)
+    total, g, stats = loss.coefficients(engine.forward(model, trie), attachments_by_sequence(trie))
     engine.backward(model, trie, loss.surrogate(g), block_size)
     return float(total.item()), stats

@@ -1677,30 +1677,54 @@ def _cat_per_token(vals, fill, seq_ptr, device):
     return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=device)
 
 
-def policy_token_inputs(loss, attach_lists, seq_ptr, device):
-    """The per-token inputs of the fused objective, concatenated in callback order behind seq_ptr: (old, ref, mask, adv, adv_per_seq), fp32
-    device vectors of N = seq_ptr[-1] elements (old / ref None: on-policy / no KL; adv one value per sequence when every attachment gives
-    a float).  Each key is checked as PolicyLoss.__call__ checks it.  A key whose tensors all live on the host is concatenated there and
-    uploaded once out of page-locked staging; tensors already on the device are concatenated there."""
-    from ._staging import upload
-    cols = {"adv": [], "old": [], "ref": [], "mask": []}
+def _sequence_fields(loss, attach_lists, seq_ptr):
+    """loss.fields(attachment, n) of every sequence, in callback order; n = len - 1 must be the sequence's extent in seq_ptr."""
     s = 0
     for attach_list in attach_lists:
         for attachment, length in attach_list:
             n = int(length) - 1
             if n != int(seq_ptr[s + 1]) - int(seq_ptr[s]):
                 raise ValueError("attach lists and seq_ptr disagree")
-            adv, old, ref, mask = loss.fields(attachment, n)
-            cols["adv"].append(adv); cols["old"].append(old); cols["ref"].append(ref); cols["mask"].append(mask)
+            yield loss.fields(attachment, n)
             s += 1
+
+
+def _f32_aligned(t):
+    """fp32, contiguous and on a 16-byte boundary (a view into a larger buffer may start anywhere); None stays None"""
+    if t is None:
+        return None
+    t = t.detach().to(torch.float32).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _carve_f32(device, **parts):
+    """One fp32 device buffer carved into the named vectors of the given lengths, in order, each on a 16-byte boundary (a part takes a
+    multiple of 4 floats): (buffer, {name: view})."""
+    r4 = lambda n: (n + 3) // 4 * 4
+    buf = torch.empty(sum(r4(n) for n in parts.values()), dtype=torch.float32, device=device)
+    views, o = {}, 0
+    for name, n in parts.items():
+        views[name] = buf[o:o + n]
+        o += r4(n)
+    return buf, views
+
+
+def policy_token_inputs(loss, attach_lists, seq_ptr, device):
+    """The per-token inputs of the fused objective, concatenated in callback order behind seq_ptr: (old, ref, mask, adv, adv_per_seq), fp32
+    device vectors of N = seq_ptr[-1] elements (old / ref None: on-policy / no KL; adv one value per sequence when every attachment gives
+    a float).  Each key is checked as PolicyLoss.__call__ checks it.  A key whose tensors all live on the host is concatenated there and
+    uploaded once out of page-locked staging; tensors already on the device are concatenated there."""
+    from ._staging import upload
+    fields = list(_sequence_fields(loss, attach_lists, seq_ptr))
+    advs, olds, refs, masks = ([f[k] for f in fields] for k in range(4))
     cat = lambda vals, fill: _cat_per_token(vals, fill, seq_ptr, device)
-    if any(v is None for v in cols["old"]) and not all(v is None for v in cols["old"]):
+    if any(v is None for v in olds) and not all(v is None for v in olds):
         raise ValueError("old_logprobs: given for some sequences of the trie and absent for others")
-    old = None if all(v is None for v in cols["old"]) else cat(cols["old"], 0.0)
-    ref = None if loss.kl_coef == 0 else cat(cols["ref"], 0.0)
-    mask = cat(cols["mask"], 1.0)
-    adv_per_seq = all(isinstance(v, float) for v in cols["adv"])
-    adv = upload([np.asarray(cols["adv"], np.float32)], device, np.float32)[0] if adv_per_seq else cat(cols["adv"], 0.0)
+    old = None if all(v is None for v in olds) else cat(olds, 0.0)
+    ref = None if loss.kl_coef == 0 else cat(refs, 0.0)
+    mask = cat(masks, 1.0)
+    adv_per_seq = all(isinstance(v, float) for v in advs)
+    adv = upload([np.asarray(advs, np.float32)], device, np.float32)[0] if adv_per_seq else cat(advs, 0.0)
     return old, ref, mask, adv, adv_per_seq
 
 
@@ -1718,47 +1742,29 @@ def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, 
     if seq_level != (path_tables is not None):
         raise ValueError(f"ratio = {loss.ratio!r}: path_tables (packing.policy_path_tables) go with the sequence-level ratio, and only with it")
     T, S = int(lp.shape[0]), int(seq_ptr.shape[0]) - 1
-    def f32(t):                 # fp32, contiguous and on a 16-byte boundary (a view into a larger buffer may start anywhere)
-        if t is None:
-            return None
-        t = t.detach().to(torch.float32).contiguous()
-        return t if t.data_ptr() % 16 == 0 else t.clone()
-    lp, ent, old, ref, mask, adv = f32(lp), f32(ent), f32(old), f32(ref), f32(mask), f32(adv)
-    _require_cuda(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv)
+    lp, ent, old, ref, mask, adv = map(_f32_aligned, (lp, ent, old, ref, mask, adv))
+    path = list(path_tables) if seq_level else []
+    _require_cuda(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, *path)
     N = int(mask.shape[0])
     assert ent.shape[0] == T and depth.shape[0] == T and row_seq_lo.shape[0] == T and row_seq_hi.shape[0] == T
-    assert depth.dtype == row_seq_lo.dtype == row_seq_hi.dtype == seq_ptr.dtype == torch.int32
+    assert all(t.dtype == torch.int32 for t in (depth, row_seq_lo, row_seq_hi, seq_ptr, *path))
     assert adv.shape[0] == (S if adv_per_seq else N) and (old is None or old.shape[0] == N) and (ref is None or ref.shape[0] == N)
     nb = lib().dta_policy_loss_seq_blocks(T, S) if seq_level else lib().dta_policy_loss_blocks(T)
-    # one fp32 buffer: dlp | dent | w | partial | stats (| c), each part a multiple of 4 floats
-    r4 = lambda n: (n + 3) // 4 * 4
-    buf = torch.empty(2 * r4(T) + r4(S) + 8 * nb + 8 + (r4(S) if seq_level else 0), dtype=torch.float32, device=lp.device)
-    dlp, dent = buf[:T], buf[r4(T):r4(T) + T]
-    o = 2 * r4(T)
-    w, partial, stats = buf[o:o + S], buf[o + r4(S):o + r4(S) + 8 * nb], buf[o + r4(S) + 8 * nb:o + r4(S) + 8 * nb + 8]
+    buf, v = _carve_f32(lp.device, dlp=T, dent=T, w=S, partial=8 * nb, stats=8, c=S if seq_level else 0)
+    # the two entries differ by the path tables (with their sizes M, R) and the per-sequence scalar c of the sequence-level ratio
+    c, sizes = [], []
     if seq_level:
-        run_ptr, run_row0, run_depth0, seq_leaf = path_tables
-        _require_cuda(run_ptr, run_row0, run_depth0, seq_leaf)
-        assert run_ptr.dtype == run_row0.dtype == run_depth0.dtype == seq_leaf.dtype == torch.int32
-        M, R = int(run_ptr.shape[0]) - 1, int(run_row0.shape[0])
-        assert seq_leaf.shape[0] == S and run_depth0.shape[0] == R
-        c = buf[o + r4(S) + 8 * nb + 8:][:S]
-        _launch("dta_policy_loss_seq", (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, old, ref,
-                                        mask, adv, buf),
-                ptr(lp), ptr(ent), ptr(depth), ptr(row_seq_lo), ptr(row_seq_hi), ptr(seq_ptr), ptr(run_ptr), ptr(run_row0), ptr(run_depth0),
-                ptr(seq_leaf), ptr(old), ptr(ref), ptr(mask), ptr(adv), int(bool(adv_per_seq)), ptr(w), ptr(c), ptr(dlp), ptr(dent),
-                ptr(partial), ptr(stats), T, S, M, R,
-                float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
-                KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
-                nbytes=4 * (4 * T + (5 + 2 * (old is not None) + (ref is not None)) * N))
-        return dlp, dent, stats, w
-    _launch("dta_policy_loss", (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, buf),
-            ptr(lp), ptr(ent), ptr(depth), ptr(row_seq_lo), ptr(row_seq_hi), ptr(seq_ptr), ptr(old), ptr(ref), ptr(mask), ptr(adv),
-            int(bool(adv_per_seq)), ptr(w), ptr(dlp), ptr(dent), ptr(partial), ptr(stats), T, S,
+        run_ptr, run_row0, run_depth0, seq_leaf = path
+        assert seq_leaf.shape[0] == S and run_depth0.shape[0] == run_row0.shape[0]
+        c, sizes = [ptr(v["c"])], [int(run_ptr.shape[0]) - 1, int(run_row0.shape[0])]
+    tensors = (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, *path, old, ref, mask, adv)
+    _launch("dta_policy_loss_seq" if seq_level else "dta_policy_loss", (*tensors, buf),
+            *map(ptr, tensors), int(bool(adv_per_seq)), ptr(v["w"]), *c, ptr(v["dlp"]), ptr(v["dent"]), ptr(v["partial"]), ptr(v["stats"]),
+            T, S, *sizes,
             float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
             KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
-            nbytes=4 * (4 * T + (3 + (old is not None) + (ref is not None)) * N))
-    return dlp, dent, stats, w
+            nbytes=4 * (4 * T + ((5 + 2 * (old is not None) if seq_level else 3 + (old is not None)) + (ref is not None)) * N))
+    return v["dlp"], v["dent"], v["stats"], v["w"]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1770,16 +1776,8 @@ def preference_token_inputs(loss, attach_lists, seq_ptr, device):
     with loss.reference_free.  Each key is checked as PreferenceLoss.fields checks it, and one form of the reference must serve every
     sequence.  Staging as policy_token_inputs (_cat_per_token)."""
     from ._staging import upload
-    masks, refs, sums = [], [], []
-    s = 0
-    for attach_list in attach_lists:
-        for attachment, length in attach_list:
-            n = int(length) - 1
-            if n != int(seq_ptr[s + 1]) - int(seq_ptr[s]):
-                raise ValueError("attach lists and seq_ptr disagree")
-            mask, ref, ref_sum = loss.fields(attachment, n)
-            masks.append(mask); refs.append(ref); sums.append(ref_sum)
-            s += 1
+    fields = list(_sequence_fields(loss, attach_lists, seq_ptr))
+    masks, refs, sums = ([f[k] for f in fields] for k in range(3))
     if not loss.reference_free and any(v is None for v in refs) and any(v is None for v in sums):
         raise ValueError("ref_logprobs for some sequences of the trie and ref_logprob_sum for others: one form of the reference per call")
 
@@ -1801,12 +1799,7 @@ def preference_loss(loss, lp: torch.Tensor, depth: torch.Tensor, row_seq_lo: tor
     gradient coefficients (d loss / d lp[row(s, j)] = g[s] mask[j]); u: the per-sequence (length-normalised) log-ratio sums."""
     from .losses import PREFERENCE_KINDS
     T, S = int(lp.shape[0]), int(seq_ptr.shape[0]) - 1
-    def f32(t):                 # fp32, contiguous and on a 16-byte boundary (a view into a larger buffer may start anywhere)
-        if t is None:
-            return None
-        t = t.detach().to(torch.float32).contiguous()
-        return t if t.data_ptr() % 16 == 0 else t.clone()
-    lp, ref_lp, ref_sum, mask = f32(lp), f32(ref_lp), f32(ref_sum), f32(mask)
+    lp, ref_lp, ref_sum, mask = map(_f32_aligned, (lp, ref_lp, ref_sum, mask))
     run_ptr, run_row0, run_depth0, seq_leaf = path_tables
     pair_c, pair_r = pair_tables
     _require_cuda(lp, depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r, ref_lp, ref_sum, mask)
@@ -1823,19 +1816,11 @@ def preference_loss(loss, lp: torch.Tensor, depth: torch.Tensor, row_seq_lo: tor
     assert all(t.dtype == torch.int32 for t in (depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r))
     assert (ref_lp is None or ref_lp.shape[0] == N) and (ref_sum is None or ref_sum.shape[0] == S)
     nb = lib().dta_preference_loss_blocks(T, S, P)
-    # one fp32 buffer: dlp | nhat | u | sft | g | partial | stats, each part a multiple of 4 floats
-    r4 = lambda n: (n + 3) // 4 * 4
-    buf = torch.empty(r4(T) + 4 * r4(S) + 8 * nb + 8, dtype=torch.float32, device=lp.device)
-    o = r4(T)
-    dlp = buf[:T]
-    nhat, u, sft, g = (buf[o + k * r4(S):o + k * r4(S) + S] for k in range(4))
-    o += 4 * r4(S)
-    partial, stats = buf[o:o + 8 * nb], buf[o + 8 * nb:o + 8 * nb + 8]
-    _launch("dta_preference_loss", (lp, depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r, ref_lp,
-                                    ref_sum, mask, buf),
-            ptr(lp), ptr(depth), ptr(row_seq_lo), ptr(row_seq_hi), ptr(seq_ptr), ptr(run_ptr), ptr(run_row0), ptr(run_depth0), ptr(seq_leaf),
-            ptr(pair_c), ptr(pair_r), ptr(ref_lp), ptr(ref_sum), ptr(mask), ptr(nhat), ptr(u), ptr(sft), ptr(g), ptr(dlp), ptr(partial),
-            ptr(stats), T, S, M, R, P, PREFERENCE_KINDS.index(loss.kind), float(loss.beta), float(loss.label_smoothing), float(loss.gamma),
+    buf, v = _carve_f32(lp.device, dlp=T, nhat=S, u=S, sft=S, g=S, partial=8 * nb, stats=8)
+    tensors = (lp, depth, row_seq_lo, row_seq_hi, seq_ptr, run_ptr, run_row0, run_depth0, seq_leaf, pair_c, pair_r, ref_lp, ref_sum, mask)
+    _launch("dta_preference_loss", (*tensors, buf), *map(ptr, tensors),
+            *(ptr(v[k]) for k in ("nhat", "u", "sft", "g", "dlp", "partial", "stats")), T, S, M, R, P,
+            PREFERENCE_KINDS.index(loss.kind), float(loss.beta), float(loss.label_smoothing), float(loss.gamma),
             int(loss.length_normalize), int(loss.reference_free), float(loss.sft_coef), float(loss.scale),
             nbytes=4 * (5 * T + (2 + (ref_lp is not None)) * N))
-    return dlp, stats, g, u
+    return v["dlp"], v["stats"], v["g"], v["u"]

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .losses import PREFERENCE_STATS, STATS as LOSS_STATS, PolicyLoss, PreferenceLoss
+from .losses import PREFERENCE_STATS, STATS as LOSS_STATS, PolicyLoss, PreferenceLoss, attachments_by_sequence
 from .model import (_head_dim, ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry,
                     longrope_boundary, packed_hidden_states)
 from .trie import pop_block_starts
@@ -503,37 +503,30 @@ class TreeTrainingEngine:
             torch.autograd.backward(roots, grads)
 
     @staticmethod
-    def _policy_rows(packed, token_trie, lp, ent, loss):
-        """The built-in objective on the packed rows: (dlp [T], dent [T], stats [8]) of ops.policy_loss.  The row -> sequence-range
-        tables come from the packing plan on the host and travel in one staged upload; the attachments' per-token tensors are
-        concatenated in callback order (ops.policy_token_inputs).  A sequence-level ratio adds the sequence -> row-run tables of
-        packing.policy_path_tables to the same upload."""
+    def _fused_rows(packed, token_trie, lp, ent, loss):
+        """A built-in objective (losses.PolicyLoss / PreferenceLoss) on the packed rows, in one C-ABI call (ops.policy_loss /
+        ops.preference_loss): ([(tensor, gradient)] to back-propagate, the statistics in the order of losses.STATS / PREFERENCE_STATS,
+        the loss first).  The row -> sequence-range tables, the sequence -> row-run tables (a sequence-level ratio, a preference
+        objective) and the pair tables (a preference objective) come from the packing plan and the attach lists on the host and travel
+        in one staged upload; the attachments' per-token tensors are concatenated in callback order (ops.*_token_inputs).  Entropy is
+        differentiated only under an entropy bonus; a preference objective does not use it."""
         from ._staging import upload
-        row_lo, row_hi, seq_ptr, _ = packing.policy_row_tables(packed.plan, token_trie.attach_lists)
+        att, dev = token_trie.attach_lists, packed.tokens.device
+        pairwise = isinstance(loss, PreferenceLoss)
+        row_lo, row_hi, seq_ptr, _ = packing.policy_row_tables(packed.plan, att)
         tables = [row_lo, row_hi, seq_ptr]
-        if loss.ratio == "sequence":
-            tables += packing.policy_path_tables(packed.plan, token_trie.attach_lists)
-        dev = packed.tokens.device
-        row_lo_d, row_hi_d, seq_ptr_d, *path_d = upload(tables, dev, np.int32)
-        old, ref, mask, adv, adv_per_seq = ops.policy_token_inputs(loss, token_trie.attach_lists, seq_ptr, dev)
-        dlp, dent, stats, _ = ops.policy_loss(loss, lp, ent, packed.depth, row_lo_d, row_hi_d, seq_ptr_d, old, ref, mask, adv, adv_per_seq,
-                                              tuple(path_d) or None)
-        return dlp, dent, stats
-
-    @staticmethod
-    def _preference_rows(packed, token_trie, lp, loss):
-        """A preference objective on the packed rows: (dlp [T], stats [8]) of ops.preference_loss.  The row tables, the path tables and the
-        pair tables come from the packing plan and the attach lists on the host and travel in one staged upload."""
-        from ._staging import upload
-        row_lo, row_hi, seq_ptr, _ = packing.policy_row_tables(packed.plan, token_trie.attach_lists)
-        tables = [row_lo, row_hi, seq_ptr, *packing.policy_path_tables(packed.plan, token_trie.attach_lists),
-                  *packing.preference_pair_tables(token_trie.attach_lists)]
-        dev = packed.tokens.device
+        if pairwise or loss.ratio == "sequence":
+            tables += packing.policy_path_tables(packed.plan, att)
+        if pairwise:
+            tables += packing.preference_pair_tables(att)
         row_lo_d, row_hi_d, seq_ptr_d, *rest = upload(tables, dev, np.int32)
-        ref_lp, ref_sum, mask = ops.preference_token_inputs(loss, token_trie.attach_lists, seq_ptr, dev)
-        dlp, stats, _, _ = ops.preference_loss(loss, lp, packed.depth, row_lo_d, row_hi_d, seq_ptr_d, tuple(rest[:4]), tuple(rest[4:]),
-                                               ref_lp, ref_sum, mask)
-        return dlp, stats
+        if pairwise:
+            dlp, stats, _, _ = ops.preference_loss(loss, lp, packed.depth, row_lo_d, row_hi_d, seq_ptr_d, tuple(rest[:4]), tuple(rest[4:]),
+                                                   *ops.preference_token_inputs(loss, att, seq_ptr, dev))
+            return [(lp, dlp)], stats[:len(PREFERENCE_STATS)]
+        dlp, dent, stats, _ = ops.policy_loss(loss, lp, ent, packed.depth, row_lo_d, row_hi_d, seq_ptr_d,
+                                              *ops.policy_token_inputs(loss, att, seq_ptr, dev), tuple(rest) or None)
+        return [(lp, dlp)] + ([(ent, dent)] if loss.entropy_coef != 0 else []), stats[:len(LOSS_STATS)]
 
     def _backward_stack_two_pass(self, model, token_trie, loss, block_rows: int) -> float:
         """A preference objective on the block-wise walk, in two passes: the sequence log-probs from a no-grad forward, the per-sequence
@@ -542,11 +535,7 @@ class TreeTrainingEngine:
         forkpos = self.forkpos_list
         logprobs = self.forward(model, token_trie)          # resets the fork positions of this call: put them back
         self.forkpos_list = forkpos
-        atts = [None] * len(logprobs)
-        for attach_list in token_trie.attach_lists:
-            for att, _ in attach_list:
-                atts[att["_sequence_batch_id"]] = att
-        total, g, stats = loss.coefficients(logprobs, atts)
+        total, g, stats = loss.coefficients(logprobs, attachments_by_sequence(token_trie))
         del logprobs
         self._backward_stack(model, token_trie, loss.surrogate(g), block_rows)
         self.last_loss_path, self.loss_stats = "two_pass", stats
@@ -623,20 +612,12 @@ class TreeTrainingEngine:
                                          packed.fork_child, packed.fork_parent, self.tp_group, packed.fork_dev, final_softcap_of(model),
                                        logit_scale_of(model))
         fused = isinstance(loss_fn, (PolicyLoss, PreferenceLoss))
-        if isinstance(loss_fn, PreferenceLoss):
-            # a pair objective couples sequences: sequence pass, pair pass and row pass in one C-ABI call; entropy takes no part
+        if fused:
+            # a built-in objective runs over the packed rows themselves (one C-ABI call): no gather along the paths, no per-sequence
+            # callback, no scatter of per-sequence gradients - the gradients come out per row
             self.last_loss_path = "fused"
-            dlp, stats = self._preference_rows(packed, token_trie, lp, loss_fn)
-            dent = None
-            self.loss_stats = stats[:len(PREFERENCE_STATS)]
-            total = stats[0]
-        elif fused:
-            # the built-in objective runs over the packed rows themselves (one C-ABI call): no gather along the paths, no per-sequence
-            # callback, no scatter of per-sequence gradients - dlp / dent come out per row
-            self.last_loss_path = "fused"
-            dlp, dent, stats = self._policy_rows(packed, token_trie, lp, ent, loss_fn)
-            self.loss_stats = stats[:len(LOSS_STATS)]
-            total = stats[0]
+            roots, self.loss_stats = self._fused_rows(packed, token_trie, lp, ent, loss_fn)
+            total = self.loss_stats[0]
         else:
             total, leaves = self._path_losses(packed, token_trie, lp, ent, loss_fn)
         if total is None:
@@ -652,7 +633,6 @@ class TreeTrainingEngine:
             self._loss_host.copy_(total.detach().reshape(1).float(), non_blocking=True)
             landed = torch.cuda.Event(); landed.record()
         if fused:
-            roots = [(lp, dlp)] + ([(ent, dent)] if dent is not None and loss_fn.entropy_coef != 0 else [])      # no entropy bonus: entropy is not differentiated
             roots = [(t, g) for t, g in roots if t.requires_grad]
             if roots and torch.is_grad_enabled():
                 torch.autograd.backward([t for t, _ in roots], [g for _, g in roots])
