@@ -11,6 +11,12 @@
 #define DTA_REFUSE_IF_PRIOR_ERROR() do { if (hipPeekAtLastError() != hipSuccess) return DTA_EPRIOR; } while (0)
 // status of THIS launch (configuration errors: invalid grid, too much LDS, no code object for the device ...)
 #define DTA_LAUNCH_STATUS() (hipGetLastError() == hipSuccess ? DTA_OK : DTA_ELAUNCH)
+// The tail of an entry whose checks have passed, where it is exactly these two around the launches: launch(hipStream_t) enqueues them
+template <class L> inline int dta_launch(void* stream, L&& launch) {
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  launch(static_cast<hipStream_t>(stream));
+  return DTA_LAUNCH_STATUS();
+}
 
 // The arguments of one dta_tree_attn_fwd / dta_tree_attn_bwd call (include/dta.h), under the field names of the kernel parameter structs.
 // Host side only: the entry fills it once, tree_attn.hip validates it once, and the launch code copies its fields into the parameter
@@ -53,6 +59,7 @@ template <class F> inline void dta_storage_type16(int32_t dtype, F&& f) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <class... P> inline bool all_aligned16(const P*... p) { return (aligned16(p) && ...); }    // a null pointer counts as aligned
 // workgroups that cover n items at `per` each; row_blocks: the same for a grid-stride kernel, at least 1 and at most cap
 inline unsigned ceil_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 inline int row_blocks(int64_t rows, int per_block, int cap) { int64_t b = (rows + per_block - 1) / per_block; return (int)(b < cap ? (b > 0 ? b : 1) : cap); }

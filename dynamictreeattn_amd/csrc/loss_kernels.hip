@@ -441,7 +441,6 @@ __global__ __launch_bounds__(PL_BLOCK) void preference_row_kernel(const PrefRowP
 }
 
 inline bool finite_f(float v) { return v == v && v - v == 0.f; }
-template <class... P> inline bool all_aligned16(const P*... p) { return (aligned16(p) && ...); }    // a null pointer counts as aligned
 
 // dta_policy_loss (SEQ = false: no path tables, no c, M and R unused) and dta_policy_loss_seq
 template <bool SEQ>

@@ -79,7 +79,7 @@ def _case(R_, H, dtype, n_delta, with_dres, eps, worst, backward=True):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("H", [8, 64, 120, 4096, 8184, 8192])
+@pytest.mark.parametrize("H", [8, 64, 120, 1024, 1032, 2048, 2056, 4096, 4104, 8184, 8192])
 def test_layernorm_every_form(H, dtype):
     """R in {1, 3, 4, 65, 257} x no / one / two deltas x dres NULL / given; dw wanted and not (inside _case)."""
     worst = {}

@@ -178,7 +178,7 @@ def _norm_add(y, w, res, eps, want_yn, label=""):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("H", [32, 2048, 5120, 8192, 16384])
+@pytest.mark.parametrize("H", [32, 1032, 2048, 2056, 4096, 4104, 5120, 8192, 16384])
 def test_rmsnorm_add_every_form(H, dtype):
     """The register forms (2 / 4 / 8 groups per lane), the two-pass form above 4096 up to 16384; 1 / 3 / 5 / 37 rows; yn given and NULL
     (the same out bits); the operator's backward - dy through the existing RMSNorm bound, d res = d out bitwise - where the backward

@@ -70,7 +70,8 @@ def test_references_are_float64_autograd(n_delta):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("R_,H", [(1, 8), (3, 64), (4, 120), (65, 4096), (7, 8184), (5, 8192)])
+@pytest.mark.parametrize("R_,H", [(1, 8), (3, 64), (4, 120), (3, 1024), (5, 1032), (4, 2048), (3, 2056), (65, 4096), (5, 4104),
+                                         (7, 8184), (5, 8192)])
 def test_emulation_stays_inside_every_bound(R_, H, dtype):
     for n_delta, with_dres in itertools.product((0, 1, 2), (False, True)):
         x, da, db, w, dy, dres = _inputs(R_, H, dtype, n_delta)
