@@ -12,6 +12,10 @@
 // walks the sequence's root path - a few contiguous row runs - for r_s, w_s, c_s and the surrogate's share of the statistics; the row
 // pass is the one above with c_s m in place of the token's own surrogate gradient; one reduction joins the partials of both.
 //
+// Off-policy corrections and CISPO (dta_policy_loss_ex): a detached rollout importance weight omega, truncated or masked, per token
+// (formed in the row term from the row's own lp when old_lp is absent) or per sequence (left by the sequence pass, which walks the path
+// only when old_lp is absent), multiplies the surrogate; with a sequence-level ratio it enters c_s.  CISPO is a second row-term form.
+//
 // Preference objectives (dta_preference_loss: DPO / cDPO / SimPO, SLiC, IPO): a pair couples two sequences, so a pair pass stands
 // between the sequence pass (u_s, one number per sequence, over the same path walk) and a row pass that sums g_s m with the pair's
 // coefficient g_s; the statistics are per pair and come from the pair pass alone.
@@ -27,7 +31,7 @@ namespace {
 constexpr int PL_BLOCK = 256;       // rows per workgroup step
 constexpr int PL_SERIAL = 16;       // longest sequence range a single thread sums
 constexpr int PL_MAX_BLOCKS = 1024; // grid cap: the rest is grid-strided, the partial-sum workspace has at most this many rows
-constexpr int PL_NSTAT = 8;         // {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0}
+constexpr int PL_NSTAT = 8;         // {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0 | sum m omega, 0 | altered weights}
 constexpr int PL_SEQ_BLOCKS = 2048; // grid cap of the sequence pass: one workgroup per sequence, the rest grid-strided
 
 // ---- the shared algorithms -----------------------------------------------------------------------------------------------------
@@ -329,6 +333,173 @@ __global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParam
   }
 }
 
+// ---- off-policy corrections and CISPO (dta_policy_loss_ex) -------------------------------------------------------------------------
+// A rollout importance weight omega = truncate | mask (rho), rho from y = old - rollout (old absent: the row's own lp - rollout), per
+// token or one per sequence, multiplies the surrogate and its gradient and nothing else; CISPO is a second form of the surrogate.  The
+// entries above keep their kernels: the token-level row term of this entry is a functor of its own (ex_terms), its sequence pass a
+// kernel of its own (policy_ex_seq_pass_kernel); a sequence-level ratio runs the row kernel above unchanged, because c_s holds omega.
+
+// omega from rho: mode 0 truncates at cap, mode 1 drops what lies outside [floor, cap].  No arithmetic on rho: an overflowed expf (inf)
+// gives cap or 0 and never NaN.  `altered`: omega != rho.
+struct IsWeight { float omega; bool altered; };
+__device__ __forceinline__ IsWeight is_weight(float rho, int mode, float cap, float floor) {
+  if (mode == 0) {
+    const bool over = rho > cap;
+    return {over ? cap : rho, over};
+  }
+  const bool keep = rho >= floor && rho <= cap;
+  return {keep ? rho : 0.f, !keep};
+}
+
+struct PolicyExParams : PolicyParams {
+  const float *rollout, *omega;              // omega [S]: the sequence pass's weight per sequence (ISL == 2 reads it)
+  int32_t is_mode;
+  float is_cap, is_floor;
+};
+struct PolicyExStats { float v[PL_NSTAT]; };
+
+// the terms a row owns for sequence s under a token-level ratio.  SUR: 0 the clipped surrogate, 1 CISPO (pg = -clamp(r) A lp with the
+// clamp detached: the gradient -clamp(r) A is never zeroed, "clipped" counts r outside [lo, hi]).  ISL: 0 no weight, 1 a weight per
+// token formed here, 2 the sequence's weight omega[s] (columns 6 and 7 are the sequence pass's then).
+template <int KL, int SUR, int ISL>
+__device__ __forceinline__ void ex_terms(const PolicyExParams& p, int s, const PolicyRow& row, PolicySum& a, PolicyExStats& st) {
+  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b, d = row.d;
+  if (n < d) return;                                       // the sequence ends above this row
+  const float w = p.w[s];
+  if (d >= 1) {
+    const int i = b + d - 1;
+    const float m = p.mask[i];
+    const float A = p.adv[p.adv_per_seq ? s : i];
+    const float r = p.old_lp ? expf(row.lp - p.old_lp[i]) : 1.f;
+    float pg, g;
+    bool clipped;
+    if (SUR == 0) {
+      const Pg q = clipped_pg(r, p.lo, p.hi, A, p.dual);
+      pg = q.pg; clipped = q.clipped;
+      g = clipped ? 0.f : -r * A;
+    } else {
+      g = -fminf(fmaxf(r, p.lo), p.hi) * A;
+      pg = g * row.lp;
+      clipped = r < p.lo || r > p.hi;
+    }
+    if (ISL == 1) {
+      const float y = (p.old_lp ? p.old_lp[i] : row.lp) - p.rollout[i];
+      const auto [omega, altered] = is_weight(expf(y), p.is_mode, p.is_cap, p.is_floor);
+      pg *= omega; g *= omega;
+      st.v[6] += m * omega;
+      st.v[7] += altered ? m : 0.f;
+    } else if (ISL == 2) {
+      const float omega = p.omega[s];
+      pg *= omega; g *= omega;
+    } else {
+      st.v[6] += m;                                        // omega == 1
+    }
+    float kl = 0.f;
+    if (KL >= 0) {
+      float dk;
+      kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
+      g += p.kl_coef * dk;
+      st.v[2] += m * kl;
+    }
+    const float wm = w * m;
+    a.glp += wm * g;
+    st.v[0] += wm * (pg + p.kl_coef * kl);
+    st.v[1] += m * pg;
+    st.v[4] += clipped ? m : 0.f;
+    st.v[5] += m;
+  }
+  if (d < n) {                                             // the entropy term (s, j = d), as entropy_term
+    const float m = p.mask[b + d];
+    const float wm = w * m;
+    a.gent -= wm * p.ent_coef;
+    st.v[0] -= wm * p.ent_coef * row.ent;
+    st.v[3] += m * row.ent;
+  }
+}
+
+template <int KL, int SUR, int ISL>
+__global__ __launch_bounds__(PL_BLOCK) void policy_loss_ex_kernel(const PolicyExParams p) {
+  PolicyExStats st = {};
+  row_sweep<PolicyRow, PolicySum, true>(
+      p.T, p.S, p.row_lo, p.row_hi, [&](int t) { return PolicyRow{p.depth[t], p.lp[t], p.ent[t]}; },
+      [&](int s, const PolicyRow& row, PolicySum& a) { ex_terms<KL, SUR, ISL>(p, s, row, a, st); },
+      [&](int t, const PolicySum& a) { p.dlp[t] = a.glp; p.dent[t] = a.gent; });
+  stat_partials(st.v, p.partial);
+}
+
+// The sequence pass of dta_policy_loss_ex: w[s], omega[s] and c[s] of every sequence, and its workgroup's row of partials - the
+// surrogate's columns under a sequence-level ratio, columns 6 and 7 under a sequence-level ratio or a sequence-level weight.
+struct ExSeqPassParams : PathParams {
+  const float *old_lp, *rollout, *mask, *adv;
+  float *w, *c, *omega, *partial;
+  int32_t adv_per_seq, seq_mean, ratio_seq, is_level, is_mode;     // is_level: 0 none, 1 token, 2 sequence, 3 sequence_mean
+  float lo, hi, dual, scale, is_cap, is_floor;
+};
+
+__global__ __launch_bounds__(256) void policy_ex_seq_pass_kernel(const ExSeqPassParams p) {
+  __shared__ float red[4];
+  float st_loss = 0.f, st_pg = 0.f, st_clip = 0.f, st_om = 0.f, st_alt = 0.f;     // thread 0: this workgroup's sequences, in order
+  const bool need_x = p.ratio_seq && p.old_lp, need_y = p.is_level >= 2;
+  for (int s = blockIdx.x; s < p.S; s += gridDim.x) {      // `s` is the same in every thread of the workgroup
+    const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
+    float sm = 0.f, sx = 0.f, sy = 0.f;
+    if (need_x || (need_y && !p.old_lp)) {                 // something reads the rows' lp: the path is walked
+      path_walk(p, s, b, n, [&](int t, int i) {
+        const float m = p.mask[i], lpt = p.lp[t];
+        sm += m;
+        if (need_x) sx += m * (lpt - p.old_lp[i]);
+        if (need_y) sy += m * ((p.old_lp ? p.old_lp[i] : lpt) - p.rollout[i]);
+      });
+    } else {
+      for (int j = threadIdx.x; j < n; j += 256) {
+        const float m = p.mask[b + j];
+        sm += m;
+        if (need_y) sy += m * (p.old_lp[b + j] - p.rollout[b + j]);
+      }
+    }
+    const float nm = block_sum(sm, red), nh = fmaxf(nm, 1.f);
+    const float r = need_x ? expf(block_sum(sx, red) / nh) : 1.f;
+    const float w = p.seq_mean ? p.scale / nh : p.scale;
+    IsWeight ws = {1.f, false};
+    if (need_y) {
+      const float e = block_sum(sy, red);
+      ws = is_weight(expf(p.is_level == 3 ? e / nh : e), p.is_mode, p.is_cap, p.is_floor);
+    }
+    float spg = 0.f, sg = 0.f, sc = 0.f, so = 0.f, sa = 0.f;
+    if (p.ratio_seq) {
+      // every token of the sequence sees the same r: its branch depends on the sign of its advantage alone
+      auto token = [&](float lpt, int i) {
+        const float m = p.mask[i];
+        const float A = p.adv[p.adv_per_seq ? s : i];
+        const auto [pg, clipped] = clipped_pg(r, p.lo, p.hi, A, p.dual);
+        IsWeight wt = ws;
+        if (p.is_level == 1) wt = is_weight(expf((p.old_lp ? p.old_lp[i] : lpt) - p.rollout[i]), p.is_mode, p.is_cap, p.is_floor);
+        spg += m * (wt.omega * pg);
+        sg += clipped ? 0.f : m * (wt.omega * -A);
+        sc += clipped ? m : 0.f;
+        so += m * wt.omega;
+        sa += wt.altered ? m : 0.f;
+      };
+      if (p.is_level == 1 && !p.old_lp) path_walk(p, s, b, n, [&](int t, int i) { token(p.lp[t], i); });
+      else for (int j = threadIdx.x; j < n; j += 256) token(0.f, b + j);
+      spg = block_sum(spg, red); sg = block_sum(sg, red); sc = block_sum(sc, red);
+      so = block_sum(so, red); sa = block_sum(sa, red);
+    } else if (need_y) {
+      so = nm * ws.omega; sa = ws.altered ? nm : 0.f;
+    }
+    if (threadIdx.x == 0) {
+      p.w[s] = w;
+      p.omega[s] = ws.omega;
+      p.c[s] = p.ratio_seq ? w * r / nh * sg : 0.f;
+      st_loss += w * spg; st_pg += spg; st_clip += sc; st_om += so; st_alt += sa;
+    }
+  }
+  if (threadIdx.x == 0) {                                  // this workgroup's row of the partial sums
+    float* out = p.partial + (size_t)blockIdx.x * PL_NSTAT;
+    out[0] = st_loss; out[1] = st_pg; out[2] = 0.f; out[3] = 0.f; out[4] = st_clip; out[5] = 0.f; out[6] = st_om; out[7] = st_alt;
+  }
+}
+
 // ---- preference objectives (dta_preference_loss): DPO / cDPO / SimPO, SLiC, IPO --------------------------------------------------
 // A pair couples two sequences, so there is a pair stage between a sequence pass and a row pass: the sequence pass leaves one
 // number u_s per sequence, the pair pass turns the two numbers of a pair into one coefficient g_s per member, and the row pass sums
@@ -492,7 +663,90 @@ int policy_loss(const float* lp, const float* ent, const int32_t* depth, const i
   return DTA_LAUNCH_STATUS();
 }
 
+// the row pass of dta_policy_loss_ex under a token-level ratio: one instantiation per (KL, surrogate, weight level)
+template <int SUR, int ISL>
+void launch_ex_rows(int kl, dim3 grid, hipStream_t st_, const PolicyExParams& p) {
+  const dim3 block(PL_BLOCK);
+  if (kl < 0) hipLaunchKernelGGL((policy_loss_ex_kernel<-1, SUR, ISL>), grid, block, 0, st_, p);
+  else if (kl == 0) hipLaunchKernelGGL((policy_loss_ex_kernel<0, SUR, ISL>), grid, block, 0, st_, p);
+  else if (kl == 1) hipLaunchKernelGGL((policy_loss_ex_kernel<1, SUR, ISL>), grid, block, 0, st_, p);
+  else hipLaunchKernelGGL((policy_loss_ex_kernel<2, SUR, ISL>), grid, block, 0, st_, p);
+}
+
 }  // namespace
+
+extern "C" int dta_policy_loss_ex_blocks(int32_t T, int32_t S) {
+  return T <= 0 || S <= 0 ? DTA_EINVAL : row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS) + (S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS);
+}
+
+extern "C" int dta_policy_loss_ex(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                                  const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                                  const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* rollout_lp, const float* mask,
+                                  const float* adv, int32_t adv_per_seq, float* w, float* c, float* omega, float* dlp, float* dent,
+                                  float* partial, float* stats, int32_t T, int32_t S, int32_t M, int32_t R, float clip_low, float clip_high,
+                                  float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg, float scale,
+                                  int32_t ratio_level, int32_t surrogate, int32_t is_level, int32_t is_mode, float is_cap, float is_floor,
+                                  void* stream) {
+  if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !mask || !adv || !w || !c || !omega || !dlp || !dent || !partial ||
+      !stats || T <= 0 || S <= 0)
+    return DTA_EINVAL;
+  if (!finite_f(clip_low) || !finite_f(clip_high) || clip_low < 0.f || clip_high < 0.f) return DTA_EINVAL;
+  if (dual_clip != 0.f && !(finite_f(dual_clip) && dual_clip > 1.f)) return DTA_EINVAL;
+  if (kl_estimator < 0 || kl_estimator > 2 || agg < 0 || agg > 1) return DTA_EINVAL;
+  if (!finite_f(kl_coef) || !finite_f(entropy_coef) || !finite_f(scale)) return DTA_EINVAL;
+  if (kl_coef != 0.f && !ref_lp) return DTA_EINVAL;
+  if (ratio_level < 0 || ratio_level > 1 || surrogate < 0 || surrogate > 1 || is_level < 0 || is_level > 3 || is_mode < 0 || is_mode > 1)
+    return DTA_EINVAL;
+  if (!finite_f(is_cap) || !(is_cap > 0.f) || !finite_f(is_floor) || is_floor < 0.f || !(is_floor < is_cap)) return DTA_EINVAL;
+  if (is_mode == 0 && is_floor != 0.f) return DTA_EINVAL;
+  if (surrogate == 1 && (ratio_level == 1 || dual_clip != 0.f)) return DTA_EINVAL;
+  if (is_level != 0 && !rollout_lp) return DTA_EINVAL;
+  const bool walks = ratio_level == 1 || (is_level >= 2 && !old_lp);       // something follows a root path
+  if (walks && (!leaf_run_ptr || !run_row0 || !run_depth0 || !seq_leaf || M <= 0 || R <= 0)) return DTA_EINVAL;
+  if (!all_aligned16(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, old_lp, ref_lp, rollout_lp,
+                     mask, adv, w, c, omega, dlp, dent, partial, stats))
+    return DTA_EALIGN;
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  DTA_REFUSE_IF_PRIOR_ERROR();
+  const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS), nsb = S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS;
+  if (is_level == 0) rollout_lp = nullptr;                                  // not read
+  ExSeqPassParams q;
+  static_cast<PathParams&>(q) = {lp, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, T, S, walks ? M : 0, walks ? R : 0};
+  q.old_lp = old_lp; q.rollout = rollout_lp; q.mask = mask; q.adv = adv; q.w = w; q.c = c; q.omega = omega;
+  q.partial = partial + (size_t)nb * PL_NSTAT;                              // its partial rows stand behind the row pass's
+  q.adv_per_seq = adv_per_seq != 0; q.seq_mean = agg == 0; q.ratio_seq = ratio_level; q.is_level = is_level; q.is_mode = is_mode;
+  q.lo = 1.f - clip_low; q.hi = 1.f + clip_high; q.dual = dual_clip; q.scale = scale; q.is_cap = is_cap; q.is_floor = is_floor;
+  hipLaunchKernelGGL(policy_ex_seq_pass_kernel, dim3(nsb), dim3(256), 0, st_, q);
+  PolicyExParams p;
+  p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
+  p.old_lp = ratio_level ? nullptr : old_lp; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w; p.c = c;
+  p.dlp = dlp; p.dent = dent; p.partial = partial;
+  p.T = T; p.S = S; p.adv_per_seq = q.adv_per_seq;
+  p.lo = q.lo; p.hi = q.hi; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
+  p.rollout = rollout_lp; p.omega = omega; p.is_mode = is_mode; p.is_cap = is_cap; p.is_floor = is_floor;
+  const dim3 grid(nb), block(PL_BLOCK);
+  const int kl = kl_coef == 0.f ? -1 : kl_estimator;
+  if (ratio_level) {                         // c_s holds the weight: the row kernel of dta_policy_loss_seq as it is
+    const PolicyParams base = p;
+    if (kl < 0) hipLaunchKernelGGL((policy_loss_kernel<-1, true>), grid, block, 0, st_, base);
+    else if (kl == 0) hipLaunchKernelGGL((policy_loss_kernel<0, true>), grid, block, 0, st_, base);
+    else if (kl == 1) hipLaunchKernelGGL((policy_loss_kernel<1, true>), grid, block, 0, st_, base);
+    else hipLaunchKernelGGL((policy_loss_kernel<2, true>), grid, block, 0, st_, base);
+  } else {
+    const int isl = is_level >= 2 ? 2 : is_level;
+    if (surrogate == 0) {
+      if (isl == 0) launch_ex_rows<0, 0>(kl, grid, st_, p);
+      else if (isl == 1) launch_ex_rows<0, 1>(kl, grid, st_, p);
+      else launch_ex_rows<0, 2>(kl, grid, st_, p);
+    } else {
+      if (isl == 0) launch_ex_rows<1, 0>(kl, grid, st_, p);
+      else if (isl == 1) launch_ex_rows<1, 1>(kl, grid, st_, p);
+      else launch_ex_rows<1, 2>(kl, grid, st_, p);
+    }
+  }
+  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb + nsb, stats);
+  return DTA_LAUNCH_STATUS();
+}
 
 extern "C" int dta_policy_loss_blocks(int32_t T) { return T <= 0 ? DTA_EINVAL : row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS); }
 

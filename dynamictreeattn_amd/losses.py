@@ -34,6 +34,33 @@ with KL, entropy, mask and w_s as above.  The gradient flows through r_s to ever
 stop-gradient "GSPO-token" variant):  d loss_s / d lp_t = c_s m_t + the token-level KL gradient, with the per-sequence scalar
 c_s = w_s r_s / max(sum m, 1) * sum_j m_j (-A_j) [pg_j not clipped].  The fused path evaluates it with ``dta_policy_loss_seq``.
 
+Off-policy corrections.  The sampler that produced a rollout (other kernels, another precision, another parallel layout) assigns a
+token another log-prob than this engine does under the same weights.  With ``is_level`` set, the attachment carries
+
+    rollout_logprobs   tensor [len-1]; the sampler's log-prob of each token     required iff is_level is not None (not looked at otherwise)
+
+and a detached importance weight multiplies the surrogate - never the KL or the entropy term:
+
+    y_j = old_j - rollout_j                               old absent: y_j = lp_j.detach() - rollout_j, no extra model forward
+    "token":          rho_j = exp(y_j)
+    "sequence":       rho_s = exp(sum_j m_j y_j)                            the product of the masked tokens' ratios
+    "sequence_mean":  rho_s = exp(sum_j m_j y_j / max(sum_j m_j, 1))        their geometric mean
+    is_mode "truncate" (TIS):          omega = min(rho, is_cap)
+    is_mode "mask" (IcePop / MIS):     omega = rho if is_floor <= rho <= is_cap else 0
+    term_j = m_j (omega pg_j + kl_coef kl_j - entropy_coef entropy_j)
+
+omega is formed by comparisons on rho, so an overflowing exponential gives is_cap ("truncate") or 0 ("mask"), never NaN.  With
+``ratio="sequence"`` the weight enters the sequence scalar: c_s = w_s r_s / n^ * sum_j m_j omega_j (-A_j) [pg_j not clipped].
+
+``surrogate="cispo"`` (MiniMax-M1) clips a detached weight instead of dropping the token's gradient, with lo = 1 - clip_low,
+hi = 1 + clip_high and r the token ratio (on-policy: r = 1):
+
+    pg = -clamp(r, lo, hi).detach() A lp,     d pg / d lp = -clamp(r, lo, hi) A   (never zeroed)
+
+"clipped" counts the tokens with r outside [lo, hi], whatever the sign of A.  It composes with omega, the KL term, the entropy term
+and the mask; it does not go with ``ratio="sequence"`` or a dual clip.  The fused path evaluates both with ``dta_policy_loss_ex`` and
+reports two more statistics (``OFFPOLICY_STATS``): sum m omega and the masked tokens whose weight was truncated or dropped.
+
 ``PreferenceLoss`` (DPO / cDPO / SimPO, SLiC, IPO) couples a chosen and a rejected sequence and is therefore no per-sequence callback:
 see the class.  ``two_pass_backward`` runs it through any engine with a ``forward`` / ``backward`` surface.
 """
@@ -45,13 +72,18 @@ from typing import Optional
 import torch
 
 __all__ = ["PolicyLoss", "KL_ESTIMATORS", "AGGREGATIONS", "RATIOS", "STATS", "PreferenceLoss", "PREFERENCE_KINDS", "PREFERENCE_STATS",
-           "two_pass_backward"]
+           "two_pass_backward", "SURROGATES", "IS_LEVELS", "IS_MODES", "OFFPOLICY_STATS"]
 
 KL_ESTIMATORS = ("k1", "k2", "k3")           # position = the estimator id of dta_policy_loss
 AGGREGATIONS = ("seq_mean", "token_sum")     # position = the aggregation id of dta_policy_loss
 RATIOS = ("token", "sequence")               # importance ratio per prediction (PPO / GRPO) or one per sequence (GSPO: dta_policy_loss_seq)
 # entries of the statistics vector of the fused path (engine.loss_stats), in order
 STATS = ("loss", "sum_pg", "sum_kl", "sum_entropy", "clipped_tokens", "masked_tokens")
+SURROGATES = ("ppo", "cispo")                # position = the surrogate id of dta_policy_loss_ex
+IS_LEVELS = ("token", "sequence", "sequence_mean")   # rollout importance weight; position + 1 = the is_level id of dta_policy_loss_ex (0: none)
+IS_MODES = ("truncate", "mask")              # position = the is_mode id of dta_policy_loss_ex
+# entries of the statistics vector under an off-policy correction or CISPO (dta_policy_loss_ex), in order
+OFFPOLICY_STATS = STATS + ("sum_is_weight", "is_clipped_tokens")
 PREFERENCE_KINDS = ("sigmoid", "hinge", "ipo")   # position = the kind id of dta_preference_loss
 # entries of the statistics vector of a PreferenceLoss (engine.loss_stats), in order
 PREFERENCE_STATS = ("loss", "sum_pair_loss", "sum_sft", "reward_margin", "chosen_reward", "rejected_reward", "correct_pairs", "pairs")
@@ -83,7 +115,8 @@ def attachments_by_sequence(trie) -> list:
 class PolicyLoss:
     def __init__(self, clip_low: float = 0.2, clip_high: float = 0.2, dual_clip: Optional[float] = None, kl_coef: float = 0.0,
                  kl_estimator: str = "k3", entropy_coef: float = 0.0, agg: str = "seq_mean", scale: float = 1.0,
-                 ratio: str = "token"):
+                 ratio: str = "token", surrogate: str = "ppo", is_level: Optional[str] = None, is_mode: str = "truncate",
+                 is_cap: float = 2.0, is_floor: float = 0.0):
         self.clip_low, self.clip_high = _finite("clip_low", clip_low), _finite("clip_high", clip_high)
         if self.clip_low < 0:
             raise ValueError(f"clip_low = {clip_low!r} is negative")
@@ -101,11 +134,38 @@ class PolicyLoss:
         if ratio not in RATIOS:
             raise ValueError(f"ratio = {ratio!r}: one of {RATIOS}")
         self.kl_estimator, self.agg, self.ratio = kl_estimator, agg, ratio
+        if surrogate not in SURROGATES:
+            raise ValueError(f"surrogate = {surrogate!r}: one of {SURROGATES}")
+        if is_level is not None and is_level not in IS_LEVELS:
+            raise ValueError(f"is_level = {is_level!r}: None or one of {IS_LEVELS}")
+        if is_mode not in IS_MODES:
+            raise ValueError(f"is_mode = {is_mode!r}: one of {IS_MODES}")
+        self.is_cap, self.is_floor = _finite("is_cap", is_cap), _finite("is_floor", is_floor)
+        if self.is_cap <= 0:
+            raise ValueError(f"is_cap = {is_cap!r} must be > 0")
+        if self.is_floor < 0 or self.is_floor >= self.is_cap:
+            raise ValueError(f"is_floor = {is_floor!r} must be in [0, is_cap = {self.is_cap})")
+        if self.is_floor != 0 and is_mode == "truncate":
+            raise ValueError(f"is_floor = {is_floor!r} goes with is_mode 'mask' only: 'truncate' has no lower edge")
+        if surrogate == "cispo" and ratio == "sequence":
+            raise ValueError("surrogate = 'cispo' clips a per-token weight: it does not go with ratio = 'sequence'")
+        if surrogate == "cispo" and self.dual_clip is not None:
+            raise ValueError(f"dual_clip = {dual_clip!r} does not go with surrogate = 'cispo' (its gradient is never zeroed)")
+        self.surrogate, self.is_level, self.is_mode = surrogate, is_level, is_mode
+
+    @property
+    def extended(self) -> bool:
+        """an off-policy correction or CISPO is configured: the fused path is dta_policy_loss_ex and reports OFFPOLICY_STATS"""
+        return self.is_level is not None or self.surrogate != "ppo"
 
     def __repr__(self):
+        more = ""
+        if (self.surrogate, self.is_level, self.is_mode, self.is_cap, self.is_floor) != ("ppo", None, "truncate", 2.0, 0.0):
+            more = (f", surrogate={self.surrogate!r}, is_level={self.is_level!r}, is_mode={self.is_mode!r}, is_cap={self.is_cap}, "
+                    f"is_floor={self.is_floor}")
         return (f"PolicyLoss(clip_low={self.clip_low}, clip_high={self.clip_high}, dual_clip={self.dual_clip}, kl_coef={self.kl_coef}, "
                 f"kl_estimator={self.kl_estimator!r}, entropy_coef={self.entropy_coef}, agg={self.agg!r}, scale={self.scale}, "
-                f"ratio={self.ratio!r})")
+                f"ratio={self.ratio!r}{more})")
 
     # ------------------------------------------------------------------------------------------
     def fields(self, attachment: dict, n: int):
@@ -129,9 +189,34 @@ class PolicyLoss:
                 _per_token(key, v, n)
         return adv, old, ref, mask
 
+    def rollout(self, attachment: dict, n: int):
+        """rollout_logprobs of one attachment, checked like the other per-token keys: a tensor [n]; None exactly when is_level is None
+        (the key is not looked at then).  KeyError / ValueError name the key."""
+        if self.is_level is None:
+            return None
+        roll = attachment.get("rollout_logprobs")
+        if roll is None:
+            raise KeyError(f"rollout_logprobs (required because is_level = {self.is_level!r})")
+        _per_token("rollout_logprobs", roll, n)
+        return roll
+
+    def is_weight(self, y: torch.Tensor, m: Optional[torch.Tensor]) -> torch.Tensor:
+        """omega from the detached log-ratios y = old - rollout [n] and the mask m ([n], or None for all ones): [n] under "token", a
+        scalar under the sequence levels.  Comparisons on rho alone: an exponential that overflowed gives is_cap or 0, never NaN."""
+        if self.is_level != "token":
+            n = int(y.shape[0])
+            y = y.sum() if m is None else (m * y).sum()
+            if self.is_level == "sequence_mean":
+                y = y / (max(n, 1) if m is None else torch.clamp(m.sum(), min=1.0))
+        rho = torch.exp(y)
+        if self.is_mode == "truncate":
+            return torch.where(rho > self.is_cap, torch.full_like(rho, self.is_cap), rho)
+        return torch.where((rho >= self.is_floor) & (rho <= self.is_cap), rho, torch.zeros_like(rho))
+
     def __call__(self, logprob: torch.Tensor, entropy: torch.Tensor, attachment: dict) -> torch.Tensor:
         n = int(logprob.shape[0])
         adv, old, ref, mask = self.fields(attachment, n)
+        roll = self.rollout(attachment, n)
         to = lambda v: v.detach().to(device=logprob.device, dtype=logprob.dtype)
         A = torch.full_like(logprob, adv) if isinstance(adv, float) else to(adv)
         old = logprob.detach() if old is None else to(old)
@@ -145,10 +230,15 @@ class PolicyLoss:
             r = r.expand(n)
         else:
             r = torch.exp(logprob - old)
-        pg = torch.maximum(-r * A, -torch.clamp(r, 1.0 - self.clip_low, 1.0 + self.clip_high) * A)
+        if self.surrogate == "cispo":         # the clamped ratio is a detached weight on lp: the gradient is never zeroed
+            pg = -torch.clamp(r, 1.0 - self.clip_low, 1.0 + self.clip_high).detach() * A * logprob
+        else:
+            pg = torch.maximum(-r * A, -torch.clamp(r, 1.0 - self.clip_low, 1.0 + self.clip_high) * A)
         if self.dual_clip is not None:
             pg = torch.where(A < 0, torch.minimum(pg, -self.dual_clip * A), pg)
         term = pg
+        if roll is not None:                  # the rollout importance weight: detached, on the surrogate alone
+            term = self.is_weight(old - to(roll), None if mask is None else to(mask)) * pg
         if self.kl_coef != 0:
             d = to(ref) - logprob
             kl = -d if self.kl_estimator == "k1" else 0.5 * d * d if self.kl_estimator == "k2" else torch.exp(d) - d - 1.0

@@ -1728,15 +1728,48 @@ def policy_token_inputs(loss, attach_lists, seq_ptr, device):
     return old, ref, mask, adv, adv_per_seq
 
 
+def policy_rollout_input(loss, attach_lists, seq_ptr, device):
+    """The rollout log-probs of an off-policy correction (attachment key rollout_logprobs), concatenated like the vectors of
+    policy_token_inputs: an fp32 device vector of N = seq_ptr[-1] elements, or None when loss.is_level is None (the key is not looked at).
+    Checked as PolicyLoss.__call__ checks it; given for some sequences and absent for others is a ValueError."""
+    if loss.is_level is None:
+        return None
+    rolls = []
+    for s, (attachment, length) in enumerate(pair for attach_list in attach_lists for pair in attach_list):
+        n = int(length) - 1
+        if n != int(seq_ptr[s + 1]) - int(seq_ptr[s]):
+            raise ValueError("attach lists and seq_ptr disagree")
+        rolls.append(attachment.get("rollout_logprobs"))
+        if rolls[-1] is not None:
+            loss.rollout(attachment, n)
+    if any(v is None for v in rolls):
+        if not all(v is None for v in rolls):
+            raise ValueError("rollout_logprobs: given for some sequences of the trie and absent for others")
+        raise KeyError(f"rollout_logprobs (required because is_level = {loss.is_level!r})")
+    return _cat_per_token(rolls, 0.0, seq_ptr, device)
+
+
+def policy_walks_paths(loss, on_policy: bool) -> bool:
+    """Whether the fused objective follows root paths and so needs packing.policy_path_tables: a sequence-level ratio, or a
+    sequence-level rollout weight formed from the rows' own log-probs (no old_logprobs: on_policy)."""
+    return loss.ratio == "sequence" or (loss.is_level in ("sequence", "sequence_mean") and on_policy)
+
+
 def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, row_seq_lo: torch.Tensor, row_seq_hi: torch.Tensor,
                 seq_ptr: torch.Tensor, old: Optional[torch.Tensor], ref: Optional[torch.Tensor], mask: torch.Tensor, adv: torch.Tensor,
-                adv_per_seq: bool, path_tables=None):
+                adv_per_seq: bool, path_tables=None, rollout: Optional[torch.Tensor] = None, workspaces: Optional[dict] = None):
     """The objective `loss` (losses.PolicyLoss) over T packed rows in one C-ABI call: returns (dlp [T], dent [T], stats [8], w [S]), fp32.
     lp / ent: the fp32 row statistics of packed_logprob_entropy (no graph is followed: the caller back-propagates dlp / dent);
     row_seq_lo / row_seq_hi / seq_ptr: packing.policy_row_tables; old / ref / mask / adv: policy_token_inputs.
     stats = {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0} (losses.STATS); w: the per-sequence weights.
     loss.ratio == "sequence" (dta_policy_loss_seq) needs path_tables = (leaf_run_ptr, run_row0, run_depth0, seq_leaf), the int32 device
-    tables of packing.policy_path_tables; "token" (dta_policy_loss) takes none."""
+    tables of packing.policy_path_tables; "token" (dta_policy_loss) takes none.
+    An off-policy correction (loss.is_level) or CISPO goes to dta_policy_loss_ex: rollout = policy_rollout_input(...) is needed exactly
+    when loss.is_level is not None, path_tables exactly when policy_walks_paths(loss, old is None), the last two statistics are those
+    of losses.OFFPOLICY_STATS, and a dict handed in as `workspaces` receives the per-sequence vectors c and omega."""
+    if loss.extended:
+        return _policy_loss_ex(loss, lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, adv_per_seq, path_tables, rollout,
+                               workspaces)
     from .losses import AGGREGATIONS, KL_ESTIMATORS
     seq_level = loss.ratio == "sequence"
     if seq_level != (path_tables is not None):
@@ -1764,6 +1797,44 @@ def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, 
             float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
             KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
             nbytes=4 * (4 * T + ((5 + 2 * (old is not None) if seq_level else 3 + (old is not None)) + (ref is not None)) * N))
+    return v["dlp"], v["dent"], v["stats"], v["w"]
+
+
+def _policy_loss_ex(loss, lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, adv_per_seq, path_tables, rollout, workspaces):
+    """policy_loss for an objective with an off-policy correction or CISPO: dta_policy_loss_ex"""
+    from .losses import AGGREGATIONS, IS_LEVELS, IS_MODES, KL_ESTIMATORS, RATIOS, SURROGATES
+    walks = policy_walks_paths(loss, old is None)
+    if walks != (path_tables is not None):
+        raise ValueError(f"ratio = {loss.ratio!r}, is_level = {loss.is_level!r}, old_logprobs {'absent' if old is None else 'given'}: "
+                         f"path_tables (packing.policy_path_tables) are {'needed' if walks else 'not used'}")
+    if (loss.is_level is not None) != (rollout is not None):
+        raise ValueError(f"is_level = {loss.is_level!r}: rollout (policy_rollout_input) goes with an off-policy correction, and only with it")
+    T, S = int(lp.shape[0]), int(seq_ptr.shape[0]) - 1
+    lp, ent, old, ref, rollout, mask, adv = map(_f32_aligned, (lp, ent, old, ref, rollout, mask, adv))
+    path = list(path_tables) if walks else [None] * 4
+    _require_cuda(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, rollout, mask, adv, *path)
+    N = int(mask.shape[0])
+    assert ent.shape[0] == T and depth.shape[0] == T and row_seq_lo.shape[0] == T and row_seq_hi.shape[0] == T
+    assert all(t.dtype == torch.int32 for t in (depth, row_seq_lo, row_seq_hi, seq_ptr, *path) if t is not None)
+    assert adv.shape[0] == (S if adv_per_seq else N) and all(t is None or t.shape[0] == N for t in (old, ref, rollout))
+    M = R = 0
+    if walks:
+        run_ptr, run_row0, run_depth0, seq_leaf = path
+        assert seq_leaf.shape[0] == S and run_depth0.shape[0] == run_row0.shape[0]
+        M, R = int(run_ptr.shape[0]) - 1, int(run_row0.shape[0])
+    nb = lib().dta_policy_loss_ex_blocks(T, S)
+    buf, v = _carve_f32(lp.device, dlp=T, dent=T, w=S, partial=8 * nb, stats=8, c=S, omega=S)
+    tensors = (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, *path, old, ref, rollout, mask, adv)
+    _launch("dta_policy_loss_ex", (*tensors, buf),
+            *map(ptr, tensors), int(bool(adv_per_seq)), *(ptr(v[k]) for k in ("w", "c", "omega", "dlp", "dent", "partial", "stats")),
+            T, S, M, R,
+            float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
+            KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
+            RATIOS.index(loss.ratio), SURROGATES.index(loss.surrogate), 0 if loss.is_level is None else IS_LEVELS.index(loss.is_level) + 1,
+            IS_MODES.index(loss.is_mode), float(loss.is_cap), float(loss.is_floor),
+            nbytes=4 * (4 * T + (4 + (old is not None) + (ref is not None) + 2 * (rollout is not None)) * N))
+    if workspaces is not None:
+        workspaces.update(c=v["c"], omega=v["omega"])
     return v["dlp"], v["dent"], v["stats"], v["w"]
 
 

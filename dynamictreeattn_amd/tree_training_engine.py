@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .losses import PREFERENCE_STATS, STATS as LOSS_STATS, PolicyLoss, PreferenceLoss, attachments_by_sequence
+from .losses import OFFPOLICY_STATS, PREFERENCE_STATS, STATS as LOSS_STATS, PolicyLoss, PreferenceLoss, attachments_by_sequence
 from .model import (_head_dim, ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry,
                     longrope_boundary, packed_hidden_states)
 from .trie import pop_block_starts
@@ -506,8 +506,9 @@ class TreeTrainingEngine:
     def _fused_rows(packed, token_trie, lp, ent, loss):
         """A built-in objective (losses.PolicyLoss / PreferenceLoss) on the packed rows, in one C-ABI call (ops.policy_loss /
         ops.preference_loss): ([(tensor, gradient)] to back-propagate, the statistics in the order of losses.STATS / PREFERENCE_STATS,
-        the loss first).  The row -> sequence-range tables, the sequence -> row-run tables (a sequence-level ratio, a preference
-        objective) and the pair tables (a preference objective) come from the packing plan and the attach lists on the host and travel
+        the loss first; OFFPOLICY_STATS under an off-policy correction or CISPO).  The row -> sequence-range tables, the sequence ->
+        row-run tables (a sequence-level ratio, a sequence-level rollout weight without old_logprobs, a preference objective) and
+        the pair tables (a preference objective) come from the packing plan and the attach lists on the host and travel
         in one staged upload; the attachments' per-token tensors are concatenated in callback order (ops.*_token_inputs).  Entropy is
         differentiated only under an entropy bonus; a preference objective does not use it."""
         from ._staging import upload
@@ -515,7 +516,9 @@ class TreeTrainingEngine:
         pairwise = isinstance(loss, PreferenceLoss)
         row_lo, row_hi, seq_ptr, _ = packing.policy_row_tables(packed.plan, att)
         tables = [row_lo, row_hi, seq_ptr]
-        if pairwise or loss.ratio == "sequence":
+        # the root paths: a preference objective, a sequence-level ratio, a sequence-level rollout weight without old_logprobs
+        on_policy = not pairwise and all(a.get("old_logprobs") is None for attach_list in att for a, _ in attach_list)
+        if pairwise or ops.policy_walks_paths(loss, on_policy):
             tables += packing.policy_path_tables(packed.plan, att)
         if pairwise:
             tables += packing.preference_pair_tables(att)
@@ -525,8 +528,10 @@ class TreeTrainingEngine:
                                                    *ops.preference_token_inputs(loss, att, seq_ptr, dev))
             return [(lp, dlp)], stats[:len(PREFERENCE_STATS)]
         dlp, dent, stats, _ = ops.policy_loss(loss, lp, ent, packed.depth, row_lo_d, row_hi_d, seq_ptr_d,
-                                              *ops.policy_token_inputs(loss, att, seq_ptr, dev), tuple(rest) or None)
-        return [(lp, dlp)] + ([(ent, dent)] if loss.entropy_coef != 0 else []), stats[:len(LOSS_STATS)]
+                                              *ops.policy_token_inputs(loss, att, seq_ptr, dev), tuple(rest) or None,
+                                              ops.policy_rollout_input(loss, att, seq_ptr, dev))
+        n_stats = len(OFFPOLICY_STATS) if loss.extended else len(LOSS_STATS)
+        return [(lp, dlp)] + ([(ent, dent)] if loss.entropy_coef != 0 else []), stats[:n_stats]
 
     def _backward_stack_two_pass(self, model, token_trie, loss, block_rows: int) -> float:
         """A preference objective on the block-wise walk, in two passes: the sequence log-probs from a no-grad forward, the per-sequence

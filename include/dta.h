@@ -476,6 +476,57 @@ int dta_policy_loss_seq(const float* lp, const float* ent, const int32_t* depth,
                         int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip, float kl_coef,
                         int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, void* stream);
 
+/* The same objective with an off-policy correction - a rollout importance weight on the surrogate - and / or the CISPO surrogate
+ * (losses.PolicyLoss(is_level=..., surrogate="cispo")).  Everything not said here is as for dta_policy_loss (ratio_level 0, "token") and
+ * dta_policy_loss_seq (ratio_level 1, "sequence"): the numbering of the sequences, the per-token inputs, the row and path tables, w_s,
+ * r, r_s, the KL and entropy terms, dlp / dent written for every row, no atomics, identical bits for identical calls.
+ * rollout_lp [N] holds the sampler's log-prob of each token (NULL allowed when is_level == 0: not read).  Per prediction j of s,
+ *       y_j = old_lp[.] - rollout_lp[.]            old_lp NULL: y_j = lp[row(s, j)] - rollout_lp[.]; y carries no gradient either way
+ *       is_level 1 "token":          rho_j = exp(y_j)
+ *       is_level 2 "sequence":       rho_s = exp(sum_j m_j y_j)
+ *       is_level 3 "sequence_mean":  rho_s = exp(sum_j m_j y_j / n^),   n^ = max(sum_j m_j, 1)
+ *       is_mode 0 "truncate":  omega = min(rho, is_cap);     is_mode 1 "mask":  omega = rho if is_floor <= rho <= is_cap, else 0
+ *       is_level 0: omega = 1
+ *       loss += w_s m_j (omega pg_j + kl_coef kl_j);   dlp[t] += w_s m_j (omega dpg_j + kl_coef dkl_j)      (ratio_level 0)
+ *       c_s = w_s r_s / n^ * sum_j m_j omega_j (-A_j) [-r_s A_j is the active branch of pg_j]                (ratio_level 1)
+ * omega multiplies the surrogate alone, never the KL or the entropy term, and is a constant of the gradient.  omega is formed by
+ * comparisons on rho, never by arithmetic on it: an exponent above 88.7, where expf gives +inf, yields is_cap under "truncate" and 0
+ * under "mask", one far below zero yields 0 (or what is_floor says of 0); no finite input gives NaN.
+ * surrogate 1 "cispo", with lo = 1 - clip_low, hi = 1 + clip_high and the token ratio r (old_lp NULL: r = 1):
+ *       pg = -clamp(r, lo, hi) A lp[t],   dpg = -clamp(r, lo, hi) A  (the clamp is a constant of the gradient: dpg is never zeroed);
+ *       "clipped" counts the masked tokens with r outside [lo, hi], whatever the sign of A.
+ * The path tables may be NULL, with M = R = 0, when nothing walks a path: ratio_level 0 with is_level 0 or 1, and ratio_level 0 with
+ * is_level 2 or 3 when old_lp is given (y is then a sweep over the per-token inputs alone).  They are required for ratio_level 1 and for
+ * is_level 2 or 3 with old_lp NULL.  w[S], c[S] and omega[S] are workspaces the caller may read afterwards: omega[s] is the sequence's
+ * weight (1 for is_level 0 and 1), c[s] is 0 for ratio_level 0.
+ * Three launches on `stream`; their geometry depends on T and S alone:
+ *   sequence pass  one workgroup per sequence (grid-strided past 2048).  It owns w[s], omega[s] and c[s].  It walks the path only for
+ *                  what reads a row's lp: sum m x of r_s (ratio_level 1 with old_lp), sum m y with old_lp NULL, and the c_s sweep when
+ *                  that forms a per-token weight with old_lp NULL; everything else is a sweep of the per-token inputs.  Under
+ *                  ratio_level 1 it owns the surrogate's share of loss, sum m pg' and the clipped tokens; under ratio_level 1 or
+ *                  is_level 2 / 3 it owns sum m omega and sum m [omega != rho].  With ratio_level 0 it stands where dta_policy_loss
+ *                  launches its weight kernel;
+ *   row pass       ratio_level 0: the row sweep of dta_policy_loss with this entry's own term - r, the surrogate form, and the weight: a
+ *                  per-token weight is formed here (y from old_lp, or from the row's lp; the accurate expf; truncate or mask), a
+ *                  sequence's weight is read from omega[s]; it owns every statistic the sequence pass does not.  ratio_level 1: the row
+ *                  kernel of dta_policy_loss_seq as it is (c_s holds the weight);
+ *   reduction      both passes' partials, partial[dta_policy_loss_ex_blocks(T, S)][8], summed in a fixed order into
+ *                  stats[8] = {loss, sum m pg' (pg' = omega pg), sum m kl, sum m ent, clipped, sum m, sum m omega, sum m [omega != rho]}
+ *                  (losses.OFFPOLICY_STATS; is_level 0: sum m omega = sum m and the last entry is 0).  The three counts are exact.
+ * Refusals come in this order: DTA_EINVAL (a null pointer other than old_lp / ref_lp / rollout_lp / the path tables, T <= 0, S <= 0, then
+ * the hyper-parameters exactly as dta_policy_loss refuses them, then ratio_level not 0 / 1, surrogate not 0 / 1, is_level not 0..3,
+ * is_mode not 0 / 1, is_cap non-finite or <= 0, is_floor non-finite, negative or not below is_cap, is_floor != 0 with is_mode 0,
+ * surrogate 1 with ratio_level 1 or with a dual clip, is_level != 0 with rollout_lp NULL, a path table NULL or M or R <= 0 where a path
+ * is walked), DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR. */
+int dta_policy_loss_ex_blocks(int32_t T, int32_t S);   /* rows of the partial workspace [blocks, 8] (float); T <= 0 or S <= 0: DTA_EINVAL */
+int dta_policy_loss_ex(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                       const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                       const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* rollout_lp, const float* mask,
+                       const float* adv, int32_t adv_per_seq, float* w, float* c, float* omega, float* dlp, float* dent, float* partial,
+                       float* stats, int32_t T, int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip,
+                       float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, int32_t ratio_level,
+                       int32_t surrogate, int32_t is_level, int32_t is_mode, float is_cap, float is_floor, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Preference objectives over the packed trie (losses.PreferenceLoss; HBM-bound, fp32 throughout): DPO / cDPO / SimPO (kind 0,
  * "sigmoid"), SLiC (1, "hinge") and IPO (2, "ipo") over P (chosen, rejected) pairs of the trie's sequences, with an optional NLL term on
