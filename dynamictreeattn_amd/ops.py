@@ -1394,8 +1394,8 @@ def moe_grouped_gemm(mode: int, route: MoeRouting, w_shape, out_dtype, x=None, w
     ref = x if x is not None else dy
     shape = (R, N) if mode == MOE_FWD else (R, K) if mode == MOE_DGRAD else (E_, N, K)
     out = torch.empty(shape, dtype=out_dtype, device=ref.device)
-    if R == 0 and mode != MOE_WGRAD:
-        return out
+    if R == 0:          # no rows: nothing to launch (an empty tensor has no address to hand over); the weight gradient of no rows is zero
+        return out.zero_() if mode == MOE_WGRAD else out
     x, w, dy = (None if t is None else t.contiguous() for t in (x, w, dy))
     esz = out.element_size()
     _launch("dta_moe_grouped_gemm", tuple(t for t in (x, w, dy) if t is not None), mode, ptr(x), ptr(w), ptr(dy), ptr(out),

@@ -3,7 +3,11 @@ three modes on the MFMA and the fp32 path, combine forward / backward): every en
 (tests/arena.py) and must return 0, leave every guard byte of its outputs and workspaces alone, write every output element
 (bit-identical payloads under the NaN / 0x7f7f7f7f and the -3.0 / 0x01010101 fill, floats finite under NaN), not depend on memory past
 an input's extent (floats: NaN against +inf; index tables: 0 against the table's largest valid value) and give, bit for bit, what the
-allocating ops.* wrapper gives for the same inputs - whose values tests/test_gpu_moe_ops.py bounds against float64.
+allocating ops.* wrapper gives for the same inputs - whose values tests/test_gpu_moe_ops.py bounds against float64 (every form called
+here, the weight gradient without the gather included).
+
+Dropped pairs (an id outside [0, E)) take no row, so the permutation leaves src_token, and the combine backward dY, unwritten from row
+offsets[E] on: those two payloads are passed as scratch (guards checked, content not) and their first offsets[E] rows compared afterwards.
 
 Guards: 128 rows (DTA_MOE_BM) at the payload's pitch around the GEMM operands and outputs, one workgroup's rows (4) around the router's
 and the combine's buffers, a chunk of pairs around the permutation's tables.  dta_moe_combine_bwd refuses a NULL topk_w, so the
@@ -20,7 +24,7 @@ import arena as A
 import moe_ref64 as R
 from dynamictreeattn_amd import ops
 from dynamictreeattn_amd._lib import lib
-from test_gpu_moe_ops import BM, COUNTS
+from test_gpu_moe_ops import BM, COUNTS, DROPPED
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -71,26 +75,35 @@ def _permute_run(ids, E):
              "expert_offsets": _out("expert_offsets", (E + 1,), I32, fill, guard_rows=256), "row_of_pair": _out("row_of_pair", (P,), I32, fill, guard_rows=256),
              "src_token": _out("src_token", (P,), I32, fill, guard_rows=256), "tiles": _out("tiles", (2 * bound,), I32, fill, guard_rows=256)}
         A.launch("dta_moe_permute", a["topk_ids"], T, k, E, a["workspace"], a["expert_offsets"], a["row_of_pair"], a["src_token"], a["tiles"])
+        run.arenas = a
         return a
     return run
 
 
-@pytest.mark.parametrize("case", ["empty_experts", "one_expert"])
+@pytest.mark.parametrize("case", ["empty_experts", "one_expert", "dropped"])
 def test_permutation(case):
     """The workspace has exactly dta_moe_permute_workspace(P, E) ints and starts as 0x7f7f7f7f or 0x01010101: the kernels may not need it
     zeroed.  tiles has exactly 2 * dta_moe_tile_bound(P, E) ints, and every entry past the last tile is written as {-1, 0}."""
     if case == "empty_experts":
         T, k, E = 300, 2, 60
         ids = torch.stack([torch.tensor([5, 40]) if i % 3 else torch.tensor([40, 59]) for i in range(T)]).int()
-    else:
+    elif case == "one_expert":
         T, k, E = 700, 1, 128
         ids = torch.full((T, k), 77, dtype=I32)
-    got = A.check_case(_permute_run(ids, E), f"permute {case}")
+    else:
+        T, k, E = DROPPED
+        ids = R.dropped_ids(T, k, E).int()
+    run = _permute_run(ids, E)
+    got = A.check_case(run, f"permute {case}", scratch=("src_token",) if case == "dropped" else ())
     r = ops.moe_permute(ids.to(DEV), E)
-    _same(got, {"expert_offsets": r.expert_offsets, "row_of_pair": r.row_of_pair, "src_token": r.src_token, "tiles": r.tiles}, f"permute {case}")
     offs, rop, src = R.permute_ref(ids.long(), E)
+    nv = int(offs[E])
+    assert (nv < T * k) == (case == "dropped")
+    got.setdefault("src_token", run.arenas["src_token"].payload())          # dropped: the tail from row offsets[E] on is unwritten
+    _same(got, {"expert_offsets": r.expert_offsets, "row_of_pair": r.row_of_pair, "tiles": r.tiles}, f"permute {case}")
+    A.assert_same_bits(got["src_token"][:nv], r.src_token[:nv], f"permute {case} src_token below offsets[E]: the arena call against the ops wrapper")
     assert got["expert_offsets"].cpu().tolist() == offs.tolist() and got["row_of_pair"].cpu().tolist() == rop.tolist()
-    assert got["src_token"].cpu().tolist() == src.tolist()
+    assert got["src_token"].cpu()[:nv].tolist() == src[:nv].tolist()
     tiles = got["tiles"].cpu().view(-1, 2)
     want = [(e, int(o)) for e in range(E) for o in range(offs[e], offs[e + 1], BM)]
     assert [tuple(t) for t in tiles[:len(want)].tolist()] == want
@@ -140,16 +153,16 @@ def test_grouped_gemm(E, H, N, dtype):
 
 
 # ------------------------------------------------------------------------------------------------ combine
-@pytest.mark.parametrize("dtype", DTYPES)
-def test_combine_forward_backward(dtype):
+def _combine_case(dtype, T, k, E, H, ids):
+    """Combine forward (with and without weights) and backward over the routing of ids [T, k].  nv = offsets[E] rows exist; with dropped
+    pairs nv < T * k, dY is unwritten from row nv on (scratch: guards only) and its first nv rows are compared afterwards."""
     g = torch.Generator().manual_seed(2)
-    T, k, E, H = 203, 4, 16, 96
-    ids = torch.stack([torch.randperm(E, generator=g)[:k] for _ in range(T)]).int()
     route = ops.moe_permute(ids.to(DEV), E)
-    rop = route.row_of_pair.cpu()
+    rop, nv = route.row_of_pair.cpu(), int(route.expert_offsets[E])
+    assert int((rop < 0).sum()) == T * k - nv
     y, w, dout = torch.randn(T * k, H, generator=g).to(dtype), torch.rand(T, k, generator=g).to(dtype), torch.randn(T, H, generator=g).to(dtype)
     for with_w in (True, False):
-        label = f"combine_fwd w={with_w}"
+        label = f"combine_fwd w={with_w} rows={nv}/{T * k}"
 
         def fwd(fill, poison):
             a = {"y": _in("y", y, poison, guard_rows=4), "row_of_pair": _in("row_of_pair", rop, poison, hi=T * k - 1, guard_rows=64),
@@ -160,11 +173,41 @@ def test_combine_forward_backward(dtype):
             return a
         _same(A.check_case(fwd, label), {"out": ops.moe_combine_fwd_raw(y.to(DEV), w.to(DEV) if with_w else None, route)}, label)
 
+    label = f"combine_bwd rows={nv}/{T * k}"
+    last = {}
+
     def bwd(fill, poison):
         a = {"dout": _in("dout", dout, poison, guard_rows=4), "y": _in("y", y, poison, guard_rows=4), "topk_w": _in("topk_w", w, poison, guard_rows=4),
              "row_of_pair": _in("row_of_pair", rop, poison, hi=T * k - 1, guard_rows=64), "dy": _out("dy", (T * k, H), dtype, fill, guard_rows=4),
              "dtopk_w": _out("dtopk_w", (T, k), dtype, fill, guard_rows=4)}
         A.launch("dta_moe_combine_bwd", a["dout"], a["y"], a["topk_w"], a["row_of_pair"], a["dy"], a["dtopk_w"], T, k, H, ops._DT[dtype])
+        last[fill, poison] = a["dy"]
         return a
     dy, dw = ops.moe_combine_bwd_raw(dout.to(DEV), y.to(DEV), w.to(DEV), route)
-    _same(A.check_case(bwd, "combine_bwd"), {"dy": dy, "dtopk_w": dw}, "combine_bwd")
+    got = A.check_case(bwd, label, scratch=("dy",) if nv < T * k else ())
+    if nv == T * k:
+        _same(got, {"dy": dy, "dtopk_w": dw}, label)
+        return
+    _same(got, {"dtopk_w": dw}, label)
+    assert bool((got["dtopk_w"][(rop < 0).view(T, k).to(DEV)] == 0).all()), label + ": the weight gradient of a dropped pair is not zero"
+    rows = {key: a.payload()[:nv] for key, a in last.items()}            # the written rows, under both fills and both input poisons
+    A.assert_written(rows["A", 0], "A", label + " dy below offsets[E]")
+    A.assert_same_bits(rows["A", 0], rows["B", 0], label + " dy below offsets[E]: fill A against fill B")
+    A.assert_same_bits(rows["A", 0], rows["A", 1], label + " dy below offsets[E]: input poison NaN/0 against +inf/max")
+    A.assert_same_bits(rows["A", 0], dy[:nv], label + " dy below offsets[E]: the arena call against the ops wrapper")
+    for (fill, _), a in last.items():                                    # ... and from row offsets[E] on nothing was stored: still the fill
+        tail = a.payload()[nv:]
+        assert bool(torch.isnan(tail).all() if fill == "A" else (tail == A.fill_value(dtype, fill)).all()), label + ": a store behind offsets[E]"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_combine_forward_backward(dtype):
+    g = torch.Generator().manual_seed(2)
+    T, k, E, H = 203, 4, 16, 96
+    _combine_case(dtype, T, k, E, H, torch.stack([torch.randperm(E, generator=g)[:k] for _ in range(T)]).int())
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_combine_dropped_routing(dtype):
+    T, k, E = DROPPED
+    _combine_case(dtype, T, k, E, 48, R.dropped_ids(T, k, E).int())

@@ -22,17 +22,16 @@ def _within(out, ref, bnd, what):
     assert not bool(bad.any()), f"{what}: {int(bad.sum())} elements out of bound, worst err/bound {float((err / bnd).max()):.3g}"
 
 
-@pytest.mark.parametrize("E,k", [(8, 1), (8, 2), (60, 2), (60, 8), (128, 8), (128, 1), (256, 16)])
+@pytest.mark.parametrize("E,k", R.ROUTER_CASES)
 @pytest.mark.parametrize("norm", [True, False])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
 def test_router_forward_backward(E, k, norm, dtype):
-    g = torch.Generator().manual_seed(E * 31 + k)
-    T = 301
-    logits = (2.0 * torch.randn(T, E, generator=g)).to(dtype)
+    logits, g = R.router_logits(E, k, dtype)
+    T = R.ROUTER_T
     ids, w, lse = ops.moe_router_fwd_raw(logits.to(DEV), k, norm)
     rid, rw, rlse, p, margin = R.router_ref(logits, k, norm)
-    ok = margin > 1e-5                        # rows whose top-k a fp32 rounding cannot reorder
-    assert int(ok.sum()) > T // 2
+    ok = margin > R.MARGIN                    # rows whose top-k a fp32 rounding cannot reorder
+    assert int(ok.sum()) >= R.MARGIN_SHARE * T          # tests/test_moe_ref64.py checks this share of every case on the CPU
     assert torch.equal(ids.cpu().long()[ok], rid[ok])
     _within(w.float()[ok.to(DEV)], rw[ok], R.U[dtype] * rw[ok].abs() + 1e-6, "weights")
     _within(lse, rlse, 1e-5 * (1 + rlse.abs()), "lse")
@@ -58,15 +57,44 @@ def test_router_ties_lower_expert_index_wins(dtype):
     assert torch.allclose(w.float().cpu()[0], torch.full((8,), 1 / 8))
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_router_ties_across_the_slots_of_one_lane(dtype):
+    """E 200: lane 5 holds experts 5, 69, 133, 197 in its four slots, lanes 4 and 6 their neighbours.  Equal maxima must come out in
+    ascending expert index whether the tie is between slots of one lane, between lanes, or both; 200 equal logits give 0..7."""
+    E, k = 200, 8
+    logits = torch.zeros(4, E)
+    logits[0, [197, 133, 69, 5]] = 1.0                    # one lane's four slots; the rest tie below them
+    logits[1, [197, 133, 69, 5, 4, 6, 68, 70]] = 1.0      # ... and two slots of each neighbouring lane: exactly k equal maxima
+    logits[2, [5, 69]], logits[2, [133, 197]], logits[2, [4, 132]] = 2.0, 1.0, 1.0    # two tie groups in descending value
+    logits[3] = 0.75                                      # every expert ties
+    ids, w, _ = ops.moe_router_fwd_raw(logits.to(dtype).to(DEV), k, True)
+    ids, w = ids.cpu().tolist(), w.double().cpu()
+    assert ids[0] == [5, 69, 133, 197, 0, 1, 2, 3]
+    assert ids[1] == [4, 5, 6, 68, 69, 70, 133, 197]
+    assert ids[2] == [5, 69, 4, 132, 133, 197, 0, 1]
+    assert ids[3] == list(range(8))
+    eighth = torch.full((8,), 1 / 8, dtype=torch.float64)
+    for row in (1, 3):                                    # eight equal probabilities renormalise to 1/8 each
+        assert bool(((w[row] - eighth).abs() <= R.U[dtype] / 8 + 1e-6).all()), (row, w[row])
+
+
 def _route(ids, E):
     r = ops.moe_permute(ids.to(DEV).int(), E)
     return r
 
 
-@pytest.mark.parametrize("case", ["random", "empty_experts", "one_expert", "big"])
+@pytest.mark.parametrize("case", ["random", "empty_experts", "one_expert", "big", "P1", "P255", "P256", "P257", "T0", "dropped"])
 def test_permutation(case):
+    """P1 .. P257: P = T * k on either side of the 256-pair chunk of the counting sort.  T0: no pair at all.  dropped: every seventh id
+    outside [0, E) - such a pair takes no row, row_of_pair is -1, and src_token is defined below offsets[E] only."""
     g = torch.Generator().manual_seed(3)
-    if case == "random":
+    if case in ("P1", "P255", "P256", "P257", "T0"):
+        T, k, E = {"P1": (1, 1, 8), "P255": (85, 3, 8), "P256": (128, 2, 8), "P257": (257, 1, 8), "T0": (0, 2, 8)}[case]
+        ids = torch.stack([torch.randperm(E, generator=g)[:k] for _ in range(T)]) if T else torch.empty((0, k), dtype=torch.long)
+    elif case == "dropped":
+        T, k, E = 300, 2, 60
+        ids = R.dropped_ids(T, k, E)
+    elif case == "random":
         T, k, E = 517, 2, 8
         ids = torch.stack([torch.randperm(E, generator=g)[:k] for _ in range(T)])
     elif case == "empty_experts":
@@ -80,16 +108,24 @@ def test_permutation(case):
         ids = torch.stack([torch.randperm(E, generator=g)[:k] for _ in range(T)])
     a, b = _route(ids, E), _route(ids, E)
     offs, rop, src = R.permute_ref(ids, E)
-    for x, y in ((a.expert_offsets, b.expert_offsets), (a.row_of_pair, b.row_of_pair), (a.src_token, b.src_token), (a.tiles, b.tiles)):
+    n_valid = int(offs[E])                                         # src_token is written below offsets[E] only
+    assert n_valid == T * k or case == "dropped"
+    for x, y in ((a.expert_offsets, b.expert_offsets), (a.row_of_pair, b.row_of_pair), (a.src_token[:n_valid], b.src_token[:n_valid]), (a.tiles, b.tiles)):
         assert torch.equal(x, y)                                   # bitwise repeatable
     assert a.expert_offsets.cpu().tolist() == offs.tolist()
     assert a.row_of_pair.cpu().numpy().tolist() == rop.tolist()
-    assert a.src_token.cpu().numpy().tolist() == src.tolist()
+    assert a.src_token.shape == (T * k,) and a.src_token.cpu().numpy()[:n_valid].tolist() == src[:n_valid].tolist()
     tiles = a.tiles.cpu().view(-1, 2)
     assert tiles.shape[0] == -(-T * k // BM) + E
     want = [(e, int(o)) for e in range(E) for o in range(offs[e], offs[e + 1], BM)]
     assert [tuple(t) for t in tiles[:len(want)].tolist()] == want
-    assert bool((tiles[len(want):, 0] == -1).all())
+    assert bool((tiles[len(want):, 0] == -1).all()) and bool((tiles[len(want):, 1] == 0).all())
+    if case == "T0":
+        assert offs.tolist() == [0] * (E + 1) and not want
+    if case == "dropped":
+        flat = ids.reshape(-1)
+        out_of_range = (flat < 0) | (flat >= E)
+        assert int(out_of_range.sum()) == T * k - n_valid > 0 and bool((a.row_of_pair.cpu()[out_of_range] == -1).all())
 
 
 COUNTS = [0, 1, BM - 1, BM, BM + 1, 0, 2 * BM + 3, 5]
@@ -110,13 +146,17 @@ def _gemm_case(E, counts, H, N, dtype, seed=0):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
-@pytest.mark.parametrize("shape", [(8, 32, 96), (8, 48, 32), (5, 2048, 1536), (4, 768, 2048)])
+@pytest.mark.parametrize("shape", [(8, 32, 96), (8, 48, 32), (5, 2048, 1536), (4, 768, 2048), (3, 208, 144), (3, 144, 208)])
 def test_grouped_gemm_fwd_dgrad_wgrad(dtype, shape):
+    """The last two shapes put a partial tile behind a full one in every role: 144 = 128 + 16 (a second n-tile of the MFMA path with
+    masked columns, a third 64-tile of the fp32 path) = 2 * 64 + 16 and 208 = 3 * 64 + 16 (a k-tail behind full k-steps).  Without the
+    gather (k = 1: P = T) x stands for an expert-sorted [P, H] operand: the down projection's forward and weight gradient."""
     E, H, N = shape
     route, offs, src, x, w, dy = _gemm_case(E, COUNTS, H, N, dtype, seed=H + N)
     xd, wd, dyd = x.to(DEV), w.to(DEV), dy.to(DEV)
     for mode, args, gather in ((ops.MOE_FWD, dict(x=xd, w=wd), True), (ops.MOE_FWD, dict(x=xd, w=wd), False),
-                               (ops.MOE_DGRAD, dict(w=wd, dy=dyd), False), (ops.MOE_WGRAD, dict(x=xd, dy=dyd), True)):
+                               (ops.MOE_DGRAD, dict(w=wd, dy=dyd), False), (ops.MOE_WGRAD, dict(x=xd, dy=dyd), True),
+                               (ops.MOE_WGRAD, dict(x=xd, dy=dyd), False)):
         out = ops.moe_grouped_gemm(mode, route, w.shape, dtype, gather=gather, **args)
         ref, mag, n = R.gemm_ref(mode, x, w, dy, offs, src, gather)
         _within(out, ref, R.bound(ref, mag, n, dtype), f"mode {mode} gather {gather}")
@@ -150,10 +190,73 @@ def test_grouped_gemm_qwen3_30b_a3b_geometry(dtype):
     _within(out, ref, R.bound(ref, mag, n, dtype), "gate/up wgrad")
 
 
+DROPPED = (300, 2, 60)          # T, k, E of the routing with ids outside [0, E) (R.dropped_ids)
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
-def test_combine_forward_backward(dtype):
+def test_grouped_gemm_dropped_routing(dtype):
+    """Ids outside [0, E): the P - offsets[E] dropped pairs own no row.  Every mode meets its bound on the rows below offsets[E] (the
+    rows behind them belong to no tile and are left unwritten), and the weight gradient sums an expert's own rows only."""
+    T, k, E = DROPPED
+    H, N = 144, 80
+    ids = R.dropped_ids(T, k, E)
+    route = _route(ids, E)
+    offs, rop, src = R.permute_ref(ids, E)
+    nv, P = int(offs[E]), T * k
+    assert 0 < nv < P and route.expert_offsets.cpu().tolist() == offs.tolist()
+    g = torch.Generator().manual_seed(H + N)
+    x, xs = torch.randn(T, H, generator=g).to(dtype), torch.randn(P, H, generator=g).to(dtype)
+    w = (torch.randn(E, N, H, generator=g) / H ** 0.5).to(dtype)
+    dy = torch.randn(P, N, generator=g).to(dtype)
+    xd, xsd, wd, dyd = x.to(DEV), xs.to(DEV), w.to(DEV), dy.to(DEV)
+    for mode, args, gather in ((ops.MOE_FWD, dict(x=xd, w=wd), True), (ops.MOE_FWD, dict(x=xsd, w=wd), False),
+                               (ops.MOE_DGRAD, dict(w=wd, dy=dyd), False), (ops.MOE_WGRAD, dict(x=xd, dy=dyd), True),
+                               (ops.MOE_WGRAD, dict(x=xsd, dy=dyd), False)):
+        out = ops.moe_grouped_gemm(mode, route, w.shape, dtype, gather=gather, **args)
+        ref, mag, n = R.gemm_ref(mode, x if gather else xs, w, dy, offs, src, gather)
+        if mode != ops.MOE_WGRAD:
+            assert out.shape[0] == P
+            out, ref, mag = out[:nv], ref[:nv], mag[:nv]
+        _within(out, ref, R.bound(ref, mag, n, dtype), f"dropped routing: mode {mode} gather {gather}")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_empty_batch(dtype, monkeypatch):
+    """T = 0 through every wrapper: the entries return before launching, the weight gradient of no rows is all zeros, and the forward
+    and dgrad wrappers hand back an empty [0, .] tensor without a call into the library."""
+    E, k, H, N = 8, 2, 48, 32
+    logits = torch.empty((0, E), dtype=dtype, device=DEV)
+    ids, w, lse = ops.moe_router_fwd_raw(logits, k, True)
+    assert ids.shape == (0, k) and w.shape == (0, k) and w.dtype == dtype and lse.shape == (0,)
+    assert ops.moe_router_bwd_raw(logits, lse, ids, w, True).shape == (0, E)
+    route = ops.moe_permute(ids, E)
+    assert route.expert_offsets.cpu().tolist() == [0] * (E + 1) and route.row_of_pair.shape == (0,) and route.src_token.shape == (0,)
+    x, wt, dy = torch.empty((0, H), dtype=dtype, device=DEV), torch.ones((E, N, H), dtype=dtype, device=DEV), torch.empty((0, N), dtype=dtype, device=DEV)
+    for gather in (True, False):
+        dw = ops.moe_grouped_gemm(ops.MOE_WGRAD, route, wt.shape, dtype, x=x, dy=dy, gather=gather)
+        assert dw.shape == wt.shape and dw.dtype == dtype and bool((dw == 0).all())
+    y = torch.empty((0, H), dtype=dtype, device=DEV)
+    assert ops.moe_combine_fwd_raw(y, w, route).shape == (0, H)
+    dyc, dwc = ops.moe_combine_bwd_raw(y, y, w, route)
+    assert dyc.shape == (0, H) and dwc.shape == (0, k)
+
+    def no_launch(name, *a, **kw):
+        raise AssertionError(f"{name} was launched for an empty batch")
+    monkeypatch.setattr(ops, "_launch", no_launch)
+    out = ops.moe_grouped_gemm(ops.MOE_FWD, route, wt.shape, dtype, x=x, w=wt, gather=True)
+    assert out.shape == (0, N) and out.dtype == dtype
+    out = ops.moe_grouped_gemm(ops.MOE_DGRAD, route, wt.shape, dtype, w=wt, dy=dy)
+    assert out.shape == (0, H) and out.dtype == dtype
+
+
+COMBINE_SHAPES = [(203, 4, 96), (5, 1, 16), (64, 16, 48), (130, 3, 208)]          # T, k, H; E 16, so k 16 takes every expert
+
+
+@pytest.mark.parametrize("T,k,H", COMBINE_SHAPES)
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_combine_forward_backward(dtype, T, k, H):
     g = torch.Generator().manual_seed(2)
-    T, k, E, H = 203, 4, 16, 96
+    E = 16
     ids = torch.stack([torch.randperm(E, generator=g)[:k] for _ in range(T)])
     route = _route(ids, E)
     _, rop, _ = R.permute_ref(ids, E)
@@ -176,6 +279,41 @@ def test_combine_forward_backward(dtype):
     _within(dw, ref_dw, R.bound(ref_dw, mag_dw, H, dtype), "combine dw")
     dy2, dw2 = ops.moe_combine_bwd_raw(dout.to(DEV), y.to(DEV), w.to(DEV), route)
     assert torch.equal(dy, dy2) and torch.equal(dw, dw2)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_combine_dropped_routing(dtype):
+    """row_of_pair -1 (an id outside [0, E)): the forward sums the valid slots only, the slot's weight gradient is exactly zero, and
+    dY is written - and bounded - on the rows below offsets[E], the only rows there are."""
+    T, k, E = DROPPED
+    H = 48
+    ids = R.dropped_ids(T, k, E)
+    route = _route(ids, E)
+    offs, rop, _ = R.permute_ref(ids, E)
+    nv = int(offs[E])
+    rows = torch.as_tensor(rop).view(T, k)
+    dropped = rows < 0
+    assert int(dropped.sum()) == T * k - nv > 0 and route.row_of_pair.cpu().tolist() == rop.tolist()
+    g = torch.Generator().manual_seed(2)
+    y = torch.randn(T * k, H, generator=g).to(dtype)
+    w = torch.rand(T, k, generator=g).to(dtype)
+    dout = torch.randn(T, H, generator=g).to(dtype)
+    for ww in (w, None):
+        out = ops.moe_combine_fwd_raw(y.to(DEV), None if ww is None else ww.to(DEV), route)
+        ref, mag = R.combine_ref(y, ww, rop, T, k)
+        _within(out, ref, R.bound(ref, mag, k, dtype), "combine over dropped pairs" if ww is not None else "scatter-back over dropped pairs")
+    both = dropped.all(1)
+    if bool(both.any()):
+        assert bool((out[both.to(DEV)] == 0).all())
+    dy, dw = ops.moe_combine_bwd_raw(dout.to(DEV), y.to(DEV), w.to(DEV), route)
+    assert bool((dw.cpu()[dropped] == 0).all())
+    ref_dy = torch.zeros(T * k, H, dtype=torch.float64)
+    ref_dy[rows[~dropped]] = (w.double()[..., None] * dout.double()[:, None, :])[~dropped]
+    _within(dy[:nv], ref_dy[:nv], R.U[dtype] * ref_dy[:nv].abs() + R.TINY[dtype], "combine dY below offsets[E]")
+    yv = y.double()[rows.clamp(min=0)] * (~dropped)[..., None]
+    ref_dw = (dout.double()[:, None, :] * yv).sum(-1)
+    mag_dw = (dout.double().abs()[:, None, :] * yv.abs()).sum(-1)
+    _within(dw, ref_dw, R.bound(ref_dw, mag_dw, H, dtype), "combine dw")
 
 
 def test_moe_return_codes():
