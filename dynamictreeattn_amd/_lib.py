@@ -59,20 +59,12 @@ _PROTOS = {
     "dta_lora_down": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp], C.c_int),
     "dta_lora_wgrad_slabs": ([_i32, _i32], C.c_int),
     "dta_lora_wgrad": ([_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp], C.c_int),
-    "dta_policy_loss_blocks": ([_i32], C.c_int),
-    # lp ent depth row_seq_lo row_seq_hi seq_ptr old_lp ref_lp mask adv | adv_per_seq | w dlp dent partial stats | T S |
-    # clip_low clip_high dual_clip kl_coef | kl_estimator | entropy_coef | agg | scale | stream
-    "dta_policy_loss": ([_vp] * 10 + [_i32] + [_vp] * 5 + [_i32, _i32] + [_f32] * 4 + [_i32, _f32, _i32, _f32, _vp], C.c_int),
-    "dta_policy_loss_seq_blocks": ([_i32, _i32], C.c_int),
-    # lp ent depth row_seq_lo row_seq_hi seq_ptr leaf_run_ptr run_row0 run_depth0 seq_leaf old_lp ref_lp mask adv | adv_per_seq |
-    # w c dlp dent partial stats | T S M R | clip_low clip_high dual_clip kl_coef | kl_estimator | entropy_coef | agg | scale | stream
-    "dta_policy_loss_seq": ([_vp] * 14 + [_i32] + [_vp] * 6 + [_i32] * 4 + [_f32] * 4 + [_i32, _f32, _i32, _f32, _vp], C.c_int),
-    "dta_policy_loss_ex_blocks": ([_i32, _i32], C.c_int),
+    "dta_policy_loss_blocks": ([_i32, _i32], C.c_int),
     # lp ent depth row_seq_lo row_seq_hi seq_ptr leaf_run_ptr run_row0 run_depth0 seq_leaf old_lp ref_lp rollout_lp mask adv | adv_per_seq |
     # w c omega dlp dent partial stats | T S M R | clip_low clip_high dual_clip kl_coef | kl_estimator | entropy_coef | agg | scale |
     # ratio_level surrogate is_level is_mode | is_cap is_floor | stream
-    "dta_policy_loss_ex": ([_vp] * 15 + [_i32] + [_vp] * 7 + [_i32] * 4 + [_f32] * 4 + [_i32, _f32, _i32, _f32] + [_i32] * 4 + [_f32, _f32, _vp],
-                           C.c_int),
+    "dta_policy_loss": ([_vp] * 15 + [_i32] + [_vp] * 7 + [_i32] * 4 + [_f32] * 4 + [_i32, _f32, _i32, _f32] + [_i32] * 4 + [_f32, _f32, _vp],
+                        C.c_int),
     "dta_preference_loss_blocks": ([_i32, _i32, _i32], C.c_int),
     # lp depth row_seq_lo row_seq_hi seq_ptr leaf_run_ptr run_row0 run_depth0 seq_leaf pair_c pair_r ref_lp ref_sum mask |
     # nhat u sft g dlp partial stats | T S M R P kind | beta label_smoothing gamma | length_normalize reference_free | sft_coef scale | stream

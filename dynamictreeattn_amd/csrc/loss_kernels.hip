@@ -7,14 +7,15 @@
 // A thread takes a row; a row whose range is longer than PL_SERIAL sequences is summed by its whole wave, lane-strided over s and
 // joined by the xor butterfly - a fixed order either way, so equal inputs give equal bits.
 //
-// Sequence-level ratios (dta_policy_loss_seq, GSPO): every token of sequence s is clipped on r_s = exp(sum_j m_j x_j / n^), so the
-// surrogate's gradient at token t of s is c_s m_t with one scalar c_s per sequence.  A sequence pass (one workgroup per sequence)
-// walks the sequence's root path - a few contiguous row runs - for r_s, w_s, c_s and the surrogate's share of the statistics; the row
-// pass is the one above with c_s m in place of the token's own surrogate gradient; one reduction joins the partials of both.
-//
-// Off-policy corrections and CISPO (dta_policy_loss_ex): a detached rollout importance weight omega, truncated or masked, per token
-// (formed in the row term from the row's own lp when old_lp is absent) or per sequence (left by the sequence pass, which walks the path
-// only when old_lp is absent), multiplies the surrogate; with a sequence-level ratio it enters c_s.  CISPO is a second row-term form.
+// A sequence pass (one workgroup per sequence) goes first and leaves what is one number per sequence; one reduction joins the partials
+// of both passes.  The objective's options are forms of the one row term and branches of the one sequence pass:
+//   sequence-level ratios (GSPO): every token of sequence s is clipped on r_s = exp(sum_j m_j x_j / n^), so the surrogate's gradient at
+//     token t of s is c_s m_t with one scalar c_s per sequence.  The sequence pass walks the sequence's root path - a few contiguous row
+//     runs - for r_s, c_s and the surrogate's share of the statistics; the row term takes c_s m for the token's own surrogate gradient;
+//   off-policy corrections: a detached rollout importance weight omega, truncated or masked, per token (formed in the row term, from the
+//     row's own lp when old_lp is absent) or per sequence (left by the sequence pass, which walks the path only when old_lp is absent),
+//     multiplies the surrogate; with a sequence-level ratio it enters c_s;
+//   CISPO: a second token-level form of the row term.
 //
 // Preference objectives (dta_preference_loss: DPO / cDPO / SimPO, SLiC, IPO): a pair couples two sequences, so a pair pass stands
 // between the sequence pass (u_s, one number per sequence, over the same path walk) and a row pass that sums g_s m with the pair's
@@ -127,16 +128,17 @@ __device__ __forceinline__ void stat_partials(const float (&st)[N], float* parti
   }
 }
 
-// ---- policy objective ------------------------------------------------------------------------------------------------------------
+// ---- policy objective (dta_policy_loss) --------------------------------------------------------------------------------------------
 
 struct PolicyParams {
   const float *lp, *ent;
   const int32_t *depth, *row_lo, *row_hi, *seq_ptr;
-  const float *old_lp, *ref_lp, *mask, *adv, *w;
-  const float* c;                            // sequence-level ratios only: the surrogate's gradient scalar per sequence
+  const float *old_lp, *ref_lp, *rollout, *mask, *adv;
+  const float *w, *c, *omega;                // per sequence, left by the sequence pass: the weight, the sequence-level surrogate's gradient
+                                             // scalar, the sequence-level rollout weight
   float *dlp, *dent, *partial;
-  int32_t T, S, adv_per_seq;
-  float lo, hi, dual, kl_coef, ent_coef;     // lo = 1 - clip_low, hi = 1 + clip_high, dual = 0: none
+  int32_t T, S, adv_per_seq, is_mode;
+  float lo, hi, dual, kl_coef, ent_coef, is_cap, is_floor;     // lo = 1 - clip_low, hi = 1 + clip_high, dual = 0: none
 };
 
 // a row's own values, and what it receives: dlp and dent
@@ -144,9 +146,9 @@ struct PolicyRow {
   int d; float lp, ent;
   __device__ PolicyRow from_lane(int k) const { return {__shfl(d, k), __shfl(lp, k), __shfl(ent, k)}; }
 };
-// the first six columns of the statistics.  (A struct: a bare private array that loops index becomes one vector value before the loops
-// are unrolled, and the columns an instantiation never touches then no longer fold to constants.)
-struct PolicyStats { float v[6]; };
+// a thread's share of the statistics.  (A struct: a bare private array that loops index becomes one vector value before the loops are
+// unrolled, and the columns an instantiation never touches then no longer fold to constants.)
+struct PolicyStats { float v[PL_NSTAT]; };
 struct PolicySum {
   float glp, gent;
   __device__ PolicySum wave_total() const { return {wave_sum(glp), wave_sum(gent)}; }
@@ -175,79 +177,105 @@ __device__ __forceinline__ float kl_term(float dd, float& dk) {
   return e - dd - 1.f;
 }
 
-// the entropy term (s, j = d) of a row with entropy ent_t, for a sequence with predictions from b and weight w
-__device__ __forceinline__ void entropy_term(const PolicyParams& p, int b, int d, float w, float ent_t, PolicySum& a, PolicyStats& st) {
-  const float m = p.mask[b + d];
-  const float wm = w * m;
-  a.gent -= wm * p.ent_coef;
-  st.v[0] -= wm * p.ent_coef * ent_t;
-  st.v[3] += m * ent_t;
+// the rollout weight omega from rho: mode 0 truncates at cap, mode 1 drops what lies outside [floor, cap].  No arithmetic on rho: an
+// overflowed expf (inf) gives cap or 0 and never NaN.  `altered`: omega != rho.
+struct IsWeight { float omega; bool altered; };
+__device__ __forceinline__ IsWeight is_weight(float rho, int mode, float cap, float floor) {
+  if (mode == 0) {
+    const bool over = rho > cap;
+    return {over ? cap : rho, over};
+  }
+  const bool keep = rho >= floor && rho <= cap;
+  return {keep ? rho : 0.f, !keep};
 }
 
-// the terms a row owns for sequence s
-template <int KL>
-__device__ __forceinline__ void seq_terms(const PolicyParams& p, int s, const PolicyRow& row, PolicySum& a, PolicyStats& st) {
+// the surrogate's form in the row term
+constexpr int PL_CLIPPED = 0;       // the clipped surrogate on the token's own ratio
+constexpr int PL_CISPO = 1;         // pg = -clamp(r) A lp with the clamp detached: the gradient -clamp(r) A is never zeroed, "clipped"
+                                    // counts r outside [lo, hi]
+constexpr int PL_SEQ_RATIO = 2;     // a sequence-level ratio: the gradient is c_s m, value and statistics are the sequence pass's
+
+// The terms a row owns for sequence s.  ISL (the token-level forms): 0 no rollout weight, 1 a weight per token formed here, 2 the
+// sequence's weight omega[s]; columns 6 and 7 of the statistics are the sequence pass's under ISL 2 and under PL_SEQ_RATIO.
+template <int KL, int FORM, int ISL>
+__device__ __forceinline__ void policy_terms(const PolicyParams& p, int s, const PolicyRow& row, PolicySum& a, PolicyStats& st) {
   const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b, d = row.d;
   if (n < d) return;                                       // the sequence ends above this row
   const float w = p.w[s];
-  if (d >= 1) {
+  if (d >= 1) {                                            // the log-prob term (s, j = d - 1)
     const int i = b + d - 1;
     const float m = p.mask[i];
-    const float A = p.adv[p.adv_per_seq ? s : i];
-    const float r = p.old_lp ? expf(row.lp - p.old_lp[i]) : 1.f;
-    const auto [pg, clipped] = clipped_pg(r, p.lo, p.hi, A, p.dual);
-    float g = clipped ? 0.f : -r * A;                      // d(-r A)/d lp = -r A
-    float kl = 0.f;
-    if (KL >= 0) {
-      float dk;
-      kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
-      g += p.kl_coef * dk;
-      st.v[2] += m * kl;
-    }
-    const float wm = w * m;
-    a.glp += wm * g;
-    st.v[0] += wm * (pg + p.kl_coef * kl);
-    st.v[1] += m * pg;
-    st.v[4] += clipped ? m : 0.f;
-    st.v[5] += m;
-  }
-  if (d < n) entropy_term(p, b, d, w, row.ent, a, st);
-}
-
-// the same for sequence-level ratios: the surrogate's value and statistics are the sequence pass's, its gradient here is c_s m
-template <int KL>
-__device__ __forceinline__ void seq_terms_sl(const PolicyParams& p, int s, const PolicyRow& row, PolicySum& a, PolicyStats& st) {
-  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b, d = row.d;
-  if (n < d) return;
-  const float w = p.w[s];
-  if (d >= 1) {
-    const int i = b + d - 1;
-    const float m = p.mask[i];
-    float g = p.c[s] * m;
-    if (KL >= 0) {
-      float dk;
-      const float kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
+    if (FORM == PL_SEQ_RATIO) {
+      float g = p.c[s] * m;
+      if (KL >= 0) {
+        float dk;
+        const float kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
+        const float wm = w * m;
+        g += wm * (p.kl_coef * dk);
+        st.v[0] += wm * (p.kl_coef * kl);
+        st.v[2] += m * kl;
+      }
+      a.glp += g;
+    } else {
+      const float A = p.adv[p.adv_per_seq ? s : i];
+      const float r = p.old_lp ? expf(row.lp - p.old_lp[i]) : 1.f;
+      float pg, g;
+      bool clipped;
+      if (FORM == PL_CLIPPED) {
+        const Pg q = clipped_pg(r, p.lo, p.hi, A, p.dual);
+        pg = q.pg; clipped = q.clipped;
+        g = clipped ? 0.f : -r * A;                        // d(-r A)/d lp = -r A
+      } else {
+        g = -fminf(fmaxf(r, p.lo), p.hi) * A;
+        pg = g * row.lp;
+        clipped = r < p.lo || r > p.hi;
+      }
+      if (ISL == 1) {
+        const float y = (p.old_lp ? p.old_lp[i] : row.lp) - p.rollout[i];
+        const auto [omega, altered] = is_weight(expf(y), p.is_mode, p.is_cap, p.is_floor);
+        pg *= omega; g *= omega;
+        st.v[6] += m * omega;
+        st.v[7] += altered ? m : 0.f;
+      } else if (ISL == 2) {
+        const float omega = p.omega[s];
+        pg *= omega; g *= omega;
+      } else if (FORM == PL_CISPO) {
+        st.v[6] += m;                                      // omega == 1 (the clipped form: column 5, copied after the sweep)
+      }
+      float kl = 0.f;
+      if (KL >= 0) {
+        float dk;
+        kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
+        g += p.kl_coef * dk;
+        st.v[2] += m * kl;
+      }
       const float wm = w * m;
-      g += wm * (p.kl_coef * dk);
-      st.v[0] += wm * (p.kl_coef * kl);
-      st.v[2] += m * kl;
+      a.glp += wm * g;
+      st.v[0] += wm * (pg + p.kl_coef * kl);
+      st.v[1] += m * pg;
+      st.v[4] += clipped ? m : 0.f;
     }
-    a.glp += g;
     st.v[5] += m;
   }
-  if (d < n) entropy_term(p, b, d, w, row.ent, a, st);
+  if (d < n) {                                             // the entropy term (s, j = d)
+    const float m = p.mask[b + d];
+    const float wm = w * m;
+    a.gent -= wm * p.ent_coef;
+    st.v[0] -= wm * p.ent_coef * row.ent;
+    st.v[3] += m * row.ent;
+  }
 }
 
-template <int KL, bool SEQ>
+template <int KL, int FORM, int ISL>
 __global__ __launch_bounds__(PL_BLOCK) void policy_loss_kernel(const PolicyParams p) {
   PolicyStats st = {};                                     // this thread's share of the statistics, over all its rows
   row_sweep<PolicyRow, PolicySum, true>(
       p.T, p.S, p.row_lo, p.row_hi, [&](int t) { return PolicyRow{p.depth[t], p.lp[t], p.ent[t]}; },
-      [&](int s, const PolicyRow& row, PolicySum& a) {
-        if (SEQ) seq_terms_sl<KL>(p, s, row, a, st);
-        else seq_terms<KL>(p, s, row, a, st);
-      },
+      [&](int s, const PolicyRow& row, PolicySum& a) { policy_terms<KL, FORM, ISL>(p, s, row, a, st); },
       [&](int t, const PolicySum& a) { p.dlp[t] = a.glp; p.dent[t] = a.gent; });
+  // omega == 1: sum m omega has the addends of sum m, in their order.  Copied here, not added per term: a seventh accumulator in the loop
+  // changes how the compiler contracts the clipped form's neighbouring products, and with it the last bits of dlp.
+  if (FORM == PL_CLIPPED && ISL == 0) st.v[6] = st.v[5];
   stat_partials(st.v, p.partial);
 }
 
@@ -266,180 +294,20 @@ __global__ __launch_bounds__(256) void policy_loss_reduce_kernel(const float* __
   }
 }
 
-// w[s] = scale / max(sum of the sequence's mask, 1): one workgroup per sequence, lanes strided
-__global__ __launch_bounds__(256) void policy_seq_weight_kernel(const float* __restrict__ mask, const int32_t* __restrict__ seq_ptr, int S,
-                                                               float scale, float* __restrict__ w) {
-  __shared__ float red[4];
-  for (int s = blockIdx.x; s < S; s += gridDim.x) {
-    const int b = seq_ptr[s], e = seq_ptr[s + 1];
-    float v = 0.f;
-    for (int i = b + (int)threadIdx.x; i < e; i += 256) v += mask[i];
-    v = block_sum(v, red);
-    if (threadIdx.x == 0) w[s] = scale / fmaxf(v, 1.f);
-  }
-}
-
-__global__ __launch_bounds__(256) void policy_fill_weight_kernel(int S, float scale, float* __restrict__ w) {
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  if (s < S) w[s] = scale;
-}
-
-// The sequence pass of the sequence-level objective.
+// The sequence pass: w[s], omega[s] and c[s] of every sequence, and its workgroup's row of partials - the surrogate's columns under a
+// sequence-level ratio, columns 6 and 7 under a sequence-level ratio or a sequence-level weight, 0 everywhere else.
 struct SeqPassParams : PathParams {
-  const float *old_lp, *mask, *adv;
-  float *w, *c, *partial;
-  int32_t adv_per_seq, seq_mean;
-  float lo, hi, dual, scale;
-};
-
-__global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParams p) {
-  __shared__ float red[4];
-  float st_loss = 0.f, st_pg = 0.f, st_clip = 0.f;         // thread 0: this workgroup's sequences, in order
-  for (int s = blockIdx.x; s < p.S; s += gridDim.x) {      // `s` is the same in every thread of the workgroup
-    const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
-    float sm = 0.f, sx = 0.f;
-    if (p.old_lp) {
-      path_walk(p, s, b, n, [&](int t, int i) {
-        const float m = p.mask[i];
-        sm += m;
-        sx += m * (p.lp[t] - p.old_lp[i]);
-      });
-    } else {
-      for (int j = threadIdx.x; j < n; j += 256) sm += p.mask[b + j];
-    }
-    const float nh = fmaxf(block_sum(sm, red), 1.f);
-    const float r = p.old_lp ? expf(block_sum(sx, red) / nh) : 1.f;
-    const float w = p.seq_mean ? p.scale / nh : p.scale;
-    // every token of the sequence sees the same r: its branch depends on the sign of its advantage alone
-    float spg = 0.f, sg = 0.f, sc = 0.f;
-    for (int j = threadIdx.x; j < n; j += 256) {
-      const float m = p.mask[b + j];
-      const float A = p.adv[p.adv_per_seq ? s : b + j];
-      const auto [pg, clipped] = clipped_pg(r, p.lo, p.hi, A, p.dual);
-      spg += m * pg;
-      sg += clipped ? 0.f : m * -A;
-      sc += clipped ? m : 0.f;
-    }
-    spg = block_sum(spg, red); sg = block_sum(sg, red); sc = block_sum(sc, red);
-    if (threadIdx.x == 0) {
-      p.w[s] = w;
-      p.c[s] = w * r / nh * sg;
-      st_loss += w * spg; st_pg += spg; st_clip += sc;
-    }
-  }
-  if (threadIdx.x == 0) {                                  // this workgroup's row of the partial sums: the surrogate's columns
-    float* out = p.partial + (size_t)blockIdx.x * PL_NSTAT;
-    out[0] = st_loss; out[1] = st_pg; out[2] = 0.f; out[3] = 0.f; out[4] = st_clip; out[5] = 0.f; out[6] = 0.f; out[7] = 0.f;
-  }
-}
-
-// ---- off-policy corrections and CISPO (dta_policy_loss_ex) -------------------------------------------------------------------------
-// A rollout importance weight omega = truncate | mask (rho), rho from y = old - rollout (old absent: the row's own lp - rollout), per
-// token or one per sequence, multiplies the surrogate and its gradient and nothing else; CISPO is a second form of the surrogate.  The
-// entries above keep their kernels: the token-level row term of this entry is a functor of its own (ex_terms), its sequence pass a
-// kernel of its own (policy_ex_seq_pass_kernel); a sequence-level ratio runs the row kernel above unchanged, because c_s holds omega.
-
-// omega from rho: mode 0 truncates at cap, mode 1 drops what lies outside [floor, cap].  No arithmetic on rho: an overflowed expf (inf)
-// gives cap or 0 and never NaN.  `altered`: omega != rho.
-struct IsWeight { float omega; bool altered; };
-__device__ __forceinline__ IsWeight is_weight(float rho, int mode, float cap, float floor) {
-  if (mode == 0) {
-    const bool over = rho > cap;
-    return {over ? cap : rho, over};
-  }
-  const bool keep = rho >= floor && rho <= cap;
-  return {keep ? rho : 0.f, !keep};
-}
-
-struct PolicyExParams : PolicyParams {
-  const float *rollout, *omega;              // omega [S]: the sequence pass's weight per sequence (ISL == 2 reads it)
-  int32_t is_mode;
-  float is_cap, is_floor;
-};
-struct PolicyExStats { float v[PL_NSTAT]; };
-
-// the terms a row owns for sequence s under a token-level ratio.  SUR: 0 the clipped surrogate, 1 CISPO (pg = -clamp(r) A lp with the
-// clamp detached: the gradient -clamp(r) A is never zeroed, "clipped" counts r outside [lo, hi]).  ISL: 0 no weight, 1 a weight per
-// token formed here, 2 the sequence's weight omega[s] (columns 6 and 7 are the sequence pass's then).
-template <int KL, int SUR, int ISL>
-__device__ __forceinline__ void ex_terms(const PolicyExParams& p, int s, const PolicyRow& row, PolicySum& a, PolicyExStats& st) {
-  const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b, d = row.d;
-  if (n < d) return;                                       // the sequence ends above this row
-  const float w = p.w[s];
-  if (d >= 1) {
-    const int i = b + d - 1;
-    const float m = p.mask[i];
-    const float A = p.adv[p.adv_per_seq ? s : i];
-    const float r = p.old_lp ? expf(row.lp - p.old_lp[i]) : 1.f;
-    float pg, g;
-    bool clipped;
-    if (SUR == 0) {
-      const Pg q = clipped_pg(r, p.lo, p.hi, A, p.dual);
-      pg = q.pg; clipped = q.clipped;
-      g = clipped ? 0.f : -r * A;
-    } else {
-      g = -fminf(fmaxf(r, p.lo), p.hi) * A;
-      pg = g * row.lp;
-      clipped = r < p.lo || r > p.hi;
-    }
-    if (ISL == 1) {
-      const float y = (p.old_lp ? p.old_lp[i] : row.lp) - p.rollout[i];
-      const auto [omega, altered] = is_weight(expf(y), p.is_mode, p.is_cap, p.is_floor);
-      pg *= omega; g *= omega;
-      st.v[6] += m * omega;
-      st.v[7] += altered ? m : 0.f;
-    } else if (ISL == 2) {
-      const float omega = p.omega[s];
-      pg *= omega; g *= omega;
-    } else {
-      st.v[6] += m;                                        // omega == 1
-    }
-    float kl = 0.f;
-    if (KL >= 0) {
-      float dk;
-      kl = kl_term<KL>(p.ref_lp[i] - row.lp, dk);
-      g += p.kl_coef * dk;
-      st.v[2] += m * kl;
-    }
-    const float wm = w * m;
-    a.glp += wm * g;
-    st.v[0] += wm * (pg + p.kl_coef * kl);
-    st.v[1] += m * pg;
-    st.v[4] += clipped ? m : 0.f;
-    st.v[5] += m;
-  }
-  if (d < n) {                                             // the entropy term (s, j = d), as entropy_term
-    const float m = p.mask[b + d];
-    const float wm = w * m;
-    a.gent -= wm * p.ent_coef;
-    st.v[0] -= wm * p.ent_coef * row.ent;
-    st.v[3] += m * row.ent;
-  }
-}
-
-template <int KL, int SUR, int ISL>
-__global__ __launch_bounds__(PL_BLOCK) void policy_loss_ex_kernel(const PolicyExParams p) {
-  PolicyExStats st = {};
-  row_sweep<PolicyRow, PolicySum, true>(
-      p.T, p.S, p.row_lo, p.row_hi, [&](int t) { return PolicyRow{p.depth[t], p.lp[t], p.ent[t]}; },
-      [&](int s, const PolicyRow& row, PolicySum& a) { ex_terms<KL, SUR, ISL>(p, s, row, a, st); },
-      [&](int t, const PolicySum& a) { p.dlp[t] = a.glp; p.dent[t] = a.gent; });
-  stat_partials(st.v, p.partial);
-}
-
-// The sequence pass of dta_policy_loss_ex: w[s], omega[s] and c[s] of every sequence, and its workgroup's row of partials - the
-// surrogate's columns under a sequence-level ratio, columns 6 and 7 under a sequence-level ratio or a sequence-level weight.
-struct ExSeqPassParams : PathParams {
   const float *old_lp, *rollout, *mask, *adv;
   float *w, *c, *omega, *partial;
   int32_t adv_per_seq, seq_mean, ratio_seq, is_level, is_mode;     // is_level: 0 none, 1 token, 2 sequence, 3 sequence_mean
   float lo, hi, dual, scale, is_cap, is_floor;
 };
 
-__global__ __launch_bounds__(256) void policy_ex_seq_pass_kernel(const ExSeqPassParams p) {
+__global__ __launch_bounds__(256) void policy_seq_pass_kernel(const SeqPassParams p) {
   __shared__ float red[4];
   float st_loss = 0.f, st_pg = 0.f, st_clip = 0.f, st_om = 0.f, st_alt = 0.f;     // thread 0: this workgroup's sequences, in order
   const bool need_x = p.ratio_seq && p.old_lp, need_y = p.is_level >= 2;
+  const bool need_m = p.seq_mean || p.ratio_seq || need_y;                        // something reads the sequence's sum of the mask
   for (int s = blockIdx.x; s < p.S; s += gridDim.x) {      // `s` is the same in every thread of the workgroup
     const int b = p.seq_ptr[s], n = p.seq_ptr[s + 1] - b;
     float sm = 0.f, sx = 0.f, sy = 0.f;
@@ -450,7 +318,7 @@ __global__ __launch_bounds__(256) void policy_ex_seq_pass_kernel(const ExSeqPass
         if (need_x) sx += m * (lpt - p.old_lp[i]);
         if (need_y) sy += m * ((p.old_lp ? p.old_lp[i] : lpt) - p.rollout[i]);
       });
-    } else {
+    } else if (need_m) {                                   // kernel arguments alone decide: the whole grid takes one side
       for (int j = threadIdx.x; j < n; j += 256) {
         const float m = p.mask[b + j];
         sm += m;
@@ -613,80 +481,26 @@ __global__ __launch_bounds__(PL_BLOCK) void preference_row_kernel(const PrefRowP
 
 inline bool finite_f(float v) { return v == v && v - v == 0.f; }
 
-// dta_policy_loss (SEQ = false: no path tables, no c, M and R unused) and dta_policy_loss_seq
-template <bool SEQ>
-int policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
-                const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
-                const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* mask, const float* adv, int32_t adv_per_seq,
-                float* w, float* c, float* dlp, float* dent, float* partial, float* stats, int32_t T, int32_t S, int32_t M, int32_t R,
-                float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg,
-                float scale, void* stream) {
-  if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !mask || !adv || !w || !dlp || !dent || !partial || !stats ||
-      T <= 0 || S <= 0)
-    return DTA_EINVAL;
-  if (SEQ && (!leaf_run_ptr || !run_row0 || !run_depth0 || !seq_leaf || !c || M <= 0 || R <= 0)) return DTA_EINVAL;
-  if (!finite_f(clip_low) || !finite_f(clip_high) || clip_low < 0.f || clip_high < 0.f) return DTA_EINVAL;
-  if (dual_clip != 0.f && !(finite_f(dual_clip) && dual_clip > 1.f)) return DTA_EINVAL;
-  if (kl_estimator < 0 || kl_estimator > 2 || agg < 0 || agg > 1) return DTA_EINVAL;
-  if (!finite_f(kl_coef) || !finite_f(entropy_coef) || !finite_f(scale)) return DTA_EINVAL;
-  if (kl_coef != 0.f && !ref_lp) return DTA_EINVAL;
-  if (!all_aligned16(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, old_lp, ref_lp, mask,
-                     adv, w, c, dlp, dent, partial, stats))
-    return DTA_EALIGN;
-  hipStream_t st_ = static_cast<hipStream_t>(stream);
-  DTA_REFUSE_IF_PRIOR_ERROR();
-  const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS), nsb = SEQ ? (S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS) : 0;
-  PolicyParams p;
-  p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
-  p.old_lp = SEQ ? nullptr : old_lp; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w; p.c = c;
-  p.dlp = dlp; p.dent = dent; p.partial = partial;
-  p.T = T; p.S = S; p.adv_per_seq = adv_per_seq != 0;
-  p.lo = 1.f - clip_low; p.hi = 1.f + clip_high; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
-  if (SEQ) {                                 // the sequence pass leaves w and c; its partial rows stand behind the row pass's
-    SeqPassParams q;
-    static_cast<PathParams&>(q) = {lp, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, T, S, M, R};
-    q.old_lp = old_lp; q.mask = mask; q.adv = adv; q.w = w; q.c = c; q.partial = partial + (size_t)nb * PL_NSTAT;
-    q.adv_per_seq = p.adv_per_seq; q.seq_mean = agg == 0;
-    q.lo = p.lo; q.hi = p.hi; q.dual = dual_clip; q.scale = scale;
-    hipLaunchKernelGGL(policy_seq_pass_kernel, dim3(nsb), dim3(256), 0, st_, q);
-  } else if (agg == 0) {
-    hipLaunchKernelGGL(policy_seq_weight_kernel, dim3(S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS), dim3(256), 0, st_, mask, seq_ptr, S, scale, w);
-  } else {
-    hipLaunchKernelGGL(policy_fill_weight_kernel, dim3(ceil_blocks(S, 256)), dim3(256), 0, st_, S, scale, w);
-  }
-  const dim3 grid(nb), block(PL_BLOCK);
-  if (kl_coef == 0.f) hipLaunchKernelGGL((policy_loss_kernel<-1, SEQ>), grid, block, 0, st_, p);
-  else if (kl_estimator == 0) hipLaunchKernelGGL((policy_loss_kernel<0, SEQ>), grid, block, 0, st_, p);
-  else if (kl_estimator == 1) hipLaunchKernelGGL((policy_loss_kernel<1, SEQ>), grid, block, 0, st_, p);
-  else hipLaunchKernelGGL((policy_loss_kernel<2, SEQ>), grid, block, 0, st_, p);
-  hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb + nsb, stats);
-  return DTA_LAUNCH_STATUS();
-}
-
-// the row pass of dta_policy_loss_ex under a token-level ratio: one instantiation per (KL, surrogate, weight level)
-template <int SUR, int ISL>
-void launch_ex_rows(int kl, dim3 grid, hipStream_t st_, const PolicyExParams& p) {
-  const dim3 block(PL_BLOCK);
-  if (kl < 0) hipLaunchKernelGGL((policy_loss_ex_kernel<-1, SUR, ISL>), grid, block, 0, st_, p);
-  else if (kl == 0) hipLaunchKernelGGL((policy_loss_ex_kernel<0, SUR, ISL>), grid, block, 0, st_, p);
-  else if (kl == 1) hipLaunchKernelGGL((policy_loss_ex_kernel<1, SUR, ISL>), grid, block, 0, st_, p);
-  else hipLaunchKernelGGL((policy_loss_ex_kernel<2, SUR, ISL>), grid, block, 0, st_, p);
-}
+// the row kernels of one (surrogate form, weight level), by KL estimator: none, k1, k2, k3
+typedef void (*PolicyRowKernel)(const PolicyParams);
+template <int FORM, int ISL>
+constexpr PolicyRowKernel policy_row_kernels[4] = {policy_loss_kernel<-1, FORM, ISL>, policy_loss_kernel<0, FORM, ISL>,
+                                                   policy_loss_kernel<1, FORM, ISL>, policy_loss_kernel<2, FORM, ISL>};
 
 }  // namespace
 
-extern "C" int dta_policy_loss_ex_blocks(int32_t T, int32_t S) {
+extern "C" int dta_policy_loss_blocks(int32_t T, int32_t S) {
   return T <= 0 || S <= 0 ? DTA_EINVAL : row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS) + (S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS);
 }
 
-extern "C" int dta_policy_loss_ex(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
-                                  const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
-                                  const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* rollout_lp, const float* mask,
-                                  const float* adv, int32_t adv_per_seq, float* w, float* c, float* omega, float* dlp, float* dent,
-                                  float* partial, float* stats, int32_t T, int32_t S, int32_t M, int32_t R, float clip_low, float clip_high,
-                                  float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg, float scale,
-                                  int32_t ratio_level, int32_t surrogate, int32_t is_level, int32_t is_mode, float is_cap, float is_floor,
-                                  void* stream) {
+extern "C" int dta_policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                               const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                               const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* rollout_lp, const float* mask,
+                               const float* adv, int32_t adv_per_seq, float* w, float* c, float* omega, float* dlp, float* dent,
+                               float* partial, float* stats, int32_t T, int32_t S, int32_t M, int32_t R, float clip_low, float clip_high,
+                               float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg, float scale,
+                               int32_t ratio_level, int32_t surrogate, int32_t is_level, int32_t is_mode, float is_cap, float is_floor,
+                               void* stream) {
   if (!lp || !ent || !depth || !row_seq_lo || !row_seq_hi || !seq_ptr || !mask || !adv || !w || !c || !omega || !dlp || !dent || !partial ||
       !stats || T <= 0 || S <= 0)
     return DTA_EINVAL;
@@ -710,69 +524,28 @@ extern "C" int dta_policy_loss_ex(const float* lp, const float* ent, const int32
   DTA_REFUSE_IF_PRIOR_ERROR();
   const int nb = row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS), nsb = S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS;
   if (is_level == 0) rollout_lp = nullptr;                                  // not read
-  ExSeqPassParams q;
+  SeqPassParams q;
   static_cast<PathParams&>(q) = {lp, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, T, S, walks ? M : 0, walks ? R : 0};
   q.old_lp = old_lp; q.rollout = rollout_lp; q.mask = mask; q.adv = adv; q.w = w; q.c = c; q.omega = omega;
   q.partial = partial + (size_t)nb * PL_NSTAT;                              // its partial rows stand behind the row pass's
   q.adv_per_seq = adv_per_seq != 0; q.seq_mean = agg == 0; q.ratio_seq = ratio_level; q.is_level = is_level; q.is_mode = is_mode;
   q.lo = 1.f - clip_low; q.hi = 1.f + clip_high; q.dual = dual_clip; q.scale = scale; q.is_cap = is_cap; q.is_floor = is_floor;
-  hipLaunchKernelGGL(policy_ex_seq_pass_kernel, dim3(nsb), dim3(256), 0, st_, q);
-  PolicyExParams p;
+  hipLaunchKernelGGL(policy_seq_pass_kernel, dim3(nsb), dim3(256), 0, st_, q);
+  PolicyParams p;
   p.lp = lp; p.ent = ent; p.depth = depth; p.row_lo = row_seq_lo; p.row_hi = row_seq_hi; p.seq_ptr = seq_ptr;
-  p.old_lp = ratio_level ? nullptr : old_lp; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.mask = mask; p.adv = adv; p.w = w; p.c = c;
-  p.dlp = dlp; p.dent = dent; p.partial = partial;
-  p.T = T; p.S = S; p.adv_per_seq = q.adv_per_seq;
-  p.lo = q.lo; p.hi = q.hi; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef;
-  p.rollout = rollout_lp; p.omega = omega; p.is_mode = is_mode; p.is_cap = is_cap; p.is_floor = is_floor;
-  const dim3 grid(nb), block(PL_BLOCK);
-  const int kl = kl_coef == 0.f ? -1 : kl_estimator;
-  if (ratio_level) {                         // c_s holds the weight: the row kernel of dta_policy_loss_seq as it is
-    const PolicyParams base = p;
-    if (kl < 0) hipLaunchKernelGGL((policy_loss_kernel<-1, true>), grid, block, 0, st_, base);
-    else if (kl == 0) hipLaunchKernelGGL((policy_loss_kernel<0, true>), grid, block, 0, st_, base);
-    else if (kl == 1) hipLaunchKernelGGL((policy_loss_kernel<1, true>), grid, block, 0, st_, base);
-    else hipLaunchKernelGGL((policy_loss_kernel<2, true>), grid, block, 0, st_, base);
-  } else {
-    const int isl = is_level >= 2 ? 2 : is_level;
-    if (surrogate == 0) {
-      if (isl == 0) launch_ex_rows<0, 0>(kl, grid, st_, p);
-      else if (isl == 1) launch_ex_rows<0, 1>(kl, grid, st_, p);
-      else launch_ex_rows<0, 2>(kl, grid, st_, p);
-    } else {
-      if (isl == 0) launch_ex_rows<1, 0>(kl, grid, st_, p);
-      else if (isl == 1) launch_ex_rows<1, 1>(kl, grid, st_, p);
-      else launch_ex_rows<1, 2>(kl, grid, st_, p);
-    }
-  }
+  p.old_lp = ratio_level ? nullptr : old_lp; p.ref_lp = kl_coef != 0.f ? ref_lp : nullptr; p.rollout = rollout_lp; p.mask = mask; p.adv = adv;
+  p.w = w; p.c = c; p.omega = omega; p.dlp = dlp; p.dent = dent; p.partial = partial;
+  p.T = T; p.S = S; p.adv_per_seq = q.adv_per_seq; p.is_mode = is_mode;
+  p.lo = q.lo; p.hi = q.hi; p.dual = dual_clip; p.kl_coef = kl_coef; p.ent_coef = entropy_coef; p.is_cap = is_cap; p.is_floor = is_floor;
+  // one instantiation per (KL, surrogate form, weight level); under a sequence-level ratio c_s holds the weight
+  static constexpr const PolicyRowKernel* rows[3][3] = {
+      {policy_row_kernels<PL_CLIPPED, 0>, policy_row_kernels<PL_CLIPPED, 1>, policy_row_kernels<PL_CLIPPED, 2>},
+      {policy_row_kernels<PL_CISPO, 0>, policy_row_kernels<PL_CISPO, 1>, policy_row_kernels<PL_CISPO, 2>},
+      {policy_row_kernels<PL_SEQ_RATIO, 0>, policy_row_kernels<PL_SEQ_RATIO, 0>, policy_row_kernels<PL_SEQ_RATIO, 0>}};
+  const PolicyRowKernel row_kernel = rows[ratio_level ? PL_SEQ_RATIO : surrogate][is_level >= 2 ? 2 : is_level][kl_coef == 0.f ? 0 : kl_estimator + 1];
+  hipLaunchKernelGGL(row_kernel, dim3(nb), dim3(PL_BLOCK), 0, st_, p);
   hipLaunchKernelGGL(policy_loss_reduce_kernel, dim3(1), dim3(256), 0, st_, partial, nb + nsb, stats);
   return DTA_LAUNCH_STATUS();
-}
-
-extern "C" int dta_policy_loss_blocks(int32_t T) { return T <= 0 ? DTA_EINVAL : row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS); }
-
-extern "C" int dta_policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
-                               const int32_t* seq_ptr, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
-                               int32_t adv_per_seq, float* w, float* dlp, float* dent, float* partial, float* stats, int32_t T, int32_t S,
-                               float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef,
-                               int32_t agg, float scale, void* stream) {
-  return policy_loss<false>(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, nullptr, nullptr, nullptr, nullptr, old_lp, ref_lp, mask, adv,
-                            adv_per_seq, w, nullptr, dlp, dent, partial, stats, T, S, 0, 0, clip_low, clip_high, dual_clip, kl_coef,
-                            kl_estimator, entropy_coef, agg, scale, stream);
-}
-
-extern "C" int dta_policy_loss_seq_blocks(int32_t T, int32_t S) {
-  return T <= 0 || S <= 0 ? DTA_EINVAL : row_blocks(T, PL_BLOCK, PL_MAX_BLOCKS) + (S < PL_SEQ_BLOCKS ? S : PL_SEQ_BLOCKS);
-}
-
-extern "C" int dta_policy_loss_seq(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
-                                   const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
-                                   const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
-                                   int32_t adv_per_seq, float* w, float* c, float* dlp, float* dent, float* partial, float* stats, int32_t T,
-                                   int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip, float kl_coef,
-                                   int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, void* stream) {
-  return policy_loss<true>(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, leaf_run_ptr, run_row0, run_depth0, seq_leaf, old_lp, ref_lp, mask,
-                           adv, adv_per_seq, w, c, dlp, dent, partial, stats, T, S, M, R, clip_low, clip_high, dual_clip, kl_coef,
-                           kl_estimator, entropy_coef, agg, scale, stream);
 }
 
 extern "C" int dta_preference_loss_blocks(int32_t T, int32_t S, int32_t P) {

@@ -32,7 +32,7 @@ verl): every token of a sequence is clipped on ONE ratio, the geometric mean of 
 
 with KL, entropy, mask and w_s as above.  The gradient flows through r_s to every masked token of the sequence (GSPO itself, not the
 stop-gradient "GSPO-token" variant):  d loss_s / d lp_t = c_s m_t + the token-level KL gradient, with the per-sequence scalar
-c_s = w_s r_s / max(sum m, 1) * sum_j m_j (-A_j) [pg_j not clipped].  The fused path evaluates it with ``dta_policy_loss_seq``.
+c_s = w_s r_s / max(sum m, 1) * sum_j m_j (-A_j) [pg_j not clipped].  The fused path walks each sequence's root path for it.
 
 Off-policy corrections.  The sampler that produced a rollout (other kernels, another precision, another parallel layout) assigns a
 token another log-prob than this engine does under the same weights.  With ``is_level`` set, the attachment carries
@@ -58,7 +58,7 @@ hi = 1 + clip_high and r the token ratio (on-policy: r = 1):
     pg = -clamp(r, lo, hi).detach() A lp,     d pg / d lp = -clamp(r, lo, hi) A   (never zeroed)
 
 "clipped" counts the tokens with r outside [lo, hi], whatever the sign of A.  It composes with omega, the KL term, the entropy term
-and the mask; it does not go with ``ratio="sequence"`` or a dual clip.  The fused path evaluates both with ``dta_policy_loss_ex`` and
+and the mask; it does not go with ``ratio="sequence"`` or a dual clip.  With either of the two the fused path
 reports two more statistics (``OFFPOLICY_STATS``): sum m omega and the masked tokens whose weight was truncated or dropped.
 
 ``PreferenceLoss`` (DPO / cDPO / SimPO, SLiC, IPO) couples a chosen and a rejected sequence and is therefore no per-sequence callback:
@@ -76,13 +76,13 @@ __all__ = ["PolicyLoss", "KL_ESTIMATORS", "AGGREGATIONS", "RATIOS", "STATS", "Pr
 
 KL_ESTIMATORS = ("k1", "k2", "k3")           # position = the estimator id of dta_policy_loss
 AGGREGATIONS = ("seq_mean", "token_sum")     # position = the aggregation id of dta_policy_loss
-RATIOS = ("token", "sequence")               # importance ratio per prediction (PPO / GRPO) or one per sequence (GSPO: dta_policy_loss_seq)
+RATIOS = ("token", "sequence")               # importance ratio per prediction (PPO / GRPO) or one per sequence (GSPO); position = the ratio_level id of dta_policy_loss
 # entries of the statistics vector of the fused path (engine.loss_stats), in order
 STATS = ("loss", "sum_pg", "sum_kl", "sum_entropy", "clipped_tokens", "masked_tokens")
-SURROGATES = ("ppo", "cispo")                # position = the surrogate id of dta_policy_loss_ex
-IS_LEVELS = ("token", "sequence", "sequence_mean")   # rollout importance weight; position + 1 = the is_level id of dta_policy_loss_ex (0: none)
-IS_MODES = ("truncate", "mask")              # position = the is_mode id of dta_policy_loss_ex
-# entries of the statistics vector under an off-policy correction or CISPO (dta_policy_loss_ex), in order
+SURROGATES = ("ppo", "cispo")                # position = the surrogate id of dta_policy_loss
+IS_LEVELS = ("token", "sequence", "sequence_mean")   # rollout importance weight; position + 1 = the is_level id of dta_policy_loss (0: none)
+IS_MODES = ("truncate", "mask")              # position = the is_mode id of dta_policy_loss
+# entries of the statistics vector under an off-policy correction or CISPO, in order: all the kernel writes
 OFFPOLICY_STATS = STATS + ("sum_is_weight", "is_clipped_tokens")
 PREFERENCE_KINDS = ("sigmoid", "hinge", "ipo")   # position = the kind id of dta_preference_loss
 # entries of the statistics vector of a PreferenceLoss (engine.loss_stats), in order
@@ -155,7 +155,7 @@ class PolicyLoss:
 
     @property
     def extended(self) -> bool:
-        """an off-policy correction or CISPO is configured: the fused path is dta_policy_loss_ex and reports OFFPOLICY_STATS"""
+        """an off-policy correction or CISPO is configured: the fused path reports OFFPOLICY_STATS"""
         return self.is_level is not None or self.surrogate != "ppo"
 
     def __repr__(self):

@@ -1758,51 +1758,15 @@ def policy_walks_paths(loss, on_policy: bool) -> bool:
 def policy_loss(loss, lp: torch.Tensor, ent: torch.Tensor, depth: torch.Tensor, row_seq_lo: torch.Tensor, row_seq_hi: torch.Tensor,
                 seq_ptr: torch.Tensor, old: Optional[torch.Tensor], ref: Optional[torch.Tensor], mask: torch.Tensor, adv: torch.Tensor,
                 adv_per_seq: bool, path_tables=None, rollout: Optional[torch.Tensor] = None, workspaces: Optional[dict] = None):
-    """The objective `loss` (losses.PolicyLoss) over T packed rows in one C-ABI call: returns (dlp [T], dent [T], stats [8], w [S]), fp32.
-    lp / ent: the fp32 row statistics of packed_logprob_entropy (no graph is followed: the caller back-propagates dlp / dent);
-    row_seq_lo / row_seq_hi / seq_ptr: packing.policy_row_tables; old / ref / mask / adv: policy_token_inputs.
-    stats = {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m, 0, 0} (losses.STATS); w: the per-sequence weights.
-    loss.ratio == "sequence" (dta_policy_loss_seq) needs path_tables = (leaf_run_ptr, run_row0, run_depth0, seq_leaf), the int32 device
-    tables of packing.policy_path_tables; "token" (dta_policy_loss) takes none.
-    An off-policy correction (loss.is_level) or CISPO goes to dta_policy_loss_ex: rollout = policy_rollout_input(...) is needed exactly
-    when loss.is_level is not None, path_tables exactly when policy_walks_paths(loss, old is None), the last two statistics are those
-    of losses.OFFPOLICY_STATS, and a dict handed in as `workspaces` receives the per-sequence vectors c and omega."""
-    if loss.extended:
-        return _policy_loss_ex(loss, lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, adv_per_seq, path_tables, rollout,
-                               workspaces)
-    from .losses import AGGREGATIONS, KL_ESTIMATORS
-    seq_level = loss.ratio == "sequence"
-    if seq_level != (path_tables is not None):
-        raise ValueError(f"ratio = {loss.ratio!r}: path_tables (packing.policy_path_tables) go with the sequence-level ratio, and only with it")
-    T, S = int(lp.shape[0]), int(seq_ptr.shape[0]) - 1
-    lp, ent, old, ref, mask, adv = map(_f32_aligned, (lp, ent, old, ref, mask, adv))
-    path = list(path_tables) if seq_level else []
-    _require_cuda(lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, *path)
-    N = int(mask.shape[0])
-    assert ent.shape[0] == T and depth.shape[0] == T and row_seq_lo.shape[0] == T and row_seq_hi.shape[0] == T
-    assert all(t.dtype == torch.int32 for t in (depth, row_seq_lo, row_seq_hi, seq_ptr, *path))
-    assert adv.shape[0] == (S if adv_per_seq else N) and (old is None or old.shape[0] == N) and (ref is None or ref.shape[0] == N)
-    nb = lib().dta_policy_loss_seq_blocks(T, S) if seq_level else lib().dta_policy_loss_blocks(T)
-    buf, v = _carve_f32(lp.device, dlp=T, dent=T, w=S, partial=8 * nb, stats=8, c=S if seq_level else 0)
-    # the two entries differ by the path tables (with their sizes M, R) and the per-sequence scalar c of the sequence-level ratio
-    c, sizes = [], []
-    if seq_level:
-        run_ptr, run_row0, run_depth0, seq_leaf = path
-        assert seq_leaf.shape[0] == S and run_depth0.shape[0] == run_row0.shape[0]
-        c, sizes = [ptr(v["c"])], [int(run_ptr.shape[0]) - 1, int(run_row0.shape[0])]
-    tensors = (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, *path, old, ref, mask, adv)
-    _launch("dta_policy_loss_seq" if seq_level else "dta_policy_loss", (*tensors, buf),
-            *map(ptr, tensors), int(bool(adv_per_seq)), ptr(v["w"]), *c, ptr(v["dlp"]), ptr(v["dent"]), ptr(v["partial"]), ptr(v["stats"]),
-            T, S, *sizes,
-            float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
-            KL_ESTIMATORS.index(loss.kl_estimator), float(loss.entropy_coef), AGGREGATIONS.index(loss.agg), float(loss.scale),
-            nbytes=4 * (4 * T + ((5 + 2 * (old is not None) if seq_level else 3 + (old is not None)) + (ref is not None)) * N))
-    return v["dlp"], v["dent"], v["stats"], v["w"]
-
-
-def _policy_loss_ex(loss, lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, ref, mask, adv, adv_per_seq, path_tables, rollout, workspaces):
-    """policy_loss for an objective with an off-policy correction or CISPO: dta_policy_loss_ex"""
-    from .losses import AGGREGATIONS, IS_LEVELS, IS_MODES, KL_ESTIMATORS, RATIOS, SURROGATES
+    """The objective `loss` (losses.PolicyLoss) over T packed rows in one C-ABI call (dta_policy_loss): returns (dlp [T], dent [T], stats,
+    w [S]), fp32.  lp / ent: the fp32 row statistics of packed_logprob_entropy (no graph is followed: the caller back-propagates dlp /
+    dent); row_seq_lo / row_seq_hi / seq_ptr: packing.policy_row_tables; old / ref / mask / adv: policy_token_inputs.
+    stats = {loss, sum m pg, sum m kl, sum m entropy, clipped tokens, sum m} (losses.STATS), with the two entries more of
+    losses.OFFPOLICY_STATS under an off-policy correction or CISPO (loss.extended); w: the per-sequence weights.
+    path_tables = (leaf_run_ptr, run_row0, run_depth0, seq_leaf), the int32 device tables of packing.policy_path_tables, are needed
+    exactly when policy_walks_paths(loss, old is None), rollout = policy_rollout_input(...) exactly when loss.is_level is not None.
+    A dict handed in as `workspaces` receives the per-sequence vectors c and omega."""
+    from .losses import AGGREGATIONS, IS_LEVELS, IS_MODES, KL_ESTIMATORS, OFFPOLICY_STATS, RATIOS, STATS, SURROGATES
     walks = policy_walks_paths(loss, old is None)
     if walks != (path_tables is not None):
         raise ValueError(f"ratio = {loss.ratio!r}, is_level = {loss.is_level!r}, old_logprobs {'absent' if old is None else 'given'}: "
@@ -1822,10 +1786,10 @@ def _policy_loss_ex(loss, lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, 
         run_ptr, run_row0, run_depth0, seq_leaf = path
         assert seq_leaf.shape[0] == S and run_depth0.shape[0] == run_row0.shape[0]
         M, R = int(run_ptr.shape[0]) - 1, int(run_row0.shape[0])
-    nb = lib().dta_policy_loss_ex_blocks(T, S)
+    nb = lib().dta_policy_loss_blocks(T, S)
     buf, v = _carve_f32(lp.device, dlp=T, dent=T, w=S, partial=8 * nb, stats=8, c=S, omega=S)
     tensors = (lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, *path, old, ref, rollout, mask, adv)
-    _launch("dta_policy_loss_ex", (*tensors, buf),
+    _launch("dta_policy_loss", (*tensors, buf),
             *map(ptr, tensors), int(bool(adv_per_seq)), *(ptr(v[k]) for k in ("w", "c", "omega", "dlp", "dent", "partial", "stats")),
             T, S, M, R,
             float(loss.clip_low), float(loss.clip_high), 0.0 if loss.dual_clip is None else float(loss.dual_clip), float(loss.kl_coef),
@@ -1835,7 +1799,7 @@ def _policy_loss_ex(loss, lp, ent, depth, row_seq_lo, row_seq_hi, seq_ptr, old, 
             nbytes=4 * (4 * T + (4 + (old is not None) + (ref is not None) + 2 * (rollout is not None)) * N))
     if workspaces is not None:
         workspaces.update(c=v["c"], omega=v["omega"])
-    return v["dlp"], v["dent"], v["stats"], v["w"]
+    return v["dlp"], v["dent"], v["stats"][:len(OFFPOLICY_STATS if loss.extended else STATS)], v["w"]
 
 
 # --------------------------------------------------------------------------------------------------

@@ -431,7 +431,7 @@ def policy_row_tables(plan: SegmentPlan, attach_lists):
 
 
 def policy_path_tables(plan: SegmentPlan, attach_lists):
-    """Tables of the sequence-level objective (dta_policy_loss_seq), the row <- sequence direction policy_row_tables does not need, from
+    """Tables of what follows root paths in dta_policy_loss (a sequence-level ratio or rollout weight), the row <- sequence direction policy_row_tables does not need, from
     the plan and the attach lists alone (host, no GPU): (leaf_run_ptr int32 [M+1], run_row0 int32 [R], run_depth0 int32 [R],
     seq_leaf int32 [S]).  The root path of leaf i is a short list of contiguous packed-row runs - plan.path_runs[i], then the leaf's own
     segment when it is not empty: run k of leaf i, leaf_run_ptr[i] <= k < leaf_run_ptr[i+1], starts at packed row run_row0[k] with the

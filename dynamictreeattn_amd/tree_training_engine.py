@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops, packing
-from .losses import OFFPOLICY_STATS, PREFERENCE_STATS, STATS as LOSS_STATS, PolicyLoss, PreferenceLoss, attachments_by_sequence
+from .losses import PREFERENCE_STATS, PolicyLoss, PreferenceLoss, attachments_by_sequence
 from .model import (_head_dim, ensure_supported, final_softcap_of, head_weight, is_cohere, is_gemma2, is_glm4, is_longrope, is_moe_layer, logit_scale_of, moe_geometry,
                     longrope_boundary, packed_hidden_states)
 from .trie import pop_block_starts
@@ -530,8 +530,7 @@ class TreeTrainingEngine:
         dlp, dent, stats, _ = ops.policy_loss(loss, lp, ent, packed.depth, row_lo_d, row_hi_d, seq_ptr_d,
                                               *ops.policy_token_inputs(loss, att, seq_ptr, dev), tuple(rest) or None,
                                               ops.policy_rollout_input(loss, att, seq_ptr, dev))
-        n_stats = len(OFFPOLICY_STATS) if loss.extended else len(LOSS_STATS)
-        return [(lp, dlp)] + ([(ent, dent)] if loss.entropy_coef != 0 else []), stats[:n_stats]
+        return [(lp, dlp)] + ([(ent, dent)] if loss.entropy_coef != 0 else []), stats
 
     def _backward_stack_two_pass(self, model, token_trie, loss, block_rows: int) -> float:
         """A preference objective on the block-wise walk, in two passes: the sequence log-probs from a no-grad forward, the per-sequence

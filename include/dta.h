@@ -413,126 +413,96 @@ int dta_lora_wgrad(const void* l, int64_t ldl, const void* x, int64_t ldx, float
                    int32_t T, int32_t R, int32_t K, int32_t dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Policy objective over the packed trie (HBM-bound; fp32 throughout): the clipped PPO / GRPO surrogate with an optional dual clip, a KL
- * penalty to a reference policy, an entropy bonus and a loss mask, evaluated per packed ROW.  Stands where the reference calls the
- * user's loss_fn once per sequence on gathered slices and sums the per-sequence gradients back (tree_training_engine.py:379-440).
+ * Policy objective over the packed trie (losses.PolicyLoss; HBM-bound; fp32 throughout): the clipped PPO / GRPO surrogate with an
+ * optional dual clip, a KL penalty to a reference policy, an entropy bonus and a loss mask, evaluated per packed ROW.  Stands where the
+ * reference calls the user's loss_fn once per sequence on gathered slices and sums the per-sequence gradients back
+ * (tree_training_engine.py:379-440).  Three options of this one objective: the level of the importance ratio (ratio_level), the form of
+ * the surrogate (surrogate) and a rollout importance weight on it (is_level, is_mode, is_cap, is_floor).
  *
  * Sequences are numbered in callback order: leaf by leaf in packed order, within a leaf in attach-list order.  Sequence s has
- * n_s = len_s - 1 predictions; its per-token inputs are elements [seq_ptr[s], seq_ptr[s+1]) of old_lp / ref_lp / mask / adv (fp32,
- * N = seq_ptr[S] elements each; element j belongs to the prediction of token j + 1).  adv_per_seq != 0: adv is [S], one value per
- * sequence.  old_lp NULL: on-policy (ratio 1, gradient as if old_lp == lp).  ref_lp may be NULL when kl_coef == 0 (it is not read then).
+ * n_s = len_s - 1 predictions; its per-token inputs are elements [seq_ptr[s], seq_ptr[s+1]) of old_lp / ref_lp / rollout_lp / mask / adv
+ * (fp32, N = seq_ptr[S] elements each; element j belongs to the prediction of token j + 1).  adv_per_seq != 0: adv is [S], one value per
+ * sequence.  old_lp NULL: on-policy (ratio 1, gradient as if old_lp == lp).  ref_lp may be NULL when kl_coef == 0, rollout_lp (the
+ * sampler's log-prob of each token) when is_level == 0: they are not read then.
  *
  * Row t (depth[t] = d, log-prob lp[t] of its token given its parent, entropy ent[t] of the distribution at it) lies on the path of the
  * sequences s in [row_seq_lo[t], row_seq_hi[t]) with n_s >= d - one contiguous range, because the sequences through a subtree are
  * contiguous in callback order; an empty range (filler rows) is legal.  For each such s the row owns
- *   the log-prob term (s, j = d - 1) when d >= 1:   x = lp[t] - old_lp[.],  r = exp(x),  A = adv,  m = mask
- *       pg = max(-r A, -clamp(r, 1 - clip_low, 1 + clip_high) A);  dual_clip = c > 1 and A < 0:  pg = min(pg, -c A)
+ *   the log-prob term (s, j = d - 1) when d >= 1:   x = lp[t] - old_lp[.],  r = exp(x),  A = adv,  m = mask,  lo = 1 - clip_low,
+ *                                                   hi = 1 + clip_high
+ *       pg = max(-r A, -clamp(r, lo, hi) A);  dual_clip = c > 1 and A < 0:  pg = min(pg, -c A)                   (surrogate 0, "ppo")
  *       dd = ref_lp[.] - lp[t];  kl = -dd (estimator 0, "k1") | dd^2 / 2 (1, "k2") | exp(dd) - dd - 1 (2, "k3")
- *       loss += w_s m (pg + kl_coef kl);   dlp[t] += w_s m (dpg + kl_coef dkl),  dpg = -r A where -r A is the active branch
- *       (ties included), 0 where the clamp or the dual clip is;  dkl = 1 | -dd | 1 - exp(dd)
+ *       loss += w_s m (omega pg + kl_coef kl);   dlp[t] += w_s m (omega dpg + kl_coef dkl),  dpg = -r A where -r A is the active branch
+ *       (ties included), 0 where the clamp or the dual clip is;  dkl = 1 | -dd | 1 - exp(dd);  omega: the rollout weight, below
  *   the entropy term (s, j = d) when d < n_s:       loss -= w_s m entropy_coef ent[t];   dent[t] -= w_s m entropy_coef
- * w_s = scale / max(sum_j m, 1) (agg 0, "seq_mean") or scale (agg 1, "token_sum"); the entry writes it to w[S] first (a workspace the
- * caller may read afterwards).  exp is the accurate expf.  Every (s, j) is owned by exactly one row in each role: no scatter, no
- * atomics; dlp[T] and dent[T] are written for EVERY row (0 where nothing contributes), and identical calls give identical bits.
- * stats[8] = {loss, sum m pg, sum m kl, sum m ent, sum m [clamp or dual clip active], sum m, 0, 0}: per-workgroup partials in
- * partial[dta_policy_loss_blocks(T)][8], then one workgroup sums them in a fixed order.  Three launches on `stream` (weights, rows,
- * reduction); the launch geometry depends on T and S alone.
- * Refusals come in this order: DTA_EINVAL (a null pointer other than old_lp / ref_lp, T <= 0, S <= 0, a negative or non-finite clip,
- * dual_clip neither 0 (= none) nor a finite value > 1, kl_estimator not 0..2, agg not 0 / 1, a non-finite coefficient or scale,
- * kl_coef != 0 with ref_lp NULL), DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR. */
-int dta_policy_loss_blocks(int32_t T);   /* rows of the partial workspace [blocks, 8] (float); T <= 0: DTA_EINVAL */
-int dta_policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
-                    const int32_t* seq_ptr, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
-                    int32_t adv_per_seq, float* w, float* dlp, float* dent, float* partial, float* stats, int32_t T, int32_t S,
-                    float clip_low, float clip_high, float dual_clip, float kl_coef, int32_t kl_estimator, float entropy_coef,
-                    int32_t agg, float scale, void* stream);
-
-/* The same objective with ONE importance ratio per sequence (GSPO; losses.PolicyLoss(ratio="sequence")).  Everything not said here is
- * as for dta_policy_loss: the numbering of the sequences, the per-token inputs, the row tables, w_s, the KL and entropy terms, dlp / dent
- * written for every row, no atomics, identical bits for identical calls.  With n^ = max(sum_j m_j, 1) over the predictions of s
+ * w_s = scale / n^, n^ = max(sum_j m_j, 1) (agg 0, "seq_mean") or scale (agg 1, "token_sum").  exp is the accurate expf.  Every (s, j) is
+ * owned by exactly one row in each role: no scatter, no atomics; dlp[T] and dent[T] are written for EVERY row (0 where nothing
+ * contributes), and identical calls give identical bits.
+ *
+ * surrogate 1 "cispo", on the token ratio r:
+ *       pg = -clamp(r, lo, hi) A lp[t],   dpg = -clamp(r, lo, hi) A  (the clamp is a constant of the gradient: dpg is never zeroed);
+ *       "clipped" counts the masked tokens with r outside [lo, hi], whatever the sign of A.
+ * ratio_level 1 "sequence" (GSPO; ratio_level 0 "token" is the above): ONE importance ratio per sequence,
  *       r_s  = exp( sum_j m_j (lp[row(s, j)] - old_lp[.]) / n^ )        (old_lp NULL: r_s = 1; length-normalised under agg 1 too)
- *       pg_j = max(-r_s A_j, -clamp(r_s, 1 - clip_low, 1 + clip_high) A_j);  dual_clip = c > 1 and A_j < 0:  pg_j = min(pg_j, -c A_j)
- *       loss += w_s m_j (pg_j + kl_coef kl_j);    d loss / d lp[row(s, t)] = c_s m_t + w_s m_t kl_coef dkl_t,
- *       c_s  = w_s r_s / n^ * sum_j m_j (-A_j) [-r_s A_j is the active branch of pg_j (ties included)]
+ *       pg_j = max(-r_s A_j, -clamp(r_s, lo, hi) A_j);  dual_clip = c > 1 and A_j < 0:  pg_j = min(pg_j, -c A_j)
+ *       loss += w_s m_j (omega_j pg_j + kl_coef kl_j);    d loss / d lp[row(s, t)] = c_s m_t + w_s m_t kl_coef dkl_t,
+ *       c_s  = w_s r_s / n^ * sum_j m_j omega_j (-A_j) [-r_s A_j is the active branch of pg_j (ties included)]
  * (the gradient flows through r_s to every masked token of the sequence).  row(s, j), the packed row of depth j + 1 on the root path
  * of s, comes from a path table over the M leaves: the path of leaf i is runs [leaf_run_ptr[i], leaf_run_ptr[i+1]) of contiguous packed
  * rows, root first; run k starts at row run_row0[k] with depth run_depth0[k] and ends where the leaf's next run starts (the last run:
  * at the leaf's end, which no sequence of the leaf passes); seq_leaf[s] is the leaf of sequence s.  R = leaf_run_ptr[M] runs in all.
  * Table entries that point outside [0, M), [0, R) or [0, T) are clamped or skipped, never followed.
- * Three launches on `stream`; their geometry depends on T and S alone:
- *   sequence pass  one workgroup per sequence (grid-strided past 2048): the runs of its path with the threads strided over each run's
- *                  rows for sum m and sum m x, the accurate expf for r_s, w[s]; one more sweep of adv / mask for c[s] (a workspace the
- *                  caller may read afterwards) and the sequence's share of loss, sum m pg and the clipped tokens;
- *   row pass       the row kernel of dta_policy_loss with c_s m in place of the token's own surrogate gradient;
- *   reduction      both passes' partials, partial[dta_policy_loss_seq_blocks(T, S)][8], summed in a fixed order into stats[8] (same
- *                  entries as dta_policy_loss; "clipped" counts the masked tokens whose branch is the clamp or the dual clip).
- * Refusals come in this order: DTA_EINVAL (a null pointer other than old_lp / ref_lp, T, S, M or R <= 0, then the hyper-parameters
- * exactly as dta_policy_loss refuses them), DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR. */
-int dta_policy_loss_seq_blocks(int32_t T, int32_t S);   /* rows of the partial workspace [blocks, 8] (float); T <= 0 or S <= 0: DTA_EINVAL */
-int dta_policy_loss_seq(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
-                        const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
-                        const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* mask, const float* adv,
-                        int32_t adv_per_seq, float* w, float* c, float* dlp, float* dent, float* partial, float* stats, int32_t T,
-                        int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip, float kl_coef,
-                        int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, void* stream);
-
-/* The same objective with an off-policy correction - a rollout importance weight on the surrogate - and / or the CISPO surrogate
- * (losses.PolicyLoss(is_level=..., surrogate="cispo")).  Everything not said here is as for dta_policy_loss (ratio_level 0, "token") and
- * dta_policy_loss_seq (ratio_level 1, "sequence"): the numbering of the sequences, the per-token inputs, the row and path tables, w_s,
- * r, r_s, the KL and entropy terms, dlp / dent written for every row, no atomics, identical bits for identical calls.
- * rollout_lp [N] holds the sampler's log-prob of each token (NULL allowed when is_level == 0: not read).  Per prediction j of s,
+ * The rollout importance weight omega (an off-policy correction), per prediction j of s:
  *       y_j = old_lp[.] - rollout_lp[.]            old_lp NULL: y_j = lp[row(s, j)] - rollout_lp[.]; y carries no gradient either way
+ *       is_level 0:                  omega = 1
  *       is_level 1 "token":          rho_j = exp(y_j)
  *       is_level 2 "sequence":       rho_s = exp(sum_j m_j y_j)
- *       is_level 3 "sequence_mean":  rho_s = exp(sum_j m_j y_j / n^),   n^ = max(sum_j m_j, 1)
+ *       is_level 3 "sequence_mean":  rho_s = exp(sum_j m_j y_j / n^)
  *       is_mode 0 "truncate":  omega = min(rho, is_cap);     is_mode 1 "mask":  omega = rho if is_floor <= rho <= is_cap, else 0
- *       is_level 0: omega = 1
- *       loss += w_s m_j (omega pg_j + kl_coef kl_j);   dlp[t] += w_s m_j (omega dpg_j + kl_coef dkl_j)      (ratio_level 0)
- *       c_s = w_s r_s / n^ * sum_j m_j omega_j (-A_j) [-r_s A_j is the active branch of pg_j]                (ratio_level 1)
  * omega multiplies the surrogate alone, never the KL or the entropy term, and is a constant of the gradient.  omega is formed by
  * comparisons on rho, never by arithmetic on it: an exponent above 88.7, where expf gives +inf, yields is_cap under "truncate" and 0
  * under "mask", one far below zero yields 0 (or what is_floor says of 0); no finite input gives NaN.
- * surrogate 1 "cispo", with lo = 1 - clip_low, hi = 1 + clip_high and the token ratio r (old_lp NULL: r = 1):
- *       pg = -clamp(r, lo, hi) A lp[t],   dpg = -clamp(r, lo, hi) A  (the clamp is a constant of the gradient: dpg is never zeroed);
- *       "clipped" counts the masked tokens with r outside [lo, hi], whatever the sign of A.
  * The path tables may be NULL, with M = R = 0, when nothing walks a path: ratio_level 0 with is_level 0 or 1, and ratio_level 0 with
  * is_level 2 or 3 when old_lp is given (y is then a sweep over the per-token inputs alone).  They are required for ratio_level 1 and for
- * is_level 2 or 3 with old_lp NULL.  w[S], c[S] and omega[S] are workspaces the caller may read afterwards: omega[s] is the sequence's
- * weight (1 for is_level 0 and 1), c[s] is 0 for ratio_level 0.
+ * is_level 2 or 3 with old_lp NULL.  w[S], c[S] and omega[S] are workspaces the caller may read afterwards: w[s] = w_s, omega[s] is the
+ * sequence's weight (1 for is_level 0 and 1), c[s] is 0 for ratio_level 0.
  * Three launches on `stream`; their geometry depends on T and S alone:
  *   sequence pass  one workgroup per sequence (grid-strided past 2048).  It owns w[s], omega[s] and c[s].  It walks the path only for
  *                  what reads a row's lp: sum m x of r_s (ratio_level 1 with old_lp), sum m y with old_lp NULL, and the c_s sweep when
- *                  that forms a per-token weight with old_lp NULL; everything else is a sweep of the per-token inputs.  Under
- *                  ratio_level 1 it owns the surrogate's share of loss, sum m pg' and the clipped tokens; under ratio_level 1 or
- *                  is_level 2 / 3 it owns sum m omega and sum m [omega != rho].  With ratio_level 0 it stands where dta_policy_loss
- *                  launches its weight kernel;
- *   row pass       ratio_level 0: the row sweep of dta_policy_loss with this entry's own term - r, the surrogate form, and the weight: a
- *                  per-token weight is formed here (y from old_lp, or from the row's lp; the accurate expf; truncate or mask), a
- *                  sequence's weight is read from omega[s]; it owns every statistic the sequence pass does not.  ratio_level 1: the row
- *                  kernel of dta_policy_loss_seq as it is (c_s holds the weight);
- *   reduction      both passes' partials, partial[dta_policy_loss_ex_blocks(T, S)][8], summed in a fixed order into
+ *                  that forms a per-token weight with old_lp NULL; everything else is a sweep of the per-token inputs, and the mask is
+ *                  not swept at all where nothing reads its sum (agg 1 with ratio_level 0 and is_level 0 or 1).  Under ratio_level 1 it
+ *                  owns the surrogate's share of loss, sum m pg' and the clipped tokens; under ratio_level 1 or is_level 2 / 3 it owns
+ *                  sum m omega and sum m [omega != rho];
+ *   row pass       one thread per row, a wave for a row with more than 16 sequences: the terms above.  ratio_level 0: r, the surrogate
+ *                  form and the weight - a per-token weight is formed here (y from old_lp, or from the row's lp; truncate or mask), a
+ *                  sequence's weight is read from omega[s].  ratio_level 1: c_s m in place of the token's own surrogate gradient (c_s
+ *                  holds the weight).  It owns every statistic the sequence pass does not;
+ *   reduction      both passes' partials, partial[dta_policy_loss_blocks(T, S)][8], summed in a fixed order into
  *                  stats[8] = {loss, sum m pg' (pg' = omega pg), sum m kl, sum m ent, clipped, sum m, sum m omega, sum m [omega != rho]}
- *                  (losses.OFFPOLICY_STATS; is_level 0: sum m omega = sum m and the last entry is 0).  The three counts are exact.
- * Refusals come in this order: DTA_EINVAL (a null pointer other than old_lp / ref_lp / rollout_lp / the path tables, T <= 0, S <= 0, then
- * the hyper-parameters exactly as dta_policy_loss refuses them, then ratio_level not 0 / 1, surrogate not 0 / 1, is_level not 0..3,
- * is_mode not 0 / 1, is_cap non-finite or <= 0, is_floor non-finite, negative or not below is_cap, is_floor != 0 with is_mode 0,
- * surrogate 1 with ratio_level 1 or with a dual clip, is_level != 0 with rollout_lp NULL, a path table NULL or M or R <= 0 where a path
- * is walked), DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR. */
-int dta_policy_loss_ex_blocks(int32_t T, int32_t S);   /* rows of the partial workspace [blocks, 8] (float); T <= 0 or S <= 0: DTA_EINVAL */
-int dta_policy_loss_ex(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
-                       const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
-                       const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* rollout_lp, const float* mask,
-                       const float* adv, int32_t adv_per_seq, float* w, float* c, float* omega, float* dlp, float* dent, float* partial,
-                       float* stats, int32_t T, int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip,
-                       float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, int32_t ratio_level,
-                       int32_t surrogate, int32_t is_level, int32_t is_mode, float is_cap, float is_floor, void* stream);
+ *                  (losses.OFFPOLICY_STATS), always all eight: is_level 0 gives stats[6] = sum m and stats[7] = 0.  "clipped" counts
+ *                  the masked tokens whose branch is the clamp or the dual clip.  The three counts are exact.
+ * Refusals come in this order: DTA_EINVAL (a null pointer other than old_lp / ref_lp / rollout_lp / the path tables, T <= 0, S <= 0, a
+ * negative or non-finite clip, dual_clip neither 0 (= none) nor a finite value > 1, kl_estimator not 0..2, agg not 0 / 1, a non-finite
+ * coefficient or scale, kl_coef != 0 with ref_lp NULL, ratio_level not 0 / 1, surrogate not 0 / 1, is_level not 0..3, is_mode not 0 / 1,
+ * is_cap non-finite or <= 0, is_floor non-finite, negative or not below is_cap, is_floor != 0 with is_mode 0, surrogate 1 with
+ * ratio_level 1 or with a dual clip, is_level != 0 with rollout_lp NULL, a path table NULL or M or R <= 0 where a path is walked),
+ * DTA_EALIGN (a pointer off 16 bytes), DTA_EPRIOR.  The path tables and their sizes come last among the DTA_EINVAL checks: a call with
+ * a missing path table or M <= 0 AND a bad hyper-parameter is refused for the hyper-parameter (the status is DTA_EINVAL either way). */
+int dta_policy_loss_blocks(int32_t T, int32_t S);   /* rows of the partial workspace [blocks, 8] (float); T <= 0 or S <= 0: DTA_EINVAL */
+int dta_policy_loss(const float* lp, const float* ent, const int32_t* depth, const int32_t* row_seq_lo, const int32_t* row_seq_hi,
+                    const int32_t* seq_ptr, const int32_t* leaf_run_ptr, const int32_t* run_row0, const int32_t* run_depth0,
+                    const int32_t* seq_leaf, const float* old_lp, const float* ref_lp, const float* rollout_lp, const float* mask,
+                    const float* adv, int32_t adv_per_seq, float* w, float* c, float* omega, float* dlp, float* dent, float* partial,
+                    float* stats, int32_t T, int32_t S, int32_t M, int32_t R, float clip_low, float clip_high, float dual_clip,
+                    float kl_coef, int32_t kl_estimator, float entropy_coef, int32_t agg, float scale, int32_t ratio_level,
+                    int32_t surrogate, int32_t is_level, int32_t is_mode, float is_cap, float is_floor, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Preference objectives over the packed trie (losses.PreferenceLoss; HBM-bound, fp32 throughout): DPO / cDPO / SimPO (kind 0,
  * "sigmoid"), SLiC (1, "hinge") and IPO (2, "ipo") over P (chosen, rejected) pairs of the trie's sequences, with an optional NLL term on
  * the chosen member.  A pair couples two sequences, so no per-sequence callback can state it; here the pairs are one stage between a
  * sequence pass and a row pass.  The numbering of the sequences, seq_ptr, mask, the row tables (depth, row_seq_lo, row_seq_hi) and the
- * path tables (leaf_run_ptr, run_row0, run_depth0, seq_leaf over M leaves and R runs) are those of dta_policy_loss_seq; table entries
+ * path tables (leaf_run_ptr, run_row0, run_depth0, seq_leaf over M leaves and R runs) are those of dta_policy_loss; table entries
  * that point outside [0, M), [0, R) or [0, T) are clamped or skipped, never followed.  mask [N] is required (all ones: no mask).
  *
  * The reference policy comes in exactly one of two forms: ref_lp [N], per-token reference log-probs (summed here under the mask), or

@@ -1,6 +1,6 @@
 """GPU, end to end: TreeTrainingEngine.backward with a losses.PolicyLoss that carries an off-policy correction or the CISPO surrogate,
 on the tiny model and the trie of test_gpu_engine_seq_policy_loss.py (folded sequences: a proper prefix ending exactly at a fork, a
-duplicate; filler rows), per-token masks, a KL term and an entropy bonus - (a) the object itself (the fused path, dta_policy_loss_ex),
+duplicate; filler rows), per-token masks, a KL term and an entropy bonus - (a) the object itself (the fused path, dta_policy_loss),
 (b) the same object behind a lambda (the callback path): the loss and every parameter gradient agree within that file's tolerances
 for the dtype.  The statistics have the eight entries of losses.OFFPOLICY_STATS under a correction or CISPO and the six of losses.STATS
 with the defaults.  rollout_logprobs sit a few hundredths of a nat off old_logprobs, plus a drift per sequence and a handful of outliers

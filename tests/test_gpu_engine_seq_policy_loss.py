@@ -1,6 +1,6 @@
 """GPU, end to end: TreeTrainingEngine.backward with a losses.PolicyLoss(ratio="sequence") - GSPO - on a tiny model, in bf16 and in
 fp32, on the trie of test_gpu_engine_policy_loss.py (folded sequences: a proper prefix ending exactly at a fork, a duplicate; filler
-rows), per-token masks, a KL term and an entropy bonus - (a) the object itself (the fused path, dta_policy_loss_seq), (b) the same object
+rows), per-token masks, a KL term and an entropy bonus - (a) the object itself (the fused path, dta_policy_loss), (b) the same object
 behind a lambda (the callback path), (c) the CPU oracle's restatement of the reference schedule in fp32 with the same object as its
 loss_fn.  Bounds: that file's own - the existing engine tests' for the dtype, and the fused path no worse than the callback path by more
 than 5 % + 1e-6.  old_logprobs are rebuilt so that every sequence's masked mean log-ratio is one of -0.6, -0.05, 0, 0.05, 0.6: the

@@ -1,4 +1,4 @@
-"""GPU: the fused objective with an off-policy correction or CISPO (ops.policy_loss -> dta_policy_loss_ex) against the float64 closed
+"""GPU: the fused objective with an off-policy correction or CISPO (ops.policy_loss -> dta_policy_loss) against the float64 closed
 form of offpolicy_loss_ref64 summed over packed rows: dlp and dent element by element, the per-sequence workspaces w, c and omega and
 the eight statistics entry by entry, within the bounds derived in that module's docstring; on the hand-made tries of
 policy_loss_ref64, for every configuration of offpolicy_loss_ref64.CONFIGS, with and without old_logprobs, with per-token and scalar

@@ -1,4 +1,4 @@
-"""GPU: the fused sequence-level objective (ops.policy_loss -> dta_policy_loss_seq) against the float64 closed form of
+"""GPU: the fused sequence-level objective (ops.policy_loss -> dta_policy_loss, ratio_level 1) against the float64 closed form of
 seq_policy_loss_ref64 summed over packed rows, element by element of dlp and dent and entry by entry of the statistics, within the bound
 derived in that module's docstring; on every hand-made trie of policy_loss_ref64 and the two of seq_policy_loss_ref64 (a sequence of
 more than 256 predictions over three row runs; more sequences than the sequence pass has workgroups).  Filler rows are exactly 0, the
@@ -10,6 +10,7 @@ import torch
 import seq_policy_loss_ref64 as Q
 from dynamictreeattn_amd import ops, packing
 from dynamictreeattn_amd._staging import upload
+from dynamictreeattn_amd.losses import STATS
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -41,7 +42,7 @@ def _check(name, cfg, label, **kw):
         print(f"{label} {what}: worst element {worst}: got {float(got[worst])!r} want {float(want[worst])!r} error {float(err[worst]):.3e} "
               f"bound {float(bound[worst]):.3e}; largest error / bound {float((err / np.maximum(bound, 1e-300)).max()):.3f}")
         assert (err <= bound).all(), (label, what, worst, float(got[worst]), float(want[worst]), float(err[worst]), float(bound[worst]))
-    assert stats[4] == ref["stats"][4] and stats[5] == ref["stats"][5] and (stats[6:] == 0).all()      # the counts are exact
+    assert stats[4] == ref["stats"][4] and stats[5] == ref["stats"][5] and stats.shape == (len(STATS),)  # the counts are exact
     assert (dlp[n_real:] == 0).all() and (dent[n_real:] == 0).all()                                      # filler rows: exactly 0
     if loss.entropy_coef == 0:
         assert (dent == 0).all()
@@ -75,7 +76,7 @@ def test_the_new_tries_repeat_the_loops_they_are_meant_to():
     assert run_ptr[3] - run_ptr[2] == 3 and max(att[2]) - 1 > 256 and plan.T - row0[run_ptr[3] - 1] > 256
     plan, att, _, _ = Q.build("many_seqs")
     S = sum(map(len, att))
-    assert S - (lib().dta_policy_loss_seq_blocks(plan.T, S) - lib().dta_policy_loss_blocks(plan.T)) > 0
+    assert S - (lib().dta_policy_loss_blocks(plan.T, S) - (lib().dta_policy_loss_blocks(plan.T, 1) - 1)) > 0     # sequences past the grid
     _, (plan, att_lens, _, _, lp, _, atts), _ = Q.case("long_path", "ppo", seed=11)
     assert max(float(np.abs(lp[rows[1:]] - a["old_logprobs"]).max()) for rows, a in zip(Q.paths_of(plan, att_lens), atts)) > 2.5
 
