@@ -69,6 +69,8 @@ _PROTOS = {
     # lp depth row_seq_lo row_seq_hi seq_ptr leaf_run_ptr run_row0 run_depth0 seq_leaf pair_c pair_r ref_lp ref_sum mask |
     # nhat u sft g dlp partial stats | T S M R P kind | beta label_smoothing gamma | length_normalize reference_free | sft_coef scale | stream
     "dta_preference_loss": ([_vp] * 21 + [_i32] * 6 + [_f32] * 3 + [_i32, _i32, _f32, _f32, _vp], C.c_int),
+    "dta_quant_blockwise": ([_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp], C.c_int),
+    "dta_dequant_blockwise": ([_vp, _vp, _i64, _i64, _i32, _vp, _i64, _i32, _i32, _vp], C.c_int),
 }
 EXPORTS = tuple(_PROTOS)
 _ERR = {-1: "DTA_EINVAL", -2: "DTA_EUNSUPPORTED", -3: "DTA_EALIGN", -4: "DTA_ELAUNCH", -5: "DTA_EPRIOR"}

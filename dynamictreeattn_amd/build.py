@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("DTA_LIB") or os.path.join(HERE, "libdta_mi355x.so")      # DTA_LIB: diagnostic builds only
 SOURCES = ["tree_attn.hip", "tree_attn_f32.hip", "trie_kernels.hip", "logprob_kernels.hip", "elementwise_kernels.hip", "moe_kernels.hip",
-           "lora_kernels.hip", "loss_kernels.hip"]
+           "lora_kernels.hip", "loss_kernels.hip", "quant_kernels.hip"]
 
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17"]

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void preorder_meta_kernel(const int64_t* __res
 
 }  // namespace
 
-extern "C" int dta_version(void) { return 260; }
+extern "C" int dta_version(void) { return 270; }
 
 extern "C" int dta_take_pending_error(char* msg, int32_t cap) {
   const hipError_t e = hipGetLastError();            // returns AND clears the thread's pending error

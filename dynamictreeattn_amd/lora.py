@@ -29,8 +29,7 @@ class LoraLinear(nn.Module):
 
     def __init__(self, base: nn.Module, r: int, alpha: float, adapter_name: str = "default", dtype: torch.dtype = torch.float32):
         super().__init__()
-        out_f, in_f = base.weight.shape
-        dev = base.weight.device
+        out_f, in_f, _, dev = base_geometry(base)
         self.base_layer = base
         self.in_features, self.out_features = in_f, out_f
         self.lora_A = nn.ModuleDict({adapter_name: nn.Linear(in_f, r, bias=False, device=dev, dtype=dtype)})
@@ -58,6 +57,26 @@ class LoraLinear(nn.Module):
                 A = self.lora_A[n]
                 y = (y + self.lora_B[n](A(x.to(A.weight.dtype))) * self.scaling[n]).to(y.dtype)
         return y
+
+
+QUANT_FORMATS = ("nf4", "fp8")      # quant.BLOCK's keys (quant.py imports this module, not the reverse)
+
+
+def is_quantized(m) -> bool:
+    """A base module that holds block codes of THIS project's formats instead of a weight (quant.QuantLinear, duck-typed: ``qweight``,
+    ``scales`` and ``fmt`` one of quant.BLOCK).  A GPTQ / AWQ module has the first two and another layout: it is not taken for one."""
+    return hasattr(m, "qweight") and hasattr(m, "scales") and getattr(m, "fmt", None) in QUANT_FORMATS
+
+
+def base_geometry(base):
+    """(out_features, in_features, dtype, device) of a 2-D base projection, None for anything else.  A quantised base answers from its
+    attributes: its ``weight`` is a property that dequantises the whole matrix, and nothing on the per-call path may touch it."""
+    if is_quantized(base):
+        return int(base.out_features), int(base.in_features), base.dtype, base.qweight.device
+    w = getattr(base, "weight", None)
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        return None
+    return int(w.shape[0]), int(w.shape[1]), w.dtype, w.device
 
 
 def carries_adapter(m) -> bool:
@@ -122,9 +141,8 @@ def check_supported(model) -> None:
     for name, m in _wrapped(model):
         leaf = name.rsplit(".", 1)[-1]
         base = getattr(m, "base_layer", None)
-        w = getattr(base, "weight", None)
-        if (not carries_adapter(m) or leaf not in TARGETS or ".layers." not in "." + name or not isinstance(w, torch.Tensor) or w.dim() != 2
-                or ".experts" in name):
+        geo = base_geometry(base) if base is not None else None
+        if not carries_adapter(m) or leaf not in TARGETS or ".layers." not in "." + name or geo is None or ".experts" in name:
             raise ValueError(f"{name}: an adapter on this module is not supported (adapters go on {' / '.join(TARGETS)} of the decoder "
                              f"layers; not on embeddings, lm_head, the router gate or the expert tensors)")
         if getattr(m, "disable_adapters", False) or getattr(m, "merged", False):
@@ -146,11 +164,11 @@ def check_supported(model) -> None:
             A, B = m.lora_A[n].weight, m.lora_B[n].weight
             if A.shape[0] > MAX_RANK or A.shape[0] != B.shape[1]:
                 raise ValueError(f"{name}.lora_A[{n!r}]: r = {A.shape[0]} is not supported (1..{MAX_RANK}, lora_B [out, r])")
-            if A.shape[1] != w.shape[1] or B.shape[0] != w.shape[0]:
-                raise ValueError(f"{name}.lora_A / lora_B[{n!r}]: shapes {tuple(A.shape)} / {tuple(B.shape)} do not fit the base weight {tuple(w.shape)}")
+            if A.shape[1] != geo[1] or B.shape[0] != geo[0]:
+                raise ValueError(f"{name}.lora_A / lora_B[{n!r}]: shapes {tuple(A.shape)} / {tuple(B.shape)} do not fit the base weight {geo[:2]}")
             for t, f in ((A, "lora_A"), (B, "lora_B")):
-                if t.dtype not in (torch.float32, w.dtype):
-                    raise ValueError(f"{name}.{f}[{n!r}] dtype {t.dtype} is not supported: fp32 or the model dtype ({w.dtype})")
+                if t.dtype not in (torch.float32, geo[2]):
+                    raise ValueError(f"{name}.{f}[{n!r}] dtype {t.dtype} is not supported: fp32 or the model dtype ({geo[2]})")
 
 
 def _flag(d, n) -> bool:
@@ -186,7 +204,7 @@ def attach(model, r: int, alpha: float, target_modules: Iterable[str] = TARGETS,
             p = getattr(layer, parent, None)
             for t in names:
                 m = getattr(p, t, None)
-                if t not in targets or m is None or carries_adapter(m) or getattr(getattr(m, "weight", None), "dim", lambda: 0)() != 2:
+                if t not in targets or m is None or carries_adapter(m) or base_geometry(m) is None:
                     continue
                 rank = _rank_of(f"model.layers.{li}.{parent}.{t}", r, rank_pattern)
                 if not 1 <= rank <= MAX_RANK:
@@ -238,23 +256,37 @@ def load_adapter_state_dict(model, sd: Dict[str, torch.Tensor]) -> None:
         v.copy_(sd[k])
 
 
-@torch.no_grad()
-def merged_state_dict(model) -> Dict[str, torch.Tensor]:
-    """The model's weights under their plain names with every active adapter folded in: W + scaling * B A, formed in fp32 and rounded
-    once to the weight's dtype - what a rollout engine is handed after a step."""
+def _plain_state_dict(model, fold: bool) -> Dict[str, torch.Tensor]:
+    """The model's weights under their plain names: adapter keys dropped, ``.base_layer.`` removed, a quantised base (its ``qweight`` /
+    ``scales`` buffers) as its dequantised ``weight`` and, with `fold`, every active adapter added in fp32 and rounded once."""
     delta = {}
-    for name, m in model.named_modules():
-        if carries_adapter(m):
-            _, ad = resolve(m)
-            if ad is not None:
-                A, B, s = ad
-                delta[name + ".base_layer.weight"] = s * (B.float() @ A.float())
+    if fold:
+        for name, m in model.named_modules():
+            if carries_adapter(m):
+                _, ad = resolve(m)
+                if ad is not None:
+                    A, B, s = ad
+                    delta[name + ".base_layer.weight"] = s * (B.float() @ A.float())
+    quantized = {name: m for name, m in model.named_modules() if is_quantized(m)}
     out = {}
     for k, v in model.state_dict().items():
         if _is_adapter_key(k):
             continue
         t = v.detach()
+        mod, _, leaf = k.rpartition(".")
+        if mod in quantized and leaf in ("qweight", "scales"):
+            if leaf == "scales":
+                continue
+            k, t = mod + ".weight", quantized[mod].weight
         if k in delta:
-            t = (t.float() + delta[k].to(t.device)).to(v.dtype)
+            t = (t.float() + delta[k].to(t.device)).to(t.dtype)
         out[k.replace(".base_layer.", ".")] = t.clone()
     return out
+
+
+@torch.no_grad()
+def merged_state_dict(model) -> Dict[str, torch.Tensor]:
+    """The model's weights under their plain names with every active adapter folded in: W + scaling * B A, formed in fp32 and rounded
+    once to the weight's dtype - what a rollout engine is handed after a step.  On a quantised base (quant.quantize_base) W is the
+    dequantised matrix."""
+    return _plain_state_dict(model, True)

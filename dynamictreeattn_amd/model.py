@@ -518,18 +518,25 @@ def _project(x, *mods):
     """x through the fused projection of `mods` (q|k|v, gate|up, or one module): ONE base GEMM over the stacked base weights - a module
     that carries a LoRA adapter (lora.resolve) contributes its base_layer's weight and bias - and, where members carry adapters, their
     low-rank terms on the members' column ranges of the fused output (ops.lora_linear: some members only, different ranks, a trainable
-    base all work).  Without adapters this is ops.linear, as before."""
+    base all work).  Without adapters this is ops.linear, as before.  A group whose bases are quantised (quant.quantize_base) goes
+    through ops.quant_linear, which expands the codes per use; shapes and biases are read from the modules, never from a quantised
+    module's `weight` (a property that dequantises the whole matrix)."""
     bases, ads = zip(*(lora.resolve(m_) for m_ in mods))
-    w = bases[0].weight if len(bases) == 1 else ops.stack_rows(*(b_.weight for b_ in bases))
+    quantized = [lora.is_quantized(b_) for b_ in bases]
+    if any(quantized) and not all(quantized):
+        raise ValueError("a fused projection group mixes quantised and plain members: quant.quantize_base(model) quantises all of them")
     bias = _bias(*bases)
-    if not any(a_ is not None for a_ in ads):
-        return ops.linear(x, w, bias)
     adapters, n0 = [], 0
     for b_, a_ in zip(bases, ads):
-        n = b_.weight.shape[0]
+        n = lora.base_geometry(b_)[0]
         if a_ is not None:
             adapters.append((n0, n, *a_))
         n0 += n
+    if quantized[0]:
+        return ops.quant_linear(x, bases, bias, adapters)
+    w = bases[0].weight if len(bases) == 1 else ops.stack_rows(*(b_.weight for b_ in bases))
+    if not adapters:
+        return ops.linear(x, w, bias)
     return ops.lora_linear(x, w, bias, adapters)
 
 

@@ -1266,9 +1266,14 @@ def _dgrad(dy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     index contiguous in both operands) hipBLASLt runs the same product 12-25 % faster on gfx950 (scripts/gemm_dgrad_layout_probe.py:
     q/k/v 0.252 -> 0.202 ms, gate/up 0.322 -> 0.275, down 0.183 -> 0.155, LM head 9.68 -> 8.34 at T = 28 160) - the copy (HIP transpose,
     once per weight version) costs a tenth of that."""
-    if dy.is_cuda and w.dtype in (torch.bfloat16, torch.float16) and dy.shape[0] >= 4096 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
+    if _dgrad_transposed(dy, w.shape, w.dtype):
         return dy @ _TransposedWeights.get(w).t()
     return dy @ w
+
+
+def _dgrad_transposed(dy: torch.Tensor, w_shape, w_dtype) -> bool:
+    """Whether `_dgrad` runs dy · W against a transposed copy of W [out, in] (from 4096 rows on) or against W as it is."""
+    return dy.is_cuda and w_dtype in (torch.bfloat16, torch.float16) and dy.shape[0] >= 4096 and w_shape[0] % 8 == 0 and w_shape[1] % 8 == 0
 
 
 WGRAD_SPLIT_K = 4      # slices of the packed rows in the weight-gradient GEMM of a small projection
@@ -1579,7 +1584,8 @@ class _LoraLinear(torch.autograd.Function):
     def forward(ctx, x, w, b, spec, *ab):
         dt = x.dtype
         As, Bs = ab[0::2], ab[1::2]
-        y = F.linear(x, w, b)
+        quantized = isinstance(w, QuantOperand)          # where the base operand comes from is the only difference (see QuantOperand)
+        y = F.linear(x, w.matrix(False) if quantized else w, b)
         a_cat = torch.cat([a.to(dt) for a in As]) if len(As) > 1 else As[0].to(dt)
         if not a_cat.is_contiguous():
             a_cat = a_cat.contiguous()
@@ -1588,14 +1594,16 @@ class _LoraLinear(torch.autograd.Function):
         r0 = 0
         for (n0, nlen, r, s), B_ in zip(spec, bs):                      # y_seg += s · xa_seg · B_segᵀ in place (alpha on the fp32 accumulator)
             y[:, n0:n0 + nlen].addmm_(xa[:, r0:r0 + r], B_.t(), alpha=s); r0 += r
-        ctx.save_for_backward(x, w, xa, a_cat, *bs)
+        ctx.save_for_backward(x, xa, a_cat, *bs, *(() if quantized else (w,)))
+        ctx.quant_base = w if quantized else None        # the codes and scales by reference; never the expanded matrix
         ctx.spec, ctx.has_bias, ctx.ab_dtypes = spec, b is not None, [t.dtype for t in ab]
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, xa, a_cat = ctx.saved_tensors[:4]
-        bs = ctx.saved_tensors[4:]
+        x, xa, a_cat = ctx.saved_tensors[:3]
+        bs = ctx.saved_tensors[3:3 + len(ctx.spec)]
+        w = ctx.quant_base if ctx.quant_base is not None else ctx.saved_tensors[-1]
         spec, dt = ctx.spec, x.dtype
         dy = dy.contiguous()
         R, N = a_cat.shape[0], dy.shape[1]
@@ -1614,7 +1622,7 @@ class _LoraLinear(torch.autograd.Function):
                 torch.addmm(dxa[:, q0:q0 + r], dy[:, n0:n0 + nlen], B_, beta=0, alpha=s, out=dxa[:, q0:q0 + r])
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = _dgrad(dy, w)
+            dx = w.dgrad(dy) if ctx.quant_base is not None else _dgrad(dy, w)
             dx = dx.addmm_(dxa, a_cat) if dx.is_contiguous() else dx + dxa @ a_cat
         dw = _wgrad(x, dy, w.shape[1] >= 2 * w.shape[0]) if ctx.needs_input_grad[1] else None
         db = dy.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
@@ -1653,6 +1661,98 @@ def lora_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], ada
     if o < y.shape[1]:
         cols.append(y[:, o:])
     return cols[0] if len(cols) == 1 else torch.cat(cols, dim=1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Quantised frozen base (quant.py, include/dta.h "Quantised frozen base"): block codes + fp32 scales, expanded to the model dtype per use
+# ------------------------------------------------------------------------------------------------------------------------------------
+QUANT_FMT = {"nf4": 0, "fp8": 1}
+QUANT_BLOCK = {"nf4": 64, "fp8": 128}
+
+
+def quant_blockwise(w: torch.Tensor, fmt: str):
+    """(codes uint8 [R, C / 2] (nf4) or [R, C] (fp8), scales fp32 [R, C / block]) of a weight [R, C] with contiguous rows (dta_quant_blockwise)."""
+    R, C = w.shape
+    assert w.stride(1) == 1 and C % QUANT_BLOCK[fmt] == 0
+    q = torch.empty((R, C // 2 if fmt == "nf4" else C), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((R, C // QUANT_BLOCK[fmt]), dtype=torch.float32, device=w.device)
+    _launch("dta_quant_blockwise", (w, q, scales), ptr(w), w.stride(0), R, C, _DT[w.dtype], QUANT_FMT[fmt], ptr(q), ptr(scales),
+            nbytes=R * C * w.element_size() + q.numel() + scales.numel() * 4)
+    return q, scales
+
+
+def dequant_blockwise(q: torch.Tensor, scales: torch.Tensor, fmt: str, out: torch.Tensor, transposed: bool = False) -> torch.Tensor:
+    """Expands codes + scales of a weight [R, C] into `out` (dta_dequant_blockwise): a [R, C] window with contiguous rows at any pitch -
+    a row range of a stacked operand - or, `transposed`, a [C, R] window - a column range of a transposed stacked operand."""
+    R, C = scales.shape[0], scales.shape[1] * QUANT_BLOCK[fmt]
+    assert q.is_contiguous() and scales.is_contiguous() and out.stride(1) == 1 and tuple(out.shape) == ((C, R) if transposed else (R, C))
+    _launch("dta_dequant_blockwise", (q, scales, out), ptr(q), ptr(scales), R, C, QUANT_FMT[fmt], ptr(out), out.stride(0), _DT[out.dtype],
+            int(transposed), nbytes=q.numel() + scales.numel() * 4 + R * C * out.element_size())
+    return out
+
+
+class QuantOperand:
+    """The base operand of one fused projection group (q|k|v, gate|up, or one module) held as block codes: `mods` are the group's
+    quant.QuantLinear members in row order.  `matrix` expands them into ONE transient operand from the caching allocator - each member
+    straight into its row range (or, transposed, its column range): no stack_rows copy, no transpose pass - which the caller drops after
+    its GEMM.  It never enters weight_cache, _StackRows._cache or _TransposedWeights.cache, and an autograd node holds this object (the
+    codes and scales by reference), never a matrix."""
+    __slots__ = ("mods", "dtype", "shape")
+
+    def __init__(self, mods, dtype):
+        self.mods, self.dtype = tuple(mods), dtype
+        self.shape = (sum(m.out_features for m in self.mods), self.mods[0].in_features)
+
+    def matrix(self, transposed: bool) -> torch.Tensor:
+        N, K = self.shape
+        out = torch.empty((K, N) if transposed else (N, K), dtype=self.dtype, device=self.mods[0].qweight.device)
+        o = 0
+        for m in self.mods:
+            r = m.out_features
+            dequant_blockwise(m.qweight, m.scales, m.fmt, out[:, o:o + r] if transposed else out[o:o + r], transposed)
+            o += r
+        return out
+
+    def dgrad(self, dy: torch.Tensor) -> torch.Tensor:
+        """dx = dy · W in the orientation `_dgrad` takes for this shape, on a freshly expanded operand."""
+        # a member's column range of the transposed operand must start on 16 bytes: every member's rows a multiple of 8, not the sum alone
+        if _dgrad_transposed(dy, self.shape, self.dtype) and all(m.out_features % 8 == 0 for m in self.mods):
+            return dy @ self.matrix(True).t()
+        return dy @ self.matrix(False)
+
+
+class _QuantLinear(torch.autograd.Function):
+    """y = x Wᵀ (+ b) on a quantised base without adapters (a quantised MLP beside adapted attention projections): nothing is saved but
+    the operand's codes by reference - the base has no weight gradient, so not even x."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.quant_base, ctx.has_bias = w, b is not None
+        return F.linear(x, w.matrix(False), b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx = ctx.quant_base.dgrad(dy) if ctx.needs_input_grad[0] else None
+        db = dy.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, None, db
+
+
+def quant_linear(x: torch.Tensor, qmods, b: Optional[torch.Tensor], adapters) -> torch.Tensor:
+    """x [rows, in] through a (fused) projection whose base members `qmods` are quantised (quant.QuantLinear), with `adapters` as
+    lora_linear takes them.  bf16 / f16 on the device: the group is expanded by dta_dequant_blockwise into one transient operand for the
+    forward GEMM and again, only if dx is needed, for the backward; the adapter arithmetic is _LoraLinear's.  Host tensors (the CPU
+    stand-ins): the same arithmetic in torch expressions on quant.dequantize_host."""
+    if x.is_cuda:
+        if x.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"a quantised base serves bf16 / f16 models; the input is {x.dtype}")
+        op = QuantOperand(qmods, x.dtype)
+        if not adapters:
+            return _QuantLinear.apply(x, op, b)
+        spec = tuple((int(n0), int(nlen), int(A.shape[0]), float(s)) for n0, nlen, A, B_, s in adapters)
+        return _LoraLinear.apply(x, op, b, spec, *[t for _, _, A, B_, _ in adapters for t in (A, B_)])
+    from . import quant
+    ws = [quant.dequantize_host(m.qweight, m.scales, m.fmt, x.dtype) for m in qmods]
+    return lora_linear(x, ws[0] if len(ws) == 1 else torch.cat(ws), b, adapters)
 
 
 # --------------------------------------------------------------------------------------------------

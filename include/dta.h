@@ -543,6 +543,36 @@ int dta_preference_loss(const float* lp, const int32_t* depth, const int32_t* ro
                         float beta, float label_smoothing, float gamma, int32_t length_normalize, int32_t reference_free,
                         float sft_coef, float scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Quantised frozen base (quant.py; HBM-bound): the frozen projection weights of a LoRA model stored in a 4- or 8-bit block format and
+ * expanded to the model dtype where a GEMM needs them.  A weight [R, C] (R = out, C = in) is cut into blocks along C; each block has
+ * one fp32 scale.  q: the codes, row after row without a pitch; scales: float [R, C / block].
+ *   DTA_QUANT_NF4  block 64.  scale = absmax (fp32); v = x / scale (a correctly rounded fp32 division); code = #{i < 15 : v > mid_i},
+ *                  mid_i = (c_i + c_{i+1}) / 2 formed in float64 and rounded to fp32 - a value exactly on a midpoint takes the lower
+ *                  code; c_0..c_15 the NormalFloat-4 table (csrc/dta_quant_tables.h).  absmax == 0: scale 0, code 7 (c_7 = 0).
+ *                  q: uint8 [R, C / 2], byte j of a row = element 2j in bits 7..4, element 2j + 1 in bits 3..0.
+ *   DTA_QUANT_FP8  block 128.  scale = absmax / 448 (fp32 division); q = e4m3(clamp(x / scale, -448, 448)), OCP e4m3
+ *                  (float8_e4m3fn), fp32 division, round to nearest even.  scale == 0: q = 0.  q: uint8 [R, C].
+ * Dequantisation: out = round_to(out_dtype, value(code) * scale) - one fp32 product, one rounding.  Non-finite weights are the
+ * caller's to refuse (quant.quantize_base does); the kernels do not check.  Scales in the fp32 subnormal range: DESIGN.md §4q.
+ * Refusals of both entries come in this order: DTA_EINVAL (a null pointer, R or C <= 0, a pitch below the row, transposed not 0 / 1),
+ * DTA_EUNSUPPORTED (fmt, dtype, C not a multiple of the block, C >= 2^22), DTA_EALIGN (q, scales or out off 16 bytes; w off its
+ * element size; row-major: ld_out not a multiple of 16 bytes), DTA_EPRIOR.
+ * ------------------------------------------------------------------------------------------- */
+#define DTA_QUANT_NF4 0
+#define DTA_QUANT_FP8 1
+/* w: [R, C] bf16 / f16 / f32 with ld_w elements between rows (a member of a fused weight, a slice).  One wave per block: absmax by a
+ * wave reduction, then the codes.  Runs once per weight. */
+int dta_quant_blockwise(const void* w, int64_t ld_w, int64_t R, int64_t C, int32_t w_dtype, int32_t fmt, void* q, float* scales,
+                        void* stream);
+/* transposed == 0: out [R, C] at ld_out elements between rows (>= C; a multiple of 16 bytes) - the members of a fused group (q|k|v,
+ * gate|up) go straight into their row ranges of ONE stacked operand.  16-byte stores; a lane reads its block's scale once; the codes
+ * are read non-temporally.  transposed == 1: out [C, R] at ld_out elements between rows (>= R, any; rows that start on 16 bytes get
+ * 16-byte stores, others and the ragged edge of R element stores) through a 64 x 64 LDS tile as dta_transpose, with the decode on the
+ * load side - the members of a group write their column ranges of one transposed stacked operand.  out_dtype bf16 / f16 / f32. */
+int dta_dequant_blockwise(const void* q, const float* scales, int64_t R, int64_t C, int32_t fmt, void* out, int64_t ld_out,
+                          int32_t out_dtype, int32_t transposed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
